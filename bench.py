@@ -1,14 +1,21 @@
 """Benchmark of the hot path: images/sec, forward+backward, YOLOv8s-CBAM-Swin, bs=32 per GPU, 640x640.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR   # + the last timed step's outputs as DIR/*.npy
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full               # + every sub-record below
     python bench.py --gpus N ...            # N > 1 without torchrun's environment: launches itself (see self_launch)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
 One step = forward (bf16 autocast) + v8 detection loss + backward (+ RCCL gradient mean over ranks) + grad-clip +
 SGD-nesterov update + EMA on one synthetic batch already resident in HBM.  Rank 0 prints ONE JSON line.
+A plain run sets up, warms up, times the K steps, writes the outputs (--dump-outputs) and prints the headline line
+(value, ms_per_step, loss items; several ranks: the communication record).  --full adds the sub-records, each measured
+after the timed steps and each still switched off by its own option (--no-kernel-timing, --sustained 0, --no-forward,
+--no-cpu-baseline):
   roofline      measured live: HIP events on the launch stream around every launch of the MFMA GEMM kernels
                 (algorithmic FLOP / elapsed);
+  sustained     the same step replayed back to back for seconds (--sustained replays);
   forward       north_star's target number: the train-mode forward alone (graph-replayed), ms and MFMA fraction;
   cpu_baseline  the CPU oracle (a port of the reference's PyTorch-CPU path, oracle/) timed on the host cores on a
                 bounded sample, rank 0, N=1 only (BASELINE.md section 3 protocol).
@@ -167,6 +174,34 @@ def traffic_record(family, workload):
     return best
 
 
+DUMP_ELEMS = 7_000_000  # elements kept of each dumped state: the files stay under 64 MB in all
+
+
+def dump_outputs(out_dir, items, model, ema):
+    """what the timed step hands its caller after the last timed step, as float32 .npy files in out_dir:
+      loss_items.npy  the (box, cls, dfl) loss items the step returned;
+      model.npy       the model's floating-point state_dict (parameters + BatchNorm statistics after the update), flattened
+                      and concatenated in state_dict order;
+      ema.npy         the EMA copy's, the same way.
+    A state longer than DUMP_ELEMS is reduced to a fixed, seeded sample of DUMP_ELEMS elements in their order (the same
+    indices for the same model), so that two builds are compared element for element.  Copies go through the host: no
+    device-side concatenation runs beside a captured step."""
+    import numpy as np
+
+    def flat(module):
+        parts = [v.detach().float().cpu().reshape(-1).numpy() for v in module.state_dict().values() if v.dtype.is_floating_point]
+        a = np.concatenate(parts)
+        if a.size > DUMP_ELEMS:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, DUMP_ELEMS, replace=False))]
+        return a
+
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "loss_items.npy"), items.detach().float().cpu().numpy())
+    np.save(os.path.join(out_dir, "model.npy"), flat(model))
+    if ema is not None:
+        np.save(os.path.join(out_dir, "ema.npy"), flat(ema.ema))
+
+
 def forward_record(model, batch, steps, gf_fwd):
     """north_star's target metric: the train-mode forward of the step alone (bf16 autocast, batch statistics, tensors
     saved for backward, weight pack included), replayed as a HIP graph; 1.110 TFLOP per batch of 32."""
@@ -206,9 +241,14 @@ def main():
     ap.add_argument("--batch", type=int, default=32, help="images per GPU")
     ap.add_argument("--imgsz", type=int, default=640)
     ap.add_argument("--model", default="yolov8s.yaml")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-kernel-timing", action="store_true")
-    ap.add_argument("--no-forward", action="store_true", help="skip the forward-only sub-record")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the sub-records after the timed steps: roofline (kernel timing), sustained, forward, cpu_baseline; "
+                         "off: the run does only what the headline figure needs")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed step computed (loss items, model and EMA state) as DIR/*.npy, float32 (see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the cpu_baseline sub-record")
+    ap.add_argument("--no-kernel-timing", action="store_true", help="--full without the roofline sub-record")
+    ap.add_argument("--no-forward", action="store_true", help="--full without the forward-only sub-record")
     ap.add_argument("--graph", type=int, default=1, help="1: replay the step as a HIP graph (several ranks: forward+backward graph, RCCL mean + update eager), 0: eager")
     ap.add_argument("--backend", choices=["nccl", "gloo"], default="nccl",
                     help="torch.distributed backend of the gradient mean: nccl (= RCCL over xGMI, the measured configuration) or gloo "
@@ -217,7 +257,7 @@ def main():
                     help="graph schedule: auto = one graph on one rank, three graphs with the bucket exchanges between them on several; split = "
                          "the several-rank schedule also on one rank (what it costs without the collectives); tail = round 3's several-rank form")
     ap.add_argument("--sustained", type=int, default=850,
-                    help="graph replays of the sustained-throughput sub-record (0: skip); the default keeps the device busy for >= 10 s, long enough "
+                    help="graph replays of the sustained-throughput sub-record of --full (0: skip); the default keeps the device busy for >= 10 s, long enough "
                          "for an outside 5-second GPU-busy sampler to see it")
     ap.add_argument("--forward-only", action="store_true",
                     help="profiling aid: run ONLY the train-mode forward (north_star's target metric) - warm-up + `steps` graph replays - and print "
@@ -226,6 +266,8 @@ def main():
                     help="development aid for same-box A/B runs (tools/r5_ab.sh): set a python hook (ops.HOOKS: fused_swin_mlp, detect_pair, detect_multi, "
                          "first_conv) or a library option (ymi_set_option: bn_tail, ew_cap, ...) before the model is built; the default command sets none")
     args = ap.parse_args()
+    if args.forward_only and args.dump_outputs:
+        ap.error("--dump-outputs writes the training step's outputs; --forward-only does not run the step")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(args))  # no GPU call has happened in this process
@@ -282,7 +324,7 @@ def main():
                 "bucket_bytes": [int(sum(p.numel() for p in b) * 4) for b in step.buckets.buckets]}
         step.time_exposed_communication(True)
     lib = _lib.lib()
-    timing = not args.no_kernel_timing
+    timing = args.full and not args.no_kernel_timing
     instrument_inline = timing and not use_graph  # HIP events cannot be recorded inside a replayed graph
     if instrument_inline:
         _lib.check(lib.ymi_profile_begin(args.steps * 1024), "profile_begin")
@@ -301,6 +343,8 @@ def main():
         comm["exposed_is"] = ("compute-stream time between the end of the backbone's backward graph and the end of the wait for both buckets" if step.overlap_graphs
                               else "the whole gradient exchange (nothing overlaps it in this schedule)")
         step.time_exposed_communication(False)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, items, model, step.ema)  # before any sub-record of --full steps the model further
     roof = None
     if timing:
         prof_steps = args.steps
@@ -354,7 +398,7 @@ def main():
         dt = float(tmax.item())
     value = args.gpus * args.batch * args.steps / dt
     sustained = None
-    if use_graph and args.sustained > 0:
+    if args.full and use_graph and args.sustained > 0:
         # the same step, replayed back to back for seconds instead of the K timed steps (0.3 s at the defaults): long enough for an
         # external sampler (rocm-smi, the driver's GPU-busy probe) to see the device busy and for the clock to settle; same formula
         if world > 1:
@@ -375,7 +419,7 @@ def main():
                      "images_per_sec": round(args.gpus * args.batch * args.sustained / dts, 2)}
     fwd = None
     gf_fwd, gf_both = gflop_per_img(args.model, args.imgsz)
-    if rank == 0 and not args.no_forward and gf_fwd is not None:
+    if rank == 0 and args.full and not args.no_forward and gf_fwd is not None:
         fwd = forward_record(model, batch, max(args.steps, 10), gf_fwd)
     if rank == 0:
         out = {
@@ -417,7 +461,7 @@ def main():
             out["roofline"] = roof
         if fwd:
             out["forward"] = fwd
-        if args.gpus == 1 and not args.no_cpu_baseline:
+        if args.full and args.gpus == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out), flush=True)
     if world > 1:

@@ -1,5 +1,5 @@
 """Every GEMM launch of the profiled eager steps against ITS OWN roofline bound max(FLOP / 2.5 PFLOP/s, algorithmic bytes / 8 TB/s).
-Input: the file written by YMI_PROF_DUMP=<file> python bench.py --no-cpu-baseline --no-forward --sustained 0 (one line per launch: family,
+Input: the file written by YMI_PROF_DUMP=<file> python bench.py --full --no-cpu-baseline --no-forward --sustained 0 (one line per launch: family,
 measured us, bound us, GFLOP, MB; HIP-event brackets on the launch stream, ~3 us of dispatch inside every bracket).
 usage: per_launch_bounds.py DUMP STEPS [--list]"""
 import sys

@@ -11,13 +11,13 @@ python3 -m pytest tests -m gpu -x -q > $out/tests.log 2>&1 || { tail -30 $out/te
 tail -3 $out/tests.log
 fi
 cd /tmp && export TMPDIR=/tmp
-python3 $root/bench.py --no-cpu-baseline > $out/bench.json 2> $out/bench.err
+python3 $root/bench.py --full --no-cpu-baseline > $out/bench.json 2> $out/bench.err
 cat $out/bench.json
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace_fwd -o p -- python3 $root/bench.py --forward-only --steps 27 > $out/fwd_under_rocprof.json 2> $out/trace_fwd.err
 cp $(ls $out/trace_fwd/*kernel_stats.csv $out/trace_fwd/*/*kernel_stats.csv 2>/dev/null | head -1) $out/fwd_kernel_stats.csv
 python3 $root/tools/kernel_categories.py $out/fwd_kernel_stats.csv 32 > $out/fwd_kernel_categories.txt
 cat $out/fwd_kernel_categories.txt | head -16
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o p -- python3 $root/bench.py --no-cpu-baseline --no-forward --sustained 0 > $out/bench_under_rocprof.json 2> $out/trace.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/trace -o p -- python3 $root/bench.py --full --no-cpu-baseline --no-forward --sustained 0 > $out/bench_under_rocprof.json 2> $out/trace.err
 cp $(ls $out/trace/*kernel_stats.csv $out/trace/*/*kernel_stats.csv 2>/dev/null | head -1) $out/kernel_stats.csv
 python3 $root/tools/kernel_categories.py $out/kernel_stats.csv 33 > $out/kernel_categories.txt
 cat $out/kernel_categories.txt | head -16

@@ -7,6 +7,6 @@ cd /tmp
 for rep in 1 2 3; do
 for cfg in $list; do
   IFS=, read a b c <<< "$cfg"
-  YMI_EW_PPT=$a YMI_EW_CAP=$b YMI_RED_CAP=$c python3 $root/bench.py --no-cpu-baseline --no-kernel-timing --no-forward --sustained 100 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('ppt $a cap $b redcap $c :', d['ms_per_step'], d['sustained']['ms_per_step'])"
+  YMI_EW_PPT=$a YMI_EW_CAP=$b YMI_RED_CAP=$c python3 $root/bench.py --full --no-cpu-baseline --no-kernel-timing --no-forward --sustained 100 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('ppt $a cap $b redcap $c :', d['ms_per_step'], d['sustained']['ms_per_step'])"
 done
 done

@@ -7,6 +7,6 @@ for rep in 1 2 3; do
 while IFS= read -r line; do
   [ -z "$line" ] && continue
   l=${line//@/$root}
-  env $l python3 $root/bench.py --no-cpu-baseline --no-kernel-timing --no-forward --sustained 100 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('''$line :''', d['ms_per_step'], d['sustained']['ms_per_step'])"
+  env $l python3 $root/bench.py --full --no-cpu-baseline --no-kernel-timing --no-forward --sustained 100 2>/dev/null | python3 -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print('''$line :''', d['ms_per_step'], d['sustained']['ms_per_step'])"
 done < $file
 done

@@ -5,7 +5,7 @@ out=$root/gpurun_out/r4_sched
 mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 for sc in auto split tail auto split tail; do
-  python3 $root/bench.py --no-cpu-baseline --no-kernel-timing --no-forward --sustained 100 --schedule $sc > $out/bench_$sc.json 2> $out/bench_$sc.err || { tail -5 $out/bench_$sc.err; exit 1; }
+  python3 $root/bench.py --full --no-cpu-baseline --no-kernel-timing --no-forward --sustained 100 --schedule $sc > $out/bench_$sc.json 2> $out/bench_$sc.err || { tail -5 $out/bench_$sc.err; exit 1; }
   python3 - <<PY
 import json
 d=json.load(open("$out/bench_$sc.json"))

@@ -10,7 +10,7 @@ mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
 for l in a b a b; do
   if [ $l = a ]; then export $var=$va; else export $var=$vb; fi
-  python3 $root/bench.py --no-cpu-baseline --no-kernel-timing --sustained 100 > $out/bench_$l.json 2> $out/bench_$l.err || { tail -5 $out/bench_$l.err; exit 1; }
+  python3 $root/bench.py --full --no-cpu-baseline --no-kernel-timing --sustained 100 > $out/bench_$l.json 2> $out/bench_$l.err || { tail -5 $out/bench_$l.err; exit 1; }
   python3 - <<PY
 import json
 d=json.load(open("$out/bench_$l.json"))

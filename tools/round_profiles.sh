@@ -1,7 +1,7 @@
 #!/bin/bash
 # Round-end evidence on the GPU box, written under gpurun_out/<TAG>/ (copy what is to be judged into profiles/<TAG>_*):
-#   bench.json                  default `python bench.py` line (taken again after the PMC passes, so that it carries `traffic`)
-#   kernel_stats.csv            rocprofv3 --kernel-trace --stats of `bench.py --no-forward --no-cpu-baseline --sustained 0` (33 steps)
+#   bench.json                  `python bench.py --full` line (taken again after the PMC passes, so that it carries `traffic`)
+#   kernel_stats.csv            rocprofv3 --kernel-trace --stats of `bench.py --full --no-forward --no-cpu-baseline --sustained 0` (33 steps)
 #   kernel_categories.txt       per-family ms/step of the same
 #   bench_under_rocprof.json    the bench line printed by that profiled run
 #   fwd_kernel_stats.csv / fwd_kernel_categories.txt   the same for `bench.py --forward-only` (the train-mode forward alone)
@@ -35,20 +35,20 @@ traffic() {  # output name, workload label, bench.py arguments
   echo "$name passes done"
 }
 if [ "$2" != "cfg5only" ]; then
-  stats bench 33 --no-cpu-baseline --no-forward --sustained 0
+  stats bench 33 --full --no-cpu-baseline --no-forward --sustained 0
   mv $out/bench_kernel_stats.csv $out/kernel_stats.csv; mv $out/bench_kernel_categories.txt $out/kernel_categories.txt
   stats fwd 32 --forward-only --steps 27
-  traffic pmc_traffic.json "yolov8s.yaml bs32 640" --no-cpu-baseline --no-forward --sustained 0 --steps 3 --warmup 1
+  traffic pmc_traffic.json "yolov8s.yaml bs32 640" --full --no-cpu-baseline --no-forward --sustained 0 --steps 3 --warmup 1
   # every GEMM launch against its own bound (HIP-event brackets of 4 eager steps; the last one is listed)
   rm -f $out/prof_dump.txt
-  YMI_PROF_DUMP=$out/prof_dump.txt python3 $root/bench.py --no-cpu-baseline --no-forward --sustained 0 --graph 0 --steps 4 --warmup 2 > /dev/null 2> $out/prof_dump.err
+  YMI_PROF_DUMP=$out/prof_dump.txt python3 $root/bench.py --full --no-cpu-baseline --no-forward --sustained 0 --graph 0 --steps 4 --warmup 2 > /dev/null 2> $out/prof_dump.err
   python3 $root/tools/per_launch_bounds.py $out/prof_dump.txt 4 --list > $out/per_launch_bounds.txt || true
-  # the default line, now that the PMC passes of THIS kernel revision exist (bench.py reports `traffic` only from a matching file)
-  python3 $root/bench.py > $out/bench.json 2> $out/bench.err
+  # the --full line, now that the PMC passes of THIS kernel revision exist (bench.py reports `traffic` only from a matching file)
+  python3 $root/bench.py --full > $out/bench.json 2> $out/bench.err
   echo "bench done"
 fi
 if [ "$2" = "cfg5" ] || [ "$2" = "cfg5only" ]; then
-  C5="--model yolov8m-cbam-swin384.yaml --batch 16 --imgsz 1280 --no-cpu-baseline"
+  C5="--model yolov8m-cbam-swin384.yaml --batch 16 --imgsz 1280 --full --no-cpu-baseline"
   stats cfg5 21 $C5 --no-forward --sustained 0 --steps 10 --warmup 3
   traffic cfg5_pmc_traffic.json "yolov8m-cbam-swin384.yaml bs16 1280" $C5 --no-forward --sustained 0 --steps 3 --warmup 1
   python3 $root/bench.py $C5 --steps 10 --warmup 3 --sustained 20 > $out/bench_cfg5.json 2> $out/bench_cfg5.err
