@@ -45,12 +45,7 @@ class ModelEMA:
     `update()` alone is one multi-tensor launch; attached to a FusedSGD it rides in the optimizer's update pass."""
 
     def __init__(self, model, decay=0.9999, tau=2000, updates=0):
-        arena = model.__dict__.pop("_arena", None)  # packed-operand cache of the live model: not part of its state
-        try:
-            self.ema = deepcopy(model).eval()
-        finally:
-            if arena is not None:
-                model.__dict__["_arena"] = arena
+        self.ema = deepcopy(model).eval()  # (the copy gets a fresh ops.ModelState: arenas are never copied or shared)
         self.updates = updates
         self.decay_max, self.tau = float(decay), float(tau)
         self.decay = lambda x: decay * (1 - math.exp(-x / tau))

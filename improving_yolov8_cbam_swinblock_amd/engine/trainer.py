@@ -117,6 +117,7 @@ class TrainStep:
         self._static_items = None
         self._graph_grads = None
         self._seed = None
+        self._held = []  # model-side buffers the captured graphs write (_hold_captured)
         self._comm_events = None  # time_exposed_communication(): [(event after the backward's last graph, event after the wait for the buckets)]
 
     def __call__(self, batch):
@@ -142,6 +143,7 @@ class TrainStep:
                         self._static_items = self.eager_step(self._static)
                     else:
                         self._static_items = self._forward_backward(self._static)
+                self._hold_captured()
                 if not self.full_graph:  # the gradients the replays rewrite in place
                     self._graph_grads = {p: p.grad for p in self.params if p.grad is not None}
                 elif self.ema is not None:
@@ -235,6 +237,12 @@ class TrainStep:
         if dst:
             torch._foreach_copy_(dst, src)
 
+    def _hold_captured(self):
+        """a graph just captured launches that write the model's statistics arena, pack into its weight arena and stage the batched slab sum
+        in RUN.table: keep them referenced for as long as the graphs live, whatever the model or a later pass replaces them with."""
+        st = self.model._state
+        self._held.append((st.stats, st.arena, ops.RUN.table))
+
     def _capture_overlap(self, mode):
         b = self._static
         # conv / linear weight gradients are written straight into the flat buckets (ops.grad_arena): only the small vectors (BatchNorm
@@ -243,11 +251,13 @@ class TrainStep:
         with torch.cuda.graph(self._graph, capture_error_mode=mode), ops.grad_arena(arena):
             self._static_items, hg, pairs = self._head_pass(b)
             self._pack(0, self._head_params, hg)
+        self._hold_captured()
         del hg
         self._graph2 = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self._graph2, pool=self._graph.pool(), capture_error_mode=mode), ops.grad_arena(arena):
             self._backbone_pass(pairs)
             self._pack(1, self._back_params, [p.grad for p in self._back_params])
+        self._hold_captured()
         del pairs
         self.buckets.wait_all(divide=False)  # (nothing in flight: points .grad at the flat slices the update graph will read)
         self._graph3 = torch.cuda.CUDAGraph()

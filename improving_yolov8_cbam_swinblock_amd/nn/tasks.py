@@ -123,6 +123,10 @@ def parse_model(d, ch, verbose=False):
 class BaseModel(nn.Module):
     """forward(tensor) -> predictions, forward(dict) -> loss (reference tasks.py:113-311)."""
 
+    def __init__(self):
+        super().__init__()
+        self._state = ops.ModelState()  # run-time state of the forwards (weight and statistics arenas): not part of the state_dict
+
     def forward(self, x, *args, **kwargs):
         if isinstance(x, dict):
             return self.loss(x, *args, **kwargs)
@@ -144,12 +148,11 @@ class BaseModel(nn.Module):
         taps = getattr(self, "_taps", None)
         nb_layers = len(self.yaml["backbone"]) if taps is not None else 0
         leaf_of = {}
-        # (weights used twice within ONE forward are shared: their gradients are never deferred; the BatchNorm statistics accumulators are zeroed)
-        ops.new_forward_epoch(x.device if (torch.is_tensor(x) and x.is_cuda and self.training) else None)
-        self._begin_weight_arena(x)
         plan = self._graph_plan() if (self.training and torch.is_grad_enabled() and torch.is_tensor(x) and x.is_cuda) else None
         bufs = {}
-        with ops.deferred_bn_counters():
+        # (a new forward epoch: weights used twice within it are shared, their gradients never deferred; statistics arena, weight arena and
+        # the BatchNorm counters: ops.ModelState.forward)
+        with self._state.forward(x, self.training):
             for m in self.model:
                 if m.f != -1:
                     x = y[m.f] if isinstance(m.f, int) else [x if j == -1 else y[j] for j in m.f]
@@ -232,24 +235,6 @@ class BaseModel(nn.Module):
         plan = self._plan = {"slot": slot, "consumers": {j: c for j, c in consumers.items() if c > 1 and ok[j]}}
         return plan
 
-    def _begin_weight_arena(self, x):
-        """training forwards pack every weight with one launch (ops.WeightArena): the first forward+backward records
-        the uses, the second forward builds the arena; eval / no-grad forwards keep the per-call packers."""
-        if not (self.training and torch.is_grad_enabled() and x.is_cuda):
-            ops.set_weight_arena(None)
-            return
-        dt = ops.compute_dtype(x)
-        arena = getattr(self, "_arena", None)
-        if arena is None or (arena.dtype is not None and arena.dtype != dt):
-            arena = self._arena = ops.WeightArena()
-        elif arena.built and arena.stale():  # parameter storage moved (model.to(), .float(), ...): start over
-            arena = self._arena = ops.WeightArena()
-        elif not arena.built and arena.specs:
-            arena.build()
-        ops.set_weight_arena(arena)
-        if arena.built:
-            arena.pack()
-
     def fuse(self, verbose=False):
         """fold BN into conv for inference (reference tasks.py:210-238)."""
         if not self.is_fused():
@@ -258,7 +243,7 @@ class BaseModel(nn.Module):
                     m.conv = fuse_conv_and_bn(m.conv, m.bn)
                     delattr(m, "bn")
                     m.forward = m.forward_fuse
-            self._arena = None
+            self._state.arena = None
         return self
 
     def is_fused(self, thresh=10):
@@ -268,7 +253,7 @@ class BaseModel(nn.Module):
     def _apply(self, fn):
         """keep Detect's stride / anchors on the model's device (reference tasks.py:264-282)."""
         self = super()._apply(fn)
-        self._arena = None  # packed operands and their descriptor table refer to the old parameter storage
+        self._state.arena = None  # packed operands and their descriptor table refer to the old parameter storage
         m = self.model[-1]
         if isinstance(m, Detect):
             m.stride = fn(m.stride)
@@ -288,7 +273,7 @@ class BaseModel(nn.Module):
         csd = {k: v.float() if v.dtype.is_floating_point else v for k, v in csd.items()}
         csd = intersect_dicts(csd, self.state_dict())
         self.load_state_dict(csd, strict=False)
-        self._arena = None
+        self._state.arena = None
         return len(csd)
 
     def loss(self, batch, preds=None):

@@ -10,23 +10,23 @@ Compute dtype is bfloat16 under `torch.autocast("cuda", dtype=torch.bfloat16)` a
 dtype (float32 = parity mode) otherwise; parameters stay float32 and are packed per call.
 """
 # The op layer as a package (round 5: one 2,300-line module before): base -> weights -> conv -> blocks, each importing only from the ones before it.
-# Every name is re-exported here, so `from .. import ops; ops.conv_bn_act(...)` and the tests' `ops._dgrad(...)` read as they always did.  State that is
-# REBOUND at run time (the weight arena, the gradient arena, the BatchNorm counter list) lives with its readers inside one module.
+# Every name is re-exported here, so `from .. import ops; ops.conv_bn_act(...)` and the tests' `ops._dgrad(...)` read as they always did.  Run-time
+# state has two owners: a model's ModelState (its arenas, forward epoch and counters) and the process-wide RUN (the active ModelState, backward passes).
 from .._lib import ACT_GELU, ACT_NONE, ACT_SILU, ConvProblem, DgradProblem, as_ymi, check, chunk_elems, empty_nhwc, is_nhwc, ptr, stream_ptr, workspace, ymi_dtype  # noqa: F401
 from .base import (  # noqa: F401
-    GradJoin, HOOKS, L, LazyConcatBuffer, OutSlot, _GradBuffer, _GradSlot, _ToInternal, _accumulate, _as4d, _byref, _conv_out_hw, _deferred_twice,
-    _dense_ok, _in_backward, _join_plain, _note_use, _prep_adds, _stat_acc, _stat_arena, _use_epoch, compute_dtype, grad_nhwc, join_of, mark_join,
-    new_forward_epoch, round_up, to_internal, to_nchw_float,
+    RUN, GradJoin, HOOKS, L, LazyConcatBuffer, OutSlot, _GradBuffer, _GradSlot, _ToInternal, _accumulate, _as4d, _byref, _conv_out_hw,
+    _count_batch, _deferred_twice, _dense_ok, _in_backward, _join_plain, _note_use, _prep_adds, _stat_acc, compute_dtype, grad_nhwc, join_of, mark_join,
+    round_up, to_internal, to_nchw_float,
 )
 from .weights import (  # noqa: F401
-    WeightArena, _PackDesc, _adoptable, _async, _deferred, _flush_wgrads, _new_dw, _side_stream, _side_streams, _wgrad,
+    ModelState, WeightArena, _PackDesc, _adoptable, _defer_wgrad, _flush_wgrads, _new_dw, _side_stream, _wgrad,
     _wgrad_deferred, _wgrad_maybe_async, async_wgrad, deferred_wgrad, grad_arena, join_side_stream, pack_conv_dgrad, pack_conv_dgrad_pair,
-    pack_conv_fwd, pack_conv_fwd_pair, set_weight_arena, set_wgrad_deferred, wgrad_riders,
+    pack_conv_fwd, pack_conv_fwd_pair, set_weight_arena, wgrad_riders,
 )
 from .conv import (  # noqa: F401
     _ChanSlice, _ChanSplit2, _ConvAffineAct, _ConvBnAct, _ConvBnActPair, _DT, _DetectTrain, _FirstConvBnAct, _conv_fwd_multi,
     _dgrad, _dgrad_finish, _dgrad_joined, _dgrad_joined_finish, _dgrad_joined_prepare, _dgrad_launch, _dgrad_multi, _dgrad_prepare, _width_class,
-    _zero_padded, chan_split2, conv_affine_act, conv_bn_act, conv_bn_act_pair, deferred_bn_counters, detect_train, detect_train_ok, first_conv_bn_act,
+    chan_split2, conv_affine_act, conv_bn_act, conv_bn_act_pair, detect_train, detect_train_ok, first_conv_bn_act,
     first_conv_ok, linear, padded_grad_like,
 )
 from .blocks import (  # noqa: F401

@@ -1,5 +1,5 @@
-"""Foundations of the op layer: library handle, test hooks, layout conversion at the model edges, forward epochs (shared-weight detection,
-BatchNorm statistics accumulators), gradient joins (sums of multi-consumer tensors formed inside kernels), output slots of concat buffers."""
+"""Foundations of the op layer: library handle, test hooks, the run-time state (RUN), layout conversion at the model edges, forward epochs
+(shared-weight detection, BatchNorm statistics accumulators), gradient joins (sums of multi-consumer tensors formed inside kernels), output slots of concat buffers."""
 import ctypes
 import os
 
@@ -117,54 +117,69 @@ def _conv_out_hw(h, w, k, s):
     return (h + 2 * p - k) // s + 1, (w + 2 * p - k) // s + 1
 
 
+class RunState:
+    """The op layer's process-wide run-time state (one instance: RUN).  Forward side: the ModelState of the model forward that is
+    running (ops.weights.ModelState; None outside a model forward) and the weight arena its backward packs from.  Backward side:
+    the schedules switched by deferred_wgrad / async_wgrad / wgrad_riders / grad_arena and what one backward pass carries."""
+
+    def __init__(self):
+        self.model = None           # ModelState of the running model forward
+        self.arena = None           # WeightArena of the latest model forward, read by the packers of its forward AND backward
+        self.defer = False          # deferred_wgrad: batched slab sums
+        self.records, self.keep, self.owners, self.bias = [], [], [], []  # per deferred weight gradient of the pass (weights._flush_wgrads)
+        self.task = None            # autograd graph task the records belong to
+        self.table = None           # device table of the batched slab sum (grows, never shrinks)
+        self.side = False           # async_wgrad: weight gradients on a side stream
+        self.side_pending, self.side_keep = False, []  # a side-stream branch to join, and the operands it reads until then
+        self.side_streams = {}      # device index -> side stream
+        self.grad_views = None      # grad_arena: {id(parameter): buffer its weight gradient is written to}
+        self.riders = False         # wgrad_riders: the library holds weight-gradient launches for BatchNorm-backward riders
+        self.padded = {}            # data_ptr -> channel-padded gradient buffer handed out by conv.padded_grad_like
+
+
+RUN = RunState()
+
+
 # A weight used more than once in one forward (shared weights): autograd's input buffer sums the gradients of the uses BEFORE AccumulateGrad
 # sees them, i.e. it READS them during the pass - none of them may be deferred (round-3 ADVICE).  Which weights are shared is only
-# known once the forward is over, so every weight-consuming Function counts its uses per forward "epoch" (a model forward starts a new
-# one: BaseModel._predict_once); modules called on their own never start an epoch, so a second call already counts as sharing - the
-# safe side: their gradients are complete when the Function returns.
-_use_epoch = [0]
-
-# BatchNorm statistics accumulators (ymi_conv2d_bn_silu_fwd_acc): every Conv block of a forward takes a [4][2][cout] int64 block that must be
-# ZERO when its GEMM starts.  A model forward starts an epoch: ONE fill zeroes the whole arena (sized by the previous epoch's demand) and the
-# blocks are handed out in call order; a block asked for outside an epoch - modules called on their own - or beyond the arena is a fresh
-# zeroed tensor.
-_stat_arena = {"buf": None, "cursor": 0, "need": 0}
-
-
-def new_forward_epoch(device=None):
-    _use_epoch[0] += 1
-    a = _stat_arena
-    if device is not None and HOOKS["stat_atomics"]:
-        if a["buf"] is None or a["buf"].device != device or a["need"] > a["buf"].numel():
-            a["buf"] = torch.zeros(max(a["need"] * 2, 1 << 16), dtype=torch.int64, device=device)
-        else:
-            a["buf"].zero_()
-    else:
-        a["buf"] = None
-    a["cursor"], a["need"] = 0, 0
-
-
-def _stat_acc(cout, device):
-    a = _stat_arena
-    n = 8 * cout
-    a["need"] += n
-    buf = a["buf"]
-    if buf is not None and buf.device == device and a["cursor"] + n <= buf.numel():
-        out = buf[a["cursor"]: a["cursor"] + n]
-        a["cursor"] += n
-        return out
-    return torch.zeros(n, dtype=torch.int64, device=device)
-
-
+# known once the forward is over, so every weight-consuming Function counts its uses per model forward ("epoch": ModelState.epoch);
+# outside a model forward - modules called on their own - every use counts towards the last count, so a second call already counts as
+# sharing - the safe side: their gradients are complete when the Function returns.
 def _note_use(*params):
+    m = RUN.model
+    epoch = (id(m), m.epoch) if m is not None else None
     for w in params:
         if w is None:
             continue
         st = getattr(w, "_ymi_use", None)
-        if st is None or st[0] != _use_epoch[0]:
-            w._ymi_use = [_use_epoch[0], 1]
+        if st is None or (epoch is not None and st[0] != epoch):
+            w._ymi_use = [epoch, 1]
         else:
             st[1] += 1
+
+
+# BatchNorm statistics accumulators (ymi_conv2d_bn_silu_fwd_acc): every Conv block of a forward takes a [4][2][cout] int64 block that must be
+# ZERO when its GEMM starts.  A training forward of a model hands them out in call order from its statistics arena (ModelState.acc, zeroed
+# by one fill); a block asked for outside a model forward, or beyond the arena, is a fresh zeroed tensor.
+def _stat_acc(cout, device):
+    n = 8 * cout
+    m = RUN.model
+    if m is not None:
+        m.need += n
+        if m.acc is not None and m.acc.device == device and m.cursor + n <= m.acc.numel():
+            m.cursor += n
+            return m.acc[m.cursor - n : m.cursor]
+    return torch.zeros(n, dtype=torch.int64, device=device)
+
+
+def _count_batch(bn):
+    """bn.num_batches_tracked += 1: collected by the running model forward and applied as ONE multi-tensor add when it ends."""
+    if bn.num_batches_tracked is None:
+        return
+    if RUN.model is not None:
+        RUN.model.counters.append(bn.num_batches_tracked)
+    else:
+        bn.num_batches_tracked.add_(1)
 
 
 def _deferred_twice(params):

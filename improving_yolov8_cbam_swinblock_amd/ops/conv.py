@@ -9,11 +9,11 @@ import torch
 from .. import _lib
 from .._lib import ACT_GELU, ACT_NONE, ACT_SILU, ConvProblem, DgradProblem, as_ymi, check, chunk_elems, empty_nhwc, is_nhwc, ptr, stream_ptr, workspace, ymi_dtype
 from .base import (  # noqa: F401
-    HOOKS, L, _GradBuffer, _GradSlot, _accumulate, _as4d, _byref, _conv_out_hw, _deferred_twice, _dense_ok, _in_backward, _join_plain, _note_use,
-    _prep_adds, _stat_acc, compute_dtype, grad_nhwc, join_of, mark_join, round_up,
+    HOOKS, RUN, L, _GradBuffer, _GradSlot, _accumulate, _as4d, _byref, _conv_out_hw, _count_batch, _deferred_twice, _dense_ok, _in_backward,
+    _join_plain, _note_use, _prep_adds, _stat_acc, compute_dtype, grad_nhwc, join_of, mark_join, round_up,
 )
 from .weights import (  # noqa: F401
-    _adoptable, _deferred, _flush_wgrads, _new_dw, _wgrad_maybe_async, pack_conv_dgrad, pack_conv_dgrad_pair, pack_conv_fwd, pack_conv_fwd_pair,
+    _adoptable, _defer_wgrad, _new_dw, _wgrad_maybe_async, pack_conv_dgrad, pack_conv_dgrad_pair, pack_conv_fwd, pack_conv_fwd_pair,
 )
 
 def _dgrad_prepare(dy, weight4, k, stride, in_shape, dtype, adds=None, out=None, packed=None):
@@ -237,11 +237,7 @@ def conv_bn_act(x, weight, bn, stride, act=ACT_SILU, residual=None, slot=None):
                                   f"whole 16-byte chunks (multiples of {chunk_elems(x.dtype)}); every standard YOLOv8 width is - use float32 for this width")
     out = _ConvBnAct.apply(x, weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, int(stride), float(bn.eps), float(bn.momentum), int(act), residual, slot,
                            join_of(x), join_of(residual) if residual is not None else None)
-    if bn.num_batches_tracked is not None:
-        if _deferred_counters is not None:
-            _deferred_counters.append(bn.num_batches_tracked)
-        else:
-            bn.num_batches_tracked.add_(1)
+    _count_batch(bn)
     return out
 
 
@@ -284,26 +280,18 @@ class _FirstConvBnAct(torch.autograd.Function):
         dbeta = torch.empty(o, dtype=torch.float32, device=dev)
         n, _, h, w = x4.shape
         need = int(L().ymi_first_conv_bwd_workspace(n, h, w, o))
-        defer = (ctx.needs_input_grad[1] and _deferred["on"] and _in_backward() and _adoptable((weight,)) and not _deferred_twice((weight,)))
+        defer = (ctx.needs_input_grad[1] and RUN.defer and _in_backward() and _adoptable((weight,)) and not _deferred_twice((weight,)))
         dw = _new_dw(o, cin, k, dev, (weight,), None)
         # (the slabs live in the workspace: a deferred sum needs it alive until the end-of-pass flush)
         ws = torch.empty(need, dtype=torch.uint8, device=dev) if defer else workspace(need, dev, "firstconv")
         rec = _lib.WgradPending() if defer else None
+        if defer:
+            _defer_wgrad(rec, (ws, x4, dout), weight)
         check(
             L().ymi_first_conv_bn_act_bwd(_byref(as_ymi(x4)), ptr(weight.detach()), cin, o, ptr(gamma), ptr(beta), ptr(stats[0]), ptr(stats[1]), ctx.act,
                                           _byref(as_ymi(dout)), ptr(dgamma), ptr(dbeta), ptr(dw), ptr(ws), ws.numel(), _byref(rec) if defer else None, stream_ptr()),
             "first_conv_bn_act_bwd",
         )
-        if defer:
-            task = torch._C._current_graph_task_id()
-            if _deferred["task"] != task:
-                _deferred["records"], _deferred["keep"], _deferred["owners"], _deferred["bias"] = [], [], [], []
-                torch.autograd.Variable._execution_engine.queue_callback(_flush_wgrads)
-                _deferred["task"] = task
-            _deferred["records"].append(rec)
-            _deferred["keep"].append((ws, x4, dout))
-            _deferred["owners"].append(weight)
-            _deferred["bias"].append(None)
         return None, (dw if ctx.needs_input_grad[1] else None), dgamma, dbeta, None, None, None, None, None
 
 
@@ -319,11 +307,7 @@ def first_conv_bn_act(img, weight, bn, act=ACT_SILU):
     if bn.momentum is None:
         raise RuntimeError("BatchNorm with cumulative moving average (momentum=None) is not supported")
     out = _FirstConvBnAct.apply(img, weight, bn.weight, bn.bias, bn.running_mean, bn.running_var, float(bn.eps), float(bn.momentum), int(act))
-    if bn.num_batches_tracked is not None:
-        if _deferred_counters is not None:
-            _deferred_counters.append(bn.num_batches_tracked)
-        else:
-            bn.num_batches_tracked.add_(1)
+    _count_batch(bn)
     return out
 
 
@@ -452,12 +436,8 @@ def conv_bn_act_pair(x, conv_a, bn_a, conv_b, bn_b, act=ACT_SILU):
         raise NotImplementedError(f"conv_bn_act_pair: output widths {wa.shape[0]} / {wb.shape[0]} must be multiples of {ch} in {x.dtype}")
     out = _ConvBnActPair.apply(x, wa, bn_a.weight, bn_a.bias, bn_a.running_mean, bn_a.running_var, wb, bn_b.weight, bn_b.bias, bn_b.running_mean,
                                bn_b.running_var, int(conv_a.stride[0]), float(bn_a.eps), float(bn_a.momentum), int(act), join_of(x))
-    for bn in (bn_a, bn_b):
-        if bn.num_batches_tracked is not None:
-            if _deferred_counters is not None:
-                _deferred_counters.append(bn.num_batches_tracked)
-            else:
-                bn.num_batches_tracked.add_(1)
+    _count_batch(bn_a)
+    _count_batch(bn_b)
     return out
 
 
@@ -689,35 +669,10 @@ def detect_train(xs, levels):
     outs = _DetectTrain.apply((len(levels), float(bn0.eps), float(bn0.momentum), joins, ncpad), *t)
     for lv in levels:
         for m in lv[:4]:
-            if m.bn.num_batches_tracked is not None:
-                if _deferred_counters is not None:
-                    _deferred_counters.append(m.bn.num_batches_tracked)
-                else:
-                    m.bn.num_batches_tracked.add_(1)
+            _count_batch(m.bn)
     box = list(outs[0::2])
     cls = [(_ChanSlice.apply(c, nc) if ncpad != nc else c) for c in outs[1::2]]
     return box, cls
-
-
-_deferred_counters = None
-
-
-class deferred_bn_counters:
-    """inside this context the `num_batches_tracked += 1` of every Conv is collected and applied as ONE
-    multi-tensor add on exit (59 tiny launches -> 1 per forward)."""
-
-    def __enter__(self):
-        global _deferred_counters
-        self.prev = _deferred_counters
-        _deferred_counters = []
-        return self
-
-    def __exit__(self, *exc):
-        global _deferred_counters
-        pending, _deferred_counters = _deferred_counters, self.prev
-        if pending:
-            torch._foreach_add_(pending, 1)
-        return False
 
 
 # ------------------------------------------------------------------- conv / linear with affine epilogue
@@ -823,7 +778,7 @@ class _ChanSlice(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, g):
-        base = _zero_padded.pop(g.data_ptr(), None)  # (python attributes do not survive the trip through the engine: keyed on the address)
+        base = RUN.padded.pop(g.data_ptr(), None)  # (python attributes do not survive the trip through the engine: keyed on the address)
         if (base is not None and tuple(base.shape) == ctx.shape and base.dtype == g.dtype and base.stride() == g.stride()
                 and tuple(g.shape) == (ctx.shape[0], g.shape[1]) + ctx.shape[2:]):
             return base, None
@@ -831,9 +786,6 @@ class _ChanSlice(torch.autograd.Function):
             else torch.zeros(ctx.shape, dtype=g.dtype, device=g.device)
         full[:, : g.shape[1]].copy_(g)
         return full, None
-
-
-_zero_padded = {}  # data_ptr -> padded buffer whose [:, :c] view padded_grad_like handed out (dropped when _ChanSlice.backward takes it)
 
 
 def padded_grad_like(t, zero=True):
@@ -847,9 +799,9 @@ def padded_grad_like(t, zero=True):
             base = empty_nhwc(n, ld, h, w, t.dtype, t.device)
             if zero:
                 base.zero_()
-            if len(_zero_padded) > 64:  # (gradients that never reached a _ChanSlice: do not keep their buffers alive)
-                _zero_padded.clear()
-            _zero_padded[base.data_ptr()] = base
+            if len(RUN.padded) > 64:  # (gradients that never reached a _ChanSlice: do not keep their buffers alive)
+                RUN.padded.clear()
+            RUN.padded[base.data_ptr()] = base  # (until _ChanSlice.backward takes it)
             return base, base[:, :c]
     e = torch.empty_like(t)
     return e, e

@@ -1,6 +1,7 @@
 """Weight operands and weight gradients: the per-step weight arena and its pack launches, gradient buckets as GEMM outputs (grad_arena), the
 split-K weight-gradient GEMM with its deferred (batched) slab sum, side-stream and rider schedules (reference: the backward of
 Conv / nn.Linear weights, nn/modules/conv.py:50-91)."""
+import contextlib
 import ctypes
 import os
 
@@ -9,7 +10,7 @@ import torch
 from .. import _lib
 from .._lib import ACT_GELU, ACT_NONE, ACT_SILU, ConvProblem, DgradProblem, as_ymi, check, chunk_elems, empty_nhwc, is_nhwc, ptr, stream_ptr, workspace, ymi_dtype
 from .base import (  # noqa: F401
-    HOOKS, L, _as4d, _byref, _deferred_twice, _in_backward, round_up,
+    HOOKS, RUN, L, _as4d, _byref, _deferred_twice, _in_backward, compute_dtype, round_up,
 )
 
 # ------------------------------------------------------------------------------------ weights
@@ -130,20 +131,70 @@ class WeightArena:
         return v[1] if v is not None and v[1] is not None and v[3] == opad and v[4] == stride else None
 
 
-_arena = None  # the WeightArena of the model whose forward/backward is running (set by DetectionModel)
+class ModelState:
+    """What a model carries from one forward to the next (BaseModel._state): its WeightArena, its BatchNorm statistics arena, the forward
+    epoch and, during a forward, the num_batches_tracked counters to advance.  `forward()` makes it RUN.model for one model forward.
+    A deep copy or pickle of the model gets a fresh one (the arenas hold operands of THIS model's parameters)."""
+
+    def __init__(self):
+        self.arena = None           # WeightArena of the training forwards
+        self.stats = None           # int64 statistics arena, sized by the previous training forward's demand
+        self.epoch = 0              # model forwards so far (_note_use)
+        self.acc = None             # the statistics arena while a training forward hands it out (_stat_acc)
+        self.cursor = self.need = 0
+        self.counters = []
+
+    def __reduce__(self):
+        return ModelState, ()
+
+    @contextlib.contextmanager
+    def forward(self, x, training):
+        """one model forward.  Training forwards on the GPU zero the statistics arena with one fill; with autograd recording they also pack
+        every weight with one launch: the first forward+backward records the uses, the second builds the arena.  Eval / no-grad forwards
+        keep the per-call packers and drop nothing."""
+        cuda = torch.is_tensor(x) and x.is_cuda
+        self.epoch += 1
+        self.acc = None
+        if training and cuda and HOOKS["stat_atomics"]:
+            if self.stats is None or self.stats.device != x.device or self.need > self.stats.numel():
+                self.stats = torch.zeros(max(self.need * 2, 1 << 16), dtype=torch.int64, device=x.device)
+            else:
+                self.stats.zero_()
+            self.acc = self.stats
+        self.cursor = self.need = 0
+        RUN.arena = None
+        if training and cuda and torch.is_grad_enabled():
+            dt = compute_dtype(x)
+            a = self.arena
+            if a is None or (a.dtype is not None and a.dtype != dt) or (a.built and a.stale()):  # (stale: parameter storage moved - model.to() ...)
+                a = self.arena = WeightArena()
+            elif not a.built and a.specs:
+                a.build()
+            if a.built:
+                a.pack()
+            RUN.arena = a
+        prev, RUN.model = RUN.model, self
+        try:
+            yield self
+        finally:
+            RUN.model, self.acc = prev, None
+            pending, self.counters = self.counters, []
+            if pending:
+                torch._foreach_add_(pending, 1)
 
 
 def set_weight_arena(arena):
-    global _arena
-    _arena = arena
+    """the WeightArena the packers read until the next model forward, which sets its own (ModelState.forward); None: per-call packs."""
+    RUN.arena = arena
 
 
 def pack_conv_fwd(weight, cin_pad, dtype):
-    if _arena is not None:
-        hit = _arena.lookup_fwd(weight, cin_pad, dtype)
+    arena = RUN.arena
+    if arena is not None:
+        hit = arena.lookup_fwd(weight, cin_pad, dtype)
         if hit is not None:
             return hit
-        _arena.note(weight, dtype, ipad=cin_pad)
+        arena.note(weight, dtype, ipad=cin_pad)
     weight = _as4d(weight)
     o, i, kh, kw = weight.shape
     buf = torch.empty(o * kh * kw * cin_pad, dtype=dtype, device=weight.device)
@@ -152,11 +203,12 @@ def pack_conv_fwd(weight, cin_pad, dtype):
 
 
 def pack_conv_dgrad(weight, cout_pad, stride, dtype):
-    if _arena is not None:
-        hit = _arena.lookup_dgrad(weight, cout_pad, stride, dtype)
+    arena = RUN.arena
+    if arena is not None:
+        hit = arena.lookup_dgrad(weight, cout_pad, stride, dtype)
         if hit is not None:
             return hit
-        _arena.note(weight, dtype, opad=cout_pad, stride=stride)
+        arena.note(weight, dtype, opad=cout_pad, stride=stride)
     weight = _as4d(weight)
     o, i, kh, kw = weight.shape
     buf = torch.empty(cout_pad * i * kh * kw, dtype=dtype, device=weight.device)
@@ -166,11 +218,12 @@ def pack_conv_dgrad(weight, cout_pad, stride, dtype):
 
 def pack_conv_fwd_pair(wa, wb, cin_pad, dtype):
     """forward operand of two convolutions of one input run as ONE: [oA + oB][kh][kw][cin_pad] (a view of the arena once it is built)."""
-    if _arena is not None:
-        hit = _arena.lookup_fwd(wa, cin_pad, dtype, pair=wb)
+    arena = RUN.arena
+    if arena is not None:
+        hit = arena.lookup_fwd(wa, cin_pad, dtype, pair=wb)
         if hit is not None:
             return hit
-        _arena.note(wa, dtype, ipad=cin_pad, pair=wb)
+        arena.note(wa, dtype, ipad=cin_pad, pair=wb)
     w = torch.cat([wa.detach(), wb.detach()], 0)  # (only until the arena exists - the warm-up steps - and in stand-alone use: never inside a captured graph)
     o, i, kh, kw = w.shape
     buf = torch.empty(o * kh * kw * cin_pad, dtype=dtype, device=w.device)
@@ -181,11 +234,12 @@ def pack_conv_fwd_pair(wa, wb, cin_pad, dtype):
 def pack_conv_dgrad_pair(wa, wb, stride, dtype):
     """data-gradient operand of the pair: [i][tap][oA + oB] per stride-parity class."""
     otot = wa.shape[0] + wb.shape[0]
-    if _arena is not None:
-        hit = _arena.lookup_dgrad(wa, otot, stride, dtype, pair=wb)
+    arena = RUN.arena
+    if arena is not None:
+        hit = arena.lookup_dgrad(wa, otot, stride, dtype, pair=wb)
         if hit is not None:
             return hit
-        _arena.note(wa, dtype, opad=otot, stride=stride, pair=wb)
+        arena.note(wa, dtype, opad=otot, stride=stride, pair=wb)
     w = torch.cat([wa.detach(), wb.detach()], 0)
     o, i, kh, kw = w.shape
     buf = torch.empty(o * i * kh * kw, dtype=dtype, device=w.device)
@@ -195,28 +249,25 @@ def pack_conv_dgrad_pair(wa, wb, stride, dtype):
 
 # Where weight gradients should be WRITTEN: {id(parameter): float32 tensor of the parameter's shape}.  engine.trainer's several-rank
 # schedule registers the slices of its flat all-reduce buckets here, so that a weight gradient is born inside its bucket and no pack
-# copy of the 53.6 MB of gradients is needed before the exchange (None: fresh tensors).
-_grad_arena = None
+# copy of the 53.6 MB of gradients is needed before the exchange (RUN.grad_views; None: fresh tensors).
+@contextlib.contextmanager
+def _setting(name, value):
+    """RUN.<name> = value inside the context, the previous value after it."""
+    prev = getattr(RUN, name)
+    setattr(RUN, name, value)
+    try:
+        yield
+    finally:
+        setattr(RUN, name, prev)
 
 
-class grad_arena:
-    def __init__(self, views):
-        self.views = views
-
-    def __enter__(self):
-        global _grad_arena
-        self.prev, _grad_arena = _grad_arena, self.views
-        return self
-
-    def __exit__(self, *exc):
-        global _grad_arena
-        _grad_arena = self.prev
-        return False
+def grad_arena(views):
+    return _setting("grad_views", views)
 
 
 def _new_dw(cout, cin, k, dev, params, pair_rows):
-    if _grad_arena is not None and not pair_rows and params and params[0] is not None:
-        v = _grad_arena.get(id(params[0]))
+    if RUN.grad_views is not None and not pair_rows and params and params[0] is not None:
+        v = RUN.grad_views.get(id(params[0]))
         if v is not None and v.numel() == cout * cin * k * k and v.dtype == torch.float32 and v.is_contiguous() and v.device == dev:
             return v.view(cout, cin, k, k)
     return torch.empty((cout, cin, k, k), dtype=torch.float32, device=dev)
@@ -225,7 +276,7 @@ def _new_dw(cout, cin, k, dev, params, pair_rows):
 def _wgrad(x, dy, cout, cin, k, stride, want_bias, params=(), pair_rows=None):
     """-> (dw [cout, cin, k, k] f32, dbias [cout] f32 | None).  params: the parameters these gradients belong to.
     pair_rows: params are TWO weights whose gradients are the row ranges [0, pair_rows) and [pair_rows, cout) of dw (_ConvBnActPair)."""
-    if _deferred["on"] and _in_backward() and _adoptable(params) and not _deferred_twice(params):
+    if RUN.defer and _in_backward() and _adoptable(params) and not _deferred_twice(params):
         owner = (params[0], params[1], int(pair_rows)) if pair_rows else (params[0] if params else None)
         bias_owner = params[1] if (want_bias and not pair_rows and len(params) > 1) else None
         return _wgrad_deferred(x, dy, cout, cin, k, stride, want_bias, owner, _new_dw(cout, cin, k, x.device, params, pair_rows), bias_owner)
@@ -261,51 +312,41 @@ def _adoptable(params):
 # 20x20 / 40x40 layers leave CUs idle in their tails; two independent kernel chains fill them.  Captured in a HIP graph
 # this becomes a parallel branch.  The operands are kept alive until the join so the allocator cannot hand their memory
 # to the main stream while the side stream still reads them.
-_side_streams = {}
-_async = {"on": False, "pending": False, "keep": []}
-
-
 def _side_stream(dev):
-    s = _side_streams.get(dev.index)
+    s = RUN.side_streams.get(dev.index)
     if s is None:
-        s = _side_streams[dev.index] = torch.cuda.Stream(device=dev)
+        s = RUN.side_streams[dev.index] = torch.cuda.Stream(device=dev)
     return s
 
 
-class async_wgrad:
-    def __init__(self, enabled=True):
-        self.enabled = enabled
-
-    def __enter__(self):
-        self.prev = _async["on"]
-        _async["on"] = bool(self.enabled)
-        return self
-
-    def __exit__(self, *exc):
-        join_side_stream()
-        _async["on"] = self.prev
-        return False
+@contextlib.contextmanager
+def async_wgrad(enabled=True):
+    with _setting("side", bool(enabled)):
+        try:
+            yield
+        finally:
+            join_side_stream()
 
 
 def join_side_stream():
     """make the current stream wait for the weight-gradient stream (no-op when nothing is pending)."""
-    if _async["pending"]:
+    if RUN.side_pending:
         cur = torch.cuda.current_stream()
         cur.wait_stream(_side_stream(cur.device))
-        _async["pending"] = False
-        _async["keep"].clear()
+        RUN.side_pending = False
+        RUN.side_keep.clear()
 
 
 def _wgrad_maybe_async(x, dy, cout, cin, k, stride, want_bias, params=(), pair_rows=None):
-    if not _async["on"]:
+    if not RUN.side:
         return _wgrad(x, dy, cout, cin, k, stride, want_bias, params, pair_rows)
     cur = torch.cuda.current_stream()
     side = _side_stream(x.device)
     side.wait_stream(cur)
     with torch.cuda.stream(side):
         out = _wgrad(x, dy, cout, cin, k, stride, want_bias, params, pair_rows)
-    _async["keep"].append((x, dy))
-    _async["pending"] = True
+    RUN.side_keep.append((x, dy))
+    RUN.side_pending = True
     return out
 
 
@@ -321,55 +362,64 @@ def _wgrad_maybe_async(x, dy, cout, cin, k, stride, want_bias, params=(), pair_r
 # So the deferral is OPT-IN: engine.trainer.TrainStep, which zeroes gradients with set_to_none=True after every step and
 # knows its DDP schedule, enables it around its backward.  Everywhere else (plain autograd use of the modules, gradient
 # accumulation, hooks) each weight gradient is complete when its Function returns.
-_deferred = {"on": False, "records": [], "keep": [], "owners": [], "bias": [], "task": None, "table": None}
-
-
-class deferred_wgrad:
+def deferred_wgrad(enabled=True):
     """context manager: batch the split-K slab sums of every weight gradient of the backward passes run inside it.  The
     caller guarantees the conditions above; parameters that already hold a gradient are detected by _wgrad and not deferred."""
-
-    def __init__(self, enabled=True):
-        self.enabled = bool(enabled)
-
-    def __enter__(self):
-        self.prev = _deferred["on"]
-        _deferred["on"] = self.enabled
-        return self
-
-    def __exit__(self, *exc):
-        _deferred["on"] = self.prev
-        return False
+    return _setting("defer", bool(enabled))
 
 
-class wgrad_riders:
+@contextlib.contextmanager
+def wgrad_riders(enabled=True):
     """context manager around a backward pass with deferred weight gradients on ONE stream (engine.trainer.TrainStep's captured steps): the
     library holds each deferred weight-gradient launch back until the next BatchNorm backward, whose final pass then rides in it
     (include/ymi.h: ymi_wgrad_hold).  Leaving the context issues a launch still held."""
-
-    def __init__(self, enabled=True):
-        self.enabled = bool(enabled) and HOOKS["wgrad_rider"]
-
-    def __enter__(self):
-        if self.enabled:
+    enabled = bool(enabled) and HOOKS["wgrad_rider"]
+    with _setting("riders", enabled):
+        if enabled:
             check(L().ymi_wgrad_hold(1), "wgrad_hold")
-        return self
-
-    def __exit__(self, *exc):
-        if self.enabled:
-            check(L().ymi_wgrad_hold(2 if exc[0] is not None else 0), "wgrad_hold")
-            if exc[0] is not None:
+        try:
+            yield
+        except BaseException:
+            if enabled:
+                check(L().ymi_wgrad_hold(2), "wgrad_hold")
                 L().ymi_wgrad_hold(0)
-        return False
+            raise
+        if enabled:
+            check(L().ymi_wgrad_hold(0), "wgrad_hold")
 
 
-def set_wgrad_deferred(flag):
-    """process-wide switch (tests / tools); prefer the `deferred_wgrad` context manager."""
-    _deferred["on"] = bool(flag)
+def _take_pass():
+    """-> (records, keep-alives, owners, bias) of the current pass, which RUN no longer holds."""
+    out = RUN.records, RUN.keep, RUN.owners, RUN.bias
+    RUN.records, RUN.keep, RUN.owners, RUN.bias, RUN.task = [], [], [], [], None
+    return out
+
+
+def _discard_stale_pass():
+    """records of an earlier pass whose end-of-pass callback never ran (the engine drops callbacks when a backward raises) are stale:
+    their gradient tensors are gone - discard them, and a launch the library still holds back for a rider: it belongs to that pass too."""
+    if RUN.records:
+        L().ymi_wgrad_hold(2)
+    _take_pass()
+
+
+def _defer_wgrad(rec, keep, owner, bias=None):
+    """register a deferred slab sum with the running backward pass BEFORE its launch fills `rec` (the first of a pass queues the flush).
+    keep: slabs and operands, alive until the flush has been enqueued; owner: the weight (see _flush_wgrads); bias: (bias parameter,
+    bias-gradient buffer, real width) | None."""
+    task = torch._C._current_graph_task_id()
+    if RUN.task != task:
+        _discard_stale_pass()
+        torch.autograd.Variable._execution_engine.queue_callback(_flush_wgrads)
+        RUN.task = task
+    RUN.records.append(rec)
+    RUN.keep.append(keep)
+    RUN.owners.append(owner)
+    RUN.bias.append(bias)
 
 
 def _flush_wgrads():
-    recs, keep, owners, biases = _deferred["records"], _deferred["keep"], _deferred["owners"], _deferred["bias"]
-    _deferred["records"], _deferred["keep"], _deferred["owners"], _deferred["bias"], _deferred["task"] = [], [], [], [], None
+    recs, keep, owners, biases = _take_pass()
     if not recs:
         return
     # Every node of the pass has run: a parameter's AccumulateGrad has either ADOPTED the returned tensor (p.grad is that
@@ -393,9 +443,9 @@ def _flush_wgrads():
             rec.dw = g.data_ptr()
     dev = keep[0][0].device
     n = len(recs)
-    tab = _deferred["table"]
+    tab = RUN.table
     if tab is None or tab.device != dev or tab.numel() < n * ctypes.sizeof(_lib.WgradPending):
-        tab = _deferred["table"] = torch.empty(max(n, 128) * ctypes.sizeof(_lib.WgradPending), dtype=torch.uint8, device=dev)
+        tab = RUN.table = torch.empty(max(n, 128) * ctypes.sizeof(_lib.WgradPending), dtype=torch.uint8, device=dev)
     arr = (_lib.WgradPending * n)(*recs)
     def late_bias():
         # bias gradients are summed by the batched launch too (into the buffer their Function returned a view of).  Usually AccumulateGrad
@@ -406,13 +456,13 @@ def _flush_wgrads():
                 if g is not None and g.data_ptr() != b[1].data_ptr():
                     g.copy_(b[1][: b[2]])
 
-    if _async["on"]:  # the GEMMs ran on the side stream: the sum follows them there (joined by async_wgrad's exit)
+    if RUN.side:  # the GEMMs ran on the side stream: the sum follows them there (joined by async_wgrad's exit)
         # (slabs produced on the CURRENT stream - the first layer's fused backward - must be complete too)
         _side_stream(dev).wait_stream(torch.cuda.current_stream())
         with torch.cuda.stream(_side_stream(dev)):
             check(L().ymi_wgrad_reduce_batch(arr, n, ptr(tab), stream_ptr()), "wgrad_reduce_batch")
             late_bias()
-        _async["pending"] = True
+        RUN.side_pending = True
     else:
         check(L().ymi_wgrad_reduce_batch(arr, n, ptr(tab), stream_ptr()), "wgrad_reduce_batch")
         late_bias()
@@ -420,17 +470,8 @@ def _flush_wgrads():
 
 
 def _wgrad_deferred(x, dy, cout, cin, k, stride, want_bias, owner=None, dw=None, bias_owner=None):
-    """as _wgrad, with the slab sum left to the end of the backward pass.  Slabs and operands stay alive in _deferred['keep']
-    until the flush has been enqueued; the gradient tensor itself is owned by autograd (see _flush_wgrads).  owner: the weight."""
-    task = torch._C._current_graph_task_id()
-    if _deferred["task"] != task:
-        # first deferred gradient of this pass.  Records of an earlier pass whose end-of-pass callback never ran (the engine
-        # drops callbacks when a backward raises) are stale: their gradient tensors are gone - discard them.
-        if _deferred["records"]:
-            L().ymi_wgrad_hold(2)  # (a launch the library still holds back for a rider belongs to that pass too: its operands are gone)
-        _deferred["records"], _deferred["keep"], _deferred["owners"], _deferred["bias"] = [], [], [], []
-        torch.autograd.Variable._execution_engine.queue_callback(_flush_wgrads)
-        _deferred["task"] = task
+    """as _wgrad, with the slab sum left to the end of the backward pass.  The gradient tensor itself is owned by autograd (see
+    _flush_wgrads).  owner: the weight."""
     dev = x.device
     if dw is None:
         dw = torch.empty((cout, cin, k, k), dtype=torch.float32, device=dev)
@@ -439,13 +480,10 @@ def _wgrad_deferred(x, dy, cout, cin, k, stride, want_bias, owner=None, dw=None,
     need = L().ymi_conv2d_bwd_weight_workspace(ty.n * ty.h * ty.w, ty.c, tx.c, k, k)
     ws = torch.empty(int(need), dtype=torch.uint8, device=dev)
     rec = _lib.WgradPending()
-    check(L().ymi_conv2d_bwd_weight_deferred(_byref(tx), _byref(ty), cout, cin, k, k, stride, ptr(dw), ptr(db), ptr(ws), ws.numel(), _byref(rec), stream_ptr()),
-          "conv2d_bwd_weight")
-    _deferred["records"].append(rec)
     # (db, the BASE of the returned bias-gradient view, stays referenced until the flush: the batched sum also writes the bias gradient
     # - its per-split partials come out of the GEMM - so that memory must not return to the allocator first; holding the base does not
     # keep AccumulateGrad from adopting the view)
-    _deferred["keep"].append((ws, x, dy, db))
-    _deferred["owners"].append(owner)
-    _deferred["bias"].append((bias_owner, db, cout) if want_bias else None)
+    _defer_wgrad(rec, (ws, x, dy, db), owner, (bias_owner, db, cout) if want_bias else None)
+    check(L().ymi_conv2d_bwd_weight_deferred(_byref(tx), _byref(ty), cout, cin, k, k, stride, ptr(dw), ptr(db), ptr(ws), ws.numel(), _byref(rec), stream_ptr()),
+          "conv2d_bwd_weight")
     return dw, (db[:cout] if want_bias else None)

@@ -114,7 +114,7 @@ def test_arena_pair_operands_equal_the_per_call_packers():
             arena.note(wa, dt, opad=88, stride=stride, pair=wb)
             arena.build()
             arena.pack()
-            ops.set_weight_arena(None)
+            ops.RUN.arena = None
             f_ref = ops.pack_conv_fwd(torch.cat([wa, wb], 0).detach(), 40, dt)
             d_ref = ops.pack_conv_dgrad(torch.cat([wa, wb], 0).detach(), 88, stride, dt)
             torch.cuda.synchronize()

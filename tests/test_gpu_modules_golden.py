@@ -406,7 +406,7 @@ def test_weight_arena_pack_equals_per_call_pack():
              (130, 70, 1, 1, 72, 136), (256, 128, 3, 2, 128, 256), (1, 64, 1, 1, 64, 8)]
     for dt in (torch.bfloat16, torch.float32):
         arena = ops.WeightArena()
-        ops.set_weight_arena(arena)
+        ops.RUN.arena = arena
         try:
             ws, ref = [], []
             for o, i, k, s, ipad, opad in cases:
@@ -422,4 +422,4 @@ def test_weight_arena_pack_equals_per_call_pack():
                 assert torch.equal(f, rf), ("fwd", o, i, k, s)
                 assert torch.equal(d, rd), ("dgrad", o, i, k, s)
         finally:
-            ops.set_weight_arena(None)
+            ops.RUN.arena = None

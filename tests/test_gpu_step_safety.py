@@ -71,7 +71,7 @@ def test_gradient_accumulation_is_exact_with_batched_slab_sums_enabled():
     assert all(rel(g0[n], g1[n]) <= 1e-5 for n in g1)
 
 
-def test_backward_that_raises_does_not_poison_the_next_pass():
+def test_backward_that_raises_leaves_no_stale_deferred_pass():
     """the autograd engine drops end-of-pass callbacks when a backward raises: the records of that pass must not leak into
     the next one, and the next pass must queue its own flush (else every weight gradient stays uninitialised memory)."""
     from improving_yolov8_cbam_swinblock_amd import ops
@@ -94,12 +94,12 @@ def test_backward_that_raises_does_not_poison_the_next_pass():
         with pytest.raises(Boom):
             _backward(model, batch)
         h.remove()
-        assert ops._deferred["records"], "the failed pass should have left deferred records behind (else this test checks nothing)"
+        assert ops.RUN.records, "the failed pass should have left deferred records behind (else this test checks nothing)"
         model.zero_grad(set_to_none=True)
         model.load_state_dict(stats, strict=False)
         _backward(model, batch)
         got = _grads(model)
-    assert not ops._deferred["records"] and ops._deferred["task"] is None
+    assert not ops.RUN.records and ops.RUN.task is None
     assert set(got) == set(ref)
     bad = [(n, rel(got[n], ref[n])) for n in ref if not rel(got[n], ref[n]) <= 1e-5]   # (uninitialised memory would be O(1) or NaN)
     assert not bad, bad[:5]
@@ -144,6 +144,43 @@ def test_ema_update_count_set_after_the_tables_exist_reaches_the_device():
     e1, p1 = gs.ema.ema.state_dict()[key], model2.state_dict()[key]
     want = d * e0 + (1 - d) * p1
     assert float((e1 - want).abs().max()) <= 1e-6 * max(1.0, float(want.abs().max()))
+
+
+def test_graph_step_buffers_outlive_eval_forward_and_other_model():
+    """the captured step zeroes and adds into the model's BatchNorm statistics arena, packs into its weight arena and
+    stages the batched slab sum in the device table.  Validation through the EMA model (an eval forward) and a training forward of a
+    wider model between replays must not return that memory to the allocator: tensors of the same sizes allocated afterwards keep their
+    contents over further replays, and the steps equal an uninterrupted run."""
+    from improving_yolov8_cbam_swinblock_amd import ops
+    from improving_yolov8_cbam_swinblock_amd.nn.tasks import DetectionModel
+    from improving_yolov8_cbam_swinblock_amd.engine.trainer import TrainStep
+
+    runs = []
+    for interrupt in (False, True):
+        model, batch = _small_model()
+        step = TrainStep(model, world_size=1, lr=0.01, graph=True)
+        items = [step(batch).detach().clone() for _ in range(2)]  # (3 eager warm-up steps, the capture, 2 replays)
+        junk = []
+        if interrupt:
+            st = model._state
+            sizes = [st.stats.numel() * st.stats.element_size(), st.arena.arena.numel() * st.arena.arena.element_size(), ops.RUN.table.numel()]
+            with torch.no_grad():
+                step.ema.ema(batch["img"])
+            torch.manual_seed(1)
+            wide = DetectionModel("yolov8s-cbam.yaml", ch=3, nc=1).to(dev()).train()
+            with torch.autocast("cuda", dtype=torch.bfloat16):
+                wide(batch)
+            del wide
+            junk = [torch.full((n,), 0xA5, dtype=torch.uint8, device=dev()) for n in sizes for _ in range(3)]
+        items += [step(batch).detach().clone() for _ in range(3)]
+        torch.cuda.synchronize()
+        assert all(bool((j == 0xA5).all()) for j in junk), "a replay wrote into memory handed to other tensors"
+        runs.append((torch.stack(items).cpu(), {n: p.detach().clone() for n, p in model.named_parameters()}))
+        del step, model, junk
+    (i0, w0), (i1, w1) = runs
+    assert rel(i1, i0) <= 1e-5, (i1, i0)
+    bad = [(n, rel(w1[n], w0[n])) for n in w0 if not rel(w1[n], w0[n]) <= 1e-5]
+    assert not bad, bad[:5]
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16], ids=["f32", "bf16"])
