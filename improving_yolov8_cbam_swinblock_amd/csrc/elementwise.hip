@@ -500,9 +500,7 @@ struct BnFin {
     double inv_scale;  // 2^-shift of the fixed-point sums (common.h: ymi_stat_fixed_point_shift)
     float momentum, eps;
 };
-#ifndef YMI_EW_U  // pixels a thread of the affine pass keeps in flight per trip
-#define YMI_EW_U 4
-#endif
+constexpr int EW_U = 4;  // pixels a thread of the affine pass keeps in flight per trip (2 and 8: slower, profiles/r05_ew_grid_sweep.txt)
 template <typename T, int ACT, bool FIN = false>
 __global__ __launch_bounds__(256) void scale_shift_act_fixed_kernel(TV x, const float* __restrict__ scale, const float* __restrict__ shift,
                                                                     TV res, TV o, int groups, int64_t Pall, int64_t span, BnFin fin = BnFin{}) {
@@ -575,7 +573,7 @@ __global__ __launch_bounds__(256) void scale_shift_act_fixed_kernel(TV x, const 
     // 4 pixels per trip: the loads of all four are in flight before the first use, and the NEXT trip's (raw) loads are issued before this
     // trip's arithmetic (as in the BatchNorm backward passes, csrc/reduce_bwd.hip)
     typedef typename Raw4<T>::type R4;
-    constexpr int U = YMI_EW_U;  // pixels per trip
+    constexpr int U = EW_U;  // pixels per trip
     R4 rv[U], rres[U];
     bool have = p + (U - 1) * step < P;
     if (have) {

@@ -33,10 +33,7 @@ constexpr int FC_TH = 8, FC_TW = 64;                   // output tile: two rows 
 constexpr int FC_PR = 2 * FC_TH + 1;                   // patch rows
 constexpr int FC_ROWB = (2 * FC_TW + 2) * 8;           // bytes per patch row: 8 bytes per pixel; col 0 unused, col 1 = left halo, cols 2.. = the tile's 2 TW columns
                                                        // (so that the aligned groups of the interior start on 16-byte boundaries)
-#ifndef YMI_FC_WG_TILES
-#define YMI_FC_WG_TILES 4
-#endif
-constexpr int FC_WG_TILES = YMI_FC_WG_TILES;           // tiles per workgroup of the weight-gradient kernel (one slab per workgroup)
+constexpr int FC_WG_TILES = 4;                         // tiles per workgroup of the weight-gradient kernel, one slab each (2 and 8: slower, profiles/r04_first_conv_ab.txt)
 
 enum { FC_STATS = 0, FC_APPLY = 1, FC_BWD_REDUCE = 2, FC_BWD_WGRAD = 3 };
 

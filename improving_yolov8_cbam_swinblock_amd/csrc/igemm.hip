@@ -33,42 +33,6 @@
 
 #include "common.h"
 
-#ifdef YMI_STAMPS
-// diagnostic build only: per-wave s_memtime stamps of one workgroup's K steps 2..9 (phases marked in the loops below), kept
-// in a spare 4 KB of LDS during the loop and copied out at the end.  extern "C" ymi_debug_stamp_buffer sets the target.
-__device__ unsigned long long* g_stamp_buf = nullptr;
-extern "C" int ymi_debug_stamp_buffer(void* p) {
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_stamp_buf), &p, sizeof(p)) == hipSuccess ? 0 : -1;
-}
-#define YMI_STAMP_DECL                                                                                     \
-    const bool stamp_on = g_stamp_buf && blockIdx.x == gridDim.x / 2 && lane == 0;                         \
-    unsigned long long* stamp_lds = reinterpret_cast<unsigned long long*>(smem + stamp_off) + wave_all * 64; \
-    int stamp_i = 0;                                                                                        \
-    const unsigned long long stamp_mt0 = stamp_on ? __builtin_amdgcn_s_memtime() : 0ull, stamp_rt0 = stamp_on ? __builtin_amdgcn_s_memrealtime() : 0ull;
-#define YMI_STAMP(kt)                                                                   \
-    do {                                                                                \
-        if (stamp_on && (kt) >= 2 && (kt) < 10 && stamp_i < 64) stamp_lds[stamp_i++] = __builtin_amdgcn_s_memtime(); \
-    } while (0)
-#define YMI_STAMP_DUMP                                                                  \
-    do {                                                                                \
-        if (stamp_on) {                                                                 \
-            for (int q = 0; q < 64; ++q) g_stamp_buf[wave_all * 64 + q] = q < stamp_i ? stamp_lds[q] : 0ull; \
-            /* clock calibration: shader cycles and 100 MHz ticks over the whole K loop */ \
-            g_stamp_buf[8 * 64 + wave_all * 2 + 0] = __builtin_amdgcn_s_memtime() - stamp_mt0; \
-            g_stamp_buf[8 * 64 + wave_all * 2 + 1] = __builtin_amdgcn_s_memrealtime() - stamp_rt0; \
-        }                                                                               \
-    } while (0)
-#define YMI_STAMP_MARK(i)                                                               \
-    do {                                                                                \
-        if (stamp_on) g_stamp_buf[8 * 64 + 16 + wave_all * 8 + (i)] = __builtin_amdgcn_s_memtime() - stamp_mt0; \
-    } while (0)
-#else
-#define YMI_STAMP_MARK(i) do { } while (0)
-#define YMI_STAMP_DECL
-#define YMI_STAMP(kt) do { } while (0)
-#define YMI_STAMP_DUMP do { } while (0)
-#endif
-
 struct IgemmArgs {
     const void* x;
     const void* w;
@@ -129,9 +93,6 @@ template <int I, int N, class F> __device__ __forceinline__ void static_for(F&& 
     }
 }
 
-#ifndef YMI_IGEMM_ABL  // diagnostic builds (results wrong by design): bit 1 no LDS-DMA pieces inside the K loop, 2 no MFMAs, 4 no fragment reads,
-#define YMI_IGEMM_ABL 0  // 8 no global stores in the epilogue, 16 no epilogue at all, 32 A pieces of one tap in three only
-#endif
 template <typename T> struct Mma;
 template <> struct Mma<bf16_t> {
     // one K step = CPR 16-byte chunks per row = CPR/4 16x16x32 MFMAs per tile pair.
@@ -155,13 +116,6 @@ template <> struct Mma<bf16_t> {
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
             const uint32_t coff = (uint32_t)(((4 * ks + l4) ^ sw) << 4);
-            if (YMI_IGEMM_ABL & 4) {
-#pragma unroll
-                for (int tn = 0; tn < TN; ++tn) wf[ks][tn] = bf16x8{};
-#pragma unroll
-                for (int tm = 0; tm < TM; ++tm) xf[ks][tm] = bf16x8{};
-                continue;
-            }
 #pragma unroll
             for (int tn = 0; tn < TN; ++tn)
                 asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(wf[ks][tn]) : "v"(bbase + coff), "n"(tn * 16 * ROWB));
@@ -184,7 +138,7 @@ template <> struct Mma<bf16_t> {
             for (int tn = 0; tn < TN; ++tn)
 #pragma unroll
                 for (int tm = 0; tm < TM; ++tm)
-                    if (!(YMI_IGEMM_ABL & 2)) acc[tn][tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ks][tn], xf[ks][tm], acc[tn][tm], 0, 0, 0);
+                    acc[tn][tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ks][tn], xf[ks][tm], acc[tn][tm], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
         }
     }
@@ -270,11 +224,7 @@ __device__ __forceinline__ float row16_sum(float v) {
 // per-block BatchNorm partial sums; otherwise scale / bias / activation / up to two addends.
 template <typename T, int BM, int BN, int WM, int WN, bool STATS, int NT>
 __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& a, f32x4 (&acc)[BN / WN / 16][BM / WM / 16], char* smem, int m0, int n0, int mb, int wm,
-                                               int wn, int lane, int tid_all
-#ifdef YMI_STAMPS
-                                               , bool stamp_on = false, int wave_all = 0, unsigned long long stamp_mt0 = 0
-#endif
-                                               ) {
+                                               int wn, int lane, int tid_all) {
     constexpr int TM = BM / WM / 16, TN = BN / WN / 16;
     const int l15 = lane & 15, l4 = lane >> 4;
     T* yg = reinterpret_cast<T*>(a.y);
@@ -302,12 +252,10 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& a, f32x4 (&acc)[
     // workgroup's life on an 18-step layer and 30-45 % on 1x1 layers (instruction fetch, not arithmetic).  So the per-tile code
     // only scales, adds the aligned addends and drops the tile into LDS; activation, unaligned addends and unaligned stores
     // work on the LDS image in run-time loops below.
-#ifndef YMI_EPI_PRIO
-#define YMI_EPI_PRIO 2
-#endif
     // the co-resident workgroup is in its K loop: its MFMAs hold the SIMD's vector issue half of the time and, being older, win
     // the arbitration - raise this wave's priority for its ~500 VALU instructions so that LDS and the wave slots are freed sooner
-    if (YMI_EPI_PRIO) __builtin_amdgcn_s_setprio(YMI_EPI_PRIO);
+    constexpr int EPI_PRIO = 2;  // (0 and 3: no better in the step, profiles/r04_tile_threshold_sweep.txt)
+    __builtin_amdgcn_s_setprio(EPI_PRIO);
     const int act = STATS ? (int)YMI_ACT_NONE : a.act;
     const bool res1 = !STATS && rg && a.vec_store && (a.Cout & 3) == 0 && act == YMI_ACT_NONE;  // addends joined per tile (f32, before the one rounding)
     const bool res2nd = !STATS && rg && !res1;                              // ... or after the activation, from the LDS image
@@ -392,9 +340,7 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& a, f32x4 (&acc)[
         }
     }
     }
-    YMI_STAMP_MARK(3);  // accumulators converted and dropped into the LDS image
     __syncthreads();
-    YMI_STAMP_MARK(4);  // past the barrier
     if constexpr (STATS) {
         if (tid_all < 2 * BN) {
             const int which = tid_all / BN, chl = tid_all % BN;
@@ -431,8 +377,7 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& a, f32x4 (&acc)[
                 const int m = m0 + row, ch = n0 + cc * EPC;
                 if (m < a.M && ch < a.Cout) {
                     const u32x4 val = *reinterpret_cast<const u32x4*>(Cimg + row * CROW + cc * 16);
-                    if (YMI_IGEMM_ABL & 8) asm volatile("" :: "v"(val));
-                    else *reinterpret_cast<u32x4*>(yg + out_offset(m) + ch) = val;
+                    *reinterpret_cast<u32x4*>(yg + out_offset(m) + ch) = val;
                 }
             }
         } else {  // fused inference convolutions (SiLU, then the shortcut), element-aligned addends, activation-gradient multiplier
@@ -516,7 +461,6 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& a, f32x4 (&acc)[
             }
         }
     }
-    YMI_STAMP_MARK(5);  // stores issued
 }
 
 // The kernel has two forms.
@@ -553,16 +497,12 @@ __global__ __launch_bounds__(NTHR) void igemm_kernel(IgemmMulti P) {
     static_assert(WM * WN == NTHR / 64, "one wave tile per wave");
     static_assert((BM * CPR) % LT == 0, "every loading wave issues all A loads");
     extern __shared__ __attribute__((aligned(16))) char smem[];
-#ifdef YMI_STAMPS
-    constexpr int stamp_off = NS * STAGE;  // the launcher adds 4 KB behind the ring in this build
-#endif
 
     constexpr int NT = NTHR;
     const int tid_all = threadIdx.x, lane = tid_all & 63;
     const int wave_all = __builtin_amdgcn_readfirstlane(tid_all >> 6);  // provably wave-uniform: LDS-DMA bases go to M0 without a waterfall loop
     const int tid = tid_all, wave = wave_all;
     const int wm = wave / WN, wn = wave % WN;
-    YMI_STAMP_DECL
     // XCD-aware order: workgroups are dealt round-robin to the 8 XCDs (id & 7), each with its own L2.  Every XCD gets a
     // CONTIGUOUS range of M blocks (neighbouring pixel tiles share 3x3 halo rows) and walks the N blocks of one M block
     // back to back, so the A tile an M block gathers is fetched into that XCD's L2 once and reused by all its N blocks
@@ -742,7 +682,6 @@ __global__ __launch_bounds__(NTHR) void igemm_kernel(IgemmMulti P) {
         }
     };
 
-    YMI_STAMP_MARK(0);  // prologue (address set-up) done
     f32x4 acc[TN][TM];
 #pragma unroll
     for (int tn = 0; tn < TN; ++tn)
@@ -758,16 +697,6 @@ __global__ __launch_bounds__(NTHR) void igemm_kernel(IgemmMulti P) {
         static_assert(NTHR == 512 && NS == 3 && FAST && std::is_same<T, bf16_t>::value && WM == 4, "ping-pong form: 512 threads, 3 stages, bf16");
         const int half = wave_all >> 2;  // 0: rows 0..BM/2-1 (starts first), 1: the other rows, half a step behind
         bf16x8 wf[CPR / 4][TN], xf[CPR / 4][TM];
-#ifdef YMI_PP_STAGGER  // diagnostic: the workgroup in the upper wave slots of its SIMDs starts YMI_PP_STAGGER * 64 cycles late
-        if (__builtin_amdgcn_s_getreg(4 | (3 << 11)) & 2) {
-#ifdef YMI_PP_STAGGER_REP  // ... times 8,128 cycles: offsets of a fraction of a workgroup's lifetime (epilogue against K loop)
-#pragma unroll 1
-            for (int q = 0; q < YMI_PP_STAGGER_REP; ++q) __builtin_amdgcn_s_sleep(127);
-#else
-            __builtin_amdgcn_s_sleep(YMI_PP_STAGGER);
-#endif
-        }
-#endif
         issue(0);
         if (nkt > 1) issue(1);
         // step 0 (and only it) has landed when the pieces of step 1 may still be outstanding
@@ -786,26 +715,12 @@ __global__ __launch_bounds__(NTHR) void igemm_kernel(IgemmMulti P) {
         // The pieces of step k+2 are split between the two phases of step k (stamps, profiles/r02_igemm_phase_stamps.txt: with all
         // six in the memory phase it lasted ~1000 cycles against ~500 of MFMAs): the A rows go out in the memory phase, the
         // weight rows between the MFMAs, and the pointer / tap bookkeeping follows the last MFMA, outside the memory phase.
-#ifndef YMI_PP_ALLMEM
-#define YMI_PP_ALLMEM 0
-#endif
-#ifndef YMI_PP_ADV_MEM
-#define YMI_PP_ADV_MEM 0
-#endif
-#ifndef YMI_PP_PRIO
-#define YMI_PP_PRIO 0
-#endif
-        constexpr int NMEM = YMI_PP_ALLMEM ? NA + NB : NA;  // pieces issued in the memory phase (pieces are numbered A rows first)
         constexpr int NPC = NA + NB;       // pieces per wave and step
         constexpr int NM = (CPR / 4) * TN * TM;
         auto load_piece = [&](int s, auto pc) {  // piece p of the step whose stage is s, WITHOUT advancing the pointers
             constexpr int p = decltype(pc)::value;
             char* Ad = smem + s * STAGE;
             char* Bd = Ad + BM * ROWB;
-            if (YMI_IGEMM_ABL & 1) return;
-            if constexpr (p < NA) {
-                if ((YMI_IGEMM_ABL & 32) && (tap_s % 3) != 1) return;  // emulates an input tile shared by the three taps of a kernel row (upper bound)
-            }
             if constexpr (p < NA) __builtin_amdgcn_global_load_lds((gptr_t)a_ptr[p], (lptr_t)(Ad + (p * LT + wave * 64) * 16), 16, 0, 0);
             else __builtin_amdgcn_global_load_lds((gptr_t)b_ptr[p - NA], (lptr_t)(Bd + ((p - NA) * LT + wave * 64) * 16), 16, 0, 0);
         };
@@ -824,27 +739,18 @@ __global__ __launch_bounds__(NTHR) void igemm_kernel(IgemmMulti P) {
             const bool more = kt + 2 < nkt;
             const int sn = (kt + 2) % NS;
             // ---- memory phase of step kt
-            YMI_STAMP(kt);  // 0: phase start
             const char* As = smem + (kt % NS) * STAGE;
-            if (!(YMI_IGEMM_ABL & 4) || kt == 0) Mma<T>::template read_frags<TM, TN, CPR>(As, As + BM * ROWB, wm * TM * 16, wn * TN * 16, lane, wf, xf);
-#if YMI_PP_ADV_MEM
-            if (kt > 0 && kt + 1 < nkt) advance();  // the bookkeeping of step kt-1's pieces, behind the reads instead of behind the MFMAs
-#endif
-            if (more) static_for<0, NMEM>([&](auto pc) { load_piece(sn, pc); });
+            Mma<T>::template read_frags<TM, TN, CPR>(As, As + BM * ROWB, wm * TM * 16, wn * TN * 16, lane, wf, xf);
+            if (more) static_for<0, NA>([&](auto pc) { load_piece(sn, pc); });  // the A pieces (pieces are numbered A rows first)
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            YMI_STAMP(kt);  // 1: fragments in registers, A pieces issued
             if (half == 1) {
-                if (more) wait_vmcnt_barrier<NMEM>();  // everything older than this phase's pieces: all of step kt+1
+                if (more) wait_vmcnt_barrier<NA>();  // everything older than this phase's pieces: all of step kt+1
                 else wait_vmcnt_barrier<0>();
             } else {
                 asm volatile("s_barrier" ::: "memory");
             }
             // ---- compute phase of step kt
-            YMI_STAMP(kt);  // 2: past the barrier that ends the memory phase
             __builtin_amdgcn_sched_barrier(0);
-#if YMI_PP_PRIO
-            __builtin_amdgcn_s_setprio(1);
-#endif
             static_for<0, CPR / 4>([&](auto ksc) {
                 constexpr int ks = decltype(ksc)::value;
 #pragma unroll
@@ -856,10 +762,10 @@ __global__ __launch_bounds__(NTHR) void igemm_kernel(IgemmMulti P) {
                     static_for<0, TM>([&](auto tmc) {
                         constexpr int tm = decltype(tmc)::value;
                         constexpr int q = (ks * TN + tn) * TM + tm;
-                        if (!(YMI_IGEMM_ABL & 2)) acc[tn][tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ks][tn], xf[ks][tm], acc[tn][tm], 0, 0, 0);
-                        static_for<NMEM, NPC>([&](auto pc) {  // weight piece j after MFMA 4 + 6 j
+                        acc[tn][tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ks][tn], xf[ks][tm], acc[tn][tm], 0, 0, 0);
+                        static_for<NA, NPC>([&](auto pc) {  // weight piece j after MFMA 4 + 6 j
                             constexpr int pp = decltype(pc)::value;
-                            if constexpr (q == 4 + 6 * (pp - NMEM) && q < NM) {
+                            if constexpr (q == 4 + 6 * (pp - NA) && q < NM) {
                                 __builtin_amdgcn_sched_barrier(0);
                                 if (more) load_piece(sn, pc);
                                 __builtin_amdgcn_sched_barrier(0);
@@ -869,13 +775,7 @@ __global__ __launch_bounds__(NTHR) void igemm_kernel(IgemmMulti P) {
                 });
             });
             __builtin_amdgcn_sched_barrier(0);
-#if YMI_PP_PRIO
-            __builtin_amdgcn_s_setprio(0);
-#endif
-#if !YMI_PP_ADV_MEM
             if (more) advance();
-#endif
-            YMI_STAMP(kt);  // 3: MFMAs issued, pointers advanced
             if (half == 0) {
                 if (more) wait_vmcnt_barrier<NPC>();  // everything older than step kt+2's pieces
                 else wait_vmcnt_barrier<0>();
@@ -890,7 +790,6 @@ __global__ __launch_bounds__(NTHR) void igemm_kernel(IgemmMulti P) {
         for (int s = 0; s < NS - 1; ++s)
             if (s < nkt) issue(s);
         for (int kt = 0; kt < nkt; ++kt) {
-            YMI_STAMP(kt);  // 0: step start
             // K step kt has landed when at most the loads of the NS-2 younger steps are outstanding
             if (kt + NS - 2 < nkt) {
                 if (b_wave) wait_vmcnt_barrier<LPT_FULL * (NS - 2)>();
@@ -898,36 +797,20 @@ __global__ __launch_bounds__(NTHR) void igemm_kernel(IgemmMulti P) {
             } else {
                 wait_vmcnt_barrier<0>();  // pipeline tail: fewer steps in flight than the count assumes
             }
-            YMI_STAMP(kt);  // 1: past the wait + barrier
             // every wave has passed the barrier => nobody still reads the buffer of step kt-1: refill it
-            if (kt + NS - 1 < nkt && !(YMI_IGEMM_ABL & 1)) issue((kt + NS - 1) % NS);
-            YMI_STAMP(kt);  // 2: pieces issued
+            if (kt + NS - 1 < nkt) issue((kt + NS - 1) % NS);
             const char* As = smem + (kt % NS) * STAGE;
             Mma<T>::template step<TM, TN, CPR>(As, As + BM * ROWB, wm * TM * 16, wn * TN * 16, lane, acc);
-            YMI_STAMP(kt);  // 3: fragments read, MFMAs issued
         }
     }
     asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");  // epilogue reuses LDS
-    YMI_STAMP_DUMP;
-    YMI_STAMP_MARK(1);  // K loop done
 
     // ---- epilogue -----------------------------------------------------------------------------
     // The tile leaves through LDS: lanes drop their 4-channel groups into a [pixel][channel] image, then the
     // workgroup stores it as 16-byte chunks along C, so every store instruction writes whole 128-byte lines
     // (per-lane 8-byte stores to 16 different rows cost 2-3x the time of the same bytes stored this way).
-#ifdef YMI_STAMPS
-    igemm_epilogue<T, BM, BN, WM, WN, STATS, NT>(a, acc, smem, m0, n0, mb, wm, wn, lane, tid_all, stamp_on, wave_all, stamp_mt0);
-#else
-    if (YMI_IGEMM_ABL & 16) {
-#pragma unroll
-        for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-            for (int tm = 0; tm < TM; ++tm) asm volatile("" :: "v"(acc[tn][tm]));
-    } else
     igemm_epilogue<T, BM, BN, WM, WN, STATS, NT>(a, acc, smem, m0, n0, mb, wm, wn, lane, tid_all);
-#endif
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    YMI_STAMP_MARK(2);  // epilogue done, stores retired
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1017,14 +900,8 @@ static int launch_igemm_t(const IgemmArgs* arr, int ncls, TileChoice t, hipStrea
     const size_t epi = (size_t)t.bm * (t.bn * sizeof(T) + 16) + (STATS ? 4 * 2 * t.bn * sizeof(float) : 0);
     if (epi > lds) lds = epi;
     unsigned nthreads = 256;
-#ifdef YMI_STAMPS
-#define YMI_STAMP_LDS 4096
-#else
-#define YMI_STAMP_LDS 0
-#endif
 #define YMI_LAUNCH1(KERNEL)                                                                                          \
     do {                                                                                                             \
-        lds += YMI_STAMP_LDS;                                                                                        \
         if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
         hipLaunchKernelGGL(KERNEL, grid, dim3(nthreads), lds, stream, P);                                             \
     } while (0)

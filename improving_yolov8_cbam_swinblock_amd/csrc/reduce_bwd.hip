@@ -61,12 +61,8 @@ struct ReduceTail {
     float* out1;
     BnCoefArgs bn;
 };
-#ifndef YMI_RED_U  // pixels a thread of the reduce pass keeps in flight per trip
-#define YMI_RED_U 4
-#endif
-#ifndef YMI_APPLY_U
-#define YMI_APPLY_U 4
-#endif
+constexpr int RED_U = 4;    // pixels a thread of the reduce pass keeps in flight per trip (2, 6 and 8: slower, profiles/r05_ew_grid_sweep.txt)
+constexpr int APPLY_U = 4;  // ... and of the apply pass (2 and 8: slower, same record)
 template <typename T, int FN, int ACT>
 __global__ void chan_reduce_kernel(RV a, RV b, int64_t P, int64_t span, int C, int TG, const float* __restrict__ gamma, const float* __restrict__ beta,
                                    const float* __restrict__ mean, const float* __restrict__ inv, float* __restrict__ part, GammaBeta2 g2, ReduceTail tail) {
@@ -124,7 +120,7 @@ __global__ void chan_reduce_kernel(RV a, RV b, int64_t P, int64_t span, int C, i
         // (raw, unconverted: 2 VGPRs each in bf16) before this trip's arithmetic, so a workgroup with several trips does not pay one
         // full memory round trip per trip (4 waves per SIMD are not enough to hide it: the arithmetic of a trip is as long as its loads)
         typedef typename Raw4<T>::type R4;
-        constexpr int U = YMI_RED_U;  // pixels per trip
+        constexpr int U = RED_U;  // pixels per trip
         R4 ra[U], rb[U];
         bool have = p + (U - 1) * (int64_t)rows < p1;
         if (have) {
@@ -447,7 +443,7 @@ __global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(RV dout, RV raw, 
             }
             Pack<T, G>::store(op + p * draw.ld + g * G, o);
         };
-        constexpr int U = G == 8 ? 2 : YMI_APPLY_U;  // pixels per trip: 2*U independent loads in flight per lane
+        constexpr int U = G == 8 ? 2 : APPLY_U;  // pixels per trip: 2*U independent loads in flight per lane
         // the pixels of this workgroup's XCD (common.h, XCD ownership of the pixel axis; the grid is a multiple of 8)
         const XcdRange xr = xcd_range(Pall, span);
         P = xr.hi;

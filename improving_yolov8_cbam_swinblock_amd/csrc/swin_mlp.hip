@@ -115,11 +115,6 @@ __device__ __forceinline__ float bf16_hi(uint32_t v) { return __builtin_bit_cast
 // same six-term form with the halving folded into the coefficients and the argument scalings into the constants): 11 issue slots + two
 // transcendentals per element - the vector phases of these kernels are bound by exactly this count.
 __device__ __forceinline__ float gelu_fast(float x, float* half_erfc = nullptr, float* e_out = nullptr) {
-#if (YMI_MLP_ABL & 1)
-    if (half_erfc) *half_erfc = 0.25f;
-    if (e_out) *e_out = 0.5f;
-    return x;
-#endif
     const float ax = fabsf(x);                                                                // (a source modifier, no instruction)
     const float t = __builtin_amdgcn_rcpf(fmaf(0.3275911f * 0.70710678118654752440f, ax, 1.0f));
     const float s = ax * 0.84932180028801904272f;                                              // sqrt(0.5 log2 e) |x|
@@ -139,9 +134,6 @@ __device__ __forceinline__ float gelu_fast(float x, float* half_erfc = nullptr, 
 
 // issue the LDS-DMA pieces of hidden chunk jc into ring stage `stage` (4 per thread): two 16 KB fragment-major images, copied linearly
 __device__ __forceinline__ void mlp_issue(const bf16_t* rows_img, const bf16_t* cols_img, int jc, char* stage, int tid, int wave) {
-#if (YMI_MLP_ABL & 8)
-    return;
-#endif
     const bf16_t* a = rows_img + (size_t)jc * 32 * MLP_C + tid * 8;
     const bf16_t* b = cols_img + (size_t)jc * 32 * MLP_C + tid * 8;
 #pragma unroll
@@ -154,21 +146,7 @@ __device__ __forceinline__ void mlp_issue(const bf16_t* rows_img, const bf16_t* 
 // lgkmcnt(0) and - at 250 live registers - recycles ONE fragment buffer: an exposed LDS round trip (~130 cycles) per 32-cycle MFMA.  So the
 // reads and their counted waits are written out (as igemm.hip's K step): four fragment buffers rotate, three reads stay in flight behind
 // every MFMA.  (Other LDS operations the compiler interleaves only make a counted wait stricter: LDS operations return in order.)
-// diagnostic builds (-DYMI_MLP_ABL=mask, results wrong by design; tools/probes/r5_mlp_ablate.sh): bit 1 no GELU arithmetic, 2 no MFMAs, 4 no fragment
-// reads, 8 no weight copies, 16 no pre-activation stores, 32 in-kernel phase stamps, 64 no s_setprio around the matrix phase
-#ifndef YMI_MLP_ABL
-#define YMI_MLP_ABL 0
-#endif
-#if (YMI_MLP_ABL & 4)
-#define MLP_RD(F, ADDR, OFF) asm volatile("" : "+v"(F) : "v"(ADDR), "n"(OFF))
-#else
 #define MLP_RD(F, ADDR, OFF) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(F) : "v"(ADDR), "n"(OFF))
-#endif
-#if (YMI_MLP_ABL & 2)
-#define MLP_MFMA(A, B, C) (C)
-#else
-#define MLP_MFMA(A, B, C) __builtin_amdgcn_mfma_f32_32x32x16_bf16(A, B, C, 0, 0, 0)
-#endif
 #define MLP_WAIT(N)                                                    \
     do {                                                               \
         __builtin_amdgcn_sched_barrier(0);                             \
@@ -187,7 +165,7 @@ __device__ __forceinline__ void mlp_rows_product(uint32_t addr, const bf16x8 (&b
         const uint32_t ad = addr;  // (an odr-use outside the asm operand: clang does not capture a variable it only sees there)
         MLP_WAIT((15 - s) < 3 ? (15 - s) : 3);
         asm volatile("" : "+v"(f[s & 3]));
-        d = MLP_MFMA(f[s & 3], b[s], d);
+        d = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f[s & 3], b[s], d, 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (s + 4 < 16) MLP_RD(f[s & 3], ad, (s + 4) * 1024);
     });
@@ -204,7 +182,7 @@ __device__ __forceinline__ void mlp_cols_product(uint32_t addr, const bf16x8 (&h
         const uint32_t ad = addr;
         MLP_WAIT((15 - i) < 3 ? (15 - i) : 3);
         asm volatile("" : "+v"(f[i & 3]));
-        acc[i >> 1] = MLP_MFMA(f[i & 3], hv[i & 1], acc[i >> 1]);
+        acc[i >> 1] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f[i & 3], hv[i & 1], acc[i >> 1], 0, 0, 0);
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (i + 4 < 16) MLP_RD(f[i & 3], ad, (i + 4) * 1024);
     });
@@ -258,20 +236,6 @@ __device__ __forceinline__ void mlp_store_tile(f32x16 (&acc)[8], const float* bi
 // copied into ring stage c % 3 at the start of phase 2c - 2 (its previous tenant, chunk c - 3, was last read in phase 2c - 3), every
 // wave retires its pieces before the barrier that ends phase 2c - 1, and the first read is in phase 2c.
 __device__ __forceinline__ void mlp_barrier() { asm volatile("s_barrier" ::: "memory"); }
-#if (YMI_MLP_ABL & 32)
-// diagnostic build: s_memtime stamps of workgroup 100, waves 0 and 4, chunks 8..11, into the (otherwise unused) `mean` array of an evaluation-mode call:
-// [wave half][chunk - 8][point 0..5] = matrix phase start | after the fc2 product | after the fc1 product | past the barrier | vector work done | past the barrier
-#define MLP_STAMP(P)                                                                                                              \
-    do {                                                                                                                          \
-        __builtin_amdgcn_sched_barrier(0);                                                                                        \
-        asm volatile("" : "+v"(hv[0]), "+v"(hv[1]));                                                                              \
-        if (!TRAIN && a.mean && blockIdx.x == 100 && (wave & 3) == 0 && lane == 0 && jc >= 8 && jc < 12)                         \
-            reinterpret_cast<unsigned long long*>(a.mean)[(half * 4 + (jc - 8)) * 6 + (P)] = __builtin_amdgcn_s_memtime();           \
-        __builtin_amdgcn_sched_barrier(0);                                                                                        \
-    } while (0)
-#else
-#define MLP_STAMP(P) do { } while (0)
-#endif
 
 __global__ __launch_bounds__(512, 2) void swin_mlp_fwd_kernel(MlpFwdArgs a) {
     const bool TRAIN = a.u != nullptr;  // (kernel argument: uniform) save u, the LayerNorm statistics and the pre-activations
@@ -353,11 +317,9 @@ __global__ __launch_bounds__(512, 2) void swin_mlp_fwd_kernel(MlpFwdArgs a) {
     for (int jc = 0; jc <= nch; ++jc) {
         // ---- matrix phase: fc2 of chunk jc - 1 (acc[ct][channel 32 ct + 8 (r >> 2) + 4 h + (r & 3)][token px] += over its 32 hidden units), then
         //      fc1 of chunk jc (d1[hidden unit 8 (r >> 2) + 4 h + (r & 3)][token px] over K = 256 channels, starting at the bias)
-        MLP_STAMP(0);
         if (half == 0 && jc >= 1 && jc + 1 < nch) mlp_issue(a.w1p, a.w2q, jc + 1, smem + ((jc + 1) % 3) * MLP_STAGE, tid, wave);  // (even global phase)
-        if (!(YMI_MLP_ABL & 64)) __builtin_amdgcn_s_setprio(1);
+        __builtin_amdgcn_s_setprio(1);
         if (jc > 0) mlp_cols_product(lds0 + ((jc - 1) % 3) * MLP_STAGE + 16384, hv, acc);
-        MLP_STAMP(1);
         f32x16 d1;
         {
             const int jb = jc < nch ? jc : nch - 1;
@@ -369,15 +331,13 @@ __global__ __launch_bounds__(512, 2) void swin_mlp_fwd_kernel(MlpFwdArgs a) {
             }
         }
         if (jc < nch) mlp_rows_product(lds0 + (jc % 3) * MLP_STAGE, uf, d1);
-        if (!(YMI_MLP_ABL & 64)) __builtin_amdgcn_s_setprio(0);
-        MLP_STAMP(2);
+        __builtin_amdgcn_s_setprio(0);
         // (odd global phase for the second half) the pieces issued one phase ago have landed: only the two pre-activation stores are younger
         if (half == 1) {
-            if (TRAIN && !(YMI_MLP_ABL & 16)) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+            if (TRAIN) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         mlp_barrier();
-        MLP_STAMP(3);
         if (jc == nch) break;
         // ---- vector phase: bf16 rounding of the pre-activation (saved), exact-erf GELU, bf16 again: the B operand of fc2
         if (half == 1 && jc + 2 < nch) mlp_issue(a.w1p, a.w2q, jc + 2, smem + ((jc + 2) % 3) * MLP_STAGE, tid, wave);  // (even global phase)
@@ -387,20 +347,18 @@ __global__ __launch_bounds__(512, 2) void swin_mlp_fwd_kernel(MlpFwdArgs a) {
             pf[i] = pack_bf16x2(d1[2 * i], d1[2 * i + 1]);
             hf[i] = pack_bf16x2(gelu_fast(bf16_lo(pf[i])), gelu_fast(bf16_hi(pf[i])));
         }
-        if (TRAIN && !(YMI_MLP_ABL & 16)) {
+        if (TRAIN) {
             *reinterpret_cast<u32x4*>(prew + ((size_t)jc * 8 * 2 + 0) * 64 * 8) = u32x4{pf[0], pf[1], pf[2], pf[3]};
             *reinterpret_cast<u32x4*>(prew + ((size_t)jc * 8 * 2 + 1) * 64 * 8) = u32x4{pf[4], pf[5], pf[6], pf[7]};
         }
         u32x4 t0 = {hf[0], hf[1], hf[2], hf[3]}, t1 = {hf[4], hf[5], hf[6], hf[7]};
         hv[0] = __builtin_bit_cast(bf16x8, t0);
         hv[1] = __builtin_bit_cast(bf16x8, t1);
-        MLP_STAMP(4);
         if (half == 0) {  // (odd global phase for the first half)
-            if (TRAIN && !(YMI_MLP_ABL & 16)) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+            if (TRAIN) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
         mlp_barrier();
-        MLP_STAMP(5);
     }
     if (half == 0) mlp_barrier();  // the first half waits out the second half's last phase
     // (the last barrier: every wave has finished reading the ring, which becomes the output staging image)

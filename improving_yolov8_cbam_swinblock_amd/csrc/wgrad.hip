@@ -23,25 +23,6 @@ bool ymi_prof_enabled();
 int ymi_prof_start(hipStream_t stream, int family, double flop, double bytes, double peak_tflops);
 void ymi_prof_stop(hipStream_t stream, int idx);
 
-#ifdef YMI_STAMPS
-// diagnostic build only (see igemm.hip): cycles from kernel entry at three marks of one workgroup + the in-kernel clock
-__device__ unsigned long long* g_wstamp_buf = nullptr;
-extern "C" int ymi_debug_stamp_buffer_wgrad(void* p) {
-    return hipMemcpyToSymbol(HIP_SYMBOL(g_wstamp_buf), &p, sizeof(p)) == hipSuccess ? 0 : -1;
-}
-#define WG_MARK(i)                                                                                              \
-    do {                                                                                                        \
-        if (wstamp_on) g_wstamp_buf[8 * 64 + 16 + wave * 8 + (i)] = __builtin_amdgcn_s_memtime() - wstamp_mt0; \
-    } while (0)
-#else
-#define WG_MARK(i) do { } while (0)
-#endif
-
-#ifdef YMI_STAMPS
-#define WG_STAMP_LDS 4096
-#else
-#define WG_STAMP_LDS 0
-#endif
 struct WgradArgs {
     const void* x;
     const void* dy;
@@ -71,19 +52,9 @@ typedef __attribute__((ext_vector_type(4))) short s16x4;
 constexpr int WG_BM = 64;    // rows  (co)
 constexpr int WG_BN = 128;   // cols  ((tap, ci))
 constexpr int WG_BK = 32;    // pixels per K step (64 was measured 10-15 % slower: half as many resident workgroups per CU)
+constexpr int WG_NS = 2;     // LDS ring stages of the bf16 kernels (three and four: +9 %, profiles/r05_wgrad_patch_walk_ab.txt)
+constexpr int WG_WAVES = 5;  // waves per SIMD the 64-row tile's register allocation must allow (4 and 6: no better, profiles/r04_wgrad_targets_sweep.txt)
 
-#ifndef YMI_WGRAD_ABL  // diagnostic builds (results wrong by design): bit 1 no LDS-DMA pieces inside the K loop, 2 no MFMAs, 4 no fragment reads, 8 no pixel walk, 16 no slab stores
-#define YMI_WGRAD_ABL 0
-#endif
-#ifndef YMI_WGRAD_NS  // LDS ring stages of the bf16 kernels
-#define YMI_WGRAD_NS 2
-#endif
-#ifndef YMI_WGRAD_DIRECT_SLAB  // 1: bfloat16 slabs stored straight from the accumulators (the form before round 5; A/B builds)
-#define YMI_WGRAD_DIRECT_SLAB 0
-#endif
-#ifndef YMI_WGRAD_WAVES
-#define YMI_WGRAD_WAVES 5  // waves per SIMD the register allocation must allow (the kernel is latency-bound: occupancy pays)
-#endif
 // `buffer_load_dwordx4 ... lds`: 16 bytes per lane from base + voff + soff into LDS (lane-linear behind `dst`), zeros for lanes whose offset is
 // outside [0, bytes).  The resource is rebuilt from (base, bytes) at every call - four scalar moves - because a local of the resource type in a
 // kernel TEMPLATE makes the host pass drop the instantiation's launch stub without a word (ROCm 7.2 clang): the type stays inside this function.
@@ -135,47 +106,36 @@ template <> struct WFrag<bf16_t> {
     static __device__ __forceinline__ void step(const char* Ys, const char* Xs, int r0, int c0, int lane, f32x4 (&acc)[TR][TC], bool bias, f32x4 (&accb)[BIAS ? TR : 1]) {
         static_assert(WG_BK == 32, "one 32-deep sub-step");
         bf16x8 af[TR], bfr[TC];
-        if (YMI_WGRAD_ABL & 4) {
+        // addresses first (plain arithmetic), then every read of the step back to back: X fragments, then the dY fragments in the
+        // order the MFMA rows use them
+        Addr ay[TR], ax[TC];
 #pragma unroll
-            for (int t = 0; t < TR; ++t) { af[t] = bf16x8{}; asm volatile("" : "+v"(af[t])); }
+        for (int t = 0; t < TR; ++t) ay[t] = addr<YSwz<BM>::SW>(Ys, BM * 2, r0 + t * 16, lane);  // by the dY image's row width
+        // (512-byte X rows of the 256-column tile: the XOR only touches the low five bits of the 8-byte unit index, i.e. it
+        // permutes units inside each 256-byte bank row exactly as for 256-byte rows)
 #pragma unroll
-            for (int t = 0; t < TC; ++t) { bfr[t] = bf16x8{}; asm volatile("" : "+v"(bfr[t])); }
-        } else {
-            // addresses first (plain arithmetic), then every read of the step back to back: X fragments, then the dY fragments in the
-            // order the MFMA rows use them
-            Addr ay[TR], ax[TC];
+        for (int t = 0; t < TC; ++t) ax[t] = addr<1>(Xs, BNW * 2, c0 + t * 16, lane);
+        __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-            for (int t = 0; t < TR; ++t) ay[t] = addr<YSwz<BM>::SW>(Ys, BM * 2, r0 + t * 16, lane);  // by the dY image's row width
-            // (512-byte X rows of the 256-column tile: the XOR only touches the low five bits of the 8-byte unit index, i.e. it
-            // permutes units inside each 256-byte bank row exactly as for 256-byte rows)
+        for (int t = 0; t < TC; ++t) read2(bfr[t], ax[t]);
 #pragma unroll
-            for (int t = 0; t < TC; ++t) ax[t] = addr<1>(Xs, BNW * 2, c0 + t * 16, lane);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int t = 0; t < TC; ++t) read2(bfr[t], ax[t]);
-#pragma unroll
-            for (int t = 0; t < TR; ++t) read2(af[t], ay[t]);
-        }
+        for (int t = 0; t < TR; ++t) read2(af[t], ay[t]);
 #pragma unroll
         for (int a = 0; a < TR; ++a) {
             // row a needs the X fragments and dY fragment a: the 2 * (TR - 1 - a) younger reads may still be in flight
             __builtin_amdgcn_sched_barrier(0);
-            if (!(YMI_WGRAD_ABL & 4)) {
-                if (a == 0) asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(2 * (TR - 1)) : "memory");
-                else if (a == 1) asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(TR > 2 ? 2 * (TR - 2) : 0) : "memory");
-                else if (a == 2) asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(TR > 3 ? 2 * (TR - 3) : 0) : "memory");
-                else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-            }
+            if (a == 0) asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(2 * (TR - 1)) : "memory");
+            else if (a == 1) asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(TR > 2 ? 2 * (TR - 2) : 0) : "memory");
+            else if (a == 2) asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(TR > 3 ? 2 * (TR - 3) : 0) : "memory");
+            else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             asm volatile("" : "+v"(af[a]));
             if (a == 0) {
 #pragma unroll
                 for (int b = 0; b < TC; ++b) asm volatile("" : "+v"(bfr[b]));
             }
 #pragma unroll
-            for (int b = 0; b < TC; ++b) {
-                if (YMI_WGRAD_ABL & 2) { asm volatile("" :: "v"(bfr[b]), "v"(af[a])); continue; }
+            for (int b = 0; b < TC; ++b)
                 acc[a][b] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[b], af[a], acc[a][b], 0, 0, 0);  // operands swapped: see the epilogue
-            }
             if (BIAS && bias) {  // (wave-uniform) column sums of dY: a row of ones against the dY fragment already in registers - one more MFMA per row
                 typedef __attribute__((ext_vector_type(8))) short s16x8;
                 const s16x8 one8 = {0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80};  // 1.0 in bfloat16
@@ -285,11 +245,11 @@ __device__ __forceinline__ void wgrad_rider_final(const YmiBnRider& r, int w, ch
 // of two dividing Wo, ph dividing Ho) whose origin (n, ho0, wo0) is SCALAR state.  A lane's row of the step is a fixed (pr, pc) inside the patch, so its
 // source offset is a per-thread constant plus a scalar: the pieces become `buffer_load_dwordx4 ... lds` with the constant in the vector offset and the
 // patch origin in the scalar offset, padding taps are lanes whose vector offset is pushed out of range (the buffer unit writes zeros to LDS for them:
-// tools/probes/bar/buffer_lds_probe.hip), and the per-lane (ho, wo) walk with its wraps - as many issue slots as the MFMAs (tools/probes/
-// r5_wgrad_ablate.sh) - is five vector instructions per X piece and none per dY piece.  Any fixed order of the pixel sum is as good as raster order;
+// tools/probes/bar/buffer_lds_probe.hip), and the per-lane (ho, wo) walk with its wraps - as many issue slots as the MFMAs (profiles/
+// r05_wgrad_patch_walk_ab.txt) - is five vector instructions per X piece and none per dY piece.  Any fixed order of the pixel sum is as good as raster order;
 // maps that do not tile into such patches (20 x 20) keep the raster walk.
 template <typename T, int NS, int BM, bool BIAS = false, bool PATCH = false>
-__global__ __launch_bounds__(256, (BM == 128 ? 3 : YMI_WGRAD_WAVES)) void wgrad_kernel(WgradArgs a, YmiBnRider rider) {
+__global__ __launch_bounds__(256, (BM == 128 ? 3 : WG_WAVES)) void wgrad_kernel(WgradArgs a, YmiBnRider rider) {
     constexpr int BNW = WG_BN, NT = 256;
     constexpr int CH = ElemTraits<T>::CH;
     constexpr int ES = (int)sizeof(T);
@@ -307,10 +267,6 @@ __global__ __launch_bounds__(256, (BM == 128 ? 3 : YMI_WGRAD_WAVES)) void wgrad_
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int wr = wave / WCOLS, wc = wave % WCOLS;
-#ifdef YMI_STAMPS
-    const bool wstamp_on = g_wstamp_buf && blockIdx.x == gridDim.x / 2 && blockIdx.y == 0 && blockIdx.z == 0 && lane == 0;
-    const unsigned long long wstamp_mt0 = wstamp_on ? __builtin_amdgcn_s_memtime() : 0ull, wstamp_rt0 = wstamp_on ? __builtin_amdgcn_s_memrealtime() : 0ull;
-#endif
     // XCD-aware order (xcd_map): workgroup ids are dealt round-robin to the 8 XCDs; all tiles of one pixel split read the
     // same dY / X rows (the nine taps are the same pixels, shifted), so a split's tiles are given to ONE XCD, back to
     // back, and its rows are fetched into that L2 once.  An XCD gets CONSECUTIVE splits, z = xcd * ceil(splits / 8) + i: its
@@ -427,17 +383,16 @@ __global__ __launch_bounds__(256, (BM == 128 ? 3 : YMI_WGRAD_WAVES)) void wgrad_
     auto issue = [&](int s, int mk) {
         char* Ys = smem + s * STAGE;
         char* Xs = Ys + YBYTES;
-        const bool live = !(YMI_WGRAD_ABL & 1) || mk < m_begin + (NS - 1) * WG_BK;
         if constexpr (PATCH) {
             const uint32_t sx = __builtin_amdgcn_readfirstlane(p_sx), sy = __builtin_amdgcn_readfirstlane(p_sy);  // (scalar by construction; said so)
 #pragma unroll
             for (int i = 0; i < NY; ++i)
-                if (live) wg_buffer_to_lds(yg, a.y_bytes, (lptr_t)(Ys + (i * NT + (wave * 64) % YT) * 16), pvy[i], sy);
+                wg_buffer_to_lds(yg, a.y_bytes, (lptr_t)(Ys + (i * NT + (wave * 64) % YT) * 16), pvy[i], sy);
             const int hs0 = __builtin_amdgcn_readfirstlane(p_ho * s_), ws0 = __builtin_amdgcn_readfirstlane(p_wo * s_);
 #pragma unroll
             for (int i = 0; i < NX; ++i) {
                 const bool ok = (unsigned)(hs0 + pch[i]) < (unsigned)a.H && (unsigned)(ws0 + pcw[i]) < (unsigned)a.W;
-                if (live) wg_buffer_to_lds(xbase, a.x_bytes + xbias, (lptr_t)(Xs + (i * NT + wave * 64) * 16), ok ? pvx[i] : OOR, sx);
+                wg_buffer_to_lds(xbase, a.x_bytes + xbias, (lptr_t)(Xs + (i * NT + wave * 64) * 16), ok ? pvx[i] : OOR, sx);
             }
             // one patch on (scalar)
             p_wo += pw;
@@ -460,17 +415,14 @@ __global__ __launch_bounds__(256, (BM == 128 ? 3 : YMI_WGRAD_WAVES)) void wgrad_
         for (int i = 0; i < NY; ++i) {
             const bool ok = y_cok && y_row[i] < left;
             const T* src = ok ? yg + y_off[i] : zero;
-            if (live) __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(Ys + (i * NT + (wave * 64) % YT) * 16), 16, 0, 0);
-            else asm volatile("" :: "v"(src));
+            __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(Ys + (i * NT + (wave * 64) % YT) * 16), 16, 0, 0);
             y_off[i] += y_step;
         }
 #pragma unroll
         for (int i = 0; i < NX; ++i) {
             const bool ok = x_cok && x_row[i] < left && (unsigned)(x_hs[i] + dh) < (unsigned)a.H && (unsigned)(x_ws[i] + dw) < (unsigned)a.W;
             const T* src = ok ? xg + x_off[i] : zero;
-            if (live) __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(Xs + (i * NT + wave * 64) * 16), 16, 0, 0);
-            else asm volatile("" :: "v"(src));
-            if (YMI_WGRAD_ABL & 8) continue;
+            __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(Xs + (i * NT + wave * 64) * 16), 16, 0, 0);
             // one K step on
             x_ws[i] += r_ * s_;
             x_hs[i] += q_ * s_;
@@ -499,41 +451,21 @@ __global__ __launch_bounds__(256, (BM == 128 ? 3 : YMI_WGRAD_WAVES)) void wgrad_
     f32x4 accb[BIAS ? TR : 1];
 #pragma unroll
     for (int r = 0; r < (BIAS ? TR : 1); ++r) accb[r] = f32x4{0.f, 0.f, 0.f, 0.f};
-    WG_MARK(0);  // prologue done
     // NS-stage LDS ring, one raw barrier per K step, loads of NS-2 younger steps stay in flight (see igemm.hip)
     const int nk = (m_end - m_begin + WG_BK - 1) / WG_BK;
     constexpr int LPT = NY + NX;
 #pragma unroll
     for (int s = 0; s < NS - 1; ++s)
         if (s < nk) issue(s, m_begin + s * WG_BK);
-#ifdef YMI_STAMPS
-    int wstamp_i = 0;
-    // stamps go to a spare 2 KB of LDS behind the ring (a global store per stamp would sit in vmcnt and distort the counted waits)
-    unsigned long long* wstamp_lds = reinterpret_cast<unsigned long long*>(smem + NS * STAGE) + wave * 64;
-#define WG_STEP_STAMP() do { if (wstamp_on && kt >= 2 && kt < 10 && wstamp_i < 64) wstamp_lds[wstamp_i++] = __builtin_amdgcn_s_memtime(); } while (0)
-#else
-#define WG_STEP_STAMP() do { } while (0)
-#endif
     for (int kt = 0; kt < nk; ++kt) {
-        WG_STEP_STAMP();  // 0: step start
         if (kt + NS - 2 < nk) wait_vmcnt_barrier<LPT * (NS - 2)>();
         else wait_vmcnt_barrier<0>();
-        WG_STEP_STAMP();  // 1: past wait + barrier
         if (kt + NS - 1 < nk) issue((kt + NS - 1) % NS, m_begin + (kt + NS - 1) * WG_BK);
-        WG_STEP_STAMP();  // 2: pieces issued
         const char* Ys = smem + (kt % NS) * STAGE;
         if constexpr (BIAS) WFrag<T>::template step<BM, TR, TC, BNW, true>(Ys, Ys + YBYTES, wr * (BM / WROWS), wc * 64, lane, acc, do_bias, accb);
         else WFrag<T>::template step<BM, TR, TC, BNW, false>(Ys, Ys + YBYTES, wr * (BM / WROWS), wc * 64, lane, acc, false, accb);
-        WG_STEP_STAMP();  // 3: fragments read, MFMAs issued
     }
 
-#ifdef YMI_STAMPS
-    if (wstamp_on) for (int q = 0; q < 64; ++q) g_wstamp_buf[wave * 64 + q] = q < wstamp_i ? wstamp_lds[q] : 0ull;
-#endif
-    WG_MARK(1);  // K loop done
-#ifdef YMI_STAMPS
-    if (wstamp_on) g_wstamp_buf[8 * 64 + 16 + wave * 8 + 6] = nk;
-#endif
     const int64_t slab_off = (int64_t)bz * a.CoutP * a.NG;
     // The MFMA operands are swapped (A = the X fragment, B = the dY fragment), so a lane's four accumulator values are four
     // CONSECUTIVE (tap, ci) columns of one output channel: one 16-byte store instead of four 4-byte stores to four rows
@@ -546,10 +478,10 @@ __global__ __launch_bounds__(256, (BM == 128 ? 3 : YMI_WGRAD_WAVES)) void wgrad_
             if (co < a.CoutP) a.bias_slab[(int64_t)bz * a.CoutP + co] = accb[r][0];
         }
     }
-    if (std::is_same<T, bf16_t>::value && a.slab_bf16 && !(YMI_WGRAD_ABL & 16) && !YMI_WGRAD_DIRECT_SLAB) {
+    if (std::is_same<T, bf16_t>::value && a.slab_bf16) {
         // bfloat16 slabs leave through LDS (round 5): written straight from the accumulators, a store instruction covers 16 rows x 32 bytes -
-        // sixteen partial lines - and those stores cost 8 % of the family's time (0.7 ms per step if nothing hid them: tools/probes/
-        // r5_wgrad_ablate.sh).  Each wave drops 32 rows x 64 columns of its tile into a private padded image and stores it back as whole
+        // sixteen partial lines - and those stores cost 8 % of the family's time (0.7 ms per step if nothing hid them: profiles/
+        // r05_wgrad_slab_stores_ab.txt).  Each wave drops 32 rows x 64 columns of its tile into a private padded image and stores it back as whole
         // 128-byte row segments, eight rows per instruction.  Same values, same rounding.
         __syncthreads();  // the other waves may still read the last K step's stage
         constexpr int SROW = 144;                 // padded row: 16 rows hit 16 distinct bank groups
@@ -581,7 +513,7 @@ __global__ __launch_bounds__(256, (BM == 128 ? 3 : YMI_WGRAD_WAVES)) void wgrad_
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         }
-    } else if (std::is_same<T, bf16_t>::value && !(YMI_WGRAD_ABL & 16) && !YMI_WGRAD_DIRECT_SLAB) {
+    } else if (std::is_same<T, bf16_t>::value) {
         // float32 slabs of the bf16 path (fewer than 16 splits): the same, 16 rows x 64 columns per pass, 256-byte row segments, four rows per instruction
         __syncthreads();
         constexpr int SROW = 272;
@@ -607,34 +539,17 @@ __global__ __launch_bounds__(256, (BM == 128 ? 3 : YMI_WGRAD_WAVES)) void wgrad_
             __builtin_amdgcn_wave_barrier();
             __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
         }
-    } else
+    } else {  // f32 parity mode: float32 slabs straight from the accumulators
 #pragma unroll
-    for (int r = 0; r < TR; ++r) {
-        const int co = co0 + wr * (BM / WROWS) + r * 16 + l15;
+        for (int r = 0; r < TR; ++r) {
+            const int co = co0 + wr * (BM / WROWS) + r * 16 + l15;
 #pragma unroll
-        for (int c = 0; c < TC; ++c) {
-            const int col = j0 + wc * 64 + c * 16 + 4 * l4;
-            if (YMI_WGRAD_ABL & 16) { asm volatile("" :: "v"(acc[r][c])); continue; }
-            if (co < a.CoutP && col < a.NG) {
-                const int64_t e = slab_off + (int64_t)co * a.NG + col;
-                if (std::is_same<T, bf16_t>::value && a.slab_bf16) {
-                    const bf16x4 v = {(bf16_t)acc[r][c][0], (bf16_t)acc[r][c][1], (bf16_t)acc[r][c][2], (bf16_t)acc[r][c][3]};
-                    *reinterpret_cast<bf16x4*>(reinterpret_cast<bf16_t*>(a.slab) + e) = v;
-                } else {
-                    *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(a.slab) + e) = acc[r][c];
-                }
+            for (int c = 0; c < TC; ++c) {
+                const int col = j0 + wc * 64 + c * 16 + 4 * l4;
+                if (co < a.CoutP && col < a.NG) *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(a.slab) + slab_off + (int64_t)co * a.NG + col) = acc[r][c];
             }
         }
     }
-    WG_MARK(5);  // stores issued
-#ifdef YMI_STAMPS
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    WG_MARK(2);  // stores retired
-    if (wstamp_on) {
-        g_wstamp_buf[8 * 64 + wave * 2 + 0] = __builtin_amdgcn_s_memtime() - wstamp_mt0;
-        g_wstamp_buf[8 * 64 + wave * 2 + 1] = __builtin_amdgcn_s_memrealtime() - wstamp_rt0;
-    }
-#endif
 }
 
 // a slab element as float (slabs are float32, or bfloat16 in the bf16 path)
@@ -845,16 +760,15 @@ static void wgrad_launch(const WgradLaunch& h, const YmiBnRider* rider) {
 #define YMI_WG_LAUNCH(T, BMV, LDS)                                                                                   \
     do {                                                                                                            \
         if (a.pw_shift >= 0) {                                                                                      \
-            if (a.bias_slab) hipLaunchKernelGGL((wgrad_kernel<T, YMI_WGRAD_NS, BMV, true, true>), grid, dim3(256), (LDS), s, a, r);  \
-            else hipLaunchKernelGGL((wgrad_kernel<T, YMI_WGRAD_NS, BMV, false, true>), grid, dim3(256), (LDS), s, a, r);        \
-        } else if (a.bias_slab) hipLaunchKernelGGL((wgrad_kernel<T, YMI_WGRAD_NS, BMV, true>), grid, dim3(256), (LDS), s, a, r);  \
-        else hipLaunchKernelGGL((wgrad_kernel<T, YMI_WGRAD_NS, BMV, false>), grid, dim3(256), (LDS), s, a, r);                  \
+            if (a.bias_slab) hipLaunchKernelGGL((wgrad_kernel<T, WG_NS, BMV, true, true>), grid, dim3(256), (LDS), s, a, r);         \
+            else hipLaunchKernelGGL((wgrad_kernel<T, WG_NS, BMV, false, true>), grid, dim3(256), (LDS), s, a, r);               \
+        } else if (a.bias_slab) hipLaunchKernelGGL((wgrad_kernel<T, WG_NS, BMV, true>), grid, dim3(256), (LDS), s, a, r);         \
+        else hipLaunchKernelGGL((wgrad_kernel<T, WG_NS, BMV, false>), grid, dim3(256), (LDS), s, a, r);                         \
     } while (0)
     if (h.bf16) {
-        // two LDS stages (deeper rings measured equal: same bytes in flight per CU)
-        if (h.bm == 128) YMI_WG_LAUNCH(bf16_t, 128, (size_t)YMI_WGRAD_NS * (WG_BK * (128 + WG_BN) * 2) + WG_STAMP_LDS);
-        else if (h.bm == 32) YMI_WG_LAUNCH(bf16_t, 32, (size_t)YMI_WGRAD_NS * (WG_BK * (32 + WG_BN) * 2) + WG_STAMP_LDS);
-        else YMI_WG_LAUNCH(bf16_t, 64, (size_t)YMI_WGRAD_NS * (WG_BK * (64 + WG_BN) * 2) + WG_STAMP_LDS);
+        if (h.bm == 128) YMI_WG_LAUNCH(bf16_t, 128, (size_t)WG_NS * (WG_BK * (128 + WG_BN) * 2));
+        else if (h.bm == 32) YMI_WG_LAUNCH(bf16_t, 32, (size_t)WG_NS * (WG_BK * (32 + WG_BN) * 2));
+        else YMI_WG_LAUNCH(bf16_t, 64, (size_t)WG_NS * (WG_BK * (64 + WG_BN) * 2));
     } else {
         const size_t lds = 2 * (size_t)(WG_BK * (WG_BM + WG_BN) * 4);
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_kernel<float, 2, 64, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);

@@ -49,39 +49,6 @@ SHAPES = [
 ]
 
 
-def stamp_dump(L, fn, title, wgrad=False):
-    """one more launch with the stamp buffer armed; prints, per wave, cycles between the 4 marks of K steps 2..9."""
-    buf = torch.zeros(8 * 64 + 16 + 64, dtype=torch.int64, device="cuda:0")
-    setter = L.ymi_debug_stamp_buffer_wgrad if wgrad else L.ymi_debug_stamp_buffer
-    setter.argtypes = [ctypes.c_void_p]
-    setter(ctypes.c_void_p(buf.data_ptr()))
-    fn()
-    torch.cuda.synchronize()
-    setter(ctypes.c_void_p(0))
-    host = buf.cpu()
-    st = host[: 8 * 64].view(8, 64)
-    cal = host[8 * 64: 8 * 64 + 16].view(8, 2)
-    marks = host[8 * 64 + 16:].view(8, 8)
-    for w in range(8):
-        if int(marks[w, 2]) > 0:
-            if wgrad:
-                print(f"wave {w}: {int(marks[w, 6])} K steps; cycles from kernel entry: prologue done {int(marks[w, 0])}, K loop done {int(marks[w, 1])}, stores issued {int(marks[w, 5])}, stores retired {int(marks[w, 2])}")
-                continue
-            print(f"wave {w}: cycles from kernel entry: prologue done {int(marks[w, 0])}, K loop done {int(marks[w, 1])}, tile in LDS {int(marks[w, 3])}, past barrier {int(marks[w, 4])}, stores issued {int(marks[w, 5])}, stores retired {int(marks[w, 2])}")
-    for w in range(8):
-        if int(cal[w, 1]) > 0:
-            print(f"wave {w}: K loop {int(cal[w, 0])} shader cycles in {int(cal[w, 1]) * 10} ns -> in-kernel clock {int(cal[w, 0]) / (int(cal[w, 1]) * 10.0):.2f} GHz")
-    print(f"--- stamps: {title}  (s_memtime ticks; marks 0->1->2->3->next 0)")
-    t0 = min(int(v) for v in st[:, 0] if int(v) > 0) if (st[:, 0] > 0).any() else 0
-    for w in range(8):
-        row = [int(v) for v in st[w] if int(v) > 0]
-        if not row:
-            continue
-        d = [row[i + 1] - row[i] for i in range(len(row) - 1)]
-        steps = [d[i:i + 4] for i in range(0, len(d) - 3, 4)]
-        print(f"wave {w}: first mark at +{row[0] - t0}; per step [0->1, 1->2, 2->3, 3->next]:", " ".join(str(x) for x in steps[:8]))
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--dtype", default="bf16")
@@ -93,7 +60,6 @@ def main():
     ap.add_argument("--cold", action="store_true", help="evict the caches (1 GiB fill) before every timed launch: per-launch events, as a layer meets its operands inside the step")
     ap.add_argument("--producer", action="store_true", help="forward only: the BatchNorm affine + SiLU pass that WRITES the GEMM's input runs before every timed launch, as in "
                     "the step (chains of pass -> GEMM; columns: the pass alone, the pair, the GEMM's share); with YMI_XCD_SHIFT=k the pass works on another XCD's eighth")
-    ap.add_argument("--stamps", action="store_true", help="diagnostic build (-DYMI_STAMPS) only: print the s_memtime stamps of one workgroup's K steps")
     args = ap.parse_args()
     dt = torch.bfloat16 if args.dtype == "bf16" else torch.float32
     dev = torch.device("cuda:0")
@@ -196,8 +162,6 @@ def main():
                 e1.record()
                 torch.cuda.synchronize()
                 us = e0.elapsed_time(e1) * 1e3 / args.iters
-            if args.stamps:
-                stamp_dump(L, fn, f"{name} {nm} ({us:.1f} us)", nm == "wgrad")
             tot[nm] += us * count
             line += f" {us:8.1f} {gf / us * 1e-3 * 1e3 / 1e3 * 1e3:6.0f} |" if False else f" {us:8.1f} {gf / (us * 1e-6) / 1e3:6.0f} |"
         print(line, flush=True)

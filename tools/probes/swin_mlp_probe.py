@@ -50,15 +50,3 @@ for _ in range(3): fused(); unfused(); fused_bwd(); unfused_bwd()
 for cold in (False, True):
     print("cold" if cold else "warm", "fused train (median, min us):", timeit(lambda: fused(True), cold), "fused eval:", timeit(lambda: fused(False), cold), "unfused:", timeit(unfused, cold))
     print("cold" if cold else "warm", "fused bwd data:", timeit(fused_bwd, cold), "unfused bwd data:", timeit(unfused_bwd, cold))
-
-if os.environ.get("YMI_MLP_STAMPS") == "1":  # a -DYMI_MLP_ABL=11 build: print the in-kernel phase stamps (cycles relative to the first)
-    stamps = torch.zeros(64, dtype=torch.int64, device=dev)
-    for _ in range(3):
-        L.check(lib.ymi_swin_ln_mlp_fwd(ctypes.byref(L.as_ymi(x)), L.ptr(gamma), L.ptr(beta), eps, L.ptr(packed), L.ptr(b1), L.ptr(b2), hidden,
-                                        None, L.ptr(stamps), None, None, ctypes.byref(L.as_ymi(out)), L.stream_ptr()), "fwd")
-    torch.cuda.synchronize()
-    v = stamps[:48].view(2, 4, 6).cpu()
-    base = int(v.min())
-    for hh in range(2):
-        for j in range(4):
-            print("half", hh, "chunk", 8 + j, "stamps:", [int(t) - base for t in v[hh, j]])
