@@ -824,7 +824,9 @@ struct TileChoice {
 // Largest tile that still yields ~1.5 workgroups per CU (measured on the 40x40 / 20x20 layers of the model: 400 tiles of
 // 128x128 beat 800 of 64x128 by 25-30 %, and below that 128x64, then 64x64, win); short-K GEMMs (K <= 384) are
 // prologue/epilogue-dominated and run best as 128x64 (three resident workgroups per CU).
-static TileChoice choose_tile(int64_t M, int64_t cout, int64_t ktot, bool bf16) {
+// fast: every problem of the launch takes whole-chunk taps (cpt % 4 == 0), the K-step form the ping-pong tile needs.  (Testing ktot % 32
+// instead let the stride-2 data gradient's four-tap class pass with dy channels that are no multiple of 32: the launch then refused the tile.)
+static TileChoice choose_tile(int64_t M, int64_t cout, int64_t ktot, bool bf16, bool fast) {
     TileChoice t;
     auto blocks = [&](int bm, int bn) { return ((M + bm - 1) / bm) * ((cout + bn - 1) / bn); };
     const int64_t enough = 400;
@@ -845,11 +847,11 @@ static TileChoice choose_tile(int64_t M, int64_t cout, int64_t ktot, bool bf16) 
     // Default from 300 workgroups (measured, profiles/r02_conv_bench_pp64.txt: 64-byte rows - three 24 KB stages, TWO resident
     // workgroups per CU - win 5-19 % on every layer that yields >= 400 such tiles and lose 15-25 % at 200; step 14.71 -> 14.38 ms).
     constexpr int pp_env = 300;
-    if (bf16 && cout >= 128 && ktot % 32 == 0 && blocks(256, 128) >= pp_env) {
+    if (bf16 && cout >= 128 && fast && blocks(256, 128) >= pp_env) {
         t.bm = 256; t.bn = 128; t.pp = true;
     }
     const int fbm = ymi_opt(OPT_IGEMM_TILE_BM), fbn = ymi_opt(OPT_IGEMM_TILE_BN);  // force a tile (tools/conv_bench.py sweeps)
-    if (fbm > 0 && fbn > 0 && (fbn <= 32 ? cout <= 32 : true) && (fbm < 256 || (bf16 && ktot % 32 == 0))) {  // (the ping-pong tile: bf16, whole 32-deep steps)
+    if (fbm > 0 && fbn > 0 && (fbn <= 32 ? cout <= 32 : true) && (fbm < 256 || (bf16 && fast))) {  // (the ping-pong tile: bf16, whole 32-deep steps)
         t.bm = fbm;
         t.bn = fbn;
         t.pp = fbm == 256;
@@ -952,7 +954,9 @@ static int launch_igemm_n(const IgemmArgs* arr, int ncls, int dtype, bool stats,
     int64_t mmax = 0, msum = 0;
     int64_t kmax = 0;
     int cmax = 0, cmin = 1 << 30;
+    bool fast = true;
     for (int i = 0; i < ncls; ++i) {
+        fast = fast && (arr[i].cpt % 4) == 0;
         mmax = arr[i].M > mmax ? arr[i].M : mmax;
         msum += arr[i].M;
         kmax = arr[i].ktot > kmax ? arr[i].ktot : kmax;
@@ -960,7 +964,7 @@ static int launch_igemm_n(const IgemmArgs* arr, int ncls, int dtype, bool stats,
         cmin = arr[i].Cout < cmin ? arr[i].Cout : cmin;
     }
     // one tile form for the launch: chosen for the widest problem over all the rows (a narrower problem pads its N block)
-    TileChoice t = hetero ? choose_tile(msum, cmax, kmax, dtype == YMI_BF16) : choose_tile(mmax * ncls, arr[0].Cout, kmax, dtype == YMI_BF16);
+    TileChoice t = hetero ? choose_tile(msum, cmax, kmax, dtype == YMI_BF16, fast) : choose_tile(mmax * ncls, arr[0].Cout, kmax, dtype == YMI_BF16, fast);
     if (hetero && t.bn > 64 && cmin <= 64 && cmax > 64 && !t.pp) t.bn = 64;  // (mixed widths: 64-column tiles waste nothing on the narrow ones)
     if (host_blocks)
         for (int i = 0; i < (hetero ? ncls : 1); ++i) host_blocks[i] = (arr[i].M + t.bm - 1) / t.bm;
