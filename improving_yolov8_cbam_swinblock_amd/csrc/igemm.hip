@@ -1003,13 +1003,12 @@ static void find_divisor(int d, uint32_t* mul, uint32_t* shr) {
     *mul = (uint32_t)(((1ull << p) + (uint64_t)d - 1) / (uint64_t)d);
     *shr = (uint32_t)(p - 32);
 }
-static void finish_args(IgemmArgs& a, const ymi_tensor* y, const ymi_tensor* residual) {
+static void finish_args(IgemmArgs& a, const ymi_tensor* y) {
     find_divisor(a.Wo, &a.wo_mul, &a.wo_shr);
     find_divisor(a.Ho, &a.ho_mul, &a.ho_shr);
     const size_t es = ymi_esize(y->dtype);
     const int epc = (int)(16 / es);
     a.vec16 = a.vec_store && (y->ld % epc == 0) && (((uintptr_t)y->data) % 16 == 0) && (a.Cout % epc == 0);
-    (void)residual;
 }
 
 static void pack_taps(const int* dh, const int* dw, int n, uint64_t* pdh, uint64_t* pdw) {
@@ -1027,20 +1026,6 @@ extern "C" int64_t ymi_conv2d_stat_blocks(int64_t m_rows, int64_t cout) {
     return (m_rows + 63) / 64 + 64;  // smallest BM any tile choice uses, + the 64 staging rows ymi_bn_finalize may append
 }
 
-static int conv_fwd_args(const ymi_tensor* x, const void* w_packed, int64_t cout, int64_t kh, int64_t kw, int64_t stride,
-                         const float* scale, const float* bias, int32_t act, const ymi_tensor* residual, const ymi_tensor* y,
-                         const ymi_tensor* y2, int32_t act2, float* stat_partials, IgemmArgs* out);
-static int conv_fwd_impl(const ymi_tensor* x, const void* w_packed, int64_t cout, int64_t kh, int64_t kw, int64_t stride,
-                         const float* scale, const float* bias, int32_t act, const ymi_tensor* residual, const ymi_tensor* y,
-                         const ymi_tensor* y2, int32_t act2, float* stat_partials, int64_t* host_stat_blocks, void* stream) {
-    IgemmArgs a{};
-    int rc = conv_fwd_args(x, w_packed, cout, kh, kw, stride, scale, bias, act, residual, y, y2, act2, stat_partials, &a);
-    if (rc) return rc;
-    int blocks = 0;
-    rc = ymi_launch_igemm(a, x->dtype, stat_partials != nullptr, &blocks, (hipStream_t)stream);
-    if (host_stat_blocks) *host_stat_blocks = blocks;
-    return rc;
-}
 static int conv_fwd_args(const ymi_tensor* x, const void* w_packed, int64_t cout, int64_t kh, int64_t kw, int64_t stride,
                          const float* scale, const float* bias, int32_t act, const ymi_tensor* residual, const ymi_tensor* y,
                          const ymi_tensor* y2, int32_t act2, float* stat_partials, IgemmArgs* out) {
@@ -1082,9 +1067,21 @@ static int conv_fwd_args(const ymi_tensor* x, const void* w_packed, int64_t cout
     const int g = 4;
     a.vec_store = (y->ld % g == 0) && (((uintptr_t)y->data) % (g * ymi_esize(y->dtype)) == 0) &&
                   (!residual || (residual->ld % g == 0 && ((uintptr_t)residual->data) % (g * ymi_esize(y->dtype)) == 0));
-    finish_args(a, y, residual);
+    finish_args(a, y);
     *out = a;
     return YMI_OK;
+}
+
+static int conv_fwd_impl(const ymi_tensor* x, const void* w_packed, int64_t cout, int64_t kh, int64_t kw, int64_t stride,
+                         const float* scale, const float* bias, int32_t act, const ymi_tensor* residual, const ymi_tensor* y,
+                         const ymi_tensor* y2, int32_t act2, float* stat_partials, int64_t* host_stat_blocks, void* stream) {
+    IgemmArgs a{};
+    int rc = conv_fwd_args(x, w_packed, cout, kh, kw, stride, scale, bias, act, residual, y, y2, act2, stat_partials, &a);
+    if (rc) return rc;
+    int blocks = 0;
+    rc = ymi_launch_igemm(a, x->dtype, stat_partials != nullptr, &blocks, (hipStream_t)stream);
+    if (host_stat_blocks) *host_stat_blocks = blocks;
+    return rc;
 }
 
 // Several independent convolutions in ONE launch (problems one after another: IgemmMulti, hetero form) - the same stage of Detect's three
@@ -1138,82 +1135,80 @@ extern "C" int64_t ymi_conv_dgrad_pack_elems(int64_t o, int64_t i, int64_t kh, i
     return o * i * kh * kw;  // the classes partition the taps
 }
 
-extern "C" int ymi_conv2d_bwd_data(const ymi_tensor* dy, const void* w_dgrad_packed, int64_t cin, int64_t kh, int64_t kw,
-                                   int64_t stride, const ymi_tensor* dx, void* stream) {
-    return ymi_conv2d_bwd_data_add(dy, w_dgrad_packed, cin, kh, kw, stride, nullptr, nullptr, dx, stream);
-}
-
-static int dgrad_impl(const ymi_tensor* dy, const void* w_dgrad_packed, int64_t cin, int64_t kh, int64_t kw, int64_t stride,
-                      const ymi_tensor* add1, const ymi_tensor* add2, const ymi_tensor* mul, int32_t mul_act, const ymi_tensor* dx, void* stream);
-
-extern "C" int ymi_conv2d_bwd_data_add(const ymi_tensor* dy, const void* w_dgrad_packed, int64_t cin, int64_t kh, int64_t kw,
-                                       int64_t stride, const ymi_tensor* add1, const ymi_tensor* add2, const ymi_tensor* dx, void* stream) {
-    return dgrad_impl(dy, w_dgrad_packed, cin, kh, kw, stride, add1, add2, nullptr, YMI_ACT_NONE, dx, stream);
-}
-
-static int dgrad_impl(const ymi_tensor* dy, const void* w_dgrad_packed, int64_t cin, int64_t kh, int64_t kw, int64_t stride,
-                      const ymi_tensor* add1, const ymi_tensor* add2, const ymi_tensor* mul, int32_t mul_act, const ymi_tensor* dx, void* stream) {
-    YMI_CHECK_ARG(ymi_tensor_ok(dy) && ymi_tensor_ok(dx) && w_dgrad_packed, "conv2d_bwd_data: bad tensor");
+// The IgemmArgs of ONE parity class (ph, pw) of a data gradient at `stride` (stride 1: the only class, (0, 0)): validation of the problem and
+// field fill.  w_class: the class's part of the packed operand.  out->ntaps == 0: no tap reaches the class; out->M == 0: it has no pixels.
+// who: the entry point the caller was reached through (error texts).
+static int dgrad_class_args(const char* who, const ymi_tensor* dy, const void* w_class, int64_t cin, int64_t kh, int64_t kw, int64_t stride, int ph, int pw,
+                            const ymi_tensor* add1, const ymi_tensor* add2, const ymi_tensor* mul, int32_t mul_act, const ymi_tensor* dx, IgemmArgs* out) {
+    YMI_CHECK_ARG(ymi_tensor_ok(dy) && ymi_tensor_ok(dx) && w_class, "%s: bad tensor", who);
     if (mul) {
         const int epc = (int)(16 / ymi_esize(dx->dtype));
         YMI_CHECK_ARG(ymi_tensor_ok(mul) && ymi_same_shape(mul, dx) && mul->dtype == dx->dtype && mul->ld % 4 == 0 &&
                           ((uintptr_t)mul->data) % (4 * ymi_esize(dx->dtype)) == 0 && dx->ld % epc == 0 && ((uintptr_t)dx->data & 15) == 0 && cin % epc == 0,
-                      "conv2d_bwd_data: the multiplier needs the output's shape and 16-byte-aligned output rows");
+                      "%s: the multiplier needs the output's shape and 16-byte-aligned output rows", who);
     }
     if (add1 || add2) {
-        YMI_CHECK_ARG(add1 && ymi_tensor_ok(add1) && ymi_same_shape(add1, dx) && add1->dtype == dx->dtype, "conv2d_bwd_data_add: first addend");
-        YMI_CHECK_ARG(!add2 || (ymi_tensor_ok(add2) && ymi_same_shape(add2, dx) && add2->dtype == dx->dtype), "conv2d_bwd_data_add: second addend");
+        YMI_CHECK_ARG(add1 && ymi_tensor_ok(add1) && ymi_same_shape(add1, dx) && add1->dtype == dx->dtype, "%s: first addend", who);
+        YMI_CHECK_ARG(!add2 || (ymi_tensor_ok(add2) && ymi_same_shape(add2, dx) && add2->dtype == dx->dtype), "%s: second addend", who);
     }
-    YMI_CHECK_ARG(dy->dtype == dx->dtype, "conv2d_bwd_data: dtype mismatch");
+    YMI_CHECK_ARG(dy->dtype == dx->dtype, "%s: dtype mismatch", who);
     const int ch = dy->dtype == YMI_BF16 ? 8 : 4;
-    YMI_CHECK_ARG(dy->c % ch == 0 && dy->ld % ch == 0, "conv2d_bwd_data: dy channels must be a multiple of %d", ch);
-    YMI_CHECK_ARG(kh == kw && (kh == 1 || kh == 3) && (stride == 1 || stride == 2), "conv2d_bwd_data: k in {1,3}, stride in {1,2}");
+    YMI_CHECK_ARG(dy->c % ch == 0 && dy->ld % ch == 0, "%s: dy channels must be a multiple of %d", who, ch);
+    YMI_CHECK_ARG(kh == kw && (kh == 1 || kh == 3) && (stride == 1 || stride == 2), "%s: k in {1,3}, stride in {1,2}", who);
     const int64_t pad = kh / 2;
     YMI_CHECK_ARG(dx->c == cin && dx->n == dy->n && dy->h == (dx->h + 2 * pad - kh) / stride + 1 && dy->w == (dx->w + 2 * pad - kw) / stride + 1,
-                  "conv2d_bwd_data: shapes");
-    YMI_CHECK_ARG(ymi_pixels(dx) * dx->ld < (1ll << 31) && ymi_pixels(dy) * dy->ld < (1ll << 31), "conv2d_bwd_data: too large");
+                  "%s: shapes", who);
+    YMI_CHECK_ARG(ymi_pixels(dx) * dx->ld < (1ll << 31) && ymi_pixels(dy) * dy->ld < (1ll << 31), "%s: too large", who);
     const size_t es = ymi_esize(dy->dtype);
+    int dh[9], dw[9], nt = 0;
+    for (int i = 0; i < kh; ++i)
+        for (int j = 0; j < kw; ++j) {
+            const int nh = ph + (int)pad - i, nw = pw + (int)pad - j;
+            if (nh % (int)stride != 0 || nw % (int)stride != 0) continue;
+            dh[nt] = nh / (int)stride; dw[nt] = nw / (int)stride; ++nt;
+        }
+    const int64_t ho = (dx->h - ph + stride - 1) / stride, wo = (dx->w - pw + stride - 1) / stride;
+    IgemmArgs a{};
+    a.x = dy->data; a.w = w_class; a.y = dx->data; a.zero = ymi_zero_page();
+    a.ldx = dy->ld; a.ldy = dx->ld;
+    a.res = add1 ? add1->data : nullptr; a.ldres = add1 ? add1->ld : 0;
+    a.res2 = add2 ? add2->data : nullptr; a.ldres2 = add2 ? add2->ld : 0;
+    a.M = (int)(dx->n * ho * wo); a.H = (int)dy->h; a.W = (int)dy->w; a.Ho = (int)ho; a.Wo = (int)wo; a.Hy = (int)dx->h; a.Wy = (int)dx->w;
+    a.s_in = 1; a.s_out = (int)stride; a.oh_off = ph; a.ow_off = pw;
+    a.Cout = (int)cin; a.cpt = (int)(dy->c / ch); a.ntaps = nt; a.KC = nt * a.cpt; a.ktot = (int64_t)a.KC * ch;
+    pack_taps(dh, dw, nt, &a.tap_dh, &a.tap_dw);
+    a.act = YMI_ACT_NONE;
+    a.mul = mul ? mul->data : nullptr; a.ldmul = mul ? mul->ld : 0; a.mul_act = mul_act;
+    a.vec_store = (dx->ld % 4 == 0) && (((uintptr_t)dx->data) % (4 * es) == 0) &&
+                  (!add1 || (add1->ld % 4 == 0 && ((uintptr_t)add1->data) % (4 * es) == 0)) &&
+                  (!add2 || (add2->ld % 4 == 0 && ((uintptr_t)add2->data) % (4 * es) == 0));
+    finish_args(a, dx);
+    *out = a;
+    return YMI_OK;
+}
+
+static int dgrad_impl(const ymi_tensor* dy, const void* w_dgrad_packed, int64_t cin, int64_t kh, int64_t kw, int64_t stride,
+                      const ymi_tensor* add1, const ymi_tensor* add2, const ymi_tensor* mul, int32_t mul_act, const ymi_tensor* dx, void* stream) {
+    YMI_CHECK_ARG(dy && w_dgrad_packed, "conv2d_bwd_data: bad tensor");
     const char* wbase = reinterpret_cast<const char*>(w_dgrad_packed);
-    int64_t woff = 0;  // elements
+    int64_t woff = 0;  // elements: the classes' operands lie one after another (they partition the taps)
     const int nclass = stride == 1 ? 1 : 4;
     IgemmArgs classes[4];
     int nlaunch = 0;
     for (int cls = 0; cls < nclass; ++cls) {
-        const int ph = stride == 1 ? 0 : cls / 2, pw = stride == 1 ? 0 : cls % 2;
-        int dh[9], dw[9], nt = 0;
-        for (int i = 0; i < kh; ++i)
-            for (int j = 0; j < kw; ++j) {
-                const int nh = ph + (int)pad - i, nw = pw + (int)pad - j;
-                if (nh % (int)stride != 0 || nw % (int)stride != 0) continue;
-                dh[nt] = nh / (int)stride; dw[nt] = nw / (int)stride; ++nt;
-            }
-        const int64_t ho = (dx->h - ph + stride - 1) / stride, wo = (dx->w - pw + stride - 1) / stride;
-        if (nt > 0 && ho > 0 && wo > 0) {
-            IgemmArgs a{};
-            a.x = dy->data; a.w = wbase + woff * es; a.y = dx->data; a.zero = ymi_zero_page();
-            a.ldx = dy->ld; a.ldy = dx->ld;
-            a.res = add1 ? add1->data : nullptr; a.ldres = add1 ? add1->ld : 0;
-            a.res2 = add2 ? add2->data : nullptr; a.ldres2 = add2 ? add2->ld : 0;
-            a.M = (int)(dx->n * ho * wo); a.H = (int)dy->h; a.W = (int)dy->w; a.Ho = (int)ho; a.Wo = (int)wo; a.Hy = (int)dx->h; a.Wy = (int)dx->w;
-            a.s_in = 1; a.s_out = (int)stride; a.oh_off = ph; a.ow_off = pw;
-            a.Cout = (int)cin; a.cpt = (int)(dy->c / ch); a.ntaps = nt; a.KC = nt * a.cpt; a.ktot = (int64_t)a.KC * ch;
-            pack_taps(dh, dw, nt, &a.tap_dh, &a.tap_dw);
-            a.act = YMI_ACT_NONE;
-            a.mul = mul ? mul->data : nullptr; a.ldmul = mul ? mul->ld : 0; a.mul_act = mul_act;
-            a.vec_store = (dx->ld % 4 == 0) && (((uintptr_t)dx->data) % (4 * es) == 0) &&
-                          (!add1 || (add1->ld % 4 == 0 && ((uintptr_t)add1->data) % (4 * es) == 0)) &&
-                          (!add2 || (add2->ld % 4 == 0 && ((uintptr_t)add2->data) % (4 * es) == 0));
-            finish_args(a, dx, nullptr);
+        IgemmArgs a;
+        int rc = dgrad_class_args("conv2d_bwd_data", dy, wbase + woff * ymi_esize(dy->dtype), cin, kh, kw, stride, cls / 2, cls % 2,
+                                  add1, add2, mul, mul_act, dx, &a);
+        if (rc) return rc;
+        if (a.ntaps > 0 && a.M > 0) {
             classes[nlaunch++] = a;
-        } else if (ho > 0 && wo > 0) {
+        } else if (a.M > 0 && (add1 || add2)) {
             // a parity class no tap reaches (k = 1, stride 2: three of the four classes): its pixels receive no gradient.  They are left
             // as the caller prepared them - the contract of this case: dx pre-filled with zeros, addends applied by the caller
-            if (add1 || add2) {
-                ymi_set_error("conv2d_bwd_data: epilogue addends are not available when a parity class has no taps (k=1 stride=2): add them separately");
-                return YMI_EINVAL;
-            }
+            ymi_set_error("conv2d_bwd_data: epilogue addends are not available when a parity class has no taps (k=1 stride=2): add them separately");
+            return YMI_EINVAL;
         }
-        woff += (int64_t)nt * dy->c * cin;
+        woff += (int64_t)a.ntaps * dy->c * cin;
     }
     // the parity classes of a stride-2 data gradient as ONE multi-problem launch (measured: pays from 64 output channels up; the
     // 32-channel layer 1 is 6 % faster class by class)
@@ -1225,46 +1220,24 @@ static int dgrad_impl(const ymi_tensor* dy, const void* w_dgrad_packed, int64_t 
     return YMI_OK;
 }
 
-// Several independent stride-1 data gradients in one launch (ymi_conv2d_fwd_multi's counterpart; each problem may carry its epilogue addends).
-static int dgrad_args_s1(const ymi_tensor* dy, const void* w_dgrad_packed, int64_t cin, int64_t k, const ymi_tensor* add1, const ymi_tensor* add2, const ymi_tensor* dx, IgemmArgs* out) {
-    YMI_CHECK_ARG(ymi_tensor_ok(dy) && ymi_tensor_ok(dx) && w_dgrad_packed, "conv2d_bwd_data_multi: bad tensor");
-    if (add1 || add2) {
-        YMI_CHECK_ARG(add1 && ymi_tensor_ok(add1) && ymi_same_shape(add1, dx) && add1->dtype == dx->dtype, "conv2d_bwd_data_multi: first addend");
-        YMI_CHECK_ARG(!add2 || (ymi_tensor_ok(add2) && ymi_same_shape(add2, dx) && add2->dtype == dx->dtype), "conv2d_bwd_data_multi: second addend");
-    }
-    YMI_CHECK_ARG(dy->dtype == dx->dtype, "conv2d_bwd_data_multi: dtype mismatch");
-    const int ch = dy->dtype == YMI_BF16 ? 8 : 4;
-    YMI_CHECK_ARG(dy->c % ch == 0 && dy->ld % ch == 0 && (k == 1 || k == 3), "conv2d_bwd_data_multi: dy channels in whole chunks, k in {1, 3}");
-    YMI_CHECK_ARG(dx->c == cin && dx->n == dy->n && dy->h == dx->h && dy->w == dx->w, "conv2d_bwd_data_multi: shapes (stride 1)");
-    YMI_CHECK_ARG(ymi_pixels(dx) * dx->ld < (1ll << 31) && ymi_pixels(dy) * dy->ld < (1ll << 31), "conv2d_bwd_data_multi: too large");
-    const size_t es = ymi_esize(dy->dtype);
-    const int pad = (int)k / 2;
-    int dh[9], dw[9], nt = 0;
-    for (int i = 0; i < k; ++i)
-        for (int j = 0; j < k; ++j) { dh[nt] = pad - i; dw[nt] = pad - j; ++nt; }
-    IgemmArgs a{};
-    a.x = dy->data; a.w = w_dgrad_packed; a.y = dx->data; a.zero = ymi_zero_page();
-    a.ldx = dy->ld; a.ldy = dx->ld;
-    a.res = add1 ? add1->data : nullptr; a.ldres = add1 ? add1->ld : 0;
-    a.res2 = add2 ? add2->data : nullptr; a.ldres2 = add2 ? add2->ld : 0;
-    a.M = (int)ymi_pixels(dx); a.H = (int)dy->h; a.W = (int)dy->w; a.Ho = (int)dx->h; a.Wo = (int)dx->w; a.Hy = (int)dx->h; a.Wy = (int)dx->w;
-    a.s_in = 1; a.s_out = 1; a.oh_off = 0; a.ow_off = 0;
-    a.Cout = (int)cin; a.cpt = (int)(dy->c / ch); a.ntaps = nt; a.KC = nt * a.cpt; a.ktot = (int64_t)a.KC * ch;
-    pack_taps(dh, dw, nt, &a.tap_dh, &a.tap_dw);
-    a.act = YMI_ACT_NONE;
-    a.vec_store = (dx->ld % 4 == 0) && (((uintptr_t)dx->data) % (4 * es) == 0) && (!add1 || (add1->ld % 4 == 0 && ((uintptr_t)add1->data) % (4 * es) == 0)) &&
-                  (!add2 || (add2->ld % 4 == 0 && ((uintptr_t)add2->data) % (4 * es) == 0));
-    finish_args(a, dx, nullptr);
-    *out = a;
-    return YMI_OK;
+extern "C" int ymi_conv2d_bwd_data_add(const ymi_tensor* dy, const void* w_dgrad_packed, int64_t cin, int64_t kh, int64_t kw,
+                                       int64_t stride, const ymi_tensor* add1, const ymi_tensor* add2, const ymi_tensor* dx, void* stream) {
+    return dgrad_impl(dy, w_dgrad_packed, cin, kh, kw, stride, add1, add2, nullptr, YMI_ACT_NONE, dx, stream);
 }
+
+extern "C" int ymi_conv2d_bwd_data(const ymi_tensor* dy, const void* w_dgrad_packed, int64_t cin, int64_t kh, int64_t kw,
+                                   int64_t stride, const ymi_tensor* dx, void* stream) {
+    return ymi_conv2d_bwd_data_add(dy, w_dgrad_packed, cin, kh, kw, stride, nullptr, nullptr, dx, stream);
+}
+
+// Several independent stride-1 data gradients in one launch (ymi_conv2d_fwd_multi's counterpart; each problem may carry its epilogue addends).
 extern "C" int ymi_conv2d_bwd_data_multi(const ymi_dgrad_problem* problems, int32_t n, void* stream) {
     YMI_CHECK_ARG(problems && n >= 1 && n <= IGEMM_MAX_PROBLEMS, "conv2d_bwd_data_multi: 1..%d problems", IGEMM_MAX_PROBLEMS);
     IgemmArgs arr[IGEMM_MAX_PROBLEMS];
     for (int i = 0; i < n; ++i) {
         const ymi_dgrad_problem& p = problems[i];
         YMI_CHECK_ARG(p.dy && p.dx && p.dy->dtype == problems[0].dy->dtype, "conv2d_bwd_data_multi: problem %d", i);
-        int rc = dgrad_args_s1(p.dy, p.w_dgrad_packed, p.cin, p.k, p.add1, p.add2, p.dx, &arr[i]);
+        int rc = dgrad_class_args("conv2d_bwd_data_multi", p.dy, p.w_dgrad_packed, p.cin, p.k, p.k, 1, 0, 0, p.add1, p.add2, nullptr, YMI_ACT_NONE, p.dx, &arr[i]);
         if (rc) return rc;
     }
     return launch_igemm_n(arr, n, problems[0].dy->dtype, false, nullptr, (hipStream_t)stream, true);

@@ -24,10 +24,10 @@ from .weights import (  # noqa: F401
     pack_conv_fwd, pack_conv_fwd_pair, set_weight_arena, wgrad_riders,
 )
 from .conv import (  # noqa: F401
-    _ChanSlice, _ChanSplit2, _ConvAffineAct, _ConvBnAct, _ConvBnActPair, _DT, _DetectTrain, _FirstConvBnAct, _conv_fwd_multi,
-    _dgrad, _dgrad_finish, _dgrad_joined, _dgrad_joined_finish, _dgrad_joined_prepare, _dgrad_launch, _dgrad_multi, _dgrad_prepare, _width_class,
-    chan_split2, conv_affine_act, conv_bn_act, conv_bn_act_pair, detect_train, detect_train_ok, first_conv_bn_act,
-    first_conv_ok, linear, padded_grad_like,
+    DgradJob, FwdProblem, _ChanSlice, _ChanSplit2, _ConvAffineAct, _ConvBnAct, _ConvBnActPair, _DetectTrain, _FirstConvBnAct, _Level, _bn_act_bwd,
+    _conv_fwd_multi, _detect_args, _detect_grads, _dgrad, _dgrad_finish, _dgrad_joined, _dgrad_joined_finish, _dgrad_joined_prepare, _dgrad_launch,
+    _dgrad_multi, _dgrad_prepare, _per_level, _width_class, chan_split2, conv_affine_act, conv_bn_act, conv_bn_act_pair, detect_train, detect_train_ok,
+    first_conv_bn_act, first_conv_ok, linear, padded_grad_like,
 )
 from .blocks import (  # noqa: F401
     _Act, _AddResidual, _C2fSplit, _Cbam, _Concat, _DetectLoss, _LayerNorm, _SppfPool, _SwinLnMlp, _SwinMlp, _Upsample2x, _WindowAttention,

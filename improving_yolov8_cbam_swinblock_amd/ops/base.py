@@ -267,7 +267,7 @@ def _join_plain(join, g):
     return _accumulate(total, adds)
 
 
-def _prep_adds(adds, dtype, like4d):
+def _prep_adds(adds, dtype):
     """addends as tensors the epilogue can read: same dtype, NHWC memory (4-D) / unit channel stride (2-D)."""
     out = []
     for a in adds or ():

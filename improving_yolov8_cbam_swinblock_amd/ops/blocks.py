@@ -58,7 +58,7 @@ class _SwinMlp(torch.autograd.Function):
         dpre = torch.empty_like(pre)
         need_du = ctx.needs_input_grad[0]
         adds = (join.arrive() if join is not None else []) if need_du else []
-        fa = _prep_adds(adds, dtype, False)
+        fa = _prep_adds(adds, dtype)
         du = torch.empty((t, c), dtype=dtype, device=u.device) if need_du else None
         w2d = pack_conv_dgrad(w2, w2.shape[0], 1, dtype)
         w1d = pack_conv_dgrad(w1, hidden, 1, dtype) if need_du else None
@@ -465,7 +465,7 @@ class _LayerNorm(torch.autograd.Function):
         dgb = torch.empty((2, c), dtype=torch.float32, device=dev)
         wsb = workspace(2048 * 2 * c * 4 + 256, dev, "ln")
         adds = ctx.join.arrive() if ctx.join is not None else []
-        fa = _prep_adds(adds, x.dtype, ws > 0)
+        fa = _prep_adds(adds, x.dtype)
         if ws > 0 and fa and fa[0].shape != x.shape:
             raise RuntimeError("layernorm backward: addend shape")
         check(

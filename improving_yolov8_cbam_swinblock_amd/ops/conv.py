@@ -2,46 +2,61 @@
 the direct first layer, Detect's sibling pairs and its lockstep training path, biased convolutions / linears (reference: nn/modules/conv.py:37-91,
 nn/modules/head.py:36-76)."""
 import ctypes
-import os
+from collections import namedtuple
+from dataclasses import make_dataclass
 
 import torch
 
 from .. import _lib
-from .._lib import ACT_GELU, ACT_NONE, ACT_SILU, ConvProblem, DgradProblem, as_ymi, check, chunk_elems, empty_nhwc, is_nhwc, ptr, stream_ptr, workspace, ymi_dtype
-from .base import (  # noqa: F401
+from .._lib import ACT_NONE, ACT_SILU, ConvProblem, DgradProblem, as_ymi, check, chunk_elems, empty_nhwc, is_nhwc, ptr, stream_ptr, workspace
+from .base import (
     HOOKS, RUN, L, _GradBuffer, _GradSlot, _accumulate, _as4d, _byref, _conv_out_hw, _count_batch, _deferred_twice, _dense_ok, _in_backward,
     _join_plain, _note_use, _prep_adds, _stat_acc, compute_dtype, grad_nhwc, join_of, mark_join, round_up,
 )
-from .weights import (  # noqa: F401
+from .weights import (
     _adoptable, _defer_wgrad, _new_dw, _wgrad_maybe_async, pack_conv_dgrad, pack_conv_dgrad_pair, pack_conv_fwd, pack_conv_fwd_pair,
 )
 
+# One data-gradient GEMM, prepared (_dgrad_prepare) and not yet launched: dy and its descriptor ty, the packed operand wd, cin / k / stride, the
+# addends of the GEMM's epilogue (fused: at most two) and those beyond them (rest: accumulate launches after the GEMM), the result dx that is
+# handed out (input channels zero-padded) and dxv = dx[:, :cin], which the kernel writes.
+DgradJob = namedtuple("DgradJob", "dy ty wd cin k stride fused rest dx dxv")
+# One stride-1 convolution of _conv_fwd_multi: input, packed forward operand, output width, kernel size, output; optionally a bias, or its
+# statistics rows (part / pstride / poff: see ymi_conv_problem).  blocks: the statistics rows written, filled in by _conv_fwd_multi.
+FwdProblem = make_dataclass("FwdProblem", ["x", "wp", "cout", "k", "y", ("bias", object, None), ("part", object, None), ("pstride", int, 0), ("poff", int, 0),
+                                           ("blocks", int, 0)])
+
+
 def _dgrad_prepare(dy, weight4, k, stride, in_shape, dtype, adds=None, out=None, packed=None):
-    """the arguments of one data-gradient GEMM (see _dgrad) -> job dict; _dgrad_finish completes it after the launch."""
-    n, cp, h, w = in_shape
+    """the arguments of one data-gradient GEMM (see _dgrad) -> DgradJob; _dgrad_finish completes it after the launch.
+    in_shape: [N, C_in(padded), H, W], or [T, C_in] of a token matrix (k = 1, stride 1)."""
+    shape = tuple(in_shape)
+    cp = shape[1]
     ty = as_ymi(dy)
     if packed is not None:
         wd, cin = packed
     else:
         cin = weight4.shape[1]
         wd = pack_conv_dgrad(weight4, ty.c, stride, dtype)
-    dx = out if (out is not None and tuple(out.shape) == (n, cp, h, w) and cp == cin) else empty_nhwc(n, cp, h, w, dtype, dy.device)
+    dx = out if (out is not None and tuple(out.shape) == shape and cp == cin) else None
+    if dx is None:
+        dx = empty_nhwc(*shape, dtype, dy.device) if len(shape) == 4 else torch.empty(shape, dtype=dtype, device=dy.device)
     dxv = dx
     if cp != cin:
         dx.zero_()
         dxv = dx[:, :cin]
-    adds = _prep_adds(adds, dtype, True)
+    adds = _prep_adds(adds, dtype)
     sparse = k == 1 and stride > 1  # pixels between the strides receive no gradient: the kernel leaves them as prepared here (zeros)
     if sparse and cp == cin:
         dx.zero_()  # (_dgrad_joined never passes an in-place `out` in this case)
     fused = adds[:2] if (cp == cin and not sparse) else []
-    return {"dy": dy, "ty": ty, "wd": wd, "cin": cin, "k": k, "stride": stride, "fused": fused, "rest": adds[len(fused):], "dx": dx, "dxv": dxv}
+    return DgradJob(dy, ty, wd, cin, k, stride, fused, adds[len(fused):], dx, dxv)
 
 
 def _dgrad_finish(job):
-    if job["rest"]:
-        _accumulate(job["dxv"], job["rest"])
-    return job["dx"]
+    if job.rest:
+        _accumulate(job.dxv, job.rest)
+    return job.dx
 
 
 def _dgrad(dy, weight4, k, stride, in_shape, dtype, adds=None, out=None, packed=None):
@@ -53,11 +68,9 @@ def _dgrad(dy, weight4, k, stride, in_shape, dtype, adds=None, out=None, packed=
 
 
 def _dgrad_launch(j):
-    fused = j["fused"]
-    a1 = _byref(as_ymi(fused[0])) if len(fused) > 0 else None
-    a2 = _byref(as_ymi(fused[1])) if len(fused) > 1 else None
-    check(L().ymi_conv2d_bwd_data_add(_byref(j["ty"]), ptr(j["wd"]), j["cin"], j["k"], j["k"], j["stride"], a1, a2, _byref(as_ymi(j["dxv"])), stream_ptr()),
-          "conv2d_bwd_data")
+    a1 = _byref(as_ymi(j.fused[0])) if len(j.fused) > 0 else None
+    a2 = _byref(as_ymi(j.fused[1])) if len(j.fused) > 1 else None
+    check(L().ymi_conv2d_bwd_data_add(_byref(j.ty), ptr(j.wd), j.cin, j.k, j.k, j.stride, a1, a2, _byref(as_ymi(j.dxv)), stream_ptr()), "conv2d_bwd_data")
     return _dgrad_finish(j)
 
 
@@ -67,54 +80,55 @@ def _width_class(c, dtype):
     return (cpt % 4 == 0, cpt % 8 == 0)
 
 
-def _dgrad_multi(jobs, dtype):
-    """the stride-1 data-gradient GEMMs of several INDEPENDENT convolutions (jobs of _dgrad_prepare), one launch per width class."""
+def _launch_grouped(items, key, struct, fill, entry, what):
+    """one launch of a multi-problem entry point per group of items of equal key(item), at most 8 problems a launch.  fill(q, item) sets
+    the ctypes record q and returns what q points to (kept alive until the call returns).  -> [(item, q)] of everything launched."""
     groups = {}
-    for j in jobs:
-        if j["stride"] != 1:
-            raise RuntimeError("_dgrad_multi: stride 1 only")
-        groups.setdefault(_width_class(j["ty"].c, dtype), []).append(j)
+    for it in items:
+        groups.setdefault(key(it), []).append(it)
+    done = []
     for g in groups.values():
         for s in range(0, len(g), 8):
             chunk = g[s : s + 8]
-            arr = (DgradProblem * len(chunk))()
-            keep = []
-            for q, j in zip(arr, chunk):
-                ts = [j["ty"], as_ymi(j["dxv"])] + [as_ymi(a) for a in j["fused"]]
-                keep.append(ts)
-                q.dy, q.dx = ctypes.pointer(ts[0]), ctypes.pointer(ts[1])
-                q.w_dgrad_packed, q.cin, q.k = j["wd"].data_ptr(), j["cin"], j["k"]
-                if len(ts) > 2:
-                    q.add1 = ctypes.pointer(ts[2])
-                if len(ts) > 3:
-                    q.add2 = ctypes.pointer(ts[3])
-            check(L().ymi_conv2d_bwd_data_multi(arr, len(chunk), stream_ptr()), "conv2d_bwd_data_multi")
+            arr = (struct * len(chunk))()
+            keep = [fill(q, it) for q, it in zip(arr, chunk)]  # noqa: F841 (alive across the call)
+            check(entry(arr, len(chunk), stream_ptr()), what)
+            done += zip(chunk, arr)
+    return done
+
+
+def _fill_dgrad(q, j):
+    ts = [j.ty, as_ymi(j.dxv)] + [as_ymi(a) for a in j.fused]
+    for name, t in zip(("dy", "dx", "add1", "add2"), ts):
+        setattr(q, name, ctypes.pointer(t))
+    q.w_dgrad_packed, q.cin, q.k = j.wd.data_ptr(), j.cin, j.k
+    return ts
+
+
+def _fill_fwd(q, p):
+    ts = [as_ymi(p.x), as_ymi(p.y)]
+    q.x, q.y = ctypes.pointer(ts[0]), ctypes.pointer(ts[1])
+    q.w_packed, q.cout, q.kh, q.kw, q.stride, q.act = p.wp.data_ptr(), p.cout, p.k, p.k, 1, ACT_NONE
+    if p.bias is not None:
+        q.bias = p.bias.data_ptr()
+    if p.part is not None:
+        q.stat_partials, q.stat_stride, q.stat_offset = p.part.data_ptr(), p.pstride, p.poff
+    return ts
+
+
+def _dgrad_multi(jobs, dtype):
+    """the stride-1 data-gradient GEMMs of several INDEPENDENT convolutions (jobs of _dgrad_prepare), one launch per width class."""
+    if any(j.stride != 1 for j in jobs):
+        raise RuntimeError("_dgrad_multi: stride 1 only")
+    _launch_grouped(jobs, lambda j: _width_class(j.ty.c, dtype), DgradProblem, _fill_dgrad, L().ymi_conv2d_bwd_data_multi, "conv2d_bwd_data_multi")
     return [_dgrad_finish(j) for j in jobs]
 
 
 def _conv_fwd_multi(problems, dtype):
-    """several INDEPENDENT stride-1 convolutions, one launch per width class.  problems: dicts x, wp, cout, k, y and optionally bias, or
-    part / pstride / poff (statistics rows, see ymi_conv_problem); 'blocks' (statistics rows written) is filled in."""
-    groups = {}
-    for p in problems:
-        groups.setdefault((_width_class(p["x"].shape[1], dtype), p.get("part") is not None), []).append(p)
-    for g in groups.values():
-        for s in range(0, len(g), 8):
-            chunk = g[s : s + 8]
-            arr = (ConvProblem * len(chunk))()
-            keep = []
-            for q, p in zip(arr, chunk):
-                tx, ty = as_ymi(p["x"]), as_ymi(p["y"])
-                keep.append((tx, ty))
-                q.x, q.y = ctypes.pointer(tx), ctypes.pointer(ty)
-                q.w_packed, q.cout, q.kh, q.kw, q.stride, q.act = p["wp"].data_ptr(), p["cout"], p["k"], p["k"], 1, ACT_NONE
-                if p.get("bias") is not None:
-                    q.bias = p["bias"].data_ptr()
-                if p.get("part") is not None:
-                    q.stat_partials, q.stat_stride, q.stat_offset = p["part"].data_ptr(), p.get("pstride", 0), p.get("poff", 0)
-            check(L().ymi_conv2d_fwd_multi(arr, len(chunk), stream_ptr()), "conv2d_fwd_multi")
-            for q, p in zip(arr, chunk):
-                p["blocks"] = int(q.stat_blocks)
+    """several INDEPENDENT stride-1 convolutions (FwdProblem), one launch per width class and statistics mode; fills in their `blocks`."""
+    for p, q in _launch_grouped(problems, lambda p: (_width_class(p.x.shape[1], dtype), p.part is not None), ConvProblem, _fill_fwd,
+                                L().ymi_conv2d_fwd_multi, "conv2d_fwd_multi"):
+        p.blocks = int(q.stat_blocks)
 
 
 def _dgrad_joined_prepare(join, dy, weight4, k, stride, in_shape, dtype, packed=None):
@@ -150,6 +164,30 @@ def _dgrad_joined(join, dy, weight4, k, stride, in_shape, dtype, packed=None):
     return _dgrad_joined_finish(join, _dgrad_launch(job), deposit)
 
 
+def _stat_ws_bytes(m, o):
+    """workspace of one train-mode BatchNorm over an [m, o] GEMM output: scale, shift and the statistics rows of every row block (float32)."""
+    return (L().ymi_conv2d_stat_blocks(m, o) * 2 * o + 2 * o) * 4
+
+
+def _bn_act_bwd(dout, raw, stats, act, gamma, beta, second=None):
+    """backward of act(BatchNorm_train(raw)) -> (draw, dgamma, dbeta).  second = (gamma_b, beta_b, oa): the channels from oa on belong to a
+    second BatchNorm with these parameters (two Conv blocks side by side in one buffer)."""
+    o, dev = raw.shape[1], raw.device
+    draw = empty_nhwc(*raw.shape, raw.dtype, dev)
+    # two separate tensors: AccumulateGrad adopts them as .grad without a clone (views would be copied)
+    dgamma = torch.empty(o, dtype=torch.float32, device=dev)
+    dbeta = torch.empty(o, dtype=torch.float32, device=dev)
+    ws = workspace(2048 * 2 * o * 4 + 256, dev, "bnbwd")
+    if second is None:
+        check(L().ymi_bn_act_bwd(_byref(as_ymi(dout)), _byref(as_ymi(raw)), ptr(gamma), ptr(stats[0]), ptr(stats[1]), ptr(beta), act,
+                                 _byref(as_ymi(draw)), ptr(dgamma), ptr(dbeta), ptr(ws), ws.numel(), stream_ptr()), "bn_act_bwd")
+    else:
+        gamma_b, beta_b, oa = second
+        check(L().ymi_bn_act_bwd_pair(_byref(as_ymi(dout)), _byref(as_ymi(raw)), ptr(gamma), ptr(beta), ptr(gamma_b), ptr(beta_b), oa, ptr(stats[0]), ptr(stats[1]),
+                                      act, _byref(as_ymi(draw)), ptr(dgamma), ptr(dbeta), ptr(ws), ws.numel(), stream_ptr()), "bn_act_bwd_pair")
+    return draw, dgamma, dbeta
+
+
 class _ConvBnAct(torch.autograd.Function):
     """act(BatchNorm_train(conv(x))) (+ residual).  Reference: Conv.forward, nn/modules/conv.py:69-79
     (+ Bottleneck add, nn/modules/block.py:488)."""
@@ -166,9 +204,7 @@ class _ConvBnAct(torch.autograd.Function):
         raw = empty_nhwc(n, o, ho, wo, dtype, dev)
         out = slot.view(n, o, ho, wo, dtype) if slot is not None else empty_nhwc(n, o, ho, wo, dtype, dev)
         stats = torch.empty((2, o), dtype=torch.float32, device=dev)
-        m = n * ho * wo
-        need = (L().ymi_conv2d_stat_blocks(m, o) * 2 * o + 2 * o) * 4
-        ws = workspace(need, dev, "conv")
+        ws = workspace(_stat_ws_bytes(n * ho * wo, o), dev, "conv")
         res = residual
         tres = _byref(as_ymi(res)) if res is not None else None
         if (HOOKS["stat_atomics"] and o % 4 == 0 and L().ymi_conv2d_bn_silu_fwd_acc_ok(_byref(as_ymi(raw)), _byref(as_ymi(out)), tres)
@@ -201,18 +237,8 @@ class _ConvBnAct(torch.autograd.Function):
         stride, act, cin, has_res = ctx.cfg
         dtype = x.dtype
         o, _, k, _ = weight.shape
-        dev = x.device
         dout = grad_nhwc(dout, dtype)
-        draw = empty_nhwc(*raw.shape, dtype, dev)
-        # two separate tensors: AccumulateGrad adopts them as .grad without a clone (views would be copied)
-        dgamma = torch.empty(o, dtype=torch.float32, device=dev)
-        dbeta = torch.empty(o, dtype=torch.float32, device=dev)
-        ws = workspace(2048 * 2 * o * 4 + 256, dev, "bnbwd")
-        check(
-            L().ymi_bn_act_bwd(_byref(as_ymi(dout)), _byref(as_ymi(raw)), ptr(gamma), ptr(stats[0]), ptr(stats[1]), ptr(beta), act,
-                               _byref(as_ymi(draw)), ptr(dgamma), ptr(dbeta), ptr(ws), ws.numel(), stream_ptr()),
-            "bn_act_bwd",
-        )
+        draw, dgamma, dbeta = _bn_act_bwd(dout, raw, stats, act, gamma, beta)
         join, res_join = ctx.joins
         # the residual hand-through first: when x is both the input and the residual (Bottleneck shortcut), the data
         # gradient below is then the join's last consumer and adds `dout` in its epilogue
@@ -375,9 +401,7 @@ class _ConvBnActPair(torch.autograd.Function):
         raw = empty_nhwc(n, o, ho, wo, dtype, dev)
         out = empty_nhwc(n, o, ho, wo, dtype, dev)
         stats = torch.empty((2, o), dtype=torch.float32, device=dev)
-        m = n * ho * wo
-        need = (L().ymi_conv2d_stat_blocks(m, o) * 2 * o + 2 * o) * 4
-        ws = workspace(need, dev, "conv")
+        ws = workspace(_stat_ws_bytes(n * ho * wo, o), dev, "conv")
         check(
             L().ymi_conv2d_bn_silu_fwd_pair(
                 _byref(as_ymi(x)), ptr(wp), o, oa, k, k, stride, ptr(ga), ptr(ba), ptr(rma), ptr(rva), ptr(gb), ptr(bb), ptr(rmb), ptr(rvb),
@@ -396,19 +420,9 @@ class _ConvBnActPair(torch.autograd.Function):
         stride, act, cin = ctx.cfg
         dtype = x.dtype
         oa, _, k, _ = wa.shape
-        ob = wb.shape[0]
-        o = oa + ob
-        dev = x.device
+        o = oa + wb.shape[0]
         dout = grad_nhwc(dout, dtype)
-        draw = empty_nhwc(*raw.shape, dtype, dev)
-        dgamma = torch.empty(o, dtype=torch.float32, device=dev)
-        dbeta = torch.empty(o, dtype=torch.float32, device=dev)
-        ws = workspace(2048 * 2 * o * 4 + 256, dev, "bnbwd")
-        check(
-            L().ymi_bn_act_bwd_pair(_byref(as_ymi(dout)), _byref(as_ymi(raw)), ptr(ga), ptr(ba), ptr(gb), ptr(bb), oa, ptr(stats[0]), ptr(stats[1]), act,
-                                    _byref(as_ymi(draw)), ptr(dgamma), ptr(dbeta), ptr(ws), ws.numel(), stream_ptr()),
-            "bn_act_bwd_pair",
-        )
+        draw, dgamma, dbeta = _bn_act_bwd(dout, raw, stats, act, ga, ba, (gb, bb, oa))
         dx = None
         if ctx.needs_input_grad[0]:
             wd = pack_conv_dgrad_pair(wa, wb, stride, dtype)
@@ -441,7 +455,42 @@ def conv_bn_act_pair(x, conv_a, bn_a, conv_b, bn_b, act=ACT_SILU):
     return out
 
 
-_DT = 25  # tensors per level of _DetectTrain: x, 4 x (weight, gamma, beta, running_mean, running_var), 2 x (weight, bias)
+# One level of the Detect head as _DetectTrain takes it: the level's input, the four Conv blocks a0 = cv2[i][0], b0 = cv3[i][0], a1 = cv2[i][1],
+# b1 = cv3[i][1] (convolution weight, BatchNorm gamma, beta, running mean, running variance) and the biased 1x1 outputs oa = cv2[i][2], ob = cv3[i][2].
+# The argument order of forward, the gradient order of backward and the count per level all come from this one list.
+_Level = namedtuple("_Level", """x
+    a0_w a0_gamma a0_beta a0_mean a0_var
+    b0_w b0_gamma b0_beta b0_mean b0_var
+    a1_w a1_gamma a1_beta a1_mean a1_var
+    b1_w b1_gamma b1_beta b1_mean b1_var
+    oa_w oa_bias ob_w ob_bias""")
+# what backward needs of a level: these arguments, then per BatchNorm stage the raw convolution output, the batch statistics and the activated output
+_SAVED_ARGS = "x a0_w b0_w a0_gamma a0_beta b0_gamma b0_beta a1_w b1_w a1_gamma a1_beta b1_gamma b1_beta oa_w ob_w".split()
+_Saved = namedtuple("_Saved", _SAVED_ARGS + "raw1 st1 h1 raw2 st2 h2".split())
+# a level's sizes: input [n, cp, h, w], branch widths c2 / c3 (o = c2 + c3 side by side in one buffer), m = n * h * w rows, and its place in the workspace
+_Geo = namedtuple("_Geo", "n cp h w c2 c3 o m ws_off stat_bytes")
+
+
+def _per_level(rec, flat, nl):
+    """flat: nl consecutive groups of len(rec._fields) values -> [rec] per level."""
+    n = len(rec._fields)
+    return [rec._make(flat[l * n : (l + 1) * n]) for l in range(nl)]
+
+
+def _detect_args(xs, levels):
+    """-> the tensor arguments of _DetectTrain: per level the fields of _Level.  levels: per level (cv2[i][0], cv3[i][0], cv2[i][1], cv3[i][1], cv2[i][2], cv3[i][2])."""
+    t = []
+    for x, (a0, b0, a1, b1, oa, ob) in zip(xs, levels):
+        t.append(x)
+        for m in (a0, b0, a1, b1):
+            t += [m.conv.weight, m.bn.weight, m.bn.bias, m.bn.running_mean, m.bn.running_var]
+        t += [oa.weight, oa.bias, ob.weight, ob.bias]
+    return t
+
+
+def _detect_grads(per_level):
+    """what _DetectTrain.backward returns: None for `meta`, then one entry per field of _Level and level (per_level: dicts field -> gradient; absent: None)."""
+    return (None,) + tuple(g for d in per_level for g in _Level(**{**dict.fromkeys(_Level._fields), **d}))
 
 
 class _DetectTrain(torch.autograd.Function):
@@ -455,172 +504,154 @@ class _DetectTrain(torch.autograd.Function):
     @staticmethod
     def forward(ctx, meta, *t):
         nl, eps, momentum, joins, ncpad = meta
-        lv = [t[l * _DT : (l + 1) * _DT] for l in range(nl)]
-        dtype, dev = lv[0][0].dtype, lv[0][0].device
+        lv = _per_level(_Level, t, nl)
+        dtype, dev = lv[0].x.dtype, lv[0].x.device
         lib = L()
-        geo, bufs = [], []
+        geo = []
         need = 0
         for v in lv:
-            n, cp, h, w = v[0].shape
-            c2, c3 = v[1].shape[0], v[6].shape[0]
-            o, m = c2 + c3, n * h * w
-            rows = lib.ymi_conv2d_stat_blocks(m, o)
-            geo.append((n, cp, h, w, c2, c3, o, m, need, rows))
-            need += 2 * (rows * 2 * o + 2 * o) * 4  # two BatchNorm stages: scale, shift, statistics rows
-            _note_use(v[1], v[6], v[11], v[16], v[21], v[23])
+            n, cp, h, w = v.x.shape
+            c2, c3 = v.a0_w.shape[0], v.b0_w.shape[0]
+            g = _Geo(n, cp, h, w, c2, c3, c2 + c3, n * h * w, need, _stat_ws_bytes(n * h * w, c2 + c3))
+            geo.append(g)
+            need += 2 * g.stat_bytes  # two BatchNorm stages
+            _note_use(v.a0_w, v.b0_w, v.a1_w, v.b1_w, v.oa_w, v.ob_w)
         ws = workspace(need, dev, "detect").view(torch.float32)
 
         def region(g, stage):
-            n, cp, h, w, c2, c3, o, m, off, rows = g
-            base = off // 4 + stage * (rows * 2 * o + 2 * o)
-            return ws[base : base + o], ws[base + o : base + 2 * o], ws[base + 2 * o : base + 2 * o + rows * 2 * o]
+            """-> scale, shift, statistics rows of a level's BatchNorm stage."""
+            base, o = (g.ws_off + stage * g.stat_bytes) // 4, g.o
+            return ws[base : base + o], ws[base + o : base + 2 * o], ws[base + 2 * o : base + g.stat_bytes // 4]
 
-        def bn_stage(probs_of_level, stage, raws, params):
-            """the multi-problem GEMM of a stage, then per level: statistics -> scale / shift, affine + SiLU."""
+        def bn_stage(probs_of_level, stage, raws, bns):
+            """the multi-problem GEMM of a stage, then per level: statistics -> scale / shift, affine + SiLU.  bns: per level (gamma, beta, running mean,
+            running variance) of the cv2 block, then of the cv3 block."""
             _conv_fwd_multi([p for ps in probs_of_level for p in ps], dtype)
             outs, stats = [], []
-            for g, ps, raw, (ga, ba, rma, rva, gb, bb, rmb, rvb) in zip(geo, probs_of_level, raws, params):
-                n, cp, h, w, c2, c3, o, m, off, rows = g
-                blocks = ps[0]["blocks"]
-                if any(p["blocks"] != blocks for p in ps):
+            for g, ps, raw, bn in zip(geo, probs_of_level, raws, bns):
+                blocks = ps[0].blocks
+                if any(p.blocks != blocks for p in ps):
                     raise RuntimeError("_DetectTrain: the convolutions of one BatchNorm group ran with different row tiles")
                 scale, shift, part = region(g, stage)
-                st = torch.empty((2, o), dtype=torch.float32, device=dev)
-                out = empty_nhwc(n, o, h, w, dtype, dev)
-                check(lib.ymi_bn_finalize_pair(ptr(part), blocks, m, o, c2, ptr(ga), ptr(ba), ptr(rma), ptr(rva), ptr(gb), ptr(bb), ptr(rmb), ptr(rvb),
-                                               momentum, eps, ptr(scale), ptr(shift), ptr(st[0]), ptr(st[1]), stream_ptr()), "bn_finalize_pair")
+                st = torch.empty((2, g.o), dtype=torch.float32, device=dev)
+                out = empty_nhwc(g.n, g.o, g.h, g.w, dtype, dev)
+                check(lib.ymi_bn_finalize_pair(ptr(part), blocks, g.m, g.o, g.c2, *map(ptr, bn), momentum, eps, ptr(scale), ptr(shift), ptr(st[0]), ptr(st[1]),
+                                               stream_ptr()), "bn_finalize_pair")
                 check(lib.ymi_scale_shift_act(_byref(as_ymi(raw)), ptr(scale), ptr(shift), ACT_SILU, None, _byref(as_ymi(out)), stream_ptr()), "scale_shift_act")
                 outs.append(out)
                 stats.append(st)
             return outs, stats
 
         # stage 1: the two first convolutions of a level as ONE (they read the same input)
-        raw1 = [empty_nhwc(g[0], g[6], g[2], g[3], dtype, dev) for g in geo]
-        probs = [[{"x": v[0], "wp": pack_conv_fwd_pair(v[1], v[6], g[1], dtype), "cout": g[6], "k": v[1].shape[2], "y": r, "part": region(g, 0)[2],
-                   "pstride": g[6], "poff": 0}] for v, g, r in zip(lv, geo, raw1)]
-        h1, st1 = bn_stage(probs, 0, raw1, [(v[2], v[3], v[4], v[5], v[7], v[8], v[9], v[10]) for v in lv])
+        raw1 = [empty_nhwc(g.n, g.o, g.h, g.w, dtype, dev) for g in geo]
+        probs = [[FwdProblem(v.x, pack_conv_fwd_pair(v.a0_w, v.b0_w, g.cp, dtype), g.o, v.a0_w.shape[2], r, part=region(g, 0)[2], pstride=g.o)]
+                 for v, g, r in zip(lv, geo, raw1)]
+        h1, st1 = bn_stage(probs, 0, raw1, [(v.a0_gamma, v.a0_beta, v.a0_mean, v.a0_var, v.b0_gamma, v.b0_beta, v.b0_mean, v.b0_var) for v in lv])
         # stage 2: the second convolutions read their half of h1 and write their half of one buffer; one BatchNorm pass over both
-        raw2 = [empty_nhwc(g[0], g[6], g[2], g[3], dtype, dev) for g in geo]
+        raw2 = [empty_nhwc(g.n, g.o, g.h, g.w, dtype, dev) for g in geo]
         probs = []
         for v, g, hh, r in zip(lv, geo, h1, raw2):
-            c2, c3, o = g[4], g[5], g[6]
+            c2, c3 = g.c2, g.c3
             part = region(g, 1)[2]
-            probs.append([{"x": hh[:, :c2], "wp": pack_conv_fwd(v[11], c2, dtype), "cout": c2, "k": v[11].shape[2], "y": r[:, :c2], "part": part, "pstride": o, "poff": 0},
-                          {"x": hh[:, c2:], "wp": pack_conv_fwd(v[16], c3, dtype), "cout": c3, "k": v[16].shape[2], "y": r[:, c2:], "part": part, "pstride": o, "poff": c2}])
-        h2, st2 = bn_stage(probs, 1, raw2, [(v[12], v[13], v[14], v[15], v[17], v[18], v[19], v[20]) for v in lv])
+            probs.append([FwdProblem(hh[:, :c2], pack_conv_fwd(v.a1_w, c2, dtype), c2, v.a1_w.shape[2], r[:, :c2], part=part, pstride=g.o, poff=0),
+                          FwdProblem(hh[:, c2:], pack_conv_fwd(v.b1_w, c3, dtype), c3, v.b1_w.shape[2], r[:, c2:], part=part, pstride=g.o, poff=c2)])
+        h2, st2 = bn_stage(probs, 1, raw2, [(v.a1_gamma, v.a1_beta, v.a1_mean, v.a1_var, v.b1_gamma, v.b1_beta, v.b1_mean, v.b1_var) for v in lv])
         # stage 3: the biased 1x1 outputs
         outs, probs = [], []
         for v, g, hh in zip(lv, geo, h2):
-            n, cp, h, w, c2, c3 = g[:6]
-            ob, nc = v[21].shape[0], v[23].shape[0]
-            box = empty_nhwc(n, ob, h, w, dtype, dev)
-            cls = empty_nhwc(n, ncpad, h, w, dtype, dev)  # (padded channels are never read: see _ConvAffineAct)
-            probs += [{"x": hh[:, :c2], "wp": pack_conv_fwd(v[21], c2, dtype), "cout": ob, "k": 1, "bias": v[22], "y": box},
-                      {"x": hh[:, c2:], "wp": pack_conv_fwd(v[23], c3, dtype), "cout": nc, "k": 1, "bias": v[24], "y": cls[:, :nc] if ncpad != nc else cls}]
+            c2, c3 = g.c2, g.c3
+            ob, nc = v.oa_w.shape[0], v.ob_w.shape[0]
+            box = empty_nhwc(g.n, ob, g.h, g.w, dtype, dev)
+            cls = empty_nhwc(g.n, ncpad, g.h, g.w, dtype, dev)  # (padded channels are never read: see _ConvAffineAct)
+            probs += [FwdProblem(hh[:, :c2], pack_conv_fwd(v.oa_w, c2, dtype), ob, 1, box, bias=v.oa_bias),
+                      FwdProblem(hh[:, c2:], pack_conv_fwd(v.ob_w, c3, dtype), nc, 1, cls[:, :nc] if ncpad != nc else cls, bias=v.ob_bias)]
             outs += [box, cls]
         _conv_fwd_multi(probs, dtype)
         saved = []
         for v, r1, s1, a1, r2, s2, a2 in zip(lv, raw1, st1, h1, raw2, st2, h2):
-            saved += [v[0], v[1], v[6], v[2], v[3], v[7], v[8], r1, s1, a1, v[11], v[16], v[12], v[13], v[17], v[18], r2, s2, a2, v[21], v[23]]
+            saved += _Saved(*[getattr(v, f) for f in _SAVED_ARGS], r1, s1, a1, r2, s2, a2)
         ctx.save_for_backward(*saved)
-        ctx.bias_params = [(v[22] if v[22].requires_grad else None, v[24] if v[24].requires_grad else None) for v in lv]  # (leaf parameters: no cycle)
-        ctx.meta = (nl, joins, ncpad, [g[:7] for g in geo])
+        ctx.bias_params = [(v.oa_bias if v.oa_bias.requires_grad else None, v.ob_bias if v.ob_bias.requires_grad else None) for v in lv]  # (leaf parameters: no cycle)
+        ctx.meta = (nl, joins, ncpad, geo)
         return tuple(outs)
 
     @staticmethod
     def backward(ctx, *gout):
         nl, joins, ncpad, geo = ctx.meta
-        S = 21
-        sv = [ctx.saved_tensors[l * S : (l + 1) * S] for l in range(nl)]
-        dtype, dev = sv[0][0].dtype, sv[0][0].device
-        lib = L()
-        nig = ctx.needs_input_grad
-        grads = [None] * (1 + nl * _DT)
+        sv = _per_level(_Saved, ctx.saved_tensors, nl)
+        need = [v._asdict() for v in _per_level(_Level, ctx.needs_input_grad[1:], nl)]
+        grads = [{} for _ in range(nl)]  # per level: field of _Level -> gradient
+        dtype, dev = sv[0].x.dtype, sv[0].x.device
 
-        def need(l, i):
-            return nig[1 + l * _DT + i]
-
-        def put(l, i, g):
-            grads[1 + l * _DT + i] = g
-
-        def bn_bwd(dout, raw, ga, ba, gb, bb, c2, st, o):
-            draw = empty_nhwc(*raw.shape, dtype, dev)
-            dgamma = torch.empty(o, dtype=torch.float32, device=dev)
-            dbeta = torch.empty(o, dtype=torch.float32, device=dev)
-            ws = workspace(2048 * 2 * o * 4 + 256, dev, "bnbwd")
-            check(lib.ymi_bn_act_bwd_pair(_byref(as_ymi(dout)), _byref(as_ymi(raw)), ptr(ga), ptr(ba), ptr(gb), ptr(bb), c2, ptr(st[0]), ptr(st[1]), ACT_SILU,
-                                          _byref(as_ymi(draw)), ptr(dgamma), ptr(dbeta), ptr(ws), ws.numel(), stream_ptr()), "bn_act_bwd_pair")
-            return draw, dgamma, dbeta
+        def dgrad_halves(branches):
+            """branches(l) -> (dy, weight) of the level's cv2 and of its cv3 convolution: their data gradients into the two halves of one buffer
+            per level, ONE launch over all levels -> the buffers."""
+            jobs, bufs = [], []
+            for l, g in enumerate(geo):
+                pair = branches(l)
+                buf = empty_nhwc(g.n, g.o, g.h, g.w, dtype, dev)
+                for (dy, wt), lo, hi in zip(pair, (0, g.c2), (g.c2, g.o)):
+                    jobs.append(_dgrad_prepare(dy, None, wt.shape[2], 1, (g.n, hi - lo, g.h, g.w), dtype, [], buf[:, lo:hi],
+                                               (pack_conv_dgrad(wt, dy.shape[1], 1, dtype), hi - lo)))
+                bufs.append(buf)
+            _dgrad_multi(jobs, dtype)
+            return bufs
 
         # stage 3: data gradients of the 1x1 outputs into the two halves of dh2, weight / bias gradients per convolution
-        jobs, dh2, dys = [], [], []
-        for l in range(nl):
-            n, cp, h, w, c2, c3, o = geo[l]
-            wa2, wb2 = sv[l][19], sv[l][20]
-            dbox = gout[2 * l]
-            dcls = gout[2 * l + 1]
-            dbox = grad_nhwc(dbox, dtype) if dbox is not None else torch.zeros((n, h, w, wa2.shape[0]), dtype=dtype, device=dev).permute(0, 3, 1, 2)
-            dcls = grad_nhwc(dcls, dtype) if dcls is not None else torch.zeros((n, h, w, ncpad), dtype=dtype, device=dev).permute(0, 3, 1, 2)
-            buf = empty_nhwc(n, o, h, w, dtype, dev)
-            jobs.append(_dgrad_prepare(dbox, None, 1, 1, (n, c2, h, w), dtype, [], buf[:, :c2], (pack_conv_dgrad(wa2, dbox.shape[1], 1, dtype), c2)))
-            jobs.append(_dgrad_prepare(dcls, None, 1, 1, (n, c3, h, w), dtype, [], buf[:, c2:], (pack_conv_dgrad(wb2, dcls.shape[1], 1, dtype), c3)))
-            dh2.append(buf)
+        dys = []
+
+        def stage3(l):
+            g, s = geo[l], sv[l]
+            dbox, dcls = gout[2 * l], gout[2 * l + 1]
+            dbox = grad_nhwc(dbox, dtype) if dbox is not None else torch.zeros((g.n, g.h, g.w, s.oa_w.shape[0]), dtype=dtype, device=dev).permute(0, 3, 1, 2)
+            dcls = grad_nhwc(dcls, dtype) if dcls is not None else torch.zeros((g.n, g.h, g.w, ncpad), dtype=dtype, device=dev).permute(0, 3, 1, 2)
             dys.append((dbox, dcls))
-        _dgrad_multi(jobs, dtype)
-        for l in range(nl):
-            n, cp, h, w, c2, c3, o = geo[l]
-            h2 = sv[l][18]
-            for which, (wt, xin, cin, dy) in enumerate(((sv[l][19], h2[:, :c2], c2, dys[l][0]), (sv[l][20], h2[:, c2:], c3, dys[l][1]))):
-                iw = 21 + 2 * which
-                if need(l, iw) or need(l, iw + 1):
-                    dw, db = _wgrad_maybe_async(xin, dy, wt.shape[0], cin, 1, 1, True, (wt, ctx.bias_params[l][which]))
-                    put(l, iw, dw.view(wt.shape) if need(l, iw) else None)
-                    put(l, iw + 1, db if need(l, iw + 1) else None)
-        # stage 2
-        jobs, dh1, draws = [], [], []
-        for l in range(nl):
-            n, cp, h, w, c2, c3, o = geo[l]
-            wa1, wb1, ga, ba, gb, bb, raw2, st2 = sv[l][10:18]
-            draw, dgamma, dbeta = bn_bwd(dh2[l], raw2, ga, ba, gb, bb, c2, st2, o)
-            put(l, 12, dgamma[:c2]); put(l, 13, dbeta[:c2]); put(l, 17, dgamma[c2:]); put(l, 18, dbeta[c2:])
-            buf = empty_nhwc(n, o, h, w, dtype, dev)
-            k = wa1.shape[2]
-            jobs.append(_dgrad_prepare(draw[:, :c2], None, k, 1, (n, c2, h, w), dtype, [], buf[:, :c2], (pack_conv_dgrad(wa1, c2, 1, dtype), c2)))
-            jobs.append(_dgrad_prepare(draw[:, c2:], None, k, 1, (n, c3, h, w), dtype, [], buf[:, c2:], (pack_conv_dgrad(wb1, c3, 1, dtype), c3)))
-            dh1.append(buf)
+            return (dbox, s.oa_w), (dcls, s.ob_w)
+
+        dh2 = dgrad_halves(stage3)
+        for g, s, nd, gr, dy, bias in zip(geo, sv, need, grads, dys, ctx.bias_params):
+            for fw, fb, wt, xin, dyh, bp in (("oa_w", "oa_bias", s.oa_w, s.h2[:, : g.c2], dy[0], bias[0]), ("ob_w", "ob_bias", s.ob_w, s.h2[:, g.c2 :], dy[1], bias[1])):
+                if nd[fw] or nd[fb]:
+                    dw, db = _wgrad_maybe_async(xin, dyh, wt.shape[0], xin.shape[1], 1, 1, True, (wt, bp))
+                    gr[fw] = dw.view(wt.shape) if nd[fw] else None
+                    gr[fb] = db if nd[fb] else None
+        # stage 2: BatchNorm backward over both second convolutions, their data gradients into the halves of dh1, their weight gradients
+        draws = []
+
+        def stage2(l):
+            s, c2 = sv[l], geo[l].c2
+            draw, dgamma, dbeta = _bn_act_bwd(dh2[l], s.raw2, s.st2, ACT_SILU, s.a1_gamma, s.a1_beta, (s.b1_gamma, s.b1_beta, c2))
+            grads[l].update(a1_gamma=dgamma[:c2], a1_beta=dbeta[:c2], b1_gamma=dgamma[c2:], b1_beta=dbeta[c2:])
             draws.append(draw)
+            return (draw[:, :c2], s.a1_w), (draw[:, c2:], s.b1_w)
+
+        dh1 = dgrad_halves(stage2)
         dh2 = None
-        _dgrad_multi(jobs, dtype)
-        for l in range(nl):
-            n, cp, h, w, c2, c3, o = geo[l]
-            h1 = sv[l][9]
-            for iw, wt, lo, hi in ((11, sv[l][10], 0, c2), (16, sv[l][11], c2, o)):
-                if need(l, iw):
-                    dw, _ = _wgrad_maybe_async(h1[:, lo:hi], draws[l][:, lo:hi], hi - lo, hi - lo, wt.shape[2], 1, False, (wt,))
-                    put(l, iw, dw)
-        # stage 1
+        for g, s, nd, gr, draw in zip(geo, sv, need, grads, draws):
+            for fw, wt, lo, hi in (("a1_w", s.a1_w, 0, g.c2), ("b1_w", s.b1_w, g.c2, g.o)):
+                if nd[fw]:
+                    gr[fw], _ = _wgrad_maybe_async(s.h1[:, lo:hi], draw[:, lo:hi], hi - lo, hi - lo, wt.shape[2], 1, False, (wt,))
+        # stage 1: BatchNorm backward, ONE data gradient per level (the pair's, joined with the input's other consumers), the pair's weight gradient
         jobs, draws = [], []
-        for l in range(nl):
-            n, cp, h, w, c2, c3, o = geo[l]
-            x, wa, wb, ga, ba, gb, bb, raw1, st1 = sv[l][:9]
-            draw, dgamma, dbeta = bn_bwd(dh1[l], raw1, ga, ba, gb, bb, c2, st1, o)
-            put(l, 2, dgamma[:c2]); put(l, 3, dbeta[:c2]); put(l, 7, dgamma[c2:]); put(l, 8, dbeta[c2:])
+        for l, (g, s, gr) in enumerate(zip(geo, sv, grads)):
+            c2 = g.c2
+            draw, dgamma, dbeta = _bn_act_bwd(dh1[l], s.raw1, s.st1, ACT_SILU, s.a0_gamma, s.a0_beta, (s.b0_gamma, s.b0_beta, c2))
+            gr.update(a0_gamma=dgamma[:c2], a0_beta=dbeta[:c2], b0_gamma=dgamma[c2:], b0_beta=dbeta[c2:])
             draws.append(draw)
-            if need(l, 0):
-                jobs.append((l,) + _dgrad_joined_prepare(joins[l], draw, None, wa.shape[2], 1, x.shape, dtype, (pack_conv_dgrad_pair(wa, wb, 1, dtype), wa.shape[1])))
+            if need[l]["x"]:
+                jobs.append((l,) + _dgrad_joined_prepare(joins[l], draw, None, s.a0_w.shape[2], 1, s.x.shape, dtype,
+                                                         (pack_conv_dgrad_pair(s.a0_w, s.b0_w, 1, dtype), s.a0_w.shape[1])))
         dh1 = None
         if jobs:
             dxs = _dgrad_multi([j[1] for j in jobs], dtype)
             for (l, _, deposit), dx in zip(jobs, dxs):
-                put(l, 0, _dgrad_joined_finish(joins[l], dx, deposit))
-        for l in range(nl):
-            n, cp, h, w, c2, c3, o = geo[l]
-            x, wa, wb = sv[l][:3]
-            if need(l, 1) or need(l, 6):
-                dw, _ = _wgrad_maybe_async(x, draws[l], o, wa.shape[1], wa.shape[2], 1, False, (wa, wb), pair_rows=c2)
-                put(l, 1, dw[:c2] if need(l, 1) else None)
-                put(l, 6, dw[c2:] if need(l, 6) else None)
-        return tuple(grads)
+                grads[l]["x"] = _dgrad_joined_finish(joins[l], dx, deposit)
+        for g, s, nd, gr, draw in zip(geo, sv, need, grads, draws):
+            if nd["a0_w"] or nd["b0_w"]:
+                dw, _ = _wgrad_maybe_async(s.x, draw, g.o, s.a0_w.shape[1], s.a0_w.shape[2], 1, False, (s.a0_w, s.b0_w), pair_rows=g.c2)
+                gr["a0_w"] = dw[: g.c2] if nd["a0_w"] else None
+                gr["b0_w"] = dw[g.c2 :] if nd["b0_w"] else None
+        return _detect_grads(grads)
 
 
 def detect_train_ok(levels, dtype):
@@ -656,17 +687,10 @@ def detect_train(xs, levels):
     """xs: the internal input tensor of each level; levels: per level (cv2[i][0], cv3[i][0], cv2[i][1], cv3[i][1], cv2[i][2], cv3[i][2]) ->
     ([box map], [class map]) exactly as the per-level modules would give them."""
     dtype = xs[0].dtype
-    t, joins = [], []
-    for x, (a0, b0, a1, b1, oa, ob) in zip(xs, levels):
-        t.append(x)
-        for m in (a0, b0, a1, b1):
-            t += [m.conv.weight, m.bn.weight, m.bn.bias, m.bn.running_mean, m.bn.running_var]
-        t += [oa.weight, oa.bias, ob.weight, ob.bias]
-        joins.append(join_of(x))
     bn0 = levels[0][0].bn
     nc = levels[0][5].out_channels
     ncpad = round_up(nc, chunk_elems(dtype))
-    outs = _DetectTrain.apply((len(levels), float(bn0.eps), float(bn0.momentum), joins, ncpad), *t)
+    outs = _DetectTrain.apply((len(levels), float(bn0.eps), float(bn0.momentum), [join_of(x) for x in xs], ncpad), *_detect_args(xs, levels))
     for lv in levels:
         for m in lv[:4]:
             _count_batch(m.bn)
@@ -730,22 +754,8 @@ class _ConvAffineAct(torch.autograd.Function):
             dres = _join_plain(res_join, dy[:, :o] if cout_pad != o else dy)
         dx = None
         if ctx.needs_input_grad[0]:
-            if x.dim() == 4:
-                dx = _dgrad_joined(join, dy, w4, k, stride, x.shape, dtype)
-            else:
-                adds = join.arrive() if join is not None else []
-                ty = as_ymi(dy)
-                wd = pack_conv_dgrad(weight, ty.c, 1, dtype)
-                dx = torch.empty((x.shape[0], x.shape[1]), dtype=dtype, device=x.device)
-                fa = _prep_adds(adds, dtype, False)
-                a1 = _byref(as_ymi(fa[0])) if len(fa) > 0 else None
-                a2 = _byref(as_ymi(fa[1])) if len(fa) > 1 else None
-                check(L().ymi_conv2d_bwd_data_add(_byref(ty), ptr(wd), x.shape[1], 1, 1, 1, a1, a2, _byref(as_ymi(dx)), stream_ptr()), "conv2d_bwd_data")
-                if len(fa) > 2:
-                    _accumulate(dx, fa[2:])
-                if adds is None:
-                    join.deposit(dx)
-                    dx = None
+            # (the parameter itself, 2-D for a linear, not its 4-D view: the weight arena knows packed operands by their parameter)
+            dx = _dgrad_joined(join, dy, weight, k, stride, x.shape, dtype)
         dw = db = None
         need_w, need_b = ctx.needs_input_grad[1], has_bias and ctx.needs_input_grad[3]
         if need_w or need_b:

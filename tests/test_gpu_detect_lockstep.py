@@ -151,7 +151,7 @@ def test_multi_problem_entry_points_equal_the_single_problem_ones(dtype):
         host = empty_nhwc(n, cout + 16, h, w, dtype, d)
         y, y1 = host[:, 8 : 8 + cout], empty_nhwc(n, cout, h, w, dtype, d)
         wp = ops.pack_conv_fwd(wt, cin, dtype)
-        probs.append({"x": x, "wp": wp, "cout": cout, "k": k, "bias": bias, "y": y})
+        probs.append(ops.FwdProblem(x, wp, cout, k, y, bias=bias))
         check(L().ymi_conv2d_fwd(ctypes.byref(as_ymi(x)), ptr(wp), cout, k, k, 1, None, ptr(bias), 0, None, ctypes.byref(as_ymi(y1)), None, None, stream_ptr()), "fwd")
         singles.append(y1)
         dy = torch.randn(n, h, w, cout, device=d).to(dtype).permute(0, 3, 1, 2)
@@ -160,7 +160,7 @@ def test_multi_problem_entry_points_equal_the_single_problem_ones(dtype):
     ops._conv_fwd_multi(probs, dtype)
     torch.cuda.synchronize()
     for p, y1 in zip(probs, singles):
-        assert rel(p["y"], y1) <= (1e-6 if dtype == torch.float32 else 4e-3), (tuple(y1.shape), rel(p["y"], y1))
+        assert rel(p.y, y1) <= (1e-6 if dtype == torch.float32 else 4e-3), (tuple(y1.shape), rel(p.y, y1))
     jobs = [ops._dgrad_prepare(dy, wt, k, 1, shp, dtype, [add]) for dy, wt, k, shp, add in dprobs]
     multi = ops._dgrad_multi(jobs, dtype)
     single = [ops._dgrad(dy, wt, k, 1, shp, dtype, [add]) for dy, wt, k, shp, add in dprobs]

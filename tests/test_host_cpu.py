@@ -216,3 +216,49 @@ def test_checkpoint_layout_and_weights_only_round_trip(tmp_path):
     torch.save({"epoch": 0, "model": nn.Linear(2, 2), "ema": None}, h)
     with pytest.raises(RuntimeError, match="weights_only"):
         load_checkpoint(h)
+
+
+def test_detect_level_declaration_matches_the_module_tree():
+    """ops._Level (the one declaration of what a Detect level hands to _DetectTrain) against the module tree it is named after: every field of
+    every level IS (identity) the parameter or buffer of cv2[i] / cv3[i] its name says; the per-level count is the number of gradients
+    _DetectTrain.backward returns per level; a field's gradient lands at the position of its argument.  (The second convolutions of cv2 and
+    cv3, and their BatchNorms, have equal shapes whenever c2 = c3: a transposed index there passes every shape check.)"""
+    from improving_yolov8_cbam_swinblock_amd import ops
+    from improving_yolov8_cbam_swinblock_amd.nn.modules import Detect
+
+    for nc in (1, 3):
+        _check_level_declaration(ops, Detect(nc, (32, 64, 128)))
+
+
+def _check_level_declaration(ops, m):
+    nl = len(m.cv2)
+    assert nl == 3
+    xs = [torch.zeros(1, c, 2, 2) for c in (32, 64, 128)]
+    flat = ops._detect_args(xs, [(a[0], b[0], a[1], b[1], a[2], b[2]) for a, b in zip(m.cv2, m.cv3)])
+    fields = ops._Level._fields
+    assert len(fields) == 1 + 4 * 5 + 2 * 2 and len(set(fields)) == len(fields) and len(flat) == nl * len(fields)
+    levels = ops._per_level(ops._Level, flat, nl)
+    named = 0
+    for i, lv in enumerate(levels):
+        assert lv.x is xs[i]
+        for block, mod in (("a0", m.cv2[i][0]), ("b0", m.cv3[i][0]), ("a1", m.cv2[i][1]), ("b1", m.cv3[i][1])):
+            want = {"w": mod.conv.weight, "gamma": mod.bn.weight, "beta": mod.bn.bias, "mean": mod.bn.running_mean, "var": mod.bn.running_var}
+            for part, tensor in want.items():
+                assert getattr(lv, f"{block}_{part}") is tensor, (i, block, part)
+                named += 1
+        for out, mod in (("oa", m.cv2[i][2]), ("ob", m.cv3[i][2])):
+            assert getattr(lv, f"{out}_w") is mod.weight and getattr(lv, f"{out}_bias") is mod.bias, (i, out)
+            named += 2
+    assert named == nl * (len(fields) - 1)  # every field but x was held to a module
+    # gradients: one distinct marker per level and field; backward's return value puts each at the position of its argument in apply(meta, *flat)
+    marks = [{f: object() for f in fields} for _ in range(nl)]
+    grads = ops._detect_grads(marks)
+    args = (None,) + tuple(flat)
+    assert len(grads) == len(args) == 1 + nl * len(fields) and grads[0] is None
+    for i, lv in enumerate(levels):
+        for f in fields:
+            (pos,) = [j for j, a in enumerate(args) if a is getattr(lv, f)]
+            assert grads[pos] is marks[i][f], (i, f)
+    assert ops._detect_grads([{}] * nl) == (None,) * (1 + nl * len(fields))  # (a gradient not produced is None)
+    with pytest.raises(TypeError):
+        ops._detect_grads([{"a1_gama": 0}] + [{}] * (nl - 1))  # a name that is no field is an error, not a dropped gradient
