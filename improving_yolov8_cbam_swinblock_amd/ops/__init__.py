@@ -31,6 +31,6 @@ from .conv import (  # noqa: F401
 )
 from .blocks import (  # noqa: F401
     _Act, _AddResidual, _C2fSplit, _Cbam, _Concat, _DetectLoss, _LayerNorm, _SppfPool, _SwinLnMlp, _SwinMlp, _Upsample2x, _WindowAttention,
-    _WindowReverse, _map_array, add_residual, c2f_split, cbam, concat, detect_decode, detect_loss, detect_targets, gelu, layernorm, sppf_pool_cat,
+    _WindowReverse, _map_array, add_residual, c2f_split, cbam, concat, detect_decode, detect_loss, detect_nms, detect_targets, gelu, layernorm, sppf_pool_cat,
     swin_ln_mlp, swin_ln_mlp_ok, swin_mlp, upsample2x, window_attention, window_pad, window_partition, window_partition_index, window_reverse,
 )

@@ -640,3 +640,29 @@ def detect_decode(box_maps, cls_maps, strides):
     st = (ctypes.c_float * nl)(*[float(s) for s in strides])
     check(L().ymi_detect_decode(nl, _map_array([t.detach() for t in box_maps]), _map_array([t.detach() for t in cls_maps]), st, ptr(y), stream_ptr()), "detect_decode")
     return y
+
+
+def detect_nms(y, conf_thres=0.25, iou_thres=0.45, *, multi_label=False, agnostic=False, classes=None, max_det=300, max_nms=30000, max_wh=7680):
+    """non_max_suppression of reference utils/ops.py:181-332 on the decoded Detect output y [B, 4+nc, A] float32, on the device
+    (csrc/nms.hip): -> (det [B, max_det, 6] float32 rows (x1, y1, x2, y2, conf, cls) in kept order, zero past the count; count [B] int32).
+    Both stay on the device and nothing synchronises: the call can be captured in a graph.  Order: descending score, equal scores by
+    ascending anchor then class (the library's own tie rule).  The reference's wall-clock time limit is not reproduced."""
+    if not y.is_cuda:
+        raise RuntimeError("libyolo_mi355 kernels need tensors on the MI355X (cuda) device; there is no CPU path")
+    if y.dim() != 3 or y.shape[1] < 5 or y.dtype != torch.float32:
+        raise ValueError(f"detect_nms takes the decoded Detect output [B, 4 + nc, A] in float32, got {tuple(y.shape)} {y.dtype}")
+    y = y.detach()
+    if not y.is_contiguous():
+        y = y.contiguous()
+    b, no, a = (int(v) for v in y.shape)
+    nc = no - 4
+    cl = sorted({int(c) for c in classes}) if classes is not None else []
+    wb = ctypes.c_size_t(0)
+    check(L().ymi_detect_nms_sizes(b, a, nc, int(max_nms), int(max_det), _byref(wb)), "detect_nms_sizes")
+    ws = workspace(wb.value, y.device, "nms")
+    det = torch.empty((b, int(max_det), 6), dtype=torch.float32, device=y.device)
+    count = torch.empty((b,), dtype=torch.int32, device=y.device)
+    arr = (ctypes.c_int32 * max(len(cl), 1))(*cl) if classes is not None else None  # (an empty list is a filter that keeps nothing, as in the reference)
+    check(L().ymi_detect_nms(ptr(y), b, nc, a, float(conf_thres), float(iou_thres), int(bool(multi_label)), int(bool(agnostic)), arr, len(cl), int(max_det),
+                             int(max_nms), float(max_wh), ptr(det), ptr(count), ptr(ws), ws.numel(), stream_ptr()), "detect_nms")
+    return det, count

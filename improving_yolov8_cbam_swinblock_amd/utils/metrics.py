@@ -1,0 +1,188 @@
+"""Detection metrics under the reference's public names: box_iou, match_predictions, compute_ap, ap_per_class, Metric, DetMetrics.
+
+The text of this module is the project's own, written from the definitions of the quantities.  What is shared with the reference
+(ultralytics/utils/metrics.py, engine/validator.py) is the interface - names, signatures, result keys - and the numbers: the tp matrices are
+equal and P, R, AP per class and the means agree within 1e-9 on the reference-generated fixtures (tests/test_host_nms_check.py).
+
+Definitions.  Detections are ranked by descending confidence.  At one IoU threshold a detection is *correct* when it claims a label of its own
+class that it overlaps by at least the threshold and no better-ranked detection claimed that label (a detection claims the label it overlaps
+most).  For one class, precision after k detections is (correct among the first k) / k and recall is (correct among the first k) / labels.
+AP is the area under the precision envelope (the largest precision at any recall at least as large) over recall in [0, 1], sampled at
+101 equally spaced recalls and integrated by the trapezoid rule.  P and R are read off the precision / recall-over-confidence curves at
+the confidence where the box-filtered class-mean F1 peaks.  Host code in numpy float64: after NMS an image carries at most max_det rows,
+so a kernel would buy nothing.  No plotting and no confusion matrix."""
+import numpy as np
+import torch
+
+CONF_GRID = 1000   # confidence samples of the P / R / F1 curves
+RECALL_GRID = 101  # recall samples of the AP integral
+
+
+def box_iou(box1, box2, eps=1e-7):
+    """[N, 4] x [M, 4] xyxy -> [N, M] IoU in float32: inter / (area1 + area2 - inter + eps)."""
+    a = torch.as_tensor(box1).float()[:, None, :]
+    b = torch.as_tensor(box2).float()[None, :, :]
+    wh = (torch.min(a[..., 2:], b[..., 2:]) - torch.max(a[..., :2], b[..., :2])).clamp_(0)
+    inter = wh[..., 0] * wh[..., 1]
+    da, db = a[..., 2:] - a[..., :2], b[..., 2:] - b[..., :2]
+    return inter / (da[..., 0] * da[..., 1] + db[..., 0] * db[..., 1] - inter + eps)
+
+
+def match_predictions(pred_classes, true_classes, iou, iouv):
+    """-> bool [detections, thresholds]: which detections are correct at each threshold of iouv.  iou: [labels, detections] (box_iou(gt, pred));
+    detections are in ranked order (NMS output order).  One greedy pass per threshold: every detection claims the same-class label it overlaps
+    most, provided the overlap reaches the threshold; a label claimed more than once goes to the best-ranked claimant."""
+    pred_classes, true_classes = torch.as_tensor(pred_classes).cpu(), torch.as_tensor(true_classes).cpu()
+    n_lab, n_det = int(true_classes.shape[0]), int(pred_classes.shape[0])
+    levels = [float(t) for t in torch.as_tensor(iouv).cpu().tolist()]
+    out = np.zeros((n_det, len(levels)), dtype=bool)
+    if n_lab == 0 or n_det == 0:
+        return torch.from_numpy(out)
+    same = (true_classes.reshape(-1, 1) == pred_classes.reshape(1, -1)).numpy()
+    overlap = torch.as_tensor(iou).cpu().numpy().astype(np.float32) * same  # float32, zero where the classes differ
+    claim = overlap.argmax(axis=0)                    # per detection: the label it overlaps most
+    strength = overlap[claim, np.arange(n_det)]
+    for t, level in enumerate(levels):
+        owner = np.full(n_lab, -1)
+        for d in np.flatnonzero(strength >= np.float32(level)):   # ascending = ranked order
+            if owner[claim[d]] < 0:
+                owner[claim[d]] = d
+                out[d, t] = True
+    return torch.from_numpy(out)
+
+
+def smooth(y, f=0.05):
+    """moving average of y over a centred window of about 2 f len(y) samples (odd length), the ends continued with the end values."""
+    y = np.asarray(y, dtype=np.float64)
+    half = (int(round(2 * f * len(y))) // 2) // 2
+    width = 2 * half + 1
+    run = np.cumsum(np.concatenate(([0.0], np.pad(y, half, mode="edge"))))
+    return (run[width:] - run[:-width]) / width
+
+
+def compute_ap(recall, precision):
+    """one class, one threshold: recall / precision after each ranked detection -> (AP, precision envelope, recall points).  The curve is
+    closed with the points (0, 1) and (1, 0); the envelope makes precision non-increasing in recall."""
+    r = np.concatenate(([0.0], np.asarray(recall, dtype=np.float64), [1.0]))
+    p = np.concatenate(([1.0], np.asarray(precision, dtype=np.float64), [0.0]))
+    envelope = np.maximum.accumulate(p[::-1])[::-1]
+    grid = np.linspace(0.0, 1.0, RECALL_GRID)
+    v = np.interp(grid, r, envelope)
+    area = float(np.sum((v[1:] + v[:-1]) * np.diff(grid)) / 2)
+    return area, envelope, r
+
+
+def _ranked_curves(hits, n_labels, eps):
+    """hits [k, T] bool in ranked order -> (recall [k, T], precision [k, T]) after each detection."""
+    found = np.cumsum(hits, axis=0, dtype=np.float64)
+    seen = np.arange(1, hits.shape[0] + 1, dtype=np.float64)[:, None]
+    return found / (n_labels + eps), found / seen
+
+
+def _over_confidence(grid, conf_ranked, values_ranked, above):
+    """a ranked curve as a function of the confidence threshold: below the lowest confidence it keeps its last value, above the highest it is `above`."""
+    return np.interp(grid, conf_ranked[::-1], values_ranked[::-1], right=above)
+
+
+def ap_per_class(tp, conf, pred_cls, target_cls, eps=1e-16):
+    """tp [n, T] bool, conf [n], pred_cls [n], target_cls [m] -> (tp count, fp count, p, r, f1, ap [classes, T], classes with labels, p_curve, r_curve,
+    f1_curve, confidence grid, precision over recall at the first threshold), per class that has labels, in ascending class order."""
+    tp, conf, pred_cls = np.asarray(tp), np.asarray(conf), np.asarray(pred_cls)
+    rank = np.argsort(-conf, kind="stable")
+    tp, conf, pred_cls = tp[rank], conf[rank], pred_cls[rank]
+    classes, labels_of = np.unique(np.asarray(target_cls), return_counts=True)
+    grid = np.linspace(0.0, 1.0, CONF_GRID)
+    ap = np.zeros((len(classes), tp.shape[1]))
+    p_curve, r_curve = np.zeros((len(classes), CONF_GRID)), np.zeros((len(classes), CONF_GRID))
+    pr_rows = []
+    for row, (c, n_labels) in enumerate(zip(classes, labels_of)):
+        mine = pred_cls == c
+        if not mine.any() or n_labels == 0:
+            continue
+        recall, precision = _ranked_curves(tp[mine], n_labels, eps)
+        r_curve[row] = _over_confidence(grid, conf[mine], recall[:, 0], 0.0)
+        p_curve[row] = _over_confidence(grid, conf[mine], precision[:, 0], 1.0)
+        for t in range(tp.shape[1]):
+            ap[row, t], envelope, r_points = compute_ap(recall[:, t], precision[:, t])
+            if t == 0:
+                pr_rows.append(np.interp(grid, r_points, envelope))
+    pr_at_first = np.array(pr_rows) if pr_rows else np.zeros((1, CONF_GRID))
+    f1_curve = 2 * p_curve * r_curve / (p_curve + r_curve + eps)
+    peak = int(smooth(f1_curve.mean(axis=0), 0.1).argmax()) if len(classes) else 0
+    p, r, f1 = p_curve[:, peak], r_curve[:, peak], f1_curve[:, peak]
+    n_tp = np.round(r * labels_of)
+    n_fp = np.round(n_tp / (p + eps) - n_tp)
+    return n_tp, n_fp, p, r, f1, ap, classes.astype(int), p_curve, r_curve, f1_curve, grid, pr_at_first
+
+
+def _mean(values):
+    values = np.asarray(values, dtype=np.float64)
+    return float(values.mean()) if values.size else 0.0
+
+
+class Metric:
+    """per-class precision, recall, F1 and AP [classes, thresholds] of the classes that have labels, and their means (0 when there are none)."""
+
+    def __init__(self):
+        self.p, self.r, self.f1, self.ap_class_index = np.zeros(0), np.zeros(0), np.zeros(0), np.zeros(0, dtype=int)
+        self.all_ap = np.zeros((0, 10))
+        self.nc = 0
+
+    def update(self, results):
+        """results: ap_per_class(...)[2:]."""
+        self.p, self.r, self.f1, self.all_ap, self.ap_class_index, self.p_curve, self.r_curve, self.f1_curve, self.px, self.prec_values = results
+
+    ap50 = property(lambda self: self.all_ap[:, 0])
+    ap = property(lambda self: self.all_ap.mean(axis=1) if len(self.all_ap) else np.zeros(0))
+    mp = property(lambda self: _mean(self.p))
+    mr = property(lambda self: _mean(self.r))
+    map50 = property(lambda self: _mean(self.all_ap[:, 0]))
+    map75 = property(lambda self: _mean(self.all_ap[:, 5]))
+    map = property(lambda self: _mean(self.all_ap))
+
+    def mean_results(self):
+        return [self.mp, self.mr, self.map50, self.map]
+
+    def class_result(self, i):
+        return self.p[i], self.r[i], self.ap50[i], self.ap[i]
+
+    @property
+    def maps(self):
+        """mAP50-95 per class id; classes without labels carry the mean."""
+        per_class = np.full(self.nc, self.map, dtype=np.float64)
+        per_class[np.asarray(self.ap_class_index, dtype=int)] = self.ap
+        return per_class
+
+    def fitness(self):
+        """the model-selection score: a tenth of mAP50 and nine tenths of mAP50-95."""
+        return 0.1 * self.map50 + 0.9 * self.map
+
+
+class DetMetrics:
+    """precision, recall, mAP50 and mAP50-95 of a detector from the validator's statistics."""
+
+    keys = ["metrics/precision(B)", "metrics/recall(B)", "metrics/mAP50(B)", "metrics/mAP50-95(B)"]
+
+    def __init__(self, names=None):
+        self.names = dict(names or {})
+        self.box = Metric()
+
+    def process(self, tp, conf, pred_cls, target_cls):
+        self.box.nc = len(self.names)
+        self.box.update(ap_per_class(tp, conf, pred_cls, target_cls)[2:])
+
+    def mean_results(self):
+        return self.box.mean_results()
+
+    def class_result(self, i):
+        return self.box.class_result(i)
+
+    maps = property(lambda self: self.box.maps)
+    fitness = property(lambda self: self.box.fitness())
+    ap_class_index = property(lambda self: self.box.ap_class_index)
+
+    @property
+    def results_dict(self):
+        out = dict(zip(self.keys, self.mean_results()))
+        out["fitness"] = self.fitness
+        return out

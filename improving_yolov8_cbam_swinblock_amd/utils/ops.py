@@ -15,3 +15,28 @@ def xywh2xyxy(x):
     """reference utils/ops.py:432-449."""
     xy, half = x[..., :2], x[..., 2:] / 2
     return torch.cat((xy - half, xy + half), -1)
+
+
+def non_max_suppression(prediction, conf_thres=0.25, iou_thres=0.45, classes=None, agnostic=False, multi_label=False, max_det=300, nc=0,
+                        max_nms=30000, max_wh=7680, labels=(), rotated=False, end2end=False):
+    """reference utils/ops.py:181-332 -> list of [n_i, 6] tensors (x1, y1, x2, y2, conf, cls), one per image, on the prediction's device.
+    prediction: the decoded Detect output [B, 4 + nc, A], or the (y, maps) tuple of the eval forward.  The work is ops.detect_nms (HIP,
+    csrc/nms.hip); this wrapper adds the ONE synchronisation: the counts go to the host once, then the rows are sliced.  Equal scores are
+    ordered by ascending anchor, then class (the reference leaves ties to its libraries).  The reference's wall-clock `time_limit` break
+    (ops.py:328-330) is deliberately not reproduced: a result that depends on the host's clock cannot be pinned.  The input is not
+    modified.  An empty `classes` list keeps nothing, as in the reference.  Not built: mask channels (nc smaller than the class rows), rotated boxes, apriori labels, end2end models."""
+    from .. import ops
+
+    if not 0 <= conf_thres <= 1:
+        raise ValueError(f"invalid confidence threshold {conf_thres}: valid values are between 0.0 and 1.0")
+    if not 0 <= iou_thres <= 1:
+        raise ValueError(f"invalid IoU threshold {iou_thres}: valid values are between 0.0 and 1.0")
+    if isinstance(prediction, (list, tuple)):
+        prediction = prediction[0]
+    if rotated or end2end or (labels is not None and len(labels)) or prediction.shape[-1] == 6:
+        raise NotImplementedError("non_max_suppression: rotated boxes, apriori labels and end2end outputs are not built")
+    if nc and prediction.shape[1] - 4 - nc != 0:
+        raise NotImplementedError(f"non_max_suppression: {prediction.shape[1] - 4 - nc} mask channels behind {nc} classes are not built")
+    det, count = ops.detect_nms(prediction, conf_thres, iou_thres, multi_label=multi_label, agnostic=agnostic, classes=classes, max_det=max_det,
+                                max_nms=max_nms, max_wh=max_wh)
+    return [det[i, :n] for i, n in enumerate(count.tolist())]

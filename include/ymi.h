@@ -378,6 +378,26 @@ int ymi_detect_loss_bwd(int32_t nl, const ymi_tensor* box_maps, const ymi_tensor
  * sigmoid(class logits); anchors in the reference's order (level, y, x), centre offset 0.5. */
 int ymi_detect_decode(int32_t nl, const ymi_tensor* box_maps, const ymi_tensor* cls_maps, const float* strides, float* y, void* stream);
 
+/* non_max_suppression (utils/ops.py:181-332, as models/yolo/detect/val.py:113-133 and the predictor call it) on y [B][4+nc][A] float32 as
+ * ymi_detect_decode writes it -> det [B][max_det][6] float32, rows (x1, y1, x2, y2, conf, cls) in kept order and zero past the count, and
+ * count [B] int32 (csrc/nms.hip: three launches of B workgroups, no host round trip, no data-dependent grid: graph-capturable).
+ *   candidates : multi_label (and nc > 1): every (anchor, class) with score > conf_thres; else the anchor's best class (first maximum) if its
+ *                score > conf_thres; host_classes (HOST array of n_classes class ids) keeps only those classes: NULL = no filter, non-NULL
+ *                with n_classes 0 = a filter that keeps nothing (the reference's result for an empty list)
+ *   order      : descending score; equal scores by ascending anchor, then ascending class (the reference leaves ties to argsort and
+ *                torchvision: this rule is the library's own); the first max_nms of that order enter the suppression
+ *   suppression: greedy, the arithmetic of torchvision.ops.nms in float32 on the boxes offset by cls * max_wh (agnostic != 0: no offset):
+ *                iou = inter / (area_i + area_j - inter), one rounding per operation, suppressed when iou > iou_thres with the threshold
+ *                taken in float32 too (as torchvision's GPU kernel takes it; its CPU kernel compares the float32 iou with a double
+ *                threshold, which differs only for an iou equal to float32(iou_thres) when that lies above iou_thres, e.g. 0.6)
+ *   result     : the first max_det kept candidates with their original boxes (x -+ w/2, y -+ h/2)
+ * max_det <= 2048, max_nms <= 2^20, thresholds in [0, 1].  The reference's wall-clock time limit (ops.py:328-330) is not reproduced.
+ * workspace (8-byte aligned) of ymi_detect_nms_sizes bytes: B * pow2ceil(min(max_nms, A * nc)) 8-byte keys + the candidate counts. */
+int ymi_detect_nms_sizes(int64_t batch, int64_t anchors, int64_t nc, int64_t max_nms, int64_t max_det, size_t* workspace_bytes);
+int ymi_detect_nms(const float* y, int64_t batch, int64_t nc, int64_t anchors, float conf_thres, float iou_thres, int32_t multi_label,
+                   int32_t agnostic, const int32_t* host_classes, int32_t n_classes, int64_t max_det, int64_t max_nms, float max_wh, float* det,
+                   int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------- optimizer step ---- */
 /* The update either side of backward, reference engine/trainer.py:614-622 (optimizer_step: clip_grad_norm_(10.0),
  * SGD-nesterov step, EMA update), :788-849 (three parameter groups) and utils/torch_utils.py:657-673 (ModelEMA.update),
