@@ -5,12 +5,18 @@
 //    padding pixels) and into the final store (scatter + crop).  Stand-alone copies and the integer
 //    index map exist for the bit-exact test.
 //  * LayerNorm: one wave per token, 16 bytes per lane, two-pass statistics in registers.
-//  * window attention: one workgroup (4 waves) per window, heads in sequence; every product is a
-//    16x16-tile "NT" MFMA (both operands K-contiguous rows in LDS, rows padded by 16 B so
-//    ds_read_b128 fragment reads are conflict-free); 49 tokens pad to 64 with zero rows, pad keys
-//    masked to -inf before the softmax; V (and, in backward, dO / Q / K) are transposed on the way
-//    into LDS.  Token GEMMs (QKV, proj, MLP) are ymi_conv2d_fwd with a 1x1 "kernel".
+//  * window attention: one workgroup (4 waves) per (window, head); every product is a 16x16-tile
+//    MFMA on LDS images whose rows are padded by 16 B (conflict-free ds_read_b128 fragment reads);
+//    49 tokens pad to 64 with zero rows, pad keys masked to -inf before the softmax.  Three kernel
+//    families (attn_form): windows of more than 64 tokens (or the attn_tiled option) -> tiled,
+//    flash-style; otherwise bfloat16 -> tr (operands staged once row-major, transposed fragment
+//    reads), float32 -> one-tile (both operands K-contiguous rows: V and, in backward, dO / Q / K
+//    are transposed on the way into LDS).  They share the LDS description (AttnLds), the row
+//    softmax, the tile stores and the launch helper.
+//    Token GEMMs (QKV, proj, MLP) are ymi_conv2d_fwd with a 1x1 "kernel".
 #include <stdlib.h>
+
+#include <type_traits>
 
 #include "common.h"
 
@@ -75,10 +81,9 @@ __global__ void window_move_kernel(SV x, SV tok, int64_t Tn, int H, int W, int H
     }
 }
 
-static int window_geometry(const ymi_tensor* x, int64_t ws, int64_t* Hp, int64_t* Wp) {
+static void window_geometry(const ymi_tensor* x, int64_t ws, int64_t* Hp, int64_t* Wp) {
     *Hp = (x->h + ws - 1) / ws * ws;
     *Wp = (x->w + ws - 1) / ws * ws;
-    return 0;
 }
 
 template <int DIR>
@@ -111,15 +116,15 @@ extern "C" int ymi_window_reverse(const ymi_tensor* tokens, int64_t ws, const ym
 // C <= 64 lanes * 4 channels * 4 groups = 1024
 // the kernels are instantiated per number of ACTIVE 256-channel groups (C = 256 -> 1): the per-token loop is a serial
 // load -> reduce -> store chain hidden only by resident waves, and register arrays sized for 1024 channels cut those
-#define YMI_LN_G(LAUNCH, T)                     \
-    do {                                        \
-        const int g_ = ((int)x->c + 255) / 256; \
-        if (g_ <= 1) LAUNCH(T, 1);              \
-        else if (g_ == 2) LAUNCH(T, 2);         \
-        else if (g_ == 3) LAUNCH(T, 3);         \
-        else LAUNCH(T, 4);                      \
-    } while (0)
-#define YMI_LNF(T, G) hipLaunchKernelGGL((layernorm_fwd_kernel<T, G>), grid, dim3(256), 0, (hipStream_t)stream, xv, ov, T_, (int)x->h, (int)x->w, (int)Hp, (int)Wp, (int)ws, (int)x->c, gamma, beta, eps, mean, rstd)
+// f(std::integral_constant<int, G>) with G = the number of active groups of a C-channel row
+template <typename F>
+static void ln_for_groups(int64_t C, F&& f) {
+    const int g = ((int)C + 255) / 256;
+    if (g <= 1) f(std::integral_constant<int, 1>());
+    else if (g == 2) f(std::integral_constant<int, 2>());
+    else if (g == 3) f(std::integral_constant<int, 3>());
+    else f(std::integral_constant<int, 4>());
+}
 
 // one wave per token; ws > 0: rows are gathered from the NHWC image through the window map
 template <typename T, int G>
@@ -227,19 +232,22 @@ extern "C" int ymi_layernorm_fwd(const ymi_tensor* x, int64_t ws, const float* g
     int64_t Hp = x->h, Wp = x->w;
     if (ws > 0) window_geometry(x, ws, &Hp, &Wp);
     const int64_t T = ws > 0 ? x->n * Hp * Wp : ymi_pixels(x);
-    const int64_t T_ = T;  // (name used by the launch macros)
     YMI_CHECK_ARG(ymi_pixels(out) == T, "layernorm_fwd: output must hold %lld tokens", (long long)T);
     SV xv{x->data, x->ld}, ov{out->data, out->ld};
-    dim3 grid((unsigned)((T + 3) / 4));
-    const bool half = x->dtype == YMI_BF16 && x->c <= 256 && x->c % 8 == 0 && x->ld % 8 == 0 && out->ld % 8 == 0 &&
+    const bool bf16 = x->dtype == YMI_BF16;
+    const bool half = bf16 && x->c <= 256 && x->c % 8 == 0 && x->ld % 8 == 0 && out->ld % 8 == 0 &&
                       ((((uintptr_t)x->data) | ((uintptr_t)out->data) | ((uintptr_t)gamma) | ((uintptr_t)beta)) & 15) == 0;
+    const auto launch = [&](auto kernel, int tokens_per_block) {
+        hipLaunchKernelGGL(kernel, dim3((unsigned)((T + tokens_per_block - 1) / tokens_per_block)), dim3(256), 0, (hipStream_t)stream, xv, ov, T, (int)x->h,
+                           (int)x->w, (int)Hp, (int)Wp, (int)ws, (int)x->c, gamma, beta, eps, mean, rstd);
+    };
     if (half)
-        hipLaunchKernelGGL(layernorm_fwd_half_kernel, dim3((unsigned)((T + 7) / 8)), dim3(256), 0, (hipStream_t)stream, xv, ov, T_, (int)x->h, (int)x->w, (int)Hp,
-                           (int)Wp, (int)ws, (int)x->c, gamma, beta, eps, mean, rstd);
-    else if (x->dtype == YMI_BF16)
-        YMI_LN_G(YMI_LNF, bf16_t);
+        launch(layernorm_fwd_half_kernel, 8);
     else
-        YMI_LN_G(YMI_LNF, float);
+        ln_for_groups(x->c, [&](auto g) {
+            if (bf16) launch(layernorm_fwd_kernel<bf16_t, decltype(g)::value>, 4);
+            else launch(layernorm_fwd_kernel<float, decltype(g)::value>, 4);
+        });
     YMI_CHECK_LAUNCH("layernorm_fwd");
     return YMI_OK;
 }
@@ -330,8 +338,6 @@ __global__ __launch_bounds__(256) void layernorm_bwd_kernel(SV x, SV dy, SV dx, 
     }
 }
 
-#define YMI_LNB(T, G) hipLaunchKernelGGL((layernorm_bwd_kernel<T, G>), dim3(blocks), dim3(256), red_bytes, s, xv, dv, ov, av, T_, (int)x->h, (int)x->w, (int)Hp, (int)Wp, (int)ws, (int)x->c, gamma, mean, rstd, (float*)workspace)
-
 static int ln_bwd_blocks(int64_t T) {
     int64_t b = (T + 31) / 32;  // >= 8 tokens per wave
     if (b > 2048) b = 2048;     // the token loop is a serial load -> reduce -> store chain: many resident waves hide it
@@ -355,7 +361,6 @@ extern "C" int ymi_layernorm_bwd_add(const ymi_tensor* x, int64_t ws, const ymi_
     int64_t Hp = x->h, Wp = x->w;
     if (ws > 0) window_geometry(x, ws, &Hp, &Wp);
     const int64_t T = ws > 0 ? x->n * Hp * Wp : ymi_pixels(x);
-    const int64_t T_ = T;  // (name used by the launch macros)
     YMI_CHECK_ARG(ymi_pixels(dout) == T, "layernorm_bwd: dout must hold %lld tokens", (long long)T);
     const int blocks = ln_bwd_blocks(T);
     const size_t need = (size_t)blocks * 2 * x->c * sizeof(float);
@@ -366,10 +371,14 @@ extern "C" int ymi_layernorm_bwd_add(const ymi_tensor* x, int64_t ws, const ymi_
     SV xv{x->data, x->ld}, dv{dout->data, dout->ld}, ov{dx->data, dx->ld}, av{add ? add->data : nullptr, add ? add->ld : 0};
     hipStream_t s = (hipStream_t)stream;
     const size_t red_bytes = (size_t)8 * ((x->c + 255) / 256 * 256) * sizeof(float);
-    if (x->dtype == YMI_BF16)
-        YMI_LN_G(YMI_LNB, bf16_t);
-    else
-        YMI_LN_G(YMI_LNB, float);
+    const auto launch = [&](auto kernel) {
+        hipLaunchKernelGGL(kernel, dim3(blocks), dim3(256), red_bytes, s, xv, dv, ov, av, T, (int)x->h, (int)x->w, (int)Hp, (int)Wp, (int)ws, (int)x->c, gamma,
+                           mean, rstd, (float*)workspace);
+    };
+    ln_for_groups(x->c, [&](auto g) {
+        if (x->dtype == YMI_BF16) launch(layernorm_bwd_kernel<bf16_t, decltype(g)::value>);
+        else launch(layernorm_bwd_kernel<float, decltype(g)::value>);
+    });
     YMI_CHECK_LAUNCH("layernorm_bwd");
     return ymi_chan_reduce_final((const float*)workspace, blocks, (int)x->c, dbeta, dgamma, s);
 }
@@ -436,19 +445,129 @@ struct AttnArgs {
 };
 
 constexpr int ATT_MAXDT = 12;  // head_dim <= 192
+constexpr int ATT_HC = 96;     // head_dim columns per staging round of the tiled kernels
+constexpr size_t ATT_LDS_MAX = 160 * 1024;  // LDS of a CU; every attention kernel is allowed all of it
 
+constexpr int attn_hdp(int64_t hd) { return (int)((hd + 31) / 32 * 32); }
+// bytes of a row of `cols` elements in an LDS image (rows padded by 16 B)
+template <typename T> constexpr int attn_row_bytes(int cols) { return (cols + AT<T>::PAD) * (int)sizeof(T); }
+
+// The dynamic-LDS image of an attention kernel: `nstage` operand regions of `stage` bytes, then `nsq` [64][64] images of `sq` bytes (P, dS and
+// their transposes), then - with `tail` - 64 floats.  A kernel carves its pointers from the same description its launcher sizes the launch with.
+struct AttnLds {
+    size_t stage;
+    int nstage, nsq;
+    size_t sq;
+    bool tail;
+    constexpr size_t region(int i) const { return (size_t)i * stage; }
+    constexpr size_t square(int i) const { return (size_t)nstage * stage + (size_t)i * sq; }
+    constexpr size_t floats() const { return square(nsq); }
+    constexpr size_t bytes() const { return floats() + (tail ? 64 * sizeof(float) : 0); }
+};
+// one-tile kernels: two regions that hold a [64][hdp] or a transposed [hdp][64] operand; P (forward) | P^T, dS, dS^T and delta (backward)
+template <typename T> constexpr AttnLds attn_one_tile_lds(int hdp, bool bwd) {
+    const int rows = 64 * attn_row_bytes<T>(hdp), cols = hdp * attn_row_bytes<T>(64);
+    return AttnLds{(size_t)(rows > cols ? rows : cols), 2, bwd ? 3 : 1, (size_t)64 * attn_row_bytes<T>(64), bwd};
+}
+// bf16 tr kernels: Q, K, V (and dO) row-major; P (and dS)
+constexpr AttnLds attn_tr_lds(int hdp, bool bwd) {
+    return AttnLds{(size_t)64 * attn_row_bytes<bf16_t>(hdp), bwd ? 4 : 3, bwd ? 2 : 1, (size_t)64 * attn_row_bytes<bf16_t>(64), false};
+}
+// tiled kernels: two staging regions for an ATT_HC-column chunk of an operand, either way round; nsq images; a float per row
+template <typename T> constexpr AttnLds attn_tiled_lds(int nsq) {
+    constexpr int rows = 64 * attn_row_bytes<T>(ATT_HC), cols = ATT_HC * attn_row_bytes<T>(64);
+    return AttnLds{(size_t)(rows > cols ? rows : cols), 2, nsq, (size_t)64 * attn_row_bytes<T>(64), true};
+}
+// The launchers send every window of at most 64 tokens to a one-tile or tr kernel without looking at its LDS size: the largest images, at the
+// largest head_dim attn_common accepts, must fit.  (Raising ATT_MAXDT fails here, not at a launch.)
+static_assert(attn_one_tile_lds<float>(attn_hdp(16 * ATT_MAXDT), true).bytes() <= ATT_LDS_MAX, "one-tile float32 backward image exceeds the LDS");
+static_assert(attn_tr_lds(attn_hdp(16 * ATT_MAXDT), true).bytes() <= ATT_LDS_MAX, "tr backward image exceeds the LDS");
+static_assert(attn_one_tile_lds<float>(192, true).bytes() == 156928 && attn_tr_lds(192, true).bytes() == 120832, "tests/attn_exact.py attn_lds restates these");
+static_assert(attn_tiled_lds<float>(2).bytes() <= ATT_LDS_MAX, "tiled dK/dV image exceeds the LDS");
+
+// Row softmax of four transposed score tiles: the lane holds keys j = 16t + 4*l4 + r of ONE query, the other keys of that query are in the lanes
+// l4 = 0..3 of the same l15.  s: raw scores in, exp(score * scale - mx) out, keys >= nkeys masked.  mx = max(m_run, row maximum), where m_run is the
+// maximum over earlier key tiles (online softmax; the same in the four lanes of a query) or -inf; sum = sum of the exponentials over the 64 keys.
+__device__ __forceinline__ void attn_softmax_row(f32x4 (&s)[4], int nkeys, float scale, float m_run, int l4, float& mx, float& sum) {
+    mx = m_run;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int j = 16 * t + 4 * l4 + r;
+            s[t][r] = j < nkeys ? s[t][r] * scale : -__builtin_inff();
+            mx = fmaxf(mx, s[t][r]);
+        }
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    sum = 0.f;
+#pragma unroll
+    for (int t = 0; t < 4; ++t)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            s[t][r] = __expf(s[t][r] - mx);
+            sum += s[t][r];
+        }
+    sum += __shfl_xor(sum, 16, 64);
+    sum += __shfl_xor(sum, 32, 64);
+}
+
+// Column tile dt of N [64][cols] results, as the MFMA leaves it: wave wv holds rows 16*wv..+15, the lane rows 4*l4 + r of those and column
+// 16*dt + l15.  Scalar stores of the elements inside rows x cols; dst[i]: element (0, 0) of matrix i.
+template <typename T, int N>
+__device__ __forceinline__ void attn_store_tiles(T* const (&dst)[N], int64_t ld, const f32x4 (&v)[N], int rows, int dt, int cols) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int col = dt * 16 + (lane & 15);
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        const int row = wv * 16 + 4 * (lane >> 4) + r;
+        if (row < rows && col < cols)
+#pragma unroll
+            for (int i = 0; i < N; ++i) dst[i][(int64_t)row * ld + col] = from_f32<T>(v[i][r]);
+    }
+}
+// The same for the swapped products of the tr kernels, where the lane holds four CONSECUTIVE channels d .. d + 3 of one row.  dst[i]: the lane's
+// first element in matrix i.  One 8-byte store per matrix (vec4: the caller's alignment predicate), scalar stores where the four channels cross
+// the end of the head.
+template <int N>
+__device__ __forceinline__ void attn_store_tiles_tr(bf16_t* const (&dst)[N], const f32x4 (&v)[N], bool vec4, int d, int hd) {
+    if (vec4 && d + 3 < hd) {
+#pragma unroll
+        for (int i = 0; i < N; ++i) *reinterpret_cast<bf16x4*>(dst[i]) = bf16x4{(bf16_t)v[i][0], (bf16_t)v[i][1], (bf16_t)v[i][2], (bf16_t)v[i][3]};
+    } else {
+#pragma unroll
+        for (int r = 0; r < 4; ++r)
+            if (d + r < hd)
+#pragma unroll
+                for (int i = 0; i < N; ++i) dst[i][r] = (bf16_t)v[i][r];
+    }
+}
+
+// delta[m] = sum_d dO[m][d] * O[m][d] for 64 rows (zero from row `rows` on): one wave per row, 16 rows per wave
+template <typename T>
+__device__ __forceinline__ void attn_delta_rows(float* delta, const T* dO, int64_t ldd, const T* o, int64_t ldo, int rows, int hd) {
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    for (int m = wv; m < 64; m += 4) {
+        float acc = 0.f;
+        if (m < rows)
+            for (int d = lane; d < hd; d += 64) acc += to_f32(dO[(int64_t)m * ldd + d]) * to_f32(o[(int64_t)m * ldo + d]);
+        acc = wave_sum(acc);
+        if (lane == 0) delta[m] = acc;
+    }
+}
+
+// float32 windows of at most 64 tokens (bfloat16 ones take the tr kernels below)
 template <typename T>
 __global__ __launch_bounds__(256) void window_attn_fwd_kernel(AttnArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int ES = (int)sizeof(T);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int l15 = lane & 15, l4 = lane >> 4;
     const int hdp = a.hdp, L = a.L;
-    const int rstride = (hdp + AT<T>::PAD) * ES, tstride = (64 + AT<T>::PAD) * ES;
-    const size_t gsz = (size_t)((64 * rstride > hdp * tstride) ? 64 * rstride : hdp * tstride);
-    char* G1 = smem;
-    char* G2 = G1 + gsz;
-    char* P = G2 + gsz;  // [64][64+PAD]
+    const int rstride = attn_row_bytes<T>(hdp), tstride = attn_row_bytes<T>(64);
+    const AttnLds lds = attn_one_tile_lds<T>(hdp, false);
+    char* G1 = smem + lds.region(0);
+    char* G2 = smem + lds.region(1);
+    char* P = smem + lds.square(0);  // [64][64+PAD]
     const int64_t t0 = (int64_t)blockIdx.x * L;
     const T* qkv = reinterpret_cast<const T*>(a.qkv.p) + t0 * a.qkv.ld;
     T* out = reinterpret_cast<T*>(const_cast<void*>(a.out.p)) + t0 * a.out.ld;
@@ -468,27 +587,8 @@ __global__ __launch_bounds__(256) void window_attn_fwd_kernel(AttnArgs a) {
             AT<T>::mma(G2, rstride, t * 16, G1, rstride, wv * 16, hdp, lane, s[t]);
         }
         // lane holds query m = 16*wv + l15, keys j = 16t + 4*l4 + r
-        float mx = -__builtin_inff();
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int j = 16 * t + 4 * l4 + r;
-                s[t][r] = j < L ? s[t][r] * a.scale : -__builtin_inff();
-                mx = fmaxf(mx, s[t][r]);
-            }
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        float sum = 0.f;
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                s[t][r] = __expf(s[t][r] - mx);
-                sum += s[t][r];
-            }
-        sum += __shfl_xor(sum, 16, 64);
-        sum += __shfl_xor(sum, 32, 64);
+        float mx, sum;
+        attn_softmax_row(s, L, a.scale, -__builtin_inff(), l4, mx, sum);
         const float inv = 1.f / sum;
         const int m = 16 * wv + l15;
         if (l4 == 0 && m < L && a.lse) a.lse[(t0 + m) * a.heads + head] = mx + __logf(sum);
@@ -508,12 +608,7 @@ __global__ __launch_bounds__(256) void window_attn_fwd_kernel(AttnArgs a) {
             if (dt < ndt) {
                 f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
                 AT<T>::mma(P, tstride, wv * 16, G1, tstride, dt * 16, 64, lane, o);
-                const int d = dt * 16 + l15;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int mq = wv * 16 + 4 * l4 + r;
-                    if (mq < L && d < a.hd) out[(int64_t)mq * a.out.ld + co + d] = from_f32<T>(o[r]);
-                }
+                attn_store_tiles<T, 1>({out + co}, a.out.ld, {o}, L, dt, a.hd);
             }
         }
         __syncthreads();
@@ -523,18 +618,17 @@ __global__ __launch_bounds__(256) void window_attn_fwd_kernel(AttnArgs a) {
 template <typename T>
 __global__ __launch_bounds__(256) void window_attn_bwd_kernel(AttnArgs a) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int ES = (int)sizeof(T);
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int l15 = lane & 15, l4 = lane >> 4;
     const int hdp = a.hdp, L = a.L;
-    const int rstride = (hdp + AT<T>::PAD) * ES, tstride = (64 + AT<T>::PAD) * ES;
-    const size_t gsz = (size_t)((64 * rstride > hdp * tstride) ? 64 * rstride : hdp * tstride);
-    char* G1 = smem;
-    char* G2 = G1 + gsz;
-    char* PT = G2 + gsz;                     // P^T   [key][query]
-    char* DS = PT + (size_t)64 * tstride;    // dS    [query][key]   (scale folded in)
-    char* DST = DS + (size_t)64 * tstride;   // dS^T  [key][query]
-    float* delta = reinterpret_cast<float*>(DST + (size_t)64 * tstride);  // [64]
+    const int rstride = attn_row_bytes<T>(hdp), tstride = attn_row_bytes<T>(64);
+    const AttnLds lds = attn_one_tile_lds<T>(hdp, true);
+    char* G1 = smem + lds.region(0);
+    char* G2 = smem + lds.region(1);
+    char* PT = smem + lds.square(0);   // P^T   [key][query]
+    char* DS = smem + lds.square(1);   // dS    [query][key]   (scale folded in)
+    char* DST = smem + lds.square(2);  // dS^T  [key][query]
+    float* delta = reinterpret_cast<float*>(smem + lds.floats());  // [64]
     const int64_t t0 = (int64_t)blockIdx.x * L;
     const T* qkv = reinterpret_cast<const T*>(a.qkv.p) + t0 * a.qkv.ld;
     const T* o = reinterpret_cast<const T*>(a.out.p) + t0 * a.out.ld;
@@ -547,14 +641,7 @@ __global__ __launch_bounds__(256) void window_attn_bwd_kernel(AttnArgs a) {
         const int co = head * a.hd;
         lds_load_rows<T>(G1, qkv + co, a.qkv.ld, L, a.hd, hdp);        // Q
         lds_load_rows<T>(G2, qkv + a.C + co, a.qkv.ld, L, a.hd, hdp);  // K
-        // delta[m] = sum_d dO[m][d] * O[m][d] : one wave per row, 16 rows per wave
-        for (int m = wv; m < 64; m += 4) {
-            float acc = 0.f;
-            if (m < L)
-                for (int d = lane; d < a.hd; d += 64) acc += to_f32(dO[(int64_t)m * a.dout.ld + co + d]) * to_f32(o[(int64_t)m * a.out.ld + co + d]);
-            acc = wave_sum(acc);
-            if (lane == 0) delta[m] = acc;
-        }
+        attn_delta_rows<T>(delta, dO + co, a.dout.ld, o + co, a.out.ld, L, a.hd);
         __syncthreads();
         // S tiles: A = Q rows (i = query m), B = K rows (j = key): this wave owns queries 16*wv..+15
         f32x4 s[4], dp[4];
@@ -598,12 +685,7 @@ __global__ __launch_bounds__(256) void window_attn_bwd_kernel(AttnArgs a) {
             if (dt < ndt) {
                 f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
                 AT<T>::mma(PT, tstride, wv * 16, G1, tstride, dt * 16, 64, lane, acc);
-                const int d = dt * 16 + l15;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int j = wv * 16 + 4 * l4 + r;
-                    if (j < L && d < a.hd) dqkv[(int64_t)j * a.dqkv.ld + 2 * a.C + co + d] = from_f32<T>(acc[r]);
-                }
+                attn_store_tiles<T, 1>({dqkv + 2 * a.C + co}, a.dqkv.ld, {acc}, L, dt, a.hd);
             }
         __syncthreads();
         // dK[j][d] = sum_m dS^T[j][m] Q^T[d][m]
@@ -614,12 +696,7 @@ __global__ __launch_bounds__(256) void window_attn_bwd_kernel(AttnArgs a) {
             if (dt < ndt) {
                 f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
                 AT<T>::mma(DST, tstride, wv * 16, G1, tstride, dt * 16, 64, lane, acc);
-                const int d = dt * 16 + l15;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int j = wv * 16 + 4 * l4 + r;
-                    if (j < L && d < a.hd) dqkv[(int64_t)j * a.dqkv.ld + a.C + co + d] = from_f32<T>(acc[r]);
-                }
+                attn_store_tiles<T, 1>({dqkv + a.C + co}, a.dqkv.ld, {acc}, L, dt, a.hd);
             }
         __syncthreads();
         // dQ[m][d] = sum_j dS[m][j] K^T[d][j]
@@ -630,12 +707,7 @@ __global__ __launch_bounds__(256) void window_attn_bwd_kernel(AttnArgs a) {
             if (dt < ndt) {
                 f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
                 AT<T>::mma(DS, tstride, wv * 16, G1, tstride, dt * 16, 64, lane, acc);
-                const int d = dt * 16 + l15;
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const int m = wv * 16 + 4 * l4 + r;
-                    if (m < L && d < a.hd) dqkv[(int64_t)m * a.dqkv.ld + co + d] = from_f32<T>(acc[r]);
-                }
+                attn_store_tiles<T, 1>({dqkv + co}, a.dqkv.ld, {acc}, L, dt, a.hd);
             }
         __syncthreads();
     }
@@ -715,11 +787,12 @@ __global__ __launch_bounds__(256) void window_attn_fwd_tr_kernel(AttnArgs a) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int l15 = lane & 15, l4 = lane >> 4;
     const int hdp = a.hdp, L = a.L;
-    const int rstride = (hdp + 8) * 2, tstride = (64 + 8) * 2;
-    char* Qs = smem;
-    char* Ks = Qs + (size_t)64 * rstride;
-    char* Vs = Ks + (size_t)64 * rstride;
-    char* P = Vs + (size_t)64 * rstride;  // [query][key]
+    const int rstride = attn_row_bytes<T>(hdp), tstride = attn_row_bytes<T>(64);
+    const AttnLds lds = attn_tr_lds(hdp, false);
+    char* Qs = smem + lds.region(0);
+    char* Ks = smem + lds.region(1);
+    char* Vs = smem + lds.region(2);
+    char* P = smem + lds.square(0);  // [query][key]
     const int head = blockIdx.y;
     const int co = head * a.hd;
     const int64_t t0 = (int64_t)blockIdx.x * L;
@@ -742,27 +815,8 @@ __global__ __launch_bounds__(256) void window_attn_fwd_tr_kernel(AttnArgs a) {
         AT<T>::mma(Ks, rstride, t * 16, Qs, rstride, wv * 16, hdp, lane, s[t]);
     }
     // lane holds query m = 16*wv + l15, keys j = 16t + 4*l4 + r
-    float mx = -__builtin_inff();
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            const int j = 16 * t + 4 * l4 + r;
-            s[t][r] = j < L ? s[t][r] * a.scale : -__builtin_inff();
-            mx = fmaxf(mx, s[t][r]);
-        }
-    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-    float sum = 0.f;
-#pragma unroll
-    for (int t = 0; t < 4; ++t)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-            s[t][r] = __expf(s[t][r] - mx);
-            sum += s[t][r];
-        }
-    sum += __shfl_xor(sum, 16, 64);
-    sum += __shfl_xor(sum, 32, 64);
+    float mx, sum;
+    attn_softmax_row(s, L, a.scale, -__builtin_inff(), l4, mx, sum);
     const float inv = 1.f / sum;
     const int m = 16 * wv + l15;
     if (l4 == 0 && m < L && a.lse) a.lse[(t0 + m) * a.heads + head] = mx + __logf(sum);
@@ -787,16 +841,7 @@ __global__ __launch_bounds__(256) void window_attn_fwd_tr_kernel(AttnArgs a) {
                 o = __builtin_amdgcn_mfma_f32_16x16x32_bf16(attn_tr_frag(Vs, rstride, k0, 16 * dt, lane), af, o, 0, 0, 0);
             }
             const int d = dt * 16 + 4 * l4, mq = wv * 16 + l15;
-            if (mq < L) {
-                T* dst = out + (int64_t)mq * a.out.ld + co + d;
-                if (vec4 && d + 3 < a.hd) {
-                    *reinterpret_cast<bf16x4*>(dst) = bf16x4{(T)o[0], (T)o[1], (T)o[2], (T)o[3]};
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if (d + r < a.hd) dst[r] = (T)o[r];
-                }
-            }
+            if (mq < L) attn_store_tiles_tr<1>({out + (int64_t)mq * a.out.ld + co + d}, {o}, vec4, d, a.hd);
         }
 }
 
@@ -806,13 +851,14 @@ __global__ __launch_bounds__(256) void window_attn_bwd_tr_kernel(AttnArgs a) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int l15 = lane & 15, l4 = lane >> 4;
     const int hdp = a.hdp, L = a.L;
-    const int rstride = (hdp + 8) * 2, tstride = (64 + 8) * 2;
-    char* Qs = smem;
-    char* Ks = Qs + (size_t)64 * rstride;
-    char* Vs = Ks + (size_t)64 * rstride;
-    char* Os = Vs + (size_t)64 * rstride;   // dO
-    char* Ps = Os + (size_t)64 * rstride;   // P  [query][key]
-    char* Ds = Ps + (size_t)64 * tstride;   // dS [query][key] (scale folded in)
+    const int rstride = attn_row_bytes<T>(hdp), tstride = attn_row_bytes<T>(64);
+    const AttnLds lds = attn_tr_lds(hdp, true);
+    char* Qs = smem + lds.region(0);
+    char* Ks = smem + lds.region(1);
+    char* Vs = smem + lds.region(2);
+    char* Os = smem + lds.region(3);  // dO
+    char* Ps = smem + lds.square(0);  // P  [query][key]
+    char* Ds = smem + lds.square(1);  // dS [query][key] (scale folded in)
     const int head = blockIdx.y;
     const int co = head * a.hd;
     const int64_t t0 = (int64_t)blockIdx.x * L;
@@ -882,60 +928,26 @@ __global__ __launch_bounds__(256) void window_attn_bwd_tr_kernel(AttnArgs a) {
             const int d = dt * 16 + 4 * l4, row = wv * 16 + l15;  // row: key j for dV / dK, query m for dQ
             if (row < L) {
                 T* dst = dqkv + (int64_t)row * a.dqkv.ld + co + d;
-                if (vec4 && d + 3 < a.hd) {
-                    *reinterpret_cast<bf16x4*>(dst + 2 * a.C) = bf16x4{(T)dv[0], (T)dv[1], (T)dv[2], (T)dv[3]};
-                    *reinterpret_cast<bf16x4*>(dst + a.C) = bf16x4{(T)dk[0], (T)dk[1], (T)dk[2], (T)dk[3]};
-                    *reinterpret_cast<bf16x4*>(dst) = bf16x4{(T)dq[0], (T)dq[1], (T)dq[2], (T)dq[3]};
-                } else {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        if (d + r < a.hd) {
-                            dst[2 * a.C + r] = (T)dv[r];
-                            dst[a.C + r] = (T)dk[r];
-                            dst[r] = (T)dq[r];
-                        }
-                }
+                attn_store_tiles_tr<3>({dst + 2 * a.C, dst + a.C, dst}, {dv, dk, dq}, vec4, d, a.hd);
             }
         }
 }
 
-// ---- windows of more than 64 tokens (any window_size: swin_block.py:24) and head dims the one-tile kernels cannot hold ----
+// ---- windows of more than 64 tokens (any window_size: swin_block.py:24), both dtypes; with the attn_tiled option, every window ----
 // Flash-style tiling: 64-query x 64-key tiles, online softmax in the forward, P recomputed from the saved log-sum-exp in the
 // backward (one kernel accumulates dQ over key tiles, one accumulates dK / dV over query tiles: no atomics, deterministic).
 // The head dimension is walked in chunks of ATT_HC columns through two LDS staging buffers, so float32 at head_dim 192
 // fits the 160 KiB of a CU.  This path serves config 5's optional ws = 14 row (196 tokens); the 49-token windows of the
 // benchmark stay on the one-tile kernels above.
-constexpr int ATT_HC = 96;
-
-template <typename T> struct TiledLds {
-    static constexpr int ES = (int)sizeof(T);
-    static constexpr int PAD = AT<T>::PAD;
-    static constexpr int RS = (ATT_HC + PAD) * ES;  // row stride of a [64][chunk] image
-    static constexpr int TS = (64 + PAD) * ES;      // row stride of a [chunk][64] / [64][64] image
-    static constexpr size_t STAGE = (size_t)(64 * RS > ATT_HC * TS ? 64 * RS : ATT_HC * TS);
-};
-
-// delta[m] = sum_d dO[m][d] * O[m][d] for the 64 rows starting at row r0 of the window (zero beyond the window)
-template <typename T>
-__device__ __forceinline__ void attn_delta_rows(float* delta, const T* dO, int64_t ldd, const T* o, int64_t ldo, int rows, int hd) {
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    for (int m = wv; m < 64; m += 4) {
-        float acc = 0.f;
-        if (m < rows)
-            for (int d = lane; d < hd; d += 64) acc += to_f32(dO[(int64_t)m * ldd + d]) * to_f32(o[(int64_t)m * ldo + d]);
-        acc = wave_sum(acc);
-        if (lane == 0) delta[m] = acc;
-    }
-}
-
 template <typename T>
 __global__ __launch_bounds__(256) void window_attn_tiled_fwd_kernel(AttnArgs a) {
-    typedef TiledLds<T> LD;
+    constexpr AttnLds lds = attn_tiled_lds<T>(1);
+    constexpr int TS = attn_row_bytes<T>(64);  // row stride of a [chunk][64] / [64][64] image
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* GA = smem;
-    char* GB = GA + LD::STAGE;
-    char* P = GB + LD::STAGE;                                          // [64 queries][64 keys]
-    float* al = reinterpret_cast<float*>(P + (size_t)64 * LD::TS);     // [64] rescale factor of this key tile / final 1/l
+    char* GA = smem + lds.region(0);
+    char* GB = smem + lds.region(1);
+    char* P = smem + lds.square(0);                            // [64 queries][64 keys]
+    float* al = reinterpret_cast<float*>(smem + lds.floats());  // [64] rescale factor of this key tile / final 1/l
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int l15 = lane & 15, l4 = lane >> 4;
     const int L = a.L, hd = a.hd;
@@ -961,40 +973,20 @@ __global__ __launch_bounds__(256) void window_attn_tiled_fwd_kernel(AttnArgs a) 
             lds_load_rows<T>(GA, qkv + (int64_t)q0 * a.qkv.ld + co + d0, a.qkv.ld, qrows, hc, hcp);
             lds_load_rows<T>(GB, qkv + (int64_t)k0 * a.qkv.ld + a.C + co + d0, a.qkv.ld, krows, hc, hcp);
             __syncthreads();
-            const int rs = (hcp + AT<T>::PAD) * LD::ES;
+            const int rs = attn_row_bytes<T>(hcp);
 #pragma unroll
             for (int t = 0; t < 4; ++t) AT<T>::mma(GB, rs, t * 16, GA, rs, wv * 16, hcp, lane, s[t]);
         }
-        float mx = -__builtin_inff();
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int j = 16 * t + 4 * l4 + r;
-                s[t][r] = j < krows ? s[t][r] * a.scale : -__builtin_inff();
-                mx = fmaxf(mx, s[t][r]);
-            }
-        mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
-        mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
-        const float m_new = fmaxf(m_run, mx);
+        float m_new, sum;
+        attn_softmax_row(s, krows, a.scale, m_run, l4, m_new, sum);
         const float alpha = __expf(m_run - m_new);  // first tile: exp(-inf) = 0
-        float sum = 0.f;
-#pragma unroll
-        for (int t = 0; t < 4; ++t)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                s[t][r] = __expf(s[t][r] - m_new);
-                sum += s[t][r];
-            }
-        sum += __shfl_xor(sum, 16, 64);
-        sum += __shfl_xor(sum, 32, 64);
         l_run = l_run * alpha + sum;
         m_run = m_new;
         const int m = 16 * wv + l15;
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             float p[4] = {s[t][0], s[t][1], s[t][2], s[t][3]};
-            Pack<T, 4>::store(reinterpret_cast<T*>(P + (size_t)m * LD::TS) + 16 * t + 4 * l4, p);
+            Pack<T, 4>::store(reinterpret_cast<T*>(P + (size_t)m * TS) + 16 * t + 4 * l4, p);
         }
         if (l4 == 0) al[m] = alpha;
         __syncthreads();
@@ -1014,7 +1006,7 @@ __global__ __launch_bounds__(256) void window_attn_tiled_fwd_kernel(AttnArgs a) 
             __syncthreads();
 #pragma unroll
             for (int dt = 0; dt < ATT_MAXDT; ++dt)
-                if (dt < ndt && dt * 16 >= d0 && dt * 16 < d0 + ATT_HC) AT<T>::mma(P, LD::TS, wv * 16, GA, LD::TS, dt * 16 - d0, 64, lane, o[dt]);
+                if (dt < ndt && dt * 16 >= d0 && dt * 16 < d0 + ATT_HC) AT<T>::mma(P, TS, wv * 16, GA, TS, dt * 16 - d0, 64, lane, o[dt]);
         }
         __syncthreads();  // P / al are rewritten by the next key tile
     }
@@ -1027,12 +1019,10 @@ __global__ __launch_bounds__(256) void window_attn_tiled_fwd_kernel(AttnArgs a) 
 #pragma unroll
     for (int dt = 0; dt < ATT_MAXDT; ++dt)
         if (dt < ndt) {
-            const int d = dt * 16 + l15;
+            f32x4 on;
 #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int mq = 16 * wv + 4 * l4 + r;
-                if (mq < qrows && d < hd) out[(int64_t)(q0 + mq) * a.out.ld + co + d] = from_f32<T>(o[dt][r] * al[mq]);
-            }
+            for (int r = 0; r < 4; ++r) on[r] = o[dt][r] * al[16 * wv + 4 * l4 + r];
+            attn_store_tiles<T, 1>({out + (int64_t)q0 * a.out.ld + co}, a.out.ld, {on}, qrows, dt, hd);
         }
 }
 
@@ -1041,7 +1031,6 @@ __global__ __launch_bounds__(256) void window_attn_tiled_fwd_kernel(AttnArgs a) 
 template <typename T>
 __device__ __forceinline__ void attn_tile_p_ds(const AttnArgs& a, char* GA, char* GB, const T* qkv, const T* dO, int q0, int qrows, int k0, int krows, int co,
                                                int64_t trow0, int head, const float* delta, float (&p)[4][4], float (&ds)[4][4]) {
-    typedef TiledLds<T> LD;
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int l15 = lane & 15, l4 = lane >> 4;
     const int hd = a.hd;
@@ -1053,7 +1042,7 @@ __device__ __forceinline__ void attn_tile_p_ds(const AttnArgs& a, char* GA, char
     }
     for (int d0 = 0; d0 < hd; d0 += ATT_HC) {
         const int hc = (hd - d0 < ATT_HC) ? hd - d0 : ATT_HC, hcp = (hc + 31) / 32 * 32;
-        const int rs = (hcp + AT<T>::PAD) * LD::ES;
+        const int rs = attn_row_bytes<T>(hcp);
         __syncthreads();
         lds_load_rows<T>(GA, qkv + (int64_t)q0 * a.qkv.ld + co + d0, a.qkv.ld, qrows, hc, hcp);          // Q
         lds_load_rows<T>(GB, qkv + (int64_t)k0 * a.qkv.ld + a.C + co + d0, a.qkv.ld, krows, hc, hcp);  // K
@@ -1083,12 +1072,13 @@ __device__ __forceinline__ void attn_tile_p_ds(const AttnArgs& a, char* GA, char
 
 template <typename T>
 __global__ __launch_bounds__(256) void window_attn_tiled_dq_kernel(AttnArgs a) {
-    typedef TiledLds<T> LD;
+    constexpr AttnLds lds = attn_tiled_lds<T>(1);
+    constexpr int TS = attn_row_bytes<T>(64);
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* GA = smem;
-    char* GB = GA + LD::STAGE;
-    char* DS = GB + LD::STAGE;                                          // [64 queries][64 keys]
-    float* delta = reinterpret_cast<float*>(DS + (size_t)64 * LD::TS);  // [64]
+    char* GA = smem + lds.region(0);
+    char* GB = smem + lds.region(1);
+    char* DS = smem + lds.square(0);                               // [64 queries][64 keys]
+    float* delta = reinterpret_cast<float*>(smem + lds.floats());  // [64]
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int l15 = lane & 15, l4 = lane >> 4;
     const int L = a.L, hd = a.hd;
@@ -1112,7 +1102,7 @@ __global__ __launch_bounds__(256) void window_attn_tiled_dq_kernel(AttnArgs a) {
 #pragma unroll
         for (int t = 0; t < 4; ++t)
 #pragma unroll
-            for (int r = 0; r < 4; ++r) reinterpret_cast<T*>(DS + (size_t)(16 * wv + 4 * l4 + r) * LD::TS)[16 * t + l15] = from_f32<T>(ds[t][r]);
+            for (int r = 0; r < 4; ++r) reinterpret_cast<T*>(DS + (size_t)(16 * wv + 4 * l4 + r) * TS)[16 * t + l15] = from_f32<T>(ds[t][r]);
         // dQ[m][d] += sum_j dS[m][j] K^T[d][j]
         for (int d0 = 0; d0 < hd; d0 += ATT_HC) {
             const int hc = (hd - d0 < ATT_HC) ? hd - d0 : ATT_HC, hcp = (hc + 31) / 32 * 32;
@@ -1121,30 +1111,24 @@ __global__ __launch_bounds__(256) void window_attn_tiled_dq_kernel(AttnArgs a) {
             __syncthreads();
 #pragma unroll
             for (int dt = 0; dt < ATT_MAXDT; ++dt)
-                if (dt < ndt && dt * 16 >= d0 && dt * 16 < d0 + ATT_HC) AT<T>::mma(DS, LD::TS, wv * 16, GA, LD::TS, dt * 16 - d0, 64, lane, dq[dt]);
+                if (dt < ndt && dt * 16 >= d0 && dt * 16 < d0 + ATT_HC) AT<T>::mma(DS, TS, wv * 16, GA, TS, dt * 16 - d0, 64, lane, dq[dt]);
         }
     }
 #pragma unroll
     for (int dt = 0; dt < ATT_MAXDT; ++dt)
-        if (dt < ndt) {
-            const int d = dt * 16 + l15;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int m = 16 * wv + 4 * l4 + r;
-                if (m < qrows && d < hd) dqkv[(int64_t)(q0 + m) * a.dqkv.ld + co + d] = from_f32<T>(dq[dt][r]);
-            }
-        }
+        if (dt < ndt) attn_store_tiles<T, 1>({dqkv + (int64_t)q0 * a.dqkv.ld + co}, a.dqkv.ld, {dq[dt]}, qrows, dt, hd);
 }
 
 template <typename T>
 __global__ __launch_bounds__(256) void window_attn_tiled_dkv_kernel(AttnArgs a) {
-    typedef TiledLds<T> LD;
+    constexpr AttnLds lds = attn_tiled_lds<T>(2);
+    constexpr int TS = attn_row_bytes<T>(64);
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    char* GA = smem;
-    char* GB = GA + LD::STAGE;
-    char* PT = GB + LD::STAGE;                                           // P^T  [64 keys][64 queries]
-    char* DST = PT + (size_t)64 * LD::TS;                                // dS^T [64 keys][64 queries]
-    float* delta = reinterpret_cast<float*>(DST + (size_t)64 * LD::TS);  // [64]
+    char* GA = smem + lds.region(0);
+    char* GB = smem + lds.region(1);
+    char* PT = smem + lds.square(0);                               // P^T  [64 keys][64 queries]
+    char* DST = smem + lds.square(1);                              // dS^T [64 keys][64 queries]
+    float* delta = reinterpret_cast<float*>(smem + lds.floats());  // [64]
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int l15 = lane & 15, l4 = lane >> 4;
     const int L = a.L, hd = a.hd;
@@ -1172,8 +1156,8 @@ __global__ __launch_bounds__(256) void window_attn_tiled_dkv_kernel(AttnArgs a) 
         for (int t = 0; t < 4; ++t) {
             const int j = 16 * t + l15;
             float pv[4] = {p[t][0], p[t][1], p[t][2], p[t][3]}, dv4[4] = {ds[t][0], ds[t][1], ds[t][2], ds[t][3]};
-            Pack<T, 4>::store(reinterpret_cast<T*>(PT + (size_t)j * LD::TS) + 16 * wv + 4 * l4, pv);
-            Pack<T, 4>::store(reinterpret_cast<T*>(DST + (size_t)j * LD::TS) + 16 * wv + 4 * l4, dv4);
+            Pack<T, 4>::store(reinterpret_cast<T*>(PT + (size_t)j * TS) + 16 * wv + 4 * l4, pv);
+            Pack<T, 4>::store(reinterpret_cast<T*>(DST + (size_t)j * TS) + 16 * wv + 4 * l4, dv4);
         }
         for (int d0 = 0; d0 < hd; d0 += ATT_HC) {
             const int hc = (hd - d0 < ATT_HC) ? hd - d0 : ATT_HC, hcp = (hc + 31) / 32 * 32;
@@ -1184,32 +1168,18 @@ __global__ __launch_bounds__(256) void window_attn_tiled_dkv_kernel(AttnArgs a) 
 #pragma unroll
             for (int dt = 0; dt < ATT_MAXDT; ++dt)
                 if (dt < ndt && dt * 16 >= d0 && dt * 16 < d0 + ATT_HC) {
-                    AT<T>::mma(PT, LD::TS, wv * 16, GA, LD::TS, dt * 16 - d0, 64, lane, dv[dt]);   // dV[j][d] += sum_m P^T[j][m] dO^T[d][m]
-                    AT<T>::mma(DST, LD::TS, wv * 16, GB, LD::TS, dt * 16 - d0, 64, lane, dk[dt]);  // dK[j][d] += sum_m dS^T[j][m] Q^T[d][m]
+                    AT<T>::mma(PT, TS, wv * 16, GA, TS, dt * 16 - d0, 64, lane, dv[dt]);   // dV[j][d] += sum_m P^T[j][m] dO^T[d][m]
+                    AT<T>::mma(DST, TS, wv * 16, GB, TS, dt * 16 - d0, 64, lane, dk[dt]);  // dK[j][d] += sum_m dS^T[j][m] Q^T[d][m]
                 }
         }
     }
+    T* dst = dqkv + (int64_t)k0 * a.dqkv.ld + co;
 #pragma unroll
     for (int dt = 0; dt < ATT_MAXDT; ++dt)
-        if (dt < ndt) {
-            const int d = dt * 16 + l15;
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int j = 16 * wv + 4 * l4 + r;
-                if (j < krows && d < hd) {
-                    T* dst = dqkv + (int64_t)(k0 + j) * a.dqkv.ld + co + d;
-                    dst[a.C] = from_f32<T>(dk[dt][r]);
-                    dst[2 * a.C] = from_f32<T>(dv[dt][r]);
-                }
-            }
-        }
+        if (dt < ndt) attn_store_tiles<T, 2>({dst + a.C, dst + 2 * a.C}, a.dqkv.ld, {dk[dt], dv[dt]}, krows, dt, hd);
 }
 
-template <typename T> static size_t tiled_lds(bool bwd_kv) {
-    return 2 * TiledLds<T>::STAGE + (size_t)(bwd_kv ? 2 : 1) * 64 * TiledLds<T>::TS + 64 * sizeof(float);
-}
-
-static int attn_common(const ymi_tensor* qkv, int64_t wlen, int64_t heads, AttnArgs* a, size_t* lds, bool bwd, const char* what) {
+static int attn_common(const ymi_tensor* qkv, int64_t wlen, int64_t heads, AttnArgs* a, const char* what) {
     YMI_CHECK_ARG(ymi_tensor_ok(qkv) && wlen > 0 && heads > 0, "%s: args", what);
     YMI_CHECK_ARG(qkv->c % 3 == 0, "%s: qkv must have 3C channels", what);
     const int64_t C = qkv->c / 3;
@@ -1217,44 +1187,57 @@ static int attn_common(const ymi_tensor* qkv, int64_t wlen, int64_t heads, AttnA
     const int64_t hd = C / heads;
     YMI_CHECK_ARG(hd % 4 == 0 && hd <= 16 * ATT_MAXDT && qkv->ld % 4 == 0, "%s: head_dim must be a multiple of 4 and <= %d", what, 16 * ATT_MAXDT);
     YMI_CHECK_ARG(ymi_pixels(qkv) % wlen == 0, "%s: token count not a multiple of the window length", what);
-    a->L = (int)wlen; a->heads = (int)heads; a->C = (int)C; a->hd = (int)hd; a->hdp = (int)((hd + 31) / 32 * 32);
+    a->L = (int)wlen; a->heads = (int)heads; a->C = (int)C; a->hd = (int)hd; a->hdp = attn_hdp(hd);
     a->scale = 1.0f / sqrtf((float)hd);
-    const int es = (int)ymi_esize(qkv->dtype), pad = qkv->dtype == YMI_BF16 ? 8 : 4;
-    const size_t rs = (size_t)(a->hdp + pad) * es, ts = (size_t)(64 + pad) * es;
-    const size_t gsz = 64 * rs > a->hdp * ts ? 64 * rs : a->hdp * ts;
-    *lds = 2 * gsz + (bwd ? 3 : 1) * 64 * ts + (bwd ? 64 * sizeof(float) : 0);  // one-tile kernels; > 160 KiB or wlen > 64: tiled kernels
     return YMI_OK;
+}
+
+// Which kernels serve a launch.  More than one 64-token tile, or the attn_tiled option (tests): the tiled kernels; one tile: the tr kernels in
+// bfloat16, the generic one-tile kernels in float32.  (Every one-tile image fits the LDS: the static_asserts beside the size functions.)
+enum AttnForm { ATTN_TILED, ATTN_TR, ATTN_ONE_TILE };
+static AttnForm attn_form(int64_t wlen, int32_t dtype, int attn_tiled) {
+    if (wlen > 64 || attn_tiled) return ATTN_TILED;
+    return dtype == YMI_BF16 ? ATTN_TR : ATTN_ONE_TILE;
+}
+
+static void attn_launch(void (*kernel)(AttnArgs), dim3 grid, const AttnLds& lds, const AttnArgs& a, void* stream) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ATT_LDS_MAX);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), lds.bytes(), (hipStream_t)stream, a);
+}
+
+template <typename T>
+static void attn_launch_tiled(bool bwd, dim3 grid, const AttnArgs& a, void* stream) {
+    if (!bwd) return attn_launch(window_attn_tiled_fwd_kernel<T>, grid, attn_tiled_lds<T>(1), a, stream);
+    attn_launch(window_attn_tiled_dq_kernel<T>, grid, attn_tiled_lds<T>(1), a, stream);
+    attn_launch(window_attn_tiled_dkv_kernel<T>, grid, attn_tiled_lds<T>(2), a, stream);
+}
+
+// one workgroup per (window, head) and, in the tiled kernels, per 64-token tile of the window
+static void attn_run(bool bwd, const ymi_tensor* qkv, int64_t wlen, const AttnArgs& a, void* stream) {
+    const dim3 grid((unsigned)(ymi_pixels(qkv) / wlen), (unsigned)a.heads);
+    switch (attn_form(wlen, qkv->dtype, ymi_opt(OPT_ATTN_TILED))) {
+    case ATTN_TILED: {
+        const dim3 tg(grid.x, grid.y, (unsigned)((wlen + 63) / 64));
+        if (qkv->dtype == YMI_BF16) attn_launch_tiled<bf16_t>(bwd, tg, a, stream);
+        else attn_launch_tiled<float>(bwd, tg, a, stream);
+        break;
+    }
+    case ATTN_TR:
+        attn_launch(bwd ? window_attn_bwd_tr_kernel : window_attn_fwd_tr_kernel, grid, attn_tr_lds(a.hdp, bwd), a, stream);
+        break;
+    case ATTN_ONE_TILE:
+        attn_launch(bwd ? window_attn_bwd_kernel<float> : window_attn_fwd_kernel<float>, grid, attn_one_tile_lds<float>(a.hdp, bwd), a, stream);
+        break;
+    }
 }
 
 extern "C" int ymi_window_attention_fwd(const ymi_tensor* qkv, int64_t wlen, int64_t heads, const ymi_tensor* out, float* lse, void* stream) {
     AttnArgs a{};
-    size_t lds = 0;
-    int rc = attn_common(qkv, wlen, heads, &a, &lds, false, "window_attention_fwd");
+    int rc = attn_common(qkv, wlen, heads, &a, "window_attention_fwd");
     if (rc) return rc;
     YMI_CHECK_ARG(ymi_tensor_ok(out) && out->c == a.C && ymi_pixels(out) == ymi_pixels(qkv) && out->dtype == qkv->dtype, "window_attention_fwd: out");
     a.qkv = SV{qkv->data, qkv->ld}; a.out = SV{out->data, out->ld}; a.lse = lse;
-    dim3 grid((unsigned)(ymi_pixels(qkv) / wlen), (unsigned)heads);
-    const int attn_tiled = ymi_opt(OPT_ATTN_TILED);  // 1: tiled kernels for every window size (tests)
-    const size_t lds_tr = (size_t)3 * 64 * (a.hdp + 8) * 2 + (size_t)64 * (64 + 8) * 2;
-    if (wlen > 64 || lds > 160 * 1024 || attn_tiled) {
-        dim3 tg(grid.x, grid.y, (unsigned)((wlen + 63) / 64));
-        if (qkv->dtype == YMI_BF16) {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(window_attn_tiled_fwd_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            hipLaunchKernelGGL(window_attn_tiled_fwd_kernel<bf16_t>, tg, dim3(256), tiled_lds<bf16_t>(false), (hipStream_t)stream, a);
-        } else {
-            (void)hipFuncSetAttribute(reinterpret_cast<const void*>(window_attn_tiled_fwd_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            hipLaunchKernelGGL(window_attn_tiled_fwd_kernel<float>, tg, dim3(256), tiled_lds<float>(false), (hipStream_t)stream, a);
-        }
-    } else if (qkv->dtype == YMI_BF16 && lds_tr <= 160 * 1024) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(window_attn_fwd_tr_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipLaunchKernelGGL(window_attn_fwd_tr_kernel, grid, dim3(256), lds_tr, (hipStream_t)stream, a);
-    } else if (qkv->dtype == YMI_BF16) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(window_attn_fwd_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipLaunchKernelGGL(window_attn_fwd_kernel<bf16_t>, grid, dim3(256), lds, (hipStream_t)stream, a);
-    } else {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(window_attn_fwd_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipLaunchKernelGGL(window_attn_fwd_kernel<float>, grid, dim3(256), lds, (hipStream_t)stream, a);
-    }
+    attn_run(false, qkv, wlen, a, stream);
     YMI_CHECK_LAUNCH("window_attention_fwd");
     return YMI_OK;
 }
@@ -1262,8 +1245,7 @@ extern "C" int ymi_window_attention_fwd(const ymi_tensor* qkv, int64_t wlen, int
 extern "C" int ymi_window_attention_bwd(const ymi_tensor* qkv, const ymi_tensor* out, const ymi_tensor* dout, const float* lse, int64_t wlen,
                                         int64_t heads, const ymi_tensor* dqkv, void* stream) {
     AttnArgs a{};
-    size_t lds = 0;
-    int rc = attn_common(qkv, wlen, heads, &a, &lds, true, "window_attention_bwd");
+    int rc = attn_common(qkv, wlen, heads, &a, "window_attention_bwd");
     if (rc) return rc;
     YMI_CHECK_ARG(ymi_tensor_ok(out) && ymi_tensor_ok(dout) && ymi_tensor_ok(dqkv) && lse, "window_attention_bwd: args");
     YMI_CHECK_ARG(out->c == a.C && dout->c == a.C && dqkv->c == 3 * a.C && out->dtype == qkv->dtype && dout->dtype == qkv->dtype && dqkv->dtype == qkv->dtype,
@@ -1271,31 +1253,7 @@ extern "C" int ymi_window_attention_bwd(const ymi_tensor* qkv, const ymi_tensor*
     YMI_CHECK_ARG(ymi_pixels(out) == ymi_pixels(qkv) && ymi_pixels(dout) == ymi_pixels(qkv) && ymi_pixels(dqkv) == ymi_pixels(qkv), "window_attention_bwd: token counts");
     a.qkv = SV{qkv->data, qkv->ld}; a.out = SV{out->data, out->ld}; a.dout = SV{dout->data, dout->ld}; a.dqkv = SV{dqkv->data, dqkv->ld};
     a.lse = const_cast<float*>(lse);
-    dim3 grid((unsigned)(ymi_pixels(qkv) / wlen), (unsigned)heads);
-    const int attn_tiled = ymi_opt(OPT_ATTN_TILED);
-    const size_t lds_tr = (size_t)4 * 64 * (a.hdp + 8) * 2 + (size_t)2 * 64 * (64 + 8) * 2;
-    if (wlen > 64 || lds > 160 * 1024 || attn_tiled) {
-        dim3 tg(grid.x, grid.y, (unsigned)((wlen + 63) / 64));
-#define YMI_TILED_BWD(T)                                                                                                                          \
-    do {                                                                                                                                          \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(window_attn_tiled_dq_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);  \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(window_attn_tiled_dkv_kernel<T>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-        hipLaunchKernelGGL(window_attn_tiled_dq_kernel<T>, tg, dim3(256), tiled_lds<T>(false), (hipStream_t)stream, a);                             \
-        hipLaunchKernelGGL(window_attn_tiled_dkv_kernel<T>, tg, dim3(256), tiled_lds<T>(true), (hipStream_t)stream, a);                             \
-    } while (0)
-        if (qkv->dtype == YMI_BF16) YMI_TILED_BWD(bf16_t);
-        else YMI_TILED_BWD(float);
-#undef YMI_TILED_BWD
-    } else if (qkv->dtype == YMI_BF16 && lds_tr <= 160 * 1024) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(window_attn_bwd_tr_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipLaunchKernelGGL(window_attn_bwd_tr_kernel, grid, dim3(256), lds_tr, (hipStream_t)stream, a);
-    } else if (qkv->dtype == YMI_BF16) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(window_attn_bwd_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipLaunchKernelGGL(window_attn_bwd_kernel<bf16_t>, grid, dim3(256), lds, (hipStream_t)stream, a);
-    } else {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(window_attn_bwd_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipLaunchKernelGGL(window_attn_bwd_kernel<float>, grid, dim3(256), lds, (hipStream_t)stream, a);
-    }
+    attn_run(true, qkv, wlen, a, stream);
     YMI_CHECK_LAUNCH("window_attention_bwd");
     return YMI_OK;
 }

@@ -17,6 +17,38 @@ from .conv import (  # noqa: F401
     padded_grad_like,
 )
 
+LN_BWD_MAX_BLOCKS = 2048  # ln_bwd_blocks' cap in csrc/swin.hip: the kernel writes two float rows of C per workgroup
+
+
+def _layernorm_bwd(x, ws, dy, gamma, stats, add, dx):
+    """dx = LayerNorm'(dy) (+ add) through ymi_layernorm_bwd_add -> (dgamma, dbeta)."""
+    c = x.shape[1]
+    dgb = torch.empty((2, c), dtype=torch.float32, device=x.device)
+    wsb = workspace(LN_BWD_MAX_BLOCKS * 2 * c * 4 + 256, x.device, "ln")
+    check(
+        L().ymi_layernorm_bwd_add(_byref(as_ymi(x)), ws, _byref(as_ymi(dy)), ptr(gamma), ptr(stats[0]), ptr(stats[1]),
+                                  _byref(as_ymi(add)) if add is not None else None, _byref(as_ymi(dx)), ptr(dgb[0]), ptr(dgb[1]), ptr(wsb), wsb.numel(), stream_ptr()),
+        "layernorm_bwd",
+    )
+    return dgb[0], dgb[1]
+
+
+def _linear_wgrad(x, dy, w, b, need_w, need_b):
+    """dW (shaped like w) and db of y = x W^T + b on token rows; a frozen parameter gets None, two frozen ones no GEMM and no deferred record."""
+    if not (need_w or (b is not None and need_b)):
+        return None, None
+    dw, db = _wgrad_maybe_async(x, dy, w.shape[0], w.shape[1], 1, 1, b is not None, (w, b))
+    return (dw.view(w.shape) if need_w else None), (db if need_b else None)
+
+
+def _mlp_wgrads(u, dpre, post, dout, w1, b1, w2, b2, needs):
+    """-> (dw1, db1, dw2, db2) of fc2(gelu(fc1(u))); needs = needs_input_grad of (w1, b1, w2, b2).  fc2 first, then fc1: the deferred-reduction
+    batch and the captured graph keep the order of the calls."""
+    dw2, db2 = _linear_wgrad(post, dout, w2, b2, needs[2], needs[3])
+    dw1, db1 = _linear_wgrad(u, dpre, w1, b1, needs[0], needs[1])
+    return dw1, db1, dw2, db2
+
+
 class _SwinMlp(torch.autograd.Function):
     """out = fc2(gelu(fc1(u))) + residual on token matrices (swin_block.py:33,53) through ymi_swin_mlp_fwd / _bwd_data: GELU rides
     in fc1's epilogue (second output) and its derivative in fc2's data-gradient epilogue, so the [T, 4C] activation and its
@@ -41,18 +73,17 @@ class _SwinMlp(torch.autograd.Function):
         )
         ctx.save_for_backward(u, w1, w2, pre, post)
         ctx.biases = (b1, b2)
-        ctx.cfg = (b1 is not None, b2 is not None, residual is not None)
+        ctx.has_res = residual is not None
         ctx.joins = (join, res_join)
         return out
 
     @staticmethod
     def backward(ctx, dout):
         u, w1, w2, pre, post = ctx.saved_tensors
-        has_b1, has_b2, has_res = ctx.cfg
         dtype = u.dtype
         dout = grad_nhwc(dout, dtype)
         join, res_join = ctx.joins
-        dres = _join_plain(res_join, dout) if (has_res and ctx.needs_input_grad[5]) else None
+        dres = _join_plain(res_join, dout) if (ctx.has_res and ctx.needs_input_grad[5]) else None
         t, c = u.shape
         hidden = w1.shape[0]
         dpre = torch.empty_like(pre)
@@ -74,14 +105,7 @@ class _SwinMlp(torch.autograd.Function):
             if adds is None:
                 join.deposit(du)
                 du = None
-        nig = ctx.needs_input_grad  # (u, w1, b1, w2, b2, ...): frozen parameters get no GEMM and no deferred record
-        dw1 = db1 = dw2 = db2 = None
-        if nig[3] or (has_b2 and nig[4]):
-            dw2, db2 = _wgrad_maybe_async(post, dout, w2.shape[0], hidden, 1, 1, has_b2, (w2, ctx.biases[1]))
-            dw2, db2 = (dw2.view(w2.shape) if nig[3] else None), (db2 if nig[4] else None)
-        if nig[1] or (has_b1 and nig[2]):
-            dw1, db1 = _wgrad_maybe_async(u, dpre, hidden, c, 1, 1, has_b1, (w1, ctx.biases[0]))
-            dw1, db1 = (dw1.view(w1.shape) if nig[1] else None), (db1 if nig[2] else None)
+        dw1, db1, dw2, db2 = _mlp_wgrads(u, dpre, post, dout, w1, ctx.biases[0], w2, ctx.biases[1], ctx.needs_input_grad[1:5])  # (u, w1, b1, w2, b2, ...)
         return du, dw1, db1, dw2, db2, dres, None, None
 
 
@@ -143,24 +167,11 @@ class _SwinLnMlp(torch.autograd.Function):
         du = torch.empty((t, c), dtype=dtype, device=dev)
         check(L().ymi_swin_ln_mlp_bwd_data(_byref(as_ymi(dout)), ptr(packed), ptr(pre), hidden, _byref(as_ymi(post)), _byref(as_ymi(dpre)), _byref(as_ymi(du)),
                                            stream_ptr()), "swin_ln_mlp_bwd_data")
-        nig = ctx.needs_input_grad  # (x, gamma, beta, eps, w1, b1, w2, b2)
-        dw1 = db1 = dw2 = db2 = None
-        if nig[6] or nig[7]:
-            dw2, db2 = _wgrad_maybe_async(post, dout, c, hidden, 1, 1, True, (w2, b2))
-            dw2, db2 = (dw2.view(w2.shape) if nig[6] else None), (db2 if nig[7] else None)
-        if nig[4] or nig[5]:
-            dw1, db1 = _wgrad_maybe_async(u, dpre, hidden, c, 1, 1, True, (w1, b1))
-            dw1, db1 = (dw1.view(w1.shape) if nig[4] else None), (db1 if nig[5] else None)
+        dw1, db1, dw2, db2 = _mlp_wgrads(u, dpre, post, dout, w1, b1, w2, b2, ctx.needs_input_grad[4:8])  # (x, gamma, beta, eps, w1, b1, w2, b2)
         # LayerNorm's backward on d_u; the skip's gradient (d_out itself) is its addend: dx = LN'(d_u) + d_out
         dx = torch.empty_like(x)
-        dgb = torch.empty((2, c), dtype=torch.float32, device=dev)
-        wsb = workspace(2048 * 2 * c * 4 + 256, dev, "ln")
-        check(
-            L().ymi_layernorm_bwd_add(_byref(as_ymi(x)), 0, _byref(as_ymi(du)), ptr(gamma), ptr(stats[0]), ptr(stats[1]), _byref(as_ymi(dout)), _byref(as_ymi(dx)),
-                                      ptr(dgb[0]), ptr(dgb[1]), ptr(wsb), wsb.numel(), stream_ptr()),
-            "layernorm_bwd",
-        )
-        return dx, dgb[0], dgb[1], None, dw1, db1, dw2, db2
+        dgamma, dbeta = _layernorm_bwd(x, 0, du, gamma, stats, dout, dx)
+        return dx, dgamma, dbeta, None, dw1, db1, dw2, db2
 
 
 def swin_ln_mlp(x, ln, fc1, fc2):
@@ -460,25 +471,18 @@ class _LayerNorm(torch.autograd.Function):
         ws = ctx.ws
         dev = x.device
         g = grad_nhwc(g, x.dtype)
-        c = x.shape[1]
         dx = empty_nhwc(*x.shape, x.dtype, dev) if ws > 0 else torch.empty_like(x)
-        dgb = torch.empty((2, c), dtype=torch.float32, device=dev)
-        wsb = workspace(2048 * 2 * c * 4 + 256, dev, "ln")
         adds = ctx.join.arrive() if ctx.join is not None else []
         fa = _prep_adds(adds, x.dtype)
         if ws > 0 and fa and fa[0].shape != x.shape:
             raise RuntimeError("layernorm backward: addend shape")
-        check(
-            L().ymi_layernorm_bwd_add(_byref(as_ymi(x)), ws, _byref(as_ymi(g)), ptr(gamma), ptr(stats[0]), ptr(stats[1]),
-                                      _byref(as_ymi(fa[0])) if fa else None, _byref(as_ymi(dx)), ptr(dgb[0]), ptr(dgb[1]), ptr(wsb), wsb.numel(), stream_ptr()),
-            "layernorm_bwd",
-        )
+        dgamma, dbeta = _layernorm_bwd(x, ws, g, gamma, stats, fa[0] if fa else None, dx)
         if len(fa) > 1:
             _accumulate(dx, fa[1:])
         if adds is None:
             ctx.join.deposit(dx)
             dx = None
-        return dx, dgb[0], dgb[1], None, None, None
+        return dx, dgamma, dbeta, None, None, None
 
 
 def layernorm(x, ln, ws=0):

@@ -38,12 +38,14 @@ def _emu_all(form, dtype, q, k, v, dO):
 
 # ---------------------------------------------------------------------------------------------------------------- 1. dispatch mirror
 def test_generic_bf16_one_tile_kernels_are_unreachable():
-    """window_attn_fwd_kernel<bf16_t> / window_attn_bwd_kernel<bf16_t> run only when the tr kernels' LDS exceeds 160 KiB at L <= 64; it
-    never does for a head_dim the launcher accepts (<= 192, a multiple of 4)."""
+    """window_attn_fwd_kernel<bf16_t> / window_attn_bwd_kernel<bf16_t> would run only if the tr kernels' LDS exceeded 160 KiB at L <= 64; it
+    never does for a head_dim the launcher accepts (<= 192, a multiple of 4), nor does the float32 one-tile image, so the launchers do not
+    look at the size and the library does not hold the bfloat16 instantiations."""
     for hd in range(4, 193, 4):
         for bwd in (False, True):
             _, lds_tr = A.attn_lds(64, hd, True, bwd)
             assert lds_tr <= A.LDS_MAX, (hd, bwd, lds_tr)
+            assert A.attn_lds(64, hd, False, bwd)[0] <= A.LDS_MAX, (hd, bwd)
             for L in range(1, 65):
                 assert A.attn_form(L, hd, BF, 0, bwd) == "tr", (L, hd, bwd)
                 assert A.attn_form(L, hd, BF, 1, bwd) == "tiled"
@@ -51,6 +53,16 @@ def test_generic_bf16_one_tile_kernels_are_unreachable():
     # the float32 one-tile backward at head_dim 192: 156,928 of 163,840 bytes
     assert A.attn_lds(64, 192, False, True)[0] == 156928
     assert A.attn_form(64, 192, F32, 0, True) == "onetile-f32"
+    # every launched kernel's mangled name is in the library as a registration string
+    from improving_yolov8_cbam_swinblock_amd._lib import LIB_PATH
+
+    if not LIB_PATH.exists():
+        return  # not built: the dispatch mirror above is all there is to check
+    image = LIB_PATH.read_bytes()
+    for name in ("window_attn_fwd_kernelIf", "window_attn_bwd_kernelIf", "window_attn_fwd_tr_kernel", "window_attn_bwd_tr_kernel"):
+        assert name.encode() in image, name
+    for name in ("window_attn_fwd_kernelIDF16b", "window_attn_bwd_kernelIDF16b"):
+        assert name.encode() not in image, name
 
 
 def test_stage_and_layernorm_forms():
