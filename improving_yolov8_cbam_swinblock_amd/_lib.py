@@ -128,6 +128,9 @@ _SIGNATURES = {
     "ymi_detect_nms_sizes": (_c_i32, [_c_i64, _c_i64, _c_i64, _c_i64, _c_i64, ctypes.POINTER(ctypes.c_size_t)]),
     "ymi_detect_nms": (_c_i32, [_vp, _c_i64, _c_i64, _c_i64, _c_f32, _c_f32, _c_i32, _c_i32, ctypes.POINTER(_c_i32), _c_i32, _c_i64, _c_i64, _c_f32,
                                 _vp, _vp, _vp, _sz, _vp]),
+    "ymi_scale_image": (_c_i32, [_vp, _c_i32, _c_i64, _c_i64, _c_i64, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_f32, _c_i32, _c_i32, _c_i32, _vp]),
+    "ymi_tta_merge": (_c_i32, [_c_i32, ctypes.POINTER(_vp), ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64), ctypes.POINTER(_c_f32),
+                               ctypes.POINTER(_c_i32), ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64), _c_i64, _c_i64, _vp, _vp]),
     "ymi_opt_chunk_elems": (_c_i64, []),
     "ymi_opt_grad_norm": (_c_i32, [_vp, _vp, _c_i32, _c_i32, _c_i64, ctypes.POINTER(_vp), _vp, _vp, _c_i64, _c_i64, _vp, _c_i32, _vp]),
     "ymi_opt_update": (_c_i32, [_vp, _vp, _c_i32, _c_i32, _c_i64, ctypes.POINTER(_vp), _vp, _vp, _c_i32, _vp]),
@@ -284,6 +287,13 @@ def workspace(nbytes, device, tag="default"):
         buf = torch.empty(max(int(nbytes), 1 << 20), dtype=torch.uint8, device=device)
         _workspaces[key] = buf
     return buf
+
+
+def live_workspaces(device):
+    """the scratch buffers `workspace` currently hands out on `device`, every stream and tag.  A captured graph's launches hold the ADDRESSES
+    of the ones current at its capture, and `workspace` drops a buffer when a larger request arrives: whoever owns a captured graph keeps
+    this tuple for as long as the graph may replay (engine.trainer.TrainStep._hold_captured)."""
+    return tuple(buf for (idx, _, _), buf in _workspaces.items() if idx == device.index)
 
 
 def set_option(name, value):

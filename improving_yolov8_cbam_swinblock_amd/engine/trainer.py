@@ -1,12 +1,14 @@
 """Training step of the hot path (reference: ultralytics/engine/trainer.py:383-399,614-622,788-849 and
 models/yolo/detect/train.py:90-115), reduced to what the benchmark step needs: bf16 autocast forward,
 v8 detection loss, backward (+ RCCL gradient mean), gradient clip 10.0, SGD-nesterov step, EMA update."""
+import math
 import os
+import random
 
 import torch
 import torch.nn as nn
 
-from .. import ops
+from .. import _lib, ops
 from .ddp import GradientBuckets
 from .optim import FusedAdamax, FusedAdamW, FusedNAdam, FusedRAdam, FusedRMSprop, FusedSGD, ModelEMA
 
@@ -62,6 +64,44 @@ def synthetic_batch(batch, imgsz, device, seed, boxes_per_image=4):
     }
 
 
+def preprocess_batch(batch, imgsz, stride, multi_scale=False, rng=random, device=None):
+    """DetectionTrainer.preprocess_batch of reference models/yolo/detect/train.py:90-115 -> a NEW dict whose "img" is float32 NCHW on the
+    device: a uint8 image batch (what a dataloader produces; host or device) becomes img.float() / 255, and with multi_scale the batch is
+    stretched bilinearly to a size drawn as the reference draws it - the same `random.seed` gives the same sizes:
+        sz = rng.randrange(int(imgsz * 0.5), int(imgsz * 1.5 + stride)) // stride * stride;  sf = sz / max(h, w);
+        no resize when sf == 1, else to ceil(x * sf / stride) * stride per side.
+    Conversion and resize are ONE launch (ops.scale_image): no float copy of the input size is made on the way.  A float32 image is taken as
+    already normalised.  Labels are normalised coordinates and pass through untouched.  The result is what layer 0's direct kernels take
+    (ops.first_conv_ok).  device: where a host batch goes (default: the current cuda device)."""
+    img = batch["img"]
+    if img.dtype not in (torch.uint8, torch.float32):
+        raise TypeError(f"preprocess_batch takes uint8 or float32 images, got {img.dtype}")
+    if not img.is_cuda:
+        img = img.to(device if device is not None else torch.device("cuda", torch.cuda.current_device()), non_blocking=True)
+    h, w = (int(v) for v in img.shape[2:])
+    ns = (h, w)
+    if multi_scale:
+        stride = int(stride)
+        sz = rng.randrange(int(imgsz * 0.5), int(imgsz * 1.5 + stride)) // stride * stride
+        sf = sz / max(h, w)
+        if sf != 1:
+            ns = tuple(math.ceil(x * sf / stride) * stride for x in (h, w))
+    if ns != (h, w) or img.dtype == torch.uint8 or not img.is_contiguous():
+        img = ops.scale_image(img, ns)
+    out = dict(batch)
+    out["img"] = img
+    return out
+
+
+class _CapturedShape:
+    """what TrainStep keeps per captured image shape: the graphs, the static batch they read and the loss items they write."""
+
+    __slots__ = ("graph", "graph2", "static", "items")
+
+    def __init__(self):
+        self.graph = self.graph2 = self.static = self.items = None
+
+
 class TrainStep:
     """one optimisation step: forward under autocast, loss.sum() * world (reference trainer.py:386-388), backward
     with bucketed RCCL mean, then the reference's optimizer_step (trainer.py:614-622) as the fused HIP step: global-norm
@@ -80,6 +120,14 @@ class TrainStep:
         The backward is split with torch.autograd.grad at the boundary tensors (BaseModel.boundary_layers); gradient joins of
         boundary tensors (ops.GradJoin) carry the head's contribution into the backbone's pass.
       * graph="tail": the round-3 multi-rank form (forward + backward as one graph, gradient mean and update eager behind it).
+    image_shapes=N > 1 (multi-scale training, preprocess_batch(multi_scale=True)): up to N distinct shapes of batch["img"] are captured, one
+    graph (three with the split schedule; the update graph G3 reads no activation and is shared) per shape, in a dict keyed by the shape.  A
+    batch of a NEW shape is applied exactly once: as an eager step, after which that shape's graphs are captured WITHOUT being executed; later
+    batches of the shape replay.  Everything that does not depend on the activation shape - parameters, optimizer state, the EMA, the weight
+    arena, the gradient buckets - is shared by all shapes' graphs, which also share the first graph's memory pool.  Label tensors and
+    max_boxes stay static across all shapes.  Scratch buffers are the hazard: `_lib.workspace` and the model's statistics arena REPLACE a
+    buffer when a larger shape asks for more, while the smaller shape's graph still holds the old address, so every capture keeps what its
+    launches address alive (_hold_captured).  The default, image_shapes=1, is the single static shape described above.
     Learning rates / momentum changed through `opt.param_groups` reach a replayed graph: they are read from a device
     array (`FusedSGD.sync_hyper`).
 
@@ -90,7 +138,7 @@ class TrainStep:
     fault.  The captured step contains only kernels of this library and elementwise ATen ops."""
 
     def __init__(self, model, world_size=1, lr=0.01, dtype=torch.bfloat16, bucket_bytes=32 << 20, graph=False, ema=True, optimizer="SGD",
-                 momentum=0.937, decay=5e-4):
+                 momentum=0.937, decay=5e-4, image_shapes=1):
         self.model = model
         self.world = world_size
         self.dtype = dtype
@@ -118,12 +166,23 @@ class TrainStep:
         self._graph_grads = None
         self._seed = None
         self._held = []  # model-side buffers the captured graphs write (_hold_captured)
+        self.image_shapes = int(image_shapes)
+        if self.image_shapes < 1:
+            raise ValueError("image_shapes counts the image shapes a graph is kept for: at least 1")
+        if self.image_shapes > 1 and self.use_graph and not (self.full_graph or self.overlap_graphs):
+            raise ValueError('graph="tail" replays one static shape: image_shapes > 1 needs graph=True or graph="split"')
+        self._shapes = {}  # image_shapes > 1: tuple(img.shape) -> _CapturedShape
+        self._graph2 = self._graph3 = None
         self._comm_events = None  # time_exposed_communication(): [(event after the backward's last graph, event after the wait for the buckets)]
 
     def __call__(self, batch):
         if not self.use_graph:
             return self.eager_step(batch)
-        if self._graph is None:
+        if self.image_shapes > 1:
+            fresh = self._select_shape(batch)
+            if fresh is not None:
+                return fresh  # a new shape: applied by its eager step, its graphs are captured for the batches to come
+        elif self._graph is None:
             if batch.get("max_boxes") is None:
                 raise ValueError("graph=True needs batch['max_boxes'] (static target shape)")
             # The first batch's tensors become the graph's static inputs (later batches are copied into them).
@@ -149,13 +208,68 @@ class TrainStep:
                 elif self.ema is not None:
                     self.opt.count_updates(-1)  # the capture recorded the update without running it
         else:
+            self._load_static(batch)
+        return self._replay()
+
+    def _load_static(self, batch):
+        """copy a batch into the static tensors the (selected) graphs read"""
+        for k, v in batch.items():
+            if torch.is_tensor(v) and v is not self._static[k]:
+                if v.shape != self._static[k].shape:  # copy_ would broadcast silently (e.g. a shorter label tensor)
+                    raise ValueError(f"graph=True replays static shapes: batch['{k}'] is {tuple(v.shape)}, captured {tuple(self._static[k].shape)}")
+                self._static[k].copy_(v)
+            elif not torch.is_tensor(v) and v != self._static[k]:
+                raise ValueError(f"graph=True: batch['{k}'] = {v!r} differs from the captured value {self._static[k]!r}")
+
+    # ---- several image shapes (image_shapes > 1) ------------------------------------------------------------------------------------
+    def _select_shape(self, batch):
+        """make the graphs of batch["img"]'s shape the ones `_replay` runs and load the batch into their static tensors -> None; or, for a
+        shape not seen before, apply the batch with an eager step, capture the shape's graphs without executing them -> that step's loss items."""
+        if batch.get("max_boxes") is None:
+            raise ValueError("graph=True needs batch['max_boxes'] (static target shape)")
+        key = tuple(batch["img"].shape)
+        cap = self._shapes.get(key)
+        if cap is not None:
+            self._graph, self._graph2, self._static, self._static_items = cap.graph, cap.graph2, cap.static, cap.items
+            self._load_static(batch)
+            return None
+        if len(self._shapes) >= self.image_shapes:
+            raise ValueError(f"graph=True with image_shapes={self.image_shapes}: batch['img'] has the new shape {key}, captured are {sorted(self._shapes)}")
+        first = next(iter(self._shapes.values()), None)
+        if first is not None:  # only the image may change shape: labels and max_boxes are static across all shapes
             for k, v in batch.items():
-                if torch.is_tensor(v) and v is not self._static[k]:
-                    if v.shape != self._static[k].shape:  # copy_ would broadcast silently (e.g. a shorter label tensor)
-                        raise ValueError(f"graph=True replays static shapes: batch['{k}'] is {tuple(v.shape)}, captured {tuple(self._static[k].shape)}")
-                    self._static[k].copy_(v)
-                elif not torch.is_tensor(v) and v != self._static[k]:
-                    raise ValueError(f"graph=True: batch['{k}'] = {v!r} differs from the captured value {self._static[k]!r}")
+                ref = first.static.get(k)
+                if k == "img":
+                    continue
+                if torch.is_tensor(v):
+                    if not torch.is_tensor(ref) or v.shape != ref.shape:
+                        raise ValueError(f"graph=True replays static shapes: batch['{k}'] is {tuple(v.shape)}, captured {tuple(ref.shape) if torch.is_tensor(ref) else ref!r}")
+                elif v != ref:
+                    raise ValueError(f"graph=True: batch['{k}'] = {v!r} differs from the captured value {ref!r}")
+        cap = _CapturedShape()
+        cap.static = dict(batch)
+        items = self.eager_step(cap.static)  # this batch's one application
+        # lazy state the capture must find in place (its construction stages host tables): the weight arena is built from the uses the step recorded
+        arena = self.model._state.arena
+        if arena is not None and not arena.built and arena.specs:
+            arena.build()
+        torch.cuda.synchronize()
+        pool = first.graph.pool() if first is not None else None
+        mode = "global" if self.world == 1 else "thread_local"
+        self._graph, self._static = torch.cuda.CUDAGraph(), cap.static
+        if self.overlap_graphs:
+            self._capture_overlap(mode, pool)
+        else:
+            with torch.cuda.graph(self._graph, pool=pool, capture_error_mode=mode):
+                self._static_items = self.eager_step(self._static)
+            self._hold_captured()
+            if self.ema is not None:
+                self.opt.count_updates(-1)  # the capture recorded the update without running it
+        cap.graph, cap.graph2, cap.items = self._graph, self._graph2, self._static_items
+        self._shapes[key] = cap
+        return items
+
+    def _replay(self):
         if self.full_graph or self.overlap_graphs:
             self.opt.sync_hyper()  # scheduler changes reach the captured update through the device array
         self._graph.replay()
@@ -239,16 +353,21 @@ class TrainStep:
 
     def _hold_captured(self):
         """a graph just captured launches that write the model's statistics arena, pack into its weight arena and stage the batched slab sum
-        in RUN.table: keep them referenced for as long as the graphs live, whatever the model or a later pass replaces them with."""
+        in RUN.table, and they address the scratch buffers `_lib.workspace` handed out during the capture: keep all of them referenced for as
+        long as the graphs live, whatever the model, a later pass or a larger image shape replaces them with (a workspace is REPLACED when a
+        larger request arrives; a replay of the smaller shape's graph would otherwise write memory the allocator has given to someone else)."""
         st = self.model._state
-        self._held.append((st.stats, st.arena, ops.RUN.table))
+        dev = next(iter(self.params)).device
+        self._held.append((st.stats, st.arena, ops.RUN.table, _lib.live_workspaces(dev)))
 
-    def _capture_overlap(self, mode):
+    def _capture_overlap(self, mode, pool=None):
+        """pool: the memory pool of an earlier shape's graphs (image_shapes > 1); G3 reads the flat gradient buckets and the optimizer's own
+        state only - nothing of an activation's shape - so the first capture's is replayed for every shape."""
         b = self._static
         # conv / linear weight gradients are written straight into the flat buckets (ops.grad_arena): only the small vectors (BatchNorm
         # and LayerNorm parameters, biases, the paired Detect weights) are copied there
         arena = {id(p): v for bi in range(len(self.buckets.buckets)) for p, v in zip(self.buckets.buckets[bi], self.buckets.flat_views(bi)) if p.dim() >= 2}
-        with torch.cuda.graph(self._graph, capture_error_mode=mode), ops.grad_arena(arena):
+        with torch.cuda.graph(self._graph, pool=pool, capture_error_mode=mode), ops.grad_arena(arena):
             self._static_items, hg, pairs = self._head_pass(b)
             self._pack(0, self._head_params, hg)
         self._hold_captured()
@@ -260,11 +379,12 @@ class TrainStep:
         self._hold_captured()
         del pairs
         self.buckets.wait_all(divide=False)  # (nothing in flight: points .grad at the flat slices the update graph will read)
-        self._graph3 = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self._graph3, pool=self._graph.pool(), capture_error_mode=mode):
-            self.opt.step(None)
-        if self.ema is not None:
-            self.opt.count_updates(-1)  # captured, not executed
+        if self._graph3 is None:
+            self._graph3 = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self._graph3, pool=self._graph.pool(), capture_error_mode=mode):
+                self.opt.step(None)
+            if self.ema is not None:
+                self.opt.count_updates(-1)  # captured, not executed
         self.opt.zero_grad(set_to_none=True)
 
     def _forward_backward(self, batch):

@@ -16,8 +16,9 @@ class DetectionValidator:
     """DetectionValidator(model)(batches) -> results_dict (metrics/precision(B), metrics/recall(B), metrics/mAP50(B), metrics/mAP50-95(B),
     fitness).  `model` may be the trained model or TrainStep's `step.ema.ema`; its train / eval mode is restored."""
 
-    def __init__(self, model, conf=0.001, iou=0.7, max_det=300, single_cls=False, agnostic_nms=False, dtype=torch.bfloat16):
+    def __init__(self, model, conf=0.001, iou=0.7, max_det=300, single_cls=False, agnostic_nms=False, dtype=torch.bfloat16, augment=False):
         self.model = model
+        self.augment = bool(augment)  # test-time augmentation: the forward is model.predict(img, augment=True) (reference engine/validator.py:214)
         self.conf, self.iou, self.max_det = conf, iou, max_det
         self.single_cls, self.agnostic_nms = single_cls, agnostic_nms
         self.dtype = dtype
@@ -82,11 +83,12 @@ class DetectionValidator:
         try:
             for batch in batches:
                 with torch.no_grad():
+                    kw = {"augment": True} if self.augment else {}  # (only then: any module that maps an image batch to predictions can be validated)
                     if self.dtype == torch.float32:
-                        preds = self.model(batch["img"])
+                        preds = self.model(batch["img"], **kw)
                     else:
                         with torch.autocast("cuda", dtype=self.dtype):
-                            preds = self.model(batch["img"])
+                            preds = self.model(batch["img"], **kw)
                     det, count = self.postprocess(preds)
                 self.update_metrics(det.cpu(), count.cpu(), batch)
         finally:

@@ -6,6 +6,7 @@ rows, `scales`, `nc`), the same module-name lookup, width/depth rules and attrib
 state_dict loads with `load_state_dict`.  What runs underneath is libyolo_mi355.so.
 """
 import ast
+import math
 import re
 from copy import deepcopy
 from pathlib import Path
@@ -389,5 +390,44 @@ class DetectionModel(BaseModel):
 
     def predict(self, x, profile=False, visualize=False, augment=False, embed=None):
         if augment:
-            raise NotImplementedError("test-time augmentation is outside the accelerated path")
+            return self._predict_augment(x)
         return self._predict_once(x)
+
+    TTA_SCALES = (1, 0.83, 0.67)  # reference tasks.py:388-389
+    TTA_FLIPS = (None, 3, None)   # (2 up-down, 3 left-right)
+
+    def _predict_augment(self, x):
+        """test-time augmentation of reference tasks.py:374-397: three passes at scales 1 / 0.83 / 0.67, the middle one flipped left-right,
+        de-scaled, de-flipped, their tails clipped and concatenated -> (y [B, 4 + nc, A'], None).  Each augmented input is ONE launch
+        (flip + resize + pad: ops.scale_image; none for the first pass) and the three outputs are merged by ONE launch (ops.tta_merge:
+        no torch.cat, so the whole call can sit inside a captured region)."""
+        if self.training:
+            raise RuntimeError("predict(augment=True) merges decoded predictions: call model.eval() first")
+        img_size = x.shape[-2:]
+        det = self.model[-1]
+        ys = []
+        for si, fi in zip(self.TTA_SCALES, self.TTA_FLIPS):
+            if si == 1 and not fi:
+                xi = x
+            else:
+                gs = int(max(det._stride_host))  # (the first pass decoded with it: no device read here)
+                h, w = img_size
+                xi = ops.scale_image(x, (int(h * si), int(w * si)), tuple(math.ceil(v * si / gs) * gs for v in (h, w)), pad_value=0.447, flip=fi)
+            ys.append(self._predict_once(xi)[0])
+        ranges = ops.tta_clip_ranges([y.shape[-1] for y in ys], det.nl)
+        return ops.tta_merge(ys, self.TTA_SCALES, self.TTA_FLIPS, img_size, ranges), None
+
+    @staticmethod
+    def _descale_pred(p, flips, scale, img_size, dim=1):
+        """reference tasks.py:399-420 on one decoded prediction [B, 4 + nc, A] -> a new tensor (the reference also scales p's boxes in place;
+        nothing here reads p afterwards)."""
+        if dim != 1:
+            raise NotImplementedError("_descale_pred works on the channel axis of [B, 4 + nc, A] predictions (dim=1)")
+        return ops.tta_merge([p], [scale], [flips], img_size)
+
+    def _clip_augmented(self, y):
+        """reference tasks.py:422-439: the first prediction without its coarsest level's share of anchors, the last without its finest's."""
+        ranges = ops.tta_clip_ranges([t.shape[-1] for t in y], self.model[-1].nl)
+        for k in sorted({0, len(y) - 1}):
+            y[k] = y[k][..., ranges[k][0] : ranges[k][1]]
+        return y

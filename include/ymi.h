@@ -398,6 +398,26 @@ int ymi_detect_nms(const float* y, int64_t batch, int64_t nc, int64_t anchors, f
                    int32_t agnostic, const int32_t* host_classes, int32_t n_classes, int64_t max_det, int64_t max_nms, float max_wh, float* det,
                    int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------ image rescaling ---- */
+/* F.interpolate(mode="bilinear", align_corners=False) of an image batch with what the reference does around it, as one launch
+ * (csrc/resize.hip): utils/torch_utils.py:475-495 (scale_img), models/yolo/detect/train.py:100-114 (preprocess_batch), nn/tasks.py:392.
+ *   src   : `planes` = B * C planes [h][w], NCHW contiguous; uint8 (src_uint8 != 0) or float32
+ *   dst   : float32 planes [hp][wp]; rows < hs and columns < ws hold the interpolation to (hs, ws), the rest pad_value
+ *           (F.pad(img, [0, wp - ws, 0, hp - hs], value)); hs <= hp, ws <= wp
+ *   normalize (uint8 sources only): every source value is divided by 255 first, rounded as img.float() / 255 rounds
+ *   flip_lr / flip_ud: the source is read as x.flip(3) / x.flip(2)
+ * Arithmetic, in float32, one rounding per operation: scale = in / out, s = max((dst + 0.5) * scale - 0.5, 0), i0 = floor(s),
+ * i1 = min(i0 + 1, in - 1), l1 = s - i0, l0 = 1 - l1, out = l0y * (l0x * a + l1x * b) + l1y * (l0x * c + l1x * d).  hs == h and
+ * ws == w copies the converted source exactly. */
+int ymi_scale_image(const void* src, int32_t src_uint8, int64_t planes, int64_t h, int64_t w, float* dst, int64_t hp, int64_t wp, int64_t hs,
+                    int64_t ws, float pad_value, int32_t normalize, int32_t flip_lr, int32_t flip_ud, void* stream);
+/* _descale_pred + _clip_augmented + the final torch.cat of nn/tasks.py:394-439 as one launch: n <= 3 decoded Detect outputs
+ * src[i] [batch][rows = 4 + nc][anchors[i]] float32 (HOST arrays of n entries each); source i contributes its anchors [lo[i], hi[i]) to
+ * out [batch][rows][sum (hi - lo)], in source order.  Rows 0..3 are divided by scale[i]; then row 0 becomes img_w[i] - x for flip[i] == 3
+ * and row 1 becomes img_h[i] - y for flip[i] == 2 (flip 0: neither); the class rows are copied. */
+int ymi_tta_merge(int32_t n, const float* const* src, const int64_t* anchors, const int64_t* lo, const int64_t* hi, const float* scale,
+                  const int32_t* flip, const int64_t* img_h, const int64_t* img_w, int64_t batch, int64_t rows, float* out, void* stream);
+
 /* ------------------------------------------------------------------------- optimizer step ---- */
 /* The update either side of backward, reference engine/trainer.py:614-622 (optimizer_step: clip_grad_norm_(10.0),
  * SGD-nesterov step, EMA update), :788-849 (three parameter groups) and utils/torch_utils.py:657-673 (ModelEMA.update),
