@@ -14,6 +14,10 @@ typedef __attribute__((ext_vector_type(2))) float f32x2;
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
 
+// global-memory source and LDS destination of an LDS-DMA load (__builtin_amdgcn_global_load_lds)
+typedef const __attribute__((address_space(1))) void* gptr_t;
+typedef __attribute__((address_space(3))) void* lptr_t;
+
 #define YMI_WAVE 64
 
 // ---- error plumbing (host) -------------------------------------------------------------------
@@ -282,6 +286,17 @@ struct YmiBnRider {
 };
 // issue the held weight-gradient launch of `stream` with `rider` in it -> true; false when nothing is held there (the caller launches its final pass itself)
 bool ymi_wgrad_issue_held(const YmiBnRider* rider, hipStream_t stream);
+
+// ---- entry points one source file offers another (host) ---------------------------------------------------------------------------
+// profile.hip: per-launch roofline records of the GEMM families (igemm.hip, wgrad.hip)
+bool ymi_prof_enabled();
+int ymi_prof_start(hipStream_t stream, int family, double flop, double bytes, double peak_tflops);
+void ymi_prof_stop(hipStream_t stream, int idx);
+// igemm.hip: one GEMM launch from filled arguments; the raw convolution with fixed-point statistics behind ymi_conv2d_bn_silu_fwd_acc (elementwise.hip)
+struct IgemmArgs;
+int ymi_launch_igemm(const IgemmArgs& a, int dtype, bool stats, int* host_blocks, hipStream_t stream);
+int ymi_conv2d_fwd_statacc(const ymi_tensor* x, const void* w_packed, int64_t cout, int64_t kh, int64_t kw, int64_t stride, const ymi_tensor* y,
+                           long long* stat_acc, void* stream);
 
 // a slot of 64 ticket counters for one launch (host; round-robin over 1024 slots, zero between launches)
 unsigned* ymi_ticket_slot();

@@ -716,8 +716,6 @@ static int conv_bn_act_fwd_impl(const ymi_tensor* x, const void* w_packed, int64
 // (igemm.hip's statistics epilogue; scale_shift_act_fixed_kernel<.., FIN>).  stat_acc: [4][2][cout] int64, ZERO on entry (the caller zeroes
 // its arena of them once per forward), garbage afterwards.  Shapes the fixed-group affine kernel does not take (cout not a multiple of 4 or
 // > 1024, unaligned tensors) are refused: the caller keeps ymi_conv2d_bn_silu_fwd for them (ymi_conv2d_bn_silu_fwd_acc_ok).
-int ymi_conv2d_fwd_statacc(const ymi_tensor* x, const void* w_packed, int64_t cout, int64_t kh, int64_t kw, int64_t stride, const ymi_tensor* y,
-                           long long* stat_acc, void* stream);
 extern "C" int ymi_conv2d_bn_silu_fwd_acc_ok(const ymi_tensor* raw, const ymi_tensor* out, const ymi_tensor* residual) {
     if (!ymi_tensor_ok(raw) || !ymi_tensor_ok(out) || !ymi_same_shape(raw, out) || raw->dtype != out->dtype) return 0;
     if (residual && (!ymi_tensor_ok(residual) || !ymi_same_shape(residual, out) || residual->dtype != out->dtype)) return 0;

@@ -58,7 +58,7 @@ struct IgemmArgs {
     uint64_t tap_dh, tap_dw;
     int act, vec_store, vec16;
     uint32_t wo_mul, wo_shr, ho_mul, ho_shr;  // fast division by Wo / Ho
-    int nmb, nnb, mpx;                        // M blocks, N blocks, most M blocks any XCD owns (launch geometry, set by the launcher)
+    int nmb, nnb;                             // M blocks, N blocks (launch geometry, set by the launcher)
     int span;                                 // rows of M an XCD owns: ymi_xcd_span(M) (common.h, XCD ownership of the pixel axis)
 };
 
@@ -76,12 +76,8 @@ struct IgemmMulti {
     int hetero;
 };
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
-
 // n / d for n < 2^31 with a host-computed magic (d == 1 <=> mul == 0)
-__device__ __forceinline__ int fast_div(int n, uint32_t mul, uint32_t shr, int d) {
-    (void)d;
+__device__ __forceinline__ int fast_div(int n, uint32_t mul, uint32_t shr) {
     return mul ? (int)(__umulhi((uint32_t)n, mul) >> shr) : n;
 }
 
@@ -99,51 +95,7 @@ template <> struct Mma<bf16_t> {
     // swizzle: 64-B rows  -> chunk ^ ((-(row>>2))&3)   (rows r, r+4 share banks)
     //          128-B rows -> chunk ^ ((row>>1)&7)      (rows r, r+2 share banks); both are conflict-free for the
     //          4x16-lane groups of ds_read_b128 when a fragment's 16 rows start at a multiple of 16.
-    template <int TM, int TN, int CPR>
-    static __device__ __forceinline__ void step(const char* As, const char* Bs, int a_row0, int b_row0, int lane, f32x4 (&acc)[TN][TM]) {
-        constexpr int ROWB = CPR * 16;
-        const int l15 = lane & 15, l4 = lane >> 4;
-        const int sw = CPR == 4 ? ((-(l15 >> 2)) & 3) : ((l15 >> 1) & 7);
-        // Every fragment of the K step is requested before the first MFMA, and each 32-deep sub-step waits only for ITS
-        // reads (counted lgkmcnt): the second sub-step's reads travel while the first multiplies.  hipcc schedules LDS
-        // reads next to their uses and always waits with lgkmcnt(0) here (one exposed LDS round trip per 4-8 MFMAs; PMC,
-        // profiles/r02_pmc_igemm.txt: waves parked 39 % of their cycles), so the reads and waits are written out.
-        constexpr int KS = CPR / 4;
-        static_assert(KS <= 2, "one or two 32-deep sub-steps");
-        bf16x8 wf[KS][TN], xf[KS][TM];
-        const uint32_t bbase = (uint32_t)(uintptr_t)(lptr_t)(Bs + (b_row0 + l15) * ROWB);
-        const uint32_t abase = (uint32_t)(uintptr_t)(lptr_t)(As + (a_row0 + l15) * ROWB);
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            const uint32_t coff = (uint32_t)(((4 * ks + l4) ^ sw) << 4);
-#pragma unroll
-            for (int tn = 0; tn < TN; ++tn)
-                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(wf[ks][tn]) : "v"(bbase + coff), "n"(tn * 16 * ROWB));
-#pragma unroll
-            for (int tm = 0; tm < TM; ++tm)
-                asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(xf[ks][tm]) : "v"(abase + coff), "n"(tm * 16 * ROWB));
-        }
-#pragma unroll
-        for (int ks = 0; ks < KS; ++ks) {
-            // wait for sub-step ks: the (KS-1-ks)*(TN+TM) younger reads may still be in flight.  The fragments are tied
-            // to the wait as in/out operands so that no MFMA of this sub-step is scheduled above it.
-            __builtin_amdgcn_sched_barrier(0);  // the MFMAs of the previous sub-step stay above this wait
-            if (ks + 1 < KS) asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(TN + TM) : "memory");  // (TN + TM <= 8: fits the 4-bit counter)
-            else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-            for (int tn = 0; tn < TN; ++tn) asm volatile("" : "+v"(wf[ks][tn]));
-#pragma unroll
-            for (int tm = 0; tm < TM; ++tm) asm volatile("" : "+v"(xf[ks][tm]));
-#pragma unroll
-            for (int tn = 0; tn < TN; ++tn)
-#pragma unroll
-                for (int tm = 0; tm < TM; ++tm)
-                    acc[tn][tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ks][tn], xf[ks][tm], acc[tn][tm], 0, 0, 0);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-
-    // The two halves of a K step for the ping-pong kernel: fragment reads into registers (memory phase) ...
+    // Every fragment of the K step is requested, in sub-step order, before anything waits: [sub-step][TN weight fragments, TM pixel fragments].
     template <int TM, int TN, int CPR>
     static __device__ __forceinline__ void read_frags(const char* As, const char* Bs, int a_row0, int b_row0, int lane, bf16x8 (&wf)[CPR / 4][TN],
                                                       bf16x8 (&xf)[CPR / 4][TM]) {
@@ -164,12 +116,24 @@ template <> struct Mma<bf16_t> {
                 asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(xf[ks][tm]) : "v"(abase + coff), "n"(tm * 16 * ROWB));
         }
     }
-    // ... and the MFMAs on those registers (compute phase)
+
     template <int TM, int TN, int CPR>
-    static __device__ __forceinline__ void mma_frags(bf16x8 (&wf)[CPR / 4][TN], bf16x8 (&xf)[CPR / 4][TM], f32x4 (&acc)[TN][TM]) {
+    static __device__ __forceinline__ void step(const char* As, const char* Bs, int a_row0, int b_row0, int lane, f32x4 (&acc)[TN][TM]) {
+        // Every fragment of the K step is requested before the first MFMA, and each 32-deep sub-step waits only for ITS
+        // reads (counted lgkmcnt): the second sub-step's reads travel while the first multiplies.  hipcc schedules LDS
+        // reads next to their uses and always waits with lgkmcnt(0) here (one exposed LDS round trip per 4-8 MFMAs; PMC,
+        // profiles/r02_pmc_igemm.txt: waves parked 39 % of their cycles), so the reads and waits are written out.
         constexpr int KS = CPR / 4;
+        static_assert(KS <= 2, "one or two 32-deep sub-steps");
+        bf16x8 wf[KS][TN], xf[KS][TM];
+        read_frags<TM, TN, CPR>(As, Bs, a_row0, b_row0, lane, wf, xf);
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
+            // wait for sub-step ks: the (KS-1-ks)*(TN+TM) younger reads may still be in flight.  The fragments are tied
+            // to the wait as in/out operands so that no MFMA of this sub-step is scheduled above it.
+            __builtin_amdgcn_sched_barrier(0);  // the MFMAs of the previous sub-step stay above this wait
+            if (ks + 1 < KS) asm volatile("s_waitcnt lgkmcnt(%0)" ::"n"(TN + TM) : "memory");  // (TN + TM <= 8: fits the 4-bit counter)
+            else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
             for (int tn = 0; tn < TN; ++tn) asm volatile("" : "+v"(wf[ks][tn]));
 #pragma unroll
@@ -177,7 +141,9 @@ template <> struct Mma<bf16_t> {
 #pragma unroll
             for (int tn = 0; tn < TN; ++tn)
 #pragma unroll
-                for (int tm = 0; tm < TM; ++tm) acc[tn][tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ks][tn], xf[ks][tm], acc[tn][tm], 0, 0, 0);
+                for (int tm = 0; tm < TM; ++tm)
+                    acc[tn][tm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ks][tn], xf[ks][tm], acc[tn][tm], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
         }
     }
 };
@@ -203,7 +169,6 @@ template <> struct Mma<float> {
     }
 };
 
-
 // sum of a value over the 16 lanes of its DPP row, result in every lane: xor-1 and xor-2 quad permutes, then the half-row and
 // row mirrors (each lane already holds its quad's / half-row's total, so the mirrored partner supplies the other one)
 template <int CTRL> __device__ __forceinline__ float dpp_add(float v) {
@@ -217,19 +182,63 @@ __device__ __forceinline__ float row16_sum(float v) {
     return v;
 }
 
+// ---- LDS image of a kernel form: ONE description, read by the kernel, the epilogue and the launcher ------------------------------------------
+// K loop: a ring of NS stages; a stage holds the BM pixel rows, then the BN weight rows, CPR 16-byte chunks each.  The epilogue reuses the
+// bytes for the [BM][BN] output image (rows padded by 16 bytes) and, in statistics mode, the per-wave-row sums [IGEMM_MAX_WM][2][BN] behind it.
+constexpr int IGEMM_MAX_WM = 4;
+constexpr int igemm_stage_bytes(int bm, int bn, int cpr) { return (bm + bn) * cpr * 16; }
+constexpr int igemm_crow_bytes(int bn, int es) { return bn * es + 16; }
+constexpr int igemm_lds_bytes(int bm, int bn, int ns, int cpr, int es, bool stats) {
+    const int ring = ns * igemm_stage_bytes(bm, bn, cpr);
+    const int epi = bm * igemm_crow_bytes(bn, es) + (stats ? IGEMM_MAX_WM * 2 * bn * (int)sizeof(float) : 0);
+    return ring > epi ? ring : epi;
+}
+constexpr int IGEMM_LDS_MAX = 160 * 1024;
+
+// ---- XCD ownership of M blocks: ONE function, called by the kernel (twice) and by the launcher's grid sizing ----------------------------------
+// XCD `xcd` owns the BM-row blocks whose first row lies in its span of the pixel order (the rule every streaming kernel follows, common.h):
+// blocks [first, last) of the problem's nmb.  If kernel and launcher ever disagreed, tiles would be skipped or run twice.
+struct MBlockRange {
+    int first, last;
+    __host__ __device__ int count() const { return last > first ? last - first : 0; }
+};
+__host__ __device__ __forceinline__ MBlockRange xcd_m_blocks(int xcd, int span, int nmb, int bm) {
+    const int first = (xcd * span + bm - 1) / bm;
+    const int last = ((xcd + 1) * span + bm - 1) / bm;
+    return MBlockRange{first, last < nmb ? last : nmb};
+}
+
 // ---- epilogue shared by the GEMM kernels -------------------------------------------------------------------------
 // The tile leaves through LDS: lanes drop their 4-channel groups into a [pixel][channel] image, then the workgroup
 // stores it as 16-byte chunks along C, so every store instruction writes whole 128-byte lines (per-lane 8-byte stores
 // to 16 different rows cost 2-3x the time of the same bytes stored this way).  STATS: raw output + deterministic
 // per-block BatchNorm partial sums; otherwise scale / bias / activation / up to two addends.
-template <typename T, int BM, int BN, int WM, int WN, bool STATS, int NT>
+
+// The image as 16-byte chunks, walked by all NTHR threads: body(m, ch0, chunk) for every chunk inside M x Cout (m: GEMM row, ch0: the chunk's
+// first channel).  UNROLL: 4 for the plain store, 1 where the body is long (the code-size note in the epilogue).
+template <typename T, int BM, int BN, int NTHR, int UNROLL, class F>
+__device__ __forceinline__ void for_each_out_chunk(const IgemmArgs& a, const char* Cimg, int m0, int n0, int tid, F&& body) {
+    constexpr int ES = (int)sizeof(T), CROW = igemm_crow_bytes(BN, ES);
+    constexpr int CPW = BN * ES / 16;  // 16-byte chunks per output row
+    constexpr int EPC = 16 / ES;       // elements per chunk
+#pragma unroll UNROLL
+    for (int idx = tid; idx < BM * CPW; idx += NTHR) {
+        const int row = idx / CPW, cc = idx % CPW;
+        const int m = m0 + row, ch0 = n0 + cc * EPC;
+        if (m < a.M && ch0 < a.Cout) body(m, ch0, *reinterpret_cast<const u32x4*>(Cimg + row * CROW + cc * 16));
+    }
+}
+
+template <typename T, int BM, int BN, int WM, int WN, bool STATS>
 __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& a, f32x4 (&acc)[BN / WN / 16][BM / WM / 16], char* smem, int m0, int n0, int mb, int wm,
-                                               int wn, int lane, int tid_all) {
-    constexpr int TM = BM / WM / 16, TN = BN / WN / 16;
+                                               int wn, int lane, int tid) {
+    constexpr int TM = BM / WM / 16, TN = BN / WN / 16, NTHR = WM * WN * 64;
+    static_assert(WM <= IGEMM_MAX_WM, "igemm_lds_bytes sizes the statistics rows for IGEMM_MAX_WM wave rows");
     const int l15 = lane & 15, l4 = lane >> 4;
     T* yg = reinterpret_cast<T*>(a.y);
     constexpr int ES = (int)sizeof(T);
-    constexpr int CROW = BN * ES + 16;  // padded LDS row of the output image
+    constexpr int EPC = 16 / ES;                     // elements per 16-byte chunk
+    constexpr int CROW = igemm_crow_bytes(BN, ES);  // padded LDS row of the output image
     char* Cimg = smem;
     float* red = reinterpret_cast<float*>(smem + BM * CROW);  // [WM][2][BN] (STATS)
     const T* rg = reinterpret_cast<const T*>(a.res);    // (no __restrict__: an addend may be the output buffer itself, read before it is written)
@@ -238,13 +247,27 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& a, f32x4 (&acc)[
     // output pixel (row of y, and of the epilogue addends) that GEMM row m produces
     auto out_pixel = [&](int m) -> int64_t {
         if (a.s_out == 1 && a.Hy == a.Ho && a.Wy == a.Wo) return (int64_t)m;
-        const int t = fast_div(m, a.wo_mul, a.wo_shr, a.Wo);
+        const int t = fast_div(m, a.wo_mul, a.wo_shr);
         const int wo = m - t * a.Wo;
-        const int n = fast_div(t, a.ho_mul, a.ho_shr, a.Ho);
+        const int n = fast_div(t, a.ho_mul, a.ho_shr);
         const int ho = t - n * a.Ho;
         return ((int64_t)n * a.Hy + ho * a.s_out + a.oh_off) * a.Wy + wo * a.s_out + a.ow_off;
     };
     auto out_offset = [&](int m) -> int64_t { return out_pixel(m) * a.ldy; };
+    // the addends of four consecutive channels of output pixel px, joined in float32: res, then res2 ...
+    auto add_addends = [&](float (&v)[4], int64_t px, int ch) {
+        float rr[4];
+        Pack<T, 4>::load(rg + px * a.ldres + ch, rr);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) v[r] += rr[r];
+        if (rg2) {
+            Pack<T, 4>::load(rg2 + px * a.ldres2 + ch, rr);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) v[r] += rr[r];
+        }
+    };
+    // ... and of one channel where they are not 4-element aligned: res + res2 is formed first
+    auto addend_sum = [&](int64_t px, int ch) -> float { return to_f32(rg[px * a.ldres + ch]) + (rg2 ? to_f32(rg2[px * a.ldres2 + ch]) : 0.f); };
 
     // Code size matters here: this block is unrolled TN x TM times around register-indexed accumulators, and every workgroup runs
     // it once.  With the activation (erff), the scalar residual fall-backs and the unaligned stores inlined per tile it was 11,500
@@ -301,17 +324,7 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& a, f32x4 (&acc)[
             } else {
 #pragma unroll
                 for (int r = 0; r < 4; ++r) v[r] = acc[tn][tm][r] * sc[r] + bi[r];
-                if (res1 && rpx[tm] >= 0 && ch + 3 < a.Cout) {
-                    float rr[4];
-                    Pack<T, 4>::load(rg + rpx[tm] * a.ldres + ch, rr);
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) v[r] += rr[r];
-                    if (rg2) {
-                        Pack<T, 4>::load(rg2 + rpx[tm] * a.ldres2 + ch, rr);
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) v[r] += rr[r];
-                    }
-                }
+                if (res1 && rpx[tm] >= 0 && ch + 3 < a.Cout) add_addends(v, rpx[tm], ch);
                 if (mul1 && rpx[tm] >= 0 && ch + 3 < a.Cout) {
                     float mm[4];
                     Pack<T, 4>::load(mulq + rpx[tm] * a.ldmul + ch, mm);
@@ -342,18 +355,18 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& a, f32x4 (&acc)[
     }
     __syncthreads();
     if constexpr (STATS) {
-        if (tid_all < 2 * BN) {
-            const int which = tid_all / BN, chl = tid_all % BN;
+        if (tid < 2 * BN) {
+            const int which = tid / BN, chl = tid % BN;
             float sum = 0.f;
 #pragma unroll
             for (int q = 0; q < WM; ++q) sum += red[(q * 2 + which) * BN + chl];
             const int ch = n0 + chl;
             if (ch < a.Cout) {
                 if (a.stat_acc) {
-                    // Round 5: the per-block sums leave as 64-bit FIXED-POINT atomic adds (steps of 2^-shift) into one of four replica rows, and the
-                    // consumer - the BatchNorm affine pass, a kernel boundary later - sums the replicas and finalizes in its prologue: the
-                    // separate finalize launch (and, from 1024 row blocks up, the row pre-reduction before it: 65 launches of ~5 us a step) is
-                    // gone.  Integer addition is exact and order-free, so the statistics stay bit-for-bit reproducible whatever order the
+                    // The per-block sums leave as 64-bit FIXED-POINT atomic adds (steps of 2^-shift) into one of four replica rows, and the
+                    // consumer - the BatchNorm affine pass, a kernel boundary later - sums the replicas and finalizes in its prologue, so there
+                    // is no finalize launch (nor, from 1024 row blocks up, a row pre-reduction before it: 65 launches of ~5 us a step).
+                    // Integer addition is exact and order-free, so the statistics stay bit-for-bit reproducible whatever order the
                     // tiles finish in; a float atomic would not be.  shift = 37 - ceil(log2(pixel count)) (common.h): sums of squares up to
                     // count * 2^24 (an r.m.s. of 4096) fit with two bits to spare, and the step is 2^-15 at 3.3 M pixels, 2^-31 at 64 - after
                     // the division by the count below 1e-11 of the variance in either case, far under any BatchNorm eps.
@@ -366,97 +379,67 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& a, f32x4 (&acc)[
         }
     }
     if (a.vec16) {
-        constexpr int CPW = BN * ES / 16;  // 16-byte chunks per output row
-        constexpr int EPC = 16 / ES;       // elements per chunk
         const T* mulp = (STATS || mul1) ? nullptr : reinterpret_cast<const T*>(a.mul);
         const bool post = act != YMI_ACT_NONE || res2nd || mulp;  // (workgroup-uniform) something left to do on the stored values
-        if (!post) {
-#pragma unroll 4
-            for (int idx = tid_all; idx < BM * CPW; idx += NT) {  // every wave of the workgroup stores
-                const int row = idx / CPW, cc = idx % CPW;
-                const int m = m0 + row, ch = n0 + cc * EPC;
-                if (m < a.M && ch < a.Cout) {
-                    const u32x4 val = *reinterpret_cast<const u32x4*>(Cimg + row * CROW + cc * 16);
-                    *reinterpret_cast<u32x4*>(yg + out_offset(m) + ch) = val;
-                }
-            }
+        if (!post) {  // every wave of the workgroup stores
+            for_each_out_chunk<T, BM, BN, NTHR, 4>(a, Cimg, m0, n0, tid, [&](int m, int ch0, u32x4 val) {
+                *reinterpret_cast<u32x4*>(yg + out_offset(m) + ch0) = val;
+            });
         } else {  // fused inference convolutions (SiLU, then the shortcut), element-aligned addends, activation-gradient multiplier
-#pragma unroll 1
-            for (int idx = tid_all; idx < BM * CPW; idx += NT) {
-                const int row = idx / CPW, cc = idx % CPW;
-                const int m = m0 + row, ch0 = n0 + cc * EPC;
-                if (m < a.M && ch0 < a.Cout) {
-                    u32x4 val = *reinterpret_cast<const u32x4*>(Cimg + row * CROW + cc * 16);
-                    T* vp = reinterpret_cast<T*>(&val);
-                    const int64_t px = (res2nd || mulp) ? out_pixel(m) : 0;
+            for_each_out_chunk<T, BM, BN, NTHR, 1>(a, Cimg, m0, n0, tid, [&](int m, int ch0, u32x4 val) {
+                T* vp = reinterpret_cast<T*>(&val);
+                const int64_t px = (res2nd || mulp) ? out_pixel(m) : 0;
 #pragma unroll
-                    for (int h = 0; h < EPC / 4; ++h) {
-                        const int ch = ch0 + 4 * h;
-                        float v[4], rr[4];
-                        Pack<T, 4>::load(vp + 4 * h, v);
-                        if (act != YMI_ACT_NONE) {
+                for (int h = 0; h < EPC / 4; ++h) {
+                    const int ch = ch0 + 4 * h;
+                    float v[4], rr[4];
+                    Pack<T, 4>::load(vp + 4 * h, v);
+                    if (act != YMI_ACT_NONE) {
 #pragma unroll
-                            for (int r = 0; r < 4; ++r) v[r] = apply_act_rt(v[r], act);
-                        }
-                        if (res2nd) {
-                            if (a.vec_store) {
-                                Pack<T, 4>::load(rg + px * a.ldres + ch, rr);
-#pragma unroll
-                                for (int r = 0; r < 4; ++r) v[r] += rr[r];
-                                if (rg2) {
-                                    Pack<T, 4>::load(rg2 + px * a.ldres2 + ch, rr);
-#pragma unroll
-                                    for (int r = 0; r < 4; ++r) v[r] += rr[r];
-                                }
-                            } else {
-#pragma unroll
-                                for (int r = 0; r < 4; ++r) v[r] += to_f32(rg[px * a.ldres + ch + r]) + (rg2 ? to_f32(rg2[px * a.ldres2 + ch + r]) : 0.f);
-                            }
-                        }
-                        if (mulp) {  // (host: 4-element-aligned)
-                            Pack<T, 4>::load(mulp + px * a.ldmul + ch, rr);
-#pragma unroll
-                            for (int r = 0; r < 4; ++r) v[r] *= act_grad_rt(rr[r], a.mul_act);
-                        }
-                        Pack<T, 4>::store(vp + 4 * h, v);
+                        for (int r = 0; r < 4; ++r) v[r] = apply_act_rt(v[r], act);
                     }
-                    *reinterpret_cast<u32x4*>(yg + out_offset(m) + ch0) = val;
+                    if (res2nd) {
+                        if (a.vec_store) {
+                            add_addends(v, px, ch);
+                        } else {
+#pragma unroll
+                            for (int r = 0; r < 4; ++r) v[r] += addend_sum(px, ch + r);
+                        }
+                    }
+                    if (mulp) {  // (host: 4-element-aligned)
+                        Pack<T, 4>::load(mulp + px * a.ldmul + ch, rr);
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) v[r] *= act_grad_rt(rr[r], a.mul_act);
+                    }
+                    Pack<T, 4>::store(vp + 4 * h, v);
                 }
-            }
+                *reinterpret_cast<u32x4*>(yg + out_offset(m) + ch0) = val;
+            });
         }
         if (!STATS && a.y2) {  // second output: the activation of what was just stored (read back from the LDS image, so both outputs
                                // see the same rounded value - the arithmetic of a separate activation kernel reading the first output)
             T* y2g = reinterpret_cast<T*>(a.y2);
-#pragma unroll 1
-            for (int idx = tid_all; idx < BM * CPW; idx += NT) {
-                const int row = idx / CPW, cc = idx % CPW;
-                const int m = m0 + row, ch0 = n0 + cc * EPC;
-                if (m < a.M && ch0 < a.Cout) {
-                    u32x4 val = *reinterpret_cast<const u32x4*>(Cimg + row * CROW + cc * 16);
-                    T* vp = reinterpret_cast<T*>(&val);
+            for_each_out_chunk<T, BM, BN, NTHR, 1>(a, Cimg, m0, n0, tid, [&](int m, int ch0, u32x4 val) {
+                T* vp = reinterpret_cast<T*>(&val);
 #pragma unroll
-                    for (int h = 0; h < EPC / 4; ++h) {
-                        float v[4];
-                        Pack<T, 4>::load(vp + 4 * h, v);
+                for (int h = 0; h < EPC / 4; ++h) {
+                    float v[4];
+                    Pack<T, 4>::load(vp + 4 * h, v);
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) v[r] = apply_act_rt(v[r], a.act2);
-                        Pack<T, 4>::store(vp + 4 * h, v);
-                    }
-                    *reinterpret_cast<u32x4*>(y2g + out_pixel(m) * a.ldy2 + ch0) = val;
+                    for (int r = 0; r < 4; ++r) v[r] = apply_act_rt(v[r], a.act2);
+                    Pack<T, 4>::store(vp + 4 * h, v);
                 }
-            }
+                *reinterpret_cast<u32x4*>(y2g + out_pixel(m) * a.ldy2 + ch0) = val;
+            });
         }
     } else {
         // unaligned / odd channel counts (Detect's class maps at small nc, first-layer data gradients): one element per lane and trip
-        for (int idx = tid_all; idx < BM * BN; idx += NT) {
+        for (int idx = tid; idx < BM * BN; idx += NTHR) {
             const int row = idx / BN, col = idx % BN;
             const int m = m0 + row, ch = n0 + col;
             if (m < a.M && ch < a.Cout) {
                 float v = apply_act_rt(to_f32(reinterpret_cast<const T*>(Cimg + row * CROW)[col]), act);
-                if (res2nd) {
-                    const int64_t px = out_pixel(m);
-                    v += to_f32(rg[px * a.ldres + ch]) + (rg2 ? to_f32(rg2[px * a.ldres2 + ch]) : 0.f);
-                }
+                if (res2nd) v += addend_sum(out_pixel(m), ch);
                 yg[out_offset(m) + ch] = from_f32<T>(v);
             }
         }
@@ -471,11 +454,10 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& a, f32x4 (&acc)[
 // holds one wave in its memory phase beside one in its compute phase (the arrangement MI355X_MICROARCH.md, Two waves per SIMD,
 // describes) instead of two waves in the same phase.  Three LDS stages: the pieces of step k+2 overwrite the stage of step k-1,
 // which both halves finished reading at least one phase earlier.
-// (Round-2 variants that measured slower - wave specialisation, a lockstep 256x128 tile, ring depths 1 / 3, pieces interleaved
-// with the MFMAs, LDS-resident 3x3 input rows in linear pixel order, BatchNorm-backward sums in the data-gradient epilogue -
-// were removed in round 3; their tables are profiles/r02_conv_bench_*.txt and profiles/r02_bn_bwd_fuse.txt, the code is in git.
-// Round 3 measured two more, parity-green and removed again:
-//  * the LDS-resident 3x3 kernel rebuilt in a padded-linear pixel order (one zero column per image row, one zero row per image: a
+// Forms that measured slower and are not here (the code is in git): wave specialisation, a lockstep 256x128 tile, ring depths 1 / 3,
+// pieces interleaved with the MFMAs, LDS-resident 3x3 input rows in linear pixel order, BatchNorm-backward sums in the data-gradient
+// epilogue (tables: profiles/r02_conv_bench_*.txt, profiles/r02_bn_bwd_fuse.txt), and two that passed parity:
+//  * the LDS-resident 3x3 kernel in a padded-linear pixel order (one zero column per image row, one zero row per image: a
 //    tap is a constant row shift, no masks; image double-buffered over 32-channel chunks; 2.2x fewer operand bytes): no longer
 //    bound by bytes, yet 0-9 % on the 80x80 layers and slower wherever 256-row tiles leave fewer workgroups than CUs
 //    (profiles/r03_conv_bench_dconv3.txt);
@@ -483,44 +465,41 @@ __device__ __forceinline__ void igemm_epilogue(const IgemmArgs& a, f32x4 (&acc)[
 //    1,600 workgroups for 512 slots; 200-row tiles give 256 / 512 / 1,024): 3-7 % on some 80x80 layers in isolation
 //    (profiles/r03_conv_bench_stride200.txt), 13.98 against 13.97 ms on the whole step.
 // Both K loops sit at ~58 % MFMA-busy; what separates a layer from that figure is its grid against 512 slots (tools/quant_probe.sh,
-// profiles/r03_tile_count_probe.txt: 400 tiles of 128x128 take as long as 512) and the prologue / epilogue of a 1.5-round grid.)
+// profiles/r03_tile_count_probe.txt: 400 tiles of 128x128 take as long as 512) and the prologue / epilogue of a 1.5-round grid.
 template <typename T, int BM, int BN, int WM, int WN, int NS, int CPR, bool FAST, bool STATS, int NTHR = 256, bool PP = false>
 __global__ __launch_bounds__(NTHR) void igemm_kernel(IgemmMulti P) {
     constexpr int CH = ElemTraits<T>::CH;
     constexpr int TM = BM / WM / 16, TN = BN / WN / 16;
     constexpr int ROWB = CPR * 16;                    // bytes per LDS row = K step per row (64: 32 bf16 / 16 f32; 128: 64 bf16)
-    constexpr int LT = NTHR;                          // threads that issue loads (all of them)
-    constexpr int RPI = LT / CPR, RPW = 64 / CPR;     // rows filled per block-wide / per wave load instruction
-    constexpr int NA = (BM * CPR + LT - 1) / LT, NB = (BN * CPR + LT - 1) / LT;
-    constexpr int STAGE = (BM + BN) * ROWB;
+    constexpr int RPI = NTHR / CPR, RPW = 64 / CPR;   // rows filled per block-wide / per wave load instruction (every thread issues loads)
+    constexpr int NA = (BM * CPR + NTHR - 1) / NTHR, NB = (BN * CPR + NTHR - 1) / NTHR;
+    constexpr int NPC = NA + NB;                      // pieces (load instructions) per wave and K step: the A rows first, then the weight rows
+    constexpr int STAGE = igemm_stage_bytes(BM, BN, CPR);
+    constexpr int LDS = igemm_lds_bytes(BM, BN, NS, CPR, (int)sizeof(T), STATS);
+    static_assert(LDS <= IGEMM_LDS_MAX, "the form's LDS image exceeds a CU's 160 KiB");
+    static_assert(!PP || (LDS == 72 * 1024 && 2 * LDS <= IGEMM_LDS_MAX), "ping-pong form: 72 KB, two workgroups per CU");
     static_assert(CPR == 4 || (CPR == 8 && FAST), "128-byte rows need tap-uniform K steps");
     static_assert(WM * WN == NTHR / 64, "one wave tile per wave");
-    static_assert((BM * CPR) % LT == 0, "every loading wave issues all A loads");
+    static_assert((BM * CPR) % NTHR == 0, "every wave issues all A loads, and the weight rows' pieces follow the A rows' without a gap");
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
-    constexpr int NT = NTHR;
-    const int tid_all = threadIdx.x, lane = tid_all & 63;
-    const int wave_all = __builtin_amdgcn_readfirstlane(tid_all >> 6);  // provably wave-uniform: LDS-DMA bases go to M0 without a waterfall loop
-    const int tid = tid_all, wave = wave_all;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // provably wave-uniform: LDS-DMA bases go to M0 without a waterfall loop
     const int wm = wave / WN, wn = wave % WN;
     // XCD-aware order: workgroups are dealt round-robin to the 8 XCDs (id & 7), each with its own L2.  Every XCD gets a
     // CONTIGUOUS range of M blocks (neighbouring pixel tiles share 3x3 halo rows) and walks the N blocks of one M block
     // back to back, so the A tile an M block gathers is fetched into that XCD's L2 once and reused by all its N blocks
     // (with N blocks on grid.y they ran a whole grid apart and A came back from MALL/HBM once per N block).
-    // The range is the XCD's EIGHTH of the pixel order (round 4): the kernel that produced the rows (a BatchNorm pass, another
+    // The range is the XCD's EIGHTH of the pixel order (xcd_m_blocks): the kernel that produced the rows (a BatchNorm pass, another
     // GEMM's epilogue) wrote that eighth from this XCD too, so they are in this L2, not in another one's.
-    // The 1-D grid is padded to 8 * mpx * nnb ids; ids that fall outside the XCD's range leave before any barrier.
+    // The 1-D grid is padded to 8 * (most M blocks an XCD owns) * nnb ids; ids outside the XCD's range leave before any barrier.
     const int orig = blockIdx.x, xcd = orig & 7, seq0 = orig >> 3;
     int cls = 0, seq = seq0;  // block-uniform
     if (P.hetero) {
         // problems one after another: skip the tiles this XCD owns of problems 0 .. cls-1 (scalar arithmetic on kernel arguments)
 #pragma unroll 1
         for (; cls < P.ncls; ++cls) {
-            const int sp = P.c[cls].span, nmbc = P.c[cls].nmb;
-            const int f = (xcd * sp + BM - 1) / BM;
-            int l = ((xcd + 1) * sp + BM - 1) / BM;
-            l = l < nmbc ? l : nmbc;
-            const int cnt = (l > f ? l - f : 0) * P.c[cls].nnb;
+            const int cnt = xcd_m_blocks(xcd, P.c[cls].span, P.c[cls].nmb, BM).count() * P.c[cls].nnb;
             if (seq < cnt) break;
             seq -= cnt;
         }
@@ -531,16 +510,18 @@ __global__ __launch_bounds__(NTHR) void igemm_kernel(IgemmMulti P) {
     }
     const IgemmArgs a = P.c[cls];
     const int nb = seq % a.nnb, ml = seq / a.nnb;
-    // this XCD owns the M blocks whose first row lies in its span of the pixel order (the rule every streaming kernel follows, common.h)
-    const int first = (xcd * a.span + BM - 1) / BM;
-    int last = ((xcd + 1) * a.span + BM - 1) / BM;
-    last = last < a.nmb ? last : a.nmb;
-    const int mb = first + ml;
-    if (mb >= last) return;
+    const MBlockRange own = xcd_m_blocks(xcd, a.span, a.nmb, BM);
+    const int mb = own.first + ml;
+    if (mb >= own.last) return;
     const int m0 = mb * BM, n0 = nb * BN;
     const T* __restrict__ xg = reinterpret_cast<const T*>(a.x);
     const T* __restrict__ wg = reinterpret_cast<const T*>(a.w);
     const T* zero = reinterpret_cast<const T*>(a.zero);
+
+    // LDS-DMA destination of this wave's piece p of stage s.  A block-wide load instruction fills NTHR consecutive 16-byte chunks, 64 per
+    // wave; the A rows take exactly NA instructions, so piece NA + j is the weight rows' piece j.  (A plain pointer, cast where it is used: with a
+    // lambda that returns an address_space(3) pointer the host pass drops the kernel's stub without a diagnostic and the library loses the kernel.)
+    auto slot = [&](int s, int p) -> char* { return smem + s * STAGE + (p * NTHR + wave * 64) * 16; };
 
     // ---- warm this XCD's L2 with the weight rows of this N block ---------------------------------------------------------------------
     // Inside the training step a layer's packed weights are NOT in L2 (they were written at the start of the step), and every workgroup
@@ -550,19 +531,19 @@ __global__ __launch_bounds__(NTHR) void igemm_kernel(IgemmMulti P) {
     // line of their N block's rows up front, all requests in flight at once - as 4-byte LDS-DMA loads into the first bytes of the ring:
     // no register receives the data (a VGPR destination made the register allocator wait for the loads at once, and an inline-asm load
     // is simply wrong: the compiler reuses the register before the data lands).  A wave's loads complete in order - ONLY a wave's own: the
-    // bytes a wave aims at are the first ones its own first A-row load of stage 0 writes (wave * 64 chunks of 16 bytes), so that load,
+    // bytes a wave aims at are the first ones its own first A-row load of stage 0 writes (slot(0, 0)), so that load,
     // issued later by the same wave, overwrites them before anything reads them; the counted waits of the K loop are unaffected.
     {
         const int rows_valid = (a.Cout - n0 < BN) ? a.Cout - n0 : BN;
         const uint32_t lines = (uint32_t)(((int64_t)rows_valid * a.ktot * (int64_t)sizeof(T) + 127) >> 7);
-        const uint32_t pw = (lines + 4 * NT - 1) / (4 * NT);  // workgroups needed at 4 lines per thread
+        const uint32_t pw = (lines + 4 * NTHR - 1) / (4 * NTHR);  // workgroups needed at 4 lines per thread
         if ((uint32_t)ml < pw) {  // (workgroup-uniform)
             const char* wbase = reinterpret_cast<const char*>(wg + (int64_t)n0 * a.ktot);
-            const uint32_t last = lines - 1, st = pw * NT;
-            uint32_t li = (uint32_t)ml * NT + (uint32_t)tid_all;
+            const uint32_t last = lines - 1, st = pw * NTHR;
+            uint32_t li = (uint32_t)ml * NTHR + (uint32_t)tid;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {  // (lines beyond the last one re-touch it: every lane of a wave issues, as LDS-DMA requires)
-                __builtin_amdgcn_global_load_lds((gptr_t)(wbase + (size_t)(li < last ? li : last) * 128), (lptr_t)(smem + wave * 64 * 16), 4, 0, 0);
+                __builtin_amdgcn_global_load_lds((gptr_t)(wbase + (size_t)(li < last ? li : last) * 128), (lptr_t)slot(0, 0), 4, 0, 0);
                 li += st;
             }
         }
@@ -579,9 +560,9 @@ __global__ __launch_bounds__(NTHR) void igemm_kernel(IgemmMulti P) {
         const int m = m0 + r;
         a_ok[i] = (m < a.M);
         const int mm = a_ok[i] ? m : 0;
-        const int t = fast_div(mm, a.wo_mul, a.wo_shr, a.Wo);
+        const int t = fast_div(mm, a.wo_mul, a.wo_shr);
         const int wo = mm - t * a.Wo;
-        const int n = fast_div(t, a.ho_mul, a.ho_shr, a.Ho);
+        const int n = fast_div(t, a.ho_mul, a.ho_shr);
         const int ho = t - n * a.Ho;
         a_nH[i] = n * a.H;
         a_h[i] = ho * a.s_in;
@@ -634,26 +615,32 @@ __global__ __launch_bounds__(NTHR) void igemm_kernel(IgemmMulti P) {
         }
     }
 
+    // A FAST K step is its NPC pieces, then advance().  The default form issues them in one go (issue); the ping-pong form spreads the pieces
+    // over its two phases and advances after the last MFMA.
+    auto load_piece = [&](int s, auto pc) {  // piece p of the step whose stage is s, WITHOUT advancing the pointers
+        constexpr int p = decltype(pc)::value;
+        if constexpr (p < NA) __builtin_amdgcn_global_load_lds((gptr_t)a_ptr[p], (lptr_t)slot(s, p), 16, 0, 0);
+        else __builtin_amdgcn_global_load_lds((gptr_t)b_ptr[p - NA], (lptr_t)slot(s, p), 16, 0, 0);
+    };
+    auto advance = [&]() {  // pointers to the next K step; at a tap's last step, the next tap (scalar branch)
+#pragma unroll
+        for (int i = 0; i < NA; ++i) a_ptr[i] += a_inc[i];
+#pragma unroll
+        for (int j = 0; j < NB; ++j) b_ptr[j] += b_inc[j];
+        if (--left == 0) {
+            left = steps_per_tap;
+            if (++tap_s < a.ntaps) setup_tap(tap_s);
+        }
+    };
+    // a wave whose rows of weight piece j lie beyond the tile (BN narrower than a load instruction's rows) skips it: wave-uniform
+    auto b_piece_in_tile = [&](int j) { return wave * RPW + RPI * j < BN; };
     auto issue = [&](int s) {
-        char* As = smem + s * STAGE;
-        char* Bs = As + BM * ROWB;
         if constexpr (FAST) {
-#pragma unroll
-            for (int i = 0; i < NA; ++i) {
-                __builtin_amdgcn_global_load_lds((gptr_t)a_ptr[i], (lptr_t)(As + (i * LT + wave * 64) * 16), 16, 0, 0);
-                a_ptr[i] += a_inc[i];
-            }
-#pragma unroll
-            for (int j = 0; j < NB; ++j) {
-                if ((wave * RPW + RPI * j) < BN) {  // wave-uniform
-                    __builtin_amdgcn_global_load_lds((gptr_t)b_ptr[j], (lptr_t)(Bs + (j * LT + wave * 64) * 16), 16, 0, 0);
-                    b_ptr[j] += b_inc[j];
-                }
-            }
-            if (--left == 0) {  // next tap (scalar branch)
-                left = steps_per_tap;
-                if (++tap_s < a.ntaps) setup_tap(tap_s);
-            }
+            static_for<0, NPC>([&](auto pc) {
+                constexpr int p = decltype(pc)::value;
+                if (p < NA || b_piece_in_tile(p - NA)) load_piece(s, pc);
+            });
+            advance();
         } else {
             const bool kvalid = tap < a.ntaps;
             const int dh = (int)((a.tap_dh >> (4 * (tap & 15))) & 15) - 8;
@@ -663,14 +650,14 @@ __global__ __launch_bounds__(NTHR) void igemm_kernel(IgemmMulti P) {
                 const int hi = a_h[i] + dh, wi = a_w[i] + dw;
                 const bool ok = a_ok[i] && kvalid && (unsigned)hi < (unsigned)a.H && (unsigned)wi < (unsigned)a.W;
                 const T* src = ok ? xg + ((int64_t)(a_nH[i] + hi) * a.W + wi) * a.ldx + cic * CH : zero;
-                __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(As + (i * LT + wave * 64) * 16), 16, 0, 0);
+                __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)slot(s, i), 16, 0, 0);
             }
 #pragma unroll
             for (int j = 0; j < NB; ++j) {
-                if ((wave * RPW + RPI * j) < BN) {  // wave-uniform
+                if (b_piece_in_tile(j)) {
                     const bool ok = b_ok[j] && kvalid;
                     const T* src = ok ? b_ptr[j] + (int64_t)(tap * a.cpt + cic) * CH : zero;
-                    __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(Bs + (j * LT + wave * 64) * 16), 16, 0, 0);
+                    __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)slot(s, NA + j), 16, 0, 0);
                 }
             }
             cic += adv_c;
@@ -688,21 +675,20 @@ __global__ __launch_bounds__(NTHR) void igemm_kernel(IgemmMulti P) {
 #pragma unroll
         for (int tm = 0; tm < TM; ++tm) acc[tn][tm] = f32x4{0.f, 0.f, 0.f, 0.f};
 
-    // loads this wave issues per K step (vmcnt counts LDS-DMA operations per wave, in order)
-    constexpr int LPT_FULL = NA + NB;
-    constexpr int LPT_AONLY = NA;  // waves beyond the B tile's rows (BN < 64) issue no B loads
+    // loads this wave issues per K step (vmcnt counts LDS-DMA operations per wave, in order): NPC, or NA for the waves beyond the
+    // weight tile's rows (BN < 64), which issue no weight loads
     const bool b_wave = (BN >= RPI) || (wave * RPW < BN);
     const int nkt = (a.KC + CPR - 1) / CPR;
     if constexpr (PP) {
         static_assert(NTHR == 512 && NS == 3 && FAST && std::is_same<T, bf16_t>::value && WM == 4, "ping-pong form: 512 threads, 3 stages, bf16");
-        const int half = wave_all >> 2;  // 0: rows 0..BM/2-1 (starts first), 1: the other rows, half a step behind
+        const int half = wave >> 2;  // 0: rows 0..BM/2-1 (starts first), 1: the other rows, half a step behind
         bf16x8 wf[CPR / 4][TN], xf[CPR / 4][TM];
         issue(0);
         if (nkt > 1) issue(1);
         // step 0 (and only it) has landed when the pieces of step 1 may still be outstanding
         if (nkt > 1) {
-            if (b_wave) wait_vmcnt_barrier<LPT_FULL>();
-            else wait_vmcnt_barrier<LPT_AONLY>();
+            if (b_wave) wait_vmcnt_barrier<NPC>();
+            else wait_vmcnt_barrier<NA>();
         } else {
             wait_vmcnt_barrier<0>();
         }
@@ -715,25 +701,7 @@ __global__ __launch_bounds__(NTHR) void igemm_kernel(IgemmMulti P) {
         // The pieces of step k+2 are split between the two phases of step k (stamps, profiles/r02_igemm_phase_stamps.txt: with all
         // six in the memory phase it lasted ~1000 cycles against ~500 of MFMAs): the A rows go out in the memory phase, the
         // weight rows between the MFMAs, and the pointer / tap bookkeeping follows the last MFMA, outside the memory phase.
-        constexpr int NPC = NA + NB;       // pieces per wave and step
         constexpr int NM = (CPR / 4) * TN * TM;
-        auto load_piece = [&](int s, auto pc) {  // piece p of the step whose stage is s, WITHOUT advancing the pointers
-            constexpr int p = decltype(pc)::value;
-            char* Ad = smem + s * STAGE;
-            char* Bd = Ad + BM * ROWB;
-            if constexpr (p < NA) __builtin_amdgcn_global_load_lds((gptr_t)a_ptr[p], (lptr_t)(Ad + (p * LT + wave * 64) * 16), 16, 0, 0);
-            else __builtin_amdgcn_global_load_lds((gptr_t)b_ptr[p - NA], (lptr_t)(Bd + ((p - NA) * LT + wave * 64) * 16), 16, 0, 0);
-        };
-        auto advance = [&]() {  // what issue() does after its loads
-#pragma unroll
-            for (int i = 0; i < NA; ++i) a_ptr[i] += a_inc[i];
-#pragma unroll
-            for (int jj = 0; jj < NB; ++jj) b_ptr[jj] += b_inc[jj];
-            if (--left == 0) {
-                left = steps_per_tap;
-                if (++tap_s < a.ntaps) setup_tap(tap_s);
-            }
-        };
         static_assert(BN >= RPI * NB, "every wave issues every weight piece");
         for (int kt = 0; kt < nkt; ++kt) {
             const bool more = kt + 2 < nkt;
@@ -741,7 +709,7 @@ __global__ __launch_bounds__(NTHR) void igemm_kernel(IgemmMulti P) {
             // ---- memory phase of step kt
             const char* As = smem + (kt % NS) * STAGE;
             Mma<T>::template read_frags<TM, TN, CPR>(As, As + BM * ROWB, wm * TM * 16, wn * TN * 16, lane, wf, xf);
-            if (more) static_for<0, NA>([&](auto pc) { load_piece(sn, pc); });  // the A pieces (pieces are numbered A rows first)
+            if (more) static_for<0, NA>([&](auto pc) { load_piece(sn, pc); });  // the A pieces
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             if (half == 1) {
                 if (more) wait_vmcnt_barrier<NA>();  // everything older than this phase's pieces: all of step kt+1
@@ -792,8 +760,8 @@ __global__ __launch_bounds__(NTHR) void igemm_kernel(IgemmMulti P) {
         for (int kt = 0; kt < nkt; ++kt) {
             // K step kt has landed when at most the loads of the NS-2 younger steps are outstanding
             if (kt + NS - 2 < nkt) {
-                if (b_wave) wait_vmcnt_barrier<LPT_FULL * (NS - 2)>();
-                else wait_vmcnt_barrier<LPT_AONLY * (NS - 2)>();
+                if (b_wave) wait_vmcnt_barrier<NPC * (NS - 2)>();
+                else wait_vmcnt_barrier<NA * (NS - 2)>();
             } else {
                 wait_vmcnt_barrier<0>();  // pipeline tail: fewer steps in flight than the count assumes
             }
@@ -805,17 +773,26 @@ __global__ __launch_bounds__(NTHR) void igemm_kernel(IgemmMulti P) {
     }
     asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");  // epilogue reuses LDS
 
-    // ---- epilogue -----------------------------------------------------------------------------
-    // The tile leaves through LDS: lanes drop their 4-channel groups into a [pixel][channel] image, then the
-    // workgroup stores it as 16-byte chunks along C, so every store instruction writes whole 128-byte lines
-    // (per-lane 8-byte stores to 16 different rows cost 2-3x the time of the same bytes stored this way).
-    igemm_epilogue<T, BM, BN, WM, WN, STATS, NT>(a, acc, smem, m0, n0, mb, wm, wn, lane, tid_all);
+    igemm_epilogue<T, BM, BN, WM, WN, STATS>(a, acc, smem, m0, n0, mb, wm, wn, lane, tid);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
 // ------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------
+// The K-step form a launch runs in, the one EVERY problem of it allows: 8-chunk steps (128-byte LDS rows, bfloat16 only) need cpt % 8 == 0,
+// whole-step taps cpt % 4 == 0; otherwise the general form (first layer, Cin = 8).  128-byte rows whenever Cin allows them: every LDS-DMA
+// instruction then touches 8 full 128-byte cache lines instead of 16 half lines, and there is one barrier per 32 MFMAs per wave instead of per 16.
+enum KForm { K_GENERAL, K_FAST, K_WIDE };
+static KForm k_form(const IgemmArgs* arr, int ncls, bool bf16) {
+    bool fast = true, wide = bf16;
+    for (int i = 0; i < ncls; ++i) {
+        fast = fast && (arr[i].cpt % 4) == 0;
+        wide = wide && (arr[i].cpt % 8) == 0;
+    }
+    return wide ? K_WIDE : fast ? K_FAST : K_GENERAL;
+}
+
 struct TileChoice {
     int bm, bn;
     bool pp = false;  // ping-pong form of the 256x128 tile
@@ -824,9 +801,10 @@ struct TileChoice {
 // Largest tile that still yields ~1.5 workgroups per CU (measured on the 40x40 / 20x20 layers of the model: 400 tiles of
 // 128x128 beat 800 of 64x128 by 25-30 %, and below that 128x64, then 64x64, win); short-K GEMMs (K <= 384) are
 // prologue/epilogue-dominated and run best as 128x64 (three resident workgroups per CU).
-// fast: every problem of the launch takes whole-chunk taps (cpt % 4 == 0), the K-step form the ping-pong tile needs.  (Testing ktot % 32
-// instead let the stride-2 data gradient's four-tap class pass with dy channels that are no multiple of 32: the launch then refused the tile.)
-static TileChoice choose_tile(int64_t M, int64_t cout, int64_t ktot, bool bf16, bool fast) {
+// form: the launch's K-step form; the ping-pong tile needs whole-step taps (not K_GENERAL).  (Testing ktot % 32 instead let the stride-2
+// data gradient's four-tap class pass with dy channels that are no multiple of 32: the launch then refused the tile.)
+static TileChoice choose_tile(int64_t M, int64_t cout, int64_t ktot, bool bf16, KForm form) {
+    const bool fast = form != K_GENERAL;
     TileChoice t;
     auto blocks = [&](int bm, int bn) { return ((M + bm - 1) / bm) * ((cout + bn - 1) / bn); };
     const int64_t enough = 400;
@@ -859,118 +837,108 @@ static TileChoice choose_tile(int64_t M, int64_t cout, int64_t ktot, bool bf16, 
     return t;
 }
 
-// Row width of the LDS operand images: 128-byte rows (K step = 64 bf16) whenever Cin allows it: every LDS-DMA
-// instruction then touches 8 full 128-byte cache lines instead of 16 half lines, and there is one barrier per
-// 32 MFMAs per wave instead of per 16.
+// One kernel form: its LDS bytes come from the description the kernel itself reads.
+template <typename T, int BM, int BN, int WM, int WN, int NS, int CPR, bool FAST, bool STATS, int NTHR = 256, bool PP = false>
+static void igemm_launch(dim3 grid, const IgemmMulti& P, hipStream_t stream) {
+    constexpr int lds = igemm_lds_bytes(BM, BN, NS, CPR, (int)sizeof(T), STATS);
+    void (*kernel)(IgemmMulti) = igemm_kernel<T, BM, BN, WM, WN, NS, CPR, FAST, STATS, NTHR, PP>;
+    if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
+    hipLaunchKernelGGL(kernel, grid, dim3(NTHR), lds, stream, P);
+}
+// The K-step forms of one 256-thread tile: two-stage ring, 128-byte rows (bfloat16) or 64-byte rows.
+template <typename T, bool STATS, int BM, int BN, int WM, int WN>
+static void igemm_launch_tile(KForm form, dim3 grid, const IgemmMulti& P, hipStream_t stream) {
+    if constexpr (std::is_same<T, bf16_t>::value) {
+        if (form == K_WIDE) return igemm_launch<T, BM, BN, WM, WN, 2, 8, true, STATS>(grid, P, stream);
+    }
+    if (form != K_GENERAL) return igemm_launch<T, BM, BN, WM, WN, 2, 4, true, STATS>(grid, P, stream);
+    igemm_launch<T, BM, BN, WM, WN, 2, 4, false, STATS>(grid, P, stream);
+}
+struct TileLauncher {
+    int bm, bn;
+    void (*launch)(KForm, dim3, const IgemmMulti&, hipStream_t);
+};
+
 template <typename T, bool STATS>
-static int launch_igemm_t(const IgemmArgs* arr, int ncls, TileChoice t, hipStream_t stream, bool hetero = false) {
+static int launch_igemm_t(const IgemmArgs* arr, int ncls, TileChoice t, KForm form, hipStream_t stream, bool hetero) {
+    static const TileLauncher tiles[] = {
+        {128, 128, igemm_launch_tile<T, STATS, 128, 128, 2, 2>}, {128, 64, igemm_launch_tile<T, STATS, 128, 64, 2, 2>},
+        {128, 32, igemm_launch_tile<T, STATS, 128, 32, 4, 1>},   {64, 128, igemm_launch_tile<T, STATS, 64, 128, 2, 2>},
+        {64, 64, igemm_launch_tile<T, STATS, 64, 64, 2, 2>},
+    };
     IgemmMulti P{};
     P.ncls = ncls;
     P.hetero = hetero ? 1 : 0;
-    int64_t per_xcd[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // hetero: tiles each XCD runs, over all problems
-    int mpx = 0;
+    int64_t per_xcd[8] = {0, 0, 0, 0, 0, 0, 0, 0};  // tiles each XCD runs, over all problems
+    int mpx = 0;                                     // most M blocks any XCD owns of one problem
     for (int i = 0; i < ncls; ++i) {
         P.c[i] = arr[i];
         P.c[i].nmb = (arr[i].M + t.bm - 1) / t.bm;
         P.c[i].nnb = (arr[i].Cout + t.bn - 1) / t.bn;
         const int64_t span = ymi_xcd_span(arr[i].M);
-        YMI_CHECK_ARG(8 * span < (1ll << 31), "igemm: M too large");
+        YMI_CHECK_ARG(8 * span + t.bm < (1ll << 31), "igemm: M too large");  // (xcd_m_blocks counts in int)
         P.c[i].span = (int)span;
-        for (int x = 0; x < 8; ++x) {  // as the kernel counts them
-            const int64_t first = (x * span + t.bm - 1) / t.bm;
-            int64_t last = ((x + 1) * span + t.bm - 1) / t.bm;
-            if (last > P.c[i].nmb) last = P.c[i].nmb;
-            if (last - first > mpx) mpx = (int)(last - first);
-            if (last > first) per_xcd[x] += (last - first) * P.c[i].nnb;
+        for (int x = 0; x < 8; ++x) {
+            const int cnt = xcd_m_blocks(x, P.c[i].span, P.c[i].nmb, t.bm).count();
+            if (cnt > mpx) mpx = cnt;
+            per_xcd[x] += (int64_t)cnt * P.c[i].nnb;
         }
     }
-    for (int i = 0; i < ncls; ++i) P.c[i].mpx = mpx;  // interleaved form: one id decode for all classes (same Cout => same nnb)
-    const IgemmArgs& a = P.c[0];
-    dim3 grid((unsigned)(8 * mpx * a.nnb * ncls));
+    // interleaved problems: one id decode for all classes (same Cout => same nnb); one after another: the busiest XCD's tiles
+    dim3 grid((unsigned)(8 * mpx * P.c[0].nnb * ncls));
     if (hetero) {
         int64_t mx = 0;
         for (int x = 0; x < 8; ++x) mx = per_xcd[x] > mx ? per_xcd[x] : mx;
         grid = dim3((unsigned)(8 * mx));
     }
-    // the K-step form every problem of the launch can run under (8-chunk steps need cpt % 8, whole-step taps cpt % 4; else the general form)
-    bool fast = true, wide = std::is_same<T, bf16_t>::value;
-    for (int i = 0; i < ncls; ++i) {
-        fast = fast && (P.c[i].cpt % 4) == 0;
-        wide = wide && (P.c[i].cpt % 8) == 0;
-    }
-    size_t lds = (size_t)2 * (t.bm + t.bn) * (wide ? 128 : 64);
-    const size_t epi = (size_t)t.bm * (t.bn * sizeof(T) + 16) + (STATS ? 4 * 2 * t.bn * sizeof(float) : 0);
-    if (epi > lds) lds = epi;
-    unsigned nthreads = 256;
-#define YMI_LAUNCH1(KERNEL)                                                                                          \
-    do {                                                                                                             \
-        if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERNEL), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL(KERNEL, grid, dim3(nthreads), lds, stream, P);                                             \
-    } while (0)
-#define YMI_LAUNCH(BM, BN, WM, WN)                                                              \
-    do {                                                                                        \
-        if constexpr (std::is_same<T, bf16_t>::value) {                                         \
-            if (wide) { YMI_LAUNCH1((igemm_kernel<T, BM, BN, WM, WN, 2, 8, true, STATS>)); break; } \
-        }                                                                                       \
-        if (fast) YMI_LAUNCH1((igemm_kernel<T, BM, BN, WM, WN, 2, 4, true, STATS>));            \
-        else YMI_LAUNCH1((igemm_kernel<T, BM, BN, WM, WN, 2, 4, false, STATS>));                \
-    } while (0)
     if (t.bm == 256 && t.bn == 128) {
         if constexpr (std::is_same<T, bf16_t>::value) {
-            YMI_CHECK_ARG(t.pp && fast, "igemm: the 256x128 ping-pong tile needs input channels that are a multiple of 32");
-            nthreads = 512;
-            lds = (size_t)3 * (256 + 128) * 64;  // 64-byte rows (32-deep K steps): 72 KB, two workgroups per CU (128-byte rows: one, slower)
-            if (epi > lds) lds = epi;
-            YMI_LAUNCH1((igemm_kernel<T, 256, 128, 4, 2, 3, 4, true, STATS, 512, true>));
+            YMI_CHECK_ARG(t.pp && form != K_GENERAL, "igemm: the 256x128 ping-pong tile needs input channels that are a multiple of 32");
+            // 64-byte rows (32-deep K steps) also where 128-byte rows would do: three 24 KB stages, two workgroups per CU (128-byte rows: one, slower)
+            igemm_launch<T, 256, 128, 4, 2, 3, 4, true, STATS, 512, true>(grid, P, stream);
         } else {
             ymi_set_error("igemm: the 256x128 tile is bf16 only");
             return YMI_EINVAL;
         }
-    } else if (t.bm == 128 && t.bn == 128) YMI_LAUNCH(128, 128, 2, 2);
-    else if (t.bm == 128 && t.bn == 64) YMI_LAUNCH(128, 64, 2, 2);
-    else if (t.bm == 128 && t.bn == 32) YMI_LAUNCH(128, 32, 4, 1);
-    else if (t.bm == 64 && t.bn == 128) YMI_LAUNCH(64, 128, 2, 2);
-    else if (t.bm == 64 && t.bn == 64) YMI_LAUNCH(64, 64, 2, 2);
-    else {
-        ymi_set_error("igemm: no tile %dx%d", t.bm, t.bn);
-        return YMI_EINVAL;
+    } else {
+        const TileLauncher* tl = nullptr;
+        for (const TileLauncher& e : tiles)
+            if (e.bm == t.bm && e.bn == t.bn) tl = &e;
+        if (!tl) {
+            ymi_set_error("igemm: no tile %dx%d", t.bm, t.bn);
+            return YMI_EINVAL;
+        }
+        tl->launch(form, grid, P, stream);
     }
-#undef YMI_LAUNCH
-#undef YMI_LAUNCH1
     YMI_CHECK_LAUNCH("igemm");
     return YMI_OK;
 }
 
-
-bool ymi_prof_enabled();
-int ymi_prof_start(hipStream_t stream, int family, double flop, double bytes, double peak_tflops);
-void ymi_prof_stop(hipStream_t stream, int idx);
-
 // ncls problems in one launch.  hetero == false: same dtype, Cout, channel geometry (the interleaved form: parity classes of a stride-2
 // data gradient).  hetero == true: any shapes, one after another; they agree on dtype, and the launch runs in the K-step
-// form ALL of them allow (8-chunk steps only when every problem's input width is a multiple of 64 bf16 channels).  host_blocks: ncls entries (statistics rows per problem).
+// form ALL of them allow (k_form).  host_blocks: ncls entries (statistics rows per problem).
 static int launch_igemm_n(const IgemmArgs* arr, int ncls, int dtype, bool stats, int* host_blocks, hipStream_t stream, bool hetero = false) {
     YMI_CHECK_ARG(ncls >= 1 && ncls <= IGEMM_MAX_PROBLEMS, "igemm: %d problems in one launch (at most %d)", ncls, IGEMM_MAX_PROBLEMS);
     int64_t mmax = 0, msum = 0;
     int64_t kmax = 0;
     int cmax = 0, cmin = 1 << 30;
-    bool fast = true;
     for (int i = 0; i < ncls; ++i) {
-        fast = fast && (arr[i].cpt % 4) == 0;
         mmax = arr[i].M > mmax ? arr[i].M : mmax;
         msum += arr[i].M;
         kmax = arr[i].ktot > kmax ? arr[i].ktot : kmax;
         cmax = arr[i].Cout > cmax ? arr[i].Cout : cmax;
         cmin = arr[i].Cout < cmin ? arr[i].Cout : cmin;
     }
+    const bool bf16 = dtype == YMI_BF16;
+    const KForm form = k_form(arr, ncls, bf16);
     // one tile form for the launch: chosen for the widest problem over all the rows (a narrower problem pads its N block)
-    TileChoice t = hetero ? choose_tile(msum, cmax, kmax, dtype == YMI_BF16, fast) : choose_tile(mmax * ncls, arr[0].Cout, kmax, dtype == YMI_BF16, fast);
+    TileChoice t = hetero ? choose_tile(msum, cmax, kmax, bf16, form) : choose_tile(mmax * ncls, arr[0].Cout, kmax, bf16, form);
     if (hetero && t.bn > 64 && cmin <= 64 && cmax > 64 && !t.pp) t.bn = 64;  // (mixed widths: 64-column tiles waste nothing on the narrow ones)
     if (host_blocks)
         for (int i = 0; i < (hetero ? ncls : 1); ++i) host_blocks[i] = (arr[i].M + t.bm - 1) / t.bm;
     int prof = -1;
     if (ymi_prof_enabled()) {
-        const double es = dtype == YMI_BF16 ? 2.0 : 4.0;
+        const double es = bf16 ? 2.0 : 4.0;
         double flop = 0.0, bytes = 0.0;
         for (int i = 0; i < ncls; ++i) {
             const IgemmArgs& a = arr[i];
@@ -981,15 +949,14 @@ static int launch_igemm_n(const IgemmArgs* arr, int ncls, int dtype, bool stats,
             const IgemmArgs& a0 = arr[i];
             bytes += (double)a0.M / ((double)a0.Ho * a0.Wo) * (double)a0.H * a0.W * a0.cpt * 16.0;  // the whole input map, read once
         }
-        prof = ymi_prof_start(stream, 0, flop, bytes, dtype == YMI_BF16 ? 2500.0 : 157.3);
+        prof = ymi_prof_start(stream, 0, flop, bytes, bf16 ? 2500.0 : 157.3);
     }
     int rc;
-    if (dtype == YMI_BF16) rc = stats ? launch_igemm_t<bf16_t, true>(arr, ncls, t, stream, hetero) : launch_igemm_t<bf16_t, false>(arr, ncls, t, stream, hetero);
-    else rc = stats ? launch_igemm_t<float, true>(arr, ncls, t, stream, hetero) : launch_igemm_t<float, false>(arr, ncls, t, stream, hetero);
+    if (bf16) rc = stats ? launch_igemm_t<bf16_t, true>(arr, ncls, t, form, stream, hetero) : launch_igemm_t<bf16_t, false>(arr, ncls, t, form, stream, hetero);
+    else rc = stats ? launch_igemm_t<float, true>(arr, ncls, t, form, stream, hetero) : launch_igemm_t<float, false>(arr, ncls, t, form, stream, hetero);
     ymi_prof_stop(stream, prof);
     return rc;
 }
-
 
 int ymi_launch_igemm(const IgemmArgs& a, int dtype, bool stats, int* host_blocks, hipStream_t stream) {
     return launch_igemm_n(&a, 1, dtype, stats, host_blocks, stream);

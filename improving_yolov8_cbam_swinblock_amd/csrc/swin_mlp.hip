@@ -28,8 +28,6 @@
 #include "common.h"
 
 typedef __attribute__((ext_vector_type(16))) float f32x16;
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 
 // compile-time loop: f(std::integral_constant<int, 0>{}) ... f(std::integral_constant<int, N-1>{})
 template <int I, int N, class F> __device__ __forceinline__ void static_for(F&& f) {

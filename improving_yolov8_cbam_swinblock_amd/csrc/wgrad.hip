@@ -19,9 +19,6 @@
 #include "common.h"
 
 int ymi_chan_reduce_final(const float* part, int blocks, int C, float* out0, float* out1, hipStream_t stream);
-bool ymi_prof_enabled();
-int ymi_prof_start(hipStream_t stream, int family, double flop, double bytes, double peak_tflops);
-void ymi_prof_stop(hipStream_t stream, int idx);
 
 struct WgradArgs {
     const void* x;
@@ -45,8 +42,6 @@ struct WgradArgs {
 // (Granlund-Montgomery; exact also for d = 1 and powers of two, so the K loop needs no special case and no branch)
 __device__ __forceinline__ int wg_fast_div(int n, uint32_t mul, uint32_t shr) { return (int)((__umulhi((uint32_t)n, mul) + (uint32_t)n) >> shr); }
 
-typedef const __attribute__((address_space(1))) void* gptr_t;
-typedef __attribute__((address_space(3))) void* lptr_t;
 typedef __attribute__((ext_vector_type(4))) short s16x4;
 
 constexpr int WG_BM = 64;    // rows  (co)
