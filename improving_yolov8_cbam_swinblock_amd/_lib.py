@@ -131,12 +131,18 @@ _SIGNATURES = {
     "ymi_scale_image": (_c_i32, [_vp, _c_i32, _c_i64, _c_i64, _c_i64, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_f32, _c_i32, _c_i32, _c_i32, _vp]),
     "ymi_tta_merge": (_c_i32, [_c_i32, ctypes.POINTER(_vp), ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64), ctypes.POINTER(_c_f32),
                                ctypes.POINTER(_c_i32), ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64), _c_i64, _c_i64, _vp, _vp]),
+    "ymi_letterbox_batch": (_c_i32, [_vp, _c_i64, _vp, _c_i64, _c_i64, _c_i32, _c_i32, _c_i32, _vp]),
+    "ymi_scale_boxes": (_c_i32, [_vp, _c_i64, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_i32, _c_i32, _vp, _c_i64, _vp]),
     "ymi_opt_chunk_elems": (_c_i64, []),
     "ymi_opt_grad_norm": (_c_i32, [_vp, _vp, _c_i32, _c_i32, _c_i64, ctypes.POINTER(_vp), _vp, _vp, _c_i64, _c_i64, _vp, _c_i32, _vp]),
     "ymi_opt_update": (_c_i32, [_vp, _vp, _c_i32, _c_i32, _c_i64, ctypes.POINTER(_vp), _vp, _vp, _c_i32, _vp]),
 }
 
 OPT_MAX_GRADS = 448  # YMI_OPT_MAX_GRADS
+
+
+class LetterboxImage(ctypes.Structure):  # ymi_letterbox_image
+    _fields_ = [("src", _vp), ("h", _c_i32), ("w", _c_i32), ("hs", _c_i32), ("ws", _c_i32), ("top", _c_i32), ("left", _c_i32)]
 
 
 class ConvProblem(ctypes.Structure):  # ymi_conv_problem

@@ -2,14 +2,16 @@
 
 Per batch: the eval forward under autocast, ops.detect_nms on the device (multi_label, as val.py:123-133), one trip of (det, count)
 to the host, then per image the matching of at most max_det detections to the labels and the statistics lists - host code on a few
-hundred numbers.  There is no dataloader and no scale_boxes / ratio_pad: batches arrive as engine.trainer.synthetic_batch makes them
-(img, batch_idx, cls, bboxes as normalised xywh)."""
+hundred numbers.  There is no dataloader: batches arrive as engine.trainer.synthetic_batch makes them (img, batch_idx, cls, bboxes as
+normalised xywh).  A batch that also carries `ori_shape` and `ratio_pad` per image, as a letterboxing dataset attaches them, is matched
+in native space (val.py:135-172): the predictions go through ops.scale_boxes on the device before the one trip to the host, the labels
+through the same arithmetic on the host."""
 import numpy as np
 import torch
 
 from .. import ops
 from ..utils.metrics import DetMetrics, box_iou, match_predictions
-from ..utils.ops import xywh2xyxy
+from ..utils.ops import scale_boxes, xywh2xyxy
 
 
 class DetectionValidator:
@@ -44,6 +46,7 @@ class DetectionValidator:
         cls_all = batch["cls"].detach().cpu().float().reshape(-1)
         box_all = batch["bboxes"].detach().cpu().float().reshape(-1, 4)
         scale = torch.tensor([w, h, w, h], dtype=torch.float32)
+        native = "ori_shape" in batch and "ratio_pad" in batch
         for si in range(det.shape[0]):
             self.seen += 1
             pred = det[si, : int(count[si])].clone()
@@ -51,6 +54,8 @@ class DetectionValidator:
             cls, bbox = cls_all[sel], box_all[sel]
             if len(cls):
                 bbox = xywh2xyxy(bbox) * scale
+                if native:  # native-space labels (val.py:154); the predictions were brought there on the device
+                    scale_boxes((h, w), bbox, batch["ori_shape"][si], ratio_pad=batch["ratio_pad"][si])
             if self.single_cls:  # one class on both sides: the reference zeroes the predictions here and the labels in its dataset (which this package has not)
                 pred[:, 5] = 0
                 cls = torch.zeros_like(cls)
@@ -90,6 +95,8 @@ class DetectionValidator:
                         with torch.autocast("cuda", dtype=self.dtype):
                             preds = self.model(batch["img"], **kw)
                     det, count = self.postprocess(preds)
+                    if "ori_shape" in batch and "ratio_pad" in batch:  # native-space predictions (val.py:157-172)
+                        det = ops.scale_boxes(det, count, tuple(batch["img"].shape[2:]), batch["ori_shape"], batch["ratio_pad"], inplace=True)
                 self.update_metrics(det.cpu(), count.cpu(), batch)
         finally:
             self.model.train(was_training)

@@ -34,4 +34,4 @@ from .blocks import (  # noqa: F401
     _WindowReverse, _map_array, add_residual, c2f_split, cbam, concat, detect_decode, detect_loss, detect_nms, detect_targets, gelu, layernorm, sppf_pool_cat,
     swin_ln_mlp, swin_ln_mlp_ok, swin_mlp, upsample2x, window_attention, window_pad, window_partition, window_partition_index, window_reverse,
 )
-from .resize import scale_image, tta_clip_ranges, tta_merge  # noqa: F401
+from .resize import letterbox, letterbox_geometry, scale_boxes, scale_boxes_params, scale_image, scale_rows, tta_clip_ranges, tta_merge  # noqa: F401

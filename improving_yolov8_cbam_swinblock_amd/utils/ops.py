@@ -40,3 +40,48 @@ def non_max_suppression(prediction, conf_thres=0.25, iou_thres=0.45, classes=Non
     det, count = ops.detect_nms(prediction, conf_thres, iou_thres, multi_label=multi_label, agnostic=agnostic, classes=classes, max_det=max_det,
                                 max_nms=max_nms, max_wh=max_wh)
     return [det[i, :n] for i, n in enumerate(count.tolist())]
+
+
+def xyxy2xywh(x):
+    """reference utils/ops.py:412-429."""
+    assert x.shape[-1] == 4, f"input shape last dimension expected 4 but input shape is {x.shape}"
+    y = torch.empty_like(x)
+    y[..., 0] = (x[..., 0] + x[..., 2]) / 2  # x center
+    y[..., 1] = (x[..., 1] + x[..., 3]) / 2  # y center
+    y[..., 2] = x[..., 2] - x[..., 0]  # width
+    y[..., 3] = x[..., 3] - x[..., 1]  # height
+    return y
+
+
+def clip_boxes(boxes, shape):
+    """reference utils/ops.py:335-354: clamps x to [0, shape[1]] and y to [0, shape[0]] in place and returns its argument.  A cuda [n, 4+]
+    float32 tensor or view goes through ymi_scale_boxes (gain 1, no padding: x / 1 is x); host tensors - the validator's few label boxes -
+    take the reference's statements."""
+    if boxes.is_cuda:
+        from .. import ops
+
+        return ops.scale_rows(boxes, [1.0, 0.0, 0.0, float(shape[1]), float(shape[0])], padding=False)
+    boxes[..., 0] = boxes[..., 0].clamp(0, shape[1])  # x1
+    boxes[..., 1] = boxes[..., 1].clamp(0, shape[0])  # y1
+    boxes[..., 2] = boxes[..., 2].clamp(0, shape[1])  # x2
+    boxes[..., 3] = boxes[..., 3].clamp(0, shape[0])  # y2
+    return boxes
+
+
+def scale_boxes(img1_shape, boxes, img0_shape, ratio_pad=None, padding=True, xywh=False):
+    """reference utils/ops.py:93-127: boxes [n, 4+] from the letterboxed img1_shape (h, w) back to img0_shape, clipped, IN PLACE; returns its
+    argument.  Gain and pad are the reference's host arithmetic (ops.scale_boxes_params); a cuda tensor or view such as pred[:, :4] goes
+    through ymi_scale_boxes (csrc/resize.hip), host tensors - the validator's few label boxes - take the reference's statements."""
+    from .. import ops
+
+    gain, pad_x, pad_y, w0, h0 = ops.scale_boxes_params(img1_shape, img0_shape, ratio_pad)
+    if boxes.is_cuda:
+        return ops.scale_rows(boxes, [gain, pad_x, pad_y, w0, h0], padding=padding, xywh=xywh)
+    if padding:
+        boxes[..., 0] -= pad_x  # x padding
+        boxes[..., 1] -= pad_y  # y padding
+        if not xywh:
+            boxes[..., 2] -= pad_x  # x padding
+            boxes[..., 3] -= pad_y  # y padding
+    boxes[..., :4] /= gain
+    return clip_boxes(boxes, img0_shape)

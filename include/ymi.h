@@ -418,6 +418,43 @@ int ymi_scale_image(const void* src, int32_t src_uint8, int64_t planes, int64_t 
 int ymi_tta_merge(int32_t n, const float* const* src, const int64_t* anchors, const int64_t* lo, const int64_t* hi, const float* scale,
                   const int32_t* flip, const int64_t* img_h, const int64_t* img_w, int64_t batch, int64_t rows, float* out, void* stream);
 
+/* ------------------------------------------------------------- prediction on real images ---- */
+/* LetterBox (data/augment.py:1479-1603) and the conversion of engine/predictor.py:144-162 (BGR HWC uint8 -> RGB NCHW float / 255) for a
+ * ragged list of images (csrc/resize.hip).  The GEOMETRY is the caller's: r, int(round(w * r)), dw / 2, int(round(dh - 0.1)) and the auto /
+ * scale_fill / scaleup / center branches are host arithmetic (ops.letterbox states them as the reference does); the library receives integers.
+ *   images : HOST array of n entries; src: DEVICE pointer to a contiguous [h][w][3] uint8 image; (hs, ws): the interpolated size;
+ *            (top, left): where it lies in the destination; top + hs <= H, left + ws <= W
+ *   dst    : float32 [n][3][H][W]; every element is written exactly once
+ * The table travels in the kernel arguments, YMI_LETTERBOX_MAX images per launch; a longer list takes further launches.
+ * Per destination element (y, x) of image i, plane c, in this order:
+ *   1. outside [top, top + hs) x [left, left + ws): level = pad_value (a grey level in [0, 255]; the reference pads with 114)
+ *   2. hs == h and ws == w: level = src[y - top][x - left][cs], cs = 2 - c with bgr != 0, else c - the byte itself, no arithmetic
+ *   3. else, in float32 with one rounding per operation (the rule of ymi_scale_image; the source coordinate is OpenCV INTER_LINEAR's):
+ *      scale = in / out, s = max((dst + 0.5) * scale - 0.5, 0), i0 = floor(s), i1 = min(i0 + 1, in - 1), l1 = s - i0, l0 = 1 - l1,
+ *      v = l0y * (l0x * a + l1x * b) + l1y * (l0x * c + l1x * d) on the BYTE VALUES a..d; level = floorf(v + 0.5f)
+ *   4. normalize != 0: dst = level / 255 rounded as img.float() / 255 rounds; else dst = level.  Either way the output lies on the lattice of the
+ *      reference's uint8 image.  (OpenCV interpolates with 11-bit fixed-point coefficients: its level may differ from step 3's by one.) */
+#define YMI_LETTERBOX_MAX 32
+typedef struct ymi_letterbox_image {
+    const uint8_t* src;
+    int32_t h, w, hs, ws, top, left;
+} ymi_letterbox_image;
+int ymi_letterbox_batch(const ymi_letterbox_image* images, int64_t n, float* dst, int64_t H, int64_t W, int32_t pad_value, int32_t normalize,
+                        int32_t bgr, void* stream);
+/* scale_boxes + clip_boxes (utils/ops.py:93-127, :335-354) as one launch on det [batch][max_det] rows of `cols` >= 4 float32 columns, row
+ * stride det_ld, and count [batch] int32 as ymi_detect_nms leaves them (count == NULL: every row is live).
+ *   params : DEVICE float32 [batch][5] = (gain, pad_x, pad_y, w0, h0) per image; gain and pad are the caller's (the `ratio_pad is None` branch
+ *            of scale_boxes is host arithmetic, Python's round included)
+ * Per live row, in float32, in this order:
+ *   1. padding != 0: x1 = x1 - pad_x, y1 = y1 - pad_y and, unless xywh != 0, x2 = x2 - pad_x, y2 = y2 - pad_y
+ *   2. all four are divided by gain: the IEEE float32 quotient x / float32(gain), which is what `tensor /= python_float` computes - neither
+ *      a product with the reciprocal nor a double-precision division
+ *   3. columns 0 and 2 are clamped to [0, w0], columns 1 and 3 to [0, h0] (min(max(v, 0), hi); xywh rows are clamped the same way, as the
+ *      reference does); columns 4.. are copied
+ * Rows at or beyond count[b] are written as zeros out of place and left as they are in place (out == det, out_ld == det_ld). */
+int ymi_scale_boxes(const float* det, int64_t det_ld, const int32_t* count, const float* params, int64_t batch, int64_t max_det, int64_t cols,
+                    int32_t padding, int32_t xywh, float* out, int64_t out_ld, void* stream);
+
 /* ------------------------------------------------------------------------- optimizer step ---- */
 /* The update either side of backward, reference engine/trainer.py:614-622 (optimizer_step: clip_grad_norm_(10.0),
  * SGD-nesterov step, EMA update), :788-849 (three parameter groups) and utils/torch_utils.py:657-673 (ModelEMA.update),
