@@ -133,6 +133,8 @@ _SIGNATURES = {
                                ctypes.POINTER(_c_i32), ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64), _c_i64, _c_i64, _vp, _vp]),
     "ymi_letterbox_batch": (_c_i32, [_vp, _c_i64, _vp, _c_i64, _c_i64, _c_i32, _c_i32, _c_i32, _vp]),
     "ymi_scale_boxes": (_c_i32, [_vp, _c_i64, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_i32, _c_i32, _vp, _c_i64, _vp]),
+    "ymi_augment_batch": (_c_i32, [_vp, _vp, _c_i64, _vp, _c_i64, _c_i32, _c_i32, _c_i32, _vp]),
+    "ymi_augment_boxes": (_c_i32, [_vp, _c_i64, _vp, _c_i64, _c_f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ymi_opt_chunk_elems": (_c_i64, []),
     "ymi_opt_grad_norm": (_c_i32, [_vp, _vp, _c_i32, _c_i32, _c_i64, ctypes.POINTER(_vp), _vp, _vp, _c_i64, _c_i64, _vp, _c_i32, _vp]),
     "ymi_opt_update": (_c_i32, [_vp, _vp, _c_i32, _c_i32, _c_i64, ctypes.POINTER(_vp), _vp, _vp, _c_i32, _vp]),
@@ -143,6 +145,26 @@ OPT_MAX_GRADS = 448  # YMI_OPT_MAX_GRADS
 
 class LetterboxImage(ctypes.Structure):  # ymi_letterbox_image
     _fields_ = [("src", _vp), ("h", _c_i32), ("w", _c_i32), ("hs", _c_i32), ("ws", _c_i32), ("top", _c_i32), ("left", _c_i32)]
+
+
+AUGMENT_MAX_SRC = 4  # YMI_AUGMENT_MAX_SRC
+
+
+class AugmentSource(ctypes.Structure):  # ymi_augment_source
+    _fields_ = [("src", _vp), ("h", _c_i32), ("w", _c_i32), ("x1a", _c_i32), ("y1a", _c_i32), ("x2a", _c_i32), ("y2a", _c_i32), ("x1b", _c_i32),
+                ("y1b", _c_i32)]
+
+
+class AugmentImage(ctypes.Structure):  # ymi_augment_image
+    _fields_ = [("s", AugmentSource * AUGMENT_MAX_SRC), ("A", ctypes.c_double * 6), ("lut", _vp), ("n_src", _c_i32), ("canvas_h", _c_i32),
+                ("canvas_w", _c_i32), ("flip_ud", _c_i32), ("flip_lr", _c_i32), ("_pad", _c_i32)]
+
+
+class AugmentLabelImage(ctypes.Structure):  # ymi_augment_label_image
+    _fields_ = [("src_w", _c_f32 * AUGMENT_MAX_SRC), ("src_h", _c_f32 * AUGMENT_MAX_SRC), ("ratio_w", _c_f32 * AUGMENT_MAX_SRC),
+                ("ratio_h", _c_f32 * AUGMENT_MAX_SRC), ("padw", _c_f32 * AUGMENT_MAX_SRC), ("padh", _c_f32 * AUGMENT_MAX_SRC), ("M", _c_f32 * 6),
+                ("scale", _c_f32), ("size_w", _c_f32), ("size_h", _c_f32), ("canvas", _c_f32), ("flip_ud", _c_i32), ("flip_lr", _c_i32),
+                ("row_start", _c_i32), ("row_end", _c_i32)]
 
 
 class ConvProblem(ctypes.Structure):  # ymi_conv_problem

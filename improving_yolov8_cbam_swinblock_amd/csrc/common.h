@@ -231,6 +231,16 @@ __device__ __forceinline__ float act_grad_rt(float x, int act) {
     return act == YMI_ACT_SILU ? silu_grad_f(x) : act == YMI_ACT_GELU ? gelu_grad_f(x) : 1.0f;
 }
 
+// uint8 -> float32 / 255, correctly rounded (bit-identical to img.float() / 255) without the IEEE division sequence: q = u * fl(1/255) is
+// within an ulp of the quotient, the residual u - 255 q is exact in one fma, and one correction step lands on the rounded quotient for
+// every u in [0, 255] (resize.hip, augment.hip; tests/test_gpu_resize.py compares all 256 values with torch's division).
+__device__ __forceinline__ float unit_of_byte(uint32_t u) {
+    const float f = (float)u, rc = 1.0f / 255.0f;
+    const float q = f * rc;
+    const float r = __builtin_fmaf(-q, 255.0f, f);
+    return __builtin_fmaf(r, rc, q);
+}
+
 // ---- in-launch hand-offs between workgroups (round 5) ----------------------------------------------------------------------------
 // The per-XCD L2s are not coherent and a CU's L1 is never refreshed by another CU's stores, so a workgroup that consumes another
 // workgroup's bytes INSIDE a launch needs them written through and read past its L1.  The form used here (MI355X_MICROARCH.md,

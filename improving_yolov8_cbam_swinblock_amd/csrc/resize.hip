@@ -18,16 +18,6 @@ namespace {
 constexpr int RS_THREADS = 256;
 constexpr int RS_PX = 4;  // consecutive output pixels of a row per lane: one 16-byte store
 
-// uint8 -> float32 / 255, correctly rounded (bit-identical to img.float() / 255) without the IEEE division sequence: q = u * fl(1/255) is
-// within an ulp of the quotient, the residual u - 255 q is exact in one fma, and one correction step lands on the rounded quotient for
-// every u in [0, 255] (tests/test_gpu_resize.py compares all 256 values with torch's division).
-__device__ __forceinline__ float unit_of_byte(uint32_t u) {
-    const float f = (float)u, rc = 1.0f / 255.0f;
-    const float q = f * rc;
-    const float r = __builtin_fmaf(-q, 255.0f, f);
-    return __builtin_fmaf(r, rc, q);
-}
-
 template <typename T, bool NORM> __device__ __forceinline__ float px(const T* p) {
     if constexpr (sizeof(T) == 1) return NORM ? unit_of_byte(*p) : (float)*p;
     else return *p;

@@ -93,6 +93,36 @@ def preprocess_batch(batch, imgsz, stride, multi_scale=False, rng=random, device
     return out
 
 
+def augment_batch(samples, imgsz, hyp=None, mosaic=True, transforms=None, device=None):
+    """A training batch from loaded images, augmented on the device as the reference's v8_transforms does at its defaults (data/augment.py
+    :2375-2439: mosaic, scale / translate (/ rotate / shear), HSV, flips) -> the dict TrainStep.__call__ takes, "max_boxes" set.
+    samples[i]: {"img": (h, w, 3) uint8 BGR, "labels" [n, 5] = (cls, xywh normalised) or "cls" + "bboxes", "mix_labels": its three mosaic
+    partners, likewise} - the data loader picked the partners, so Mosaic's own pick is not drawn here (data.augment.v8_transforms(dataset,
+    ...)() draws it too, for a caller that lets the stream choose).  hyp: mapping or namespace with the reference's names; missing ones take
+    the reference's defaults.  mosaic=False is hyp.mosaic = 0.  A sample whose mosaic test fails is letterboxed to imgsz by ops.letterbox and
+    then warped alone with border 0, as RandomPerspective's pre_transform does (:1220-1221).  The draws consume `random` / `np.random`."""
+    from ..data.augment import V8_DEFAULTS, v8_transforms
+
+    if transforms is None:
+        h = dict(V8_DEFAULTS)
+        h.update(hyp if isinstance(hyp, dict) else {k: getattr(hyp, k) for k in V8_DEFAULTS if hasattr(hyp, k)} if hyp is not None else {})
+        if not mosaic:
+            h["mosaic"] = 0.0
+        transforms = v8_transforms(None, imgsz, h)
+    params = [transforms(pick_partners=False) for _ in samples]
+    alone = [i for i, p in enumerate(params) if p["mosaic"] is None]
+    samples = list(samples)
+    if alone:  # pre_transform: LetterBox(new_shape=(imgsz, imgsz)), the grey levels kept in the image's own channel order
+        boxed, ratio_pad = ops.letterbox([samples[i]["img"] for i in alone], (imgsz, imgsz), bgr=False, normalize=False, device=device)
+        boxed = boxed.permute(0, 2, 3, 1).to(torch.uint8).contiguous()
+        for j, i in enumerate(alone):
+            smp = {k: v for k, v in samples[i].items() if k != "mix_labels"}
+            smp.update(img=boxed[j], ori_shape=tuple(int(v) for v in samples[i]["img"].shape[:2]), ratio_pad=ratio_pad[j])
+            samples[i] = smp
+    out = ops.augment_batch(samples, params, imgsz, device=device)
+    return {k: out[k] for k in ("img", "batch_idx", "cls", "bboxes", "max_boxes")}
+
+
 class _CapturedShape:
     """what TrainStep keeps per captured image shape: the graphs, the static batch they read and the loss items they write."""
 

@@ -455,6 +455,90 @@ int ymi_letterbox_batch(const ymi_letterbox_image* images, int64_t n, float* dst
 int ymi_scale_boxes(const float* det, int64_t det_ld, const int32_t* count, const float* params, int64_t batch, int64_t max_det, int64_t cols,
                     int32_t padding, int32_t xywh, float* out, int64_t out_ld, void* stream);
 
+/* ------------------------------------------------------------------- training augmentation ---- */
+/* The reference's v8_transforms at perspective = 0 (data/augment.py): Mosaic._mosaic4 (:658-714), RandomPerspective (:1017-1078, :1185-1261),
+ * RandomHSV (:1346-1382), RandomFlip (:1433-1476) and the conversion to the float32 NCHW batch, csrc/augment.hip.  Every random draw and all the
+ * geometry are the caller's (data.augment draws, ops.mosaic_placement / ops.affine_matrix compute); the library receives a table row per image.
+ *
+ * DISCLOSURE.  The warp rule and the colour round trip below are OpenCV's warpAffine INTER_LINEAR fixed-point scheme and its 8-bit
+ * BGR <-> HSV conversion AS RECALLED: no OpenCV was at hand when this was written, so neither is verified against OpenCV.  The rules written here
+ * are the contract; the tests hold the kernels to them bit for bit.
+ *
+ * ymi_augment_batch: images.  One launch per YMI_AUGMENT_MAX images.
+ *   table   : HOST array of n rows, validated here (sources lie within their images, placements within the canvas, coordinates below 2^30);
+ *   table_d : the SAME n rows in DEVICE memory (the caller uploads them together with the images: one copy); the kernel reads these
+ *   dst     : float32 [n][3][size][size]; every element is written exactly once
+ * A row: n_src (1..4) sources, each a DEVICE pointer to a contiguous [h][w][3] uint8 image and its placement (x1a, y1a, x2a, y2a, x1b, y1b) as
+ * _mosaic4 computes it: canvas pixel (cy, cx) with x1a <= cx < x2a, y1a <= cy < y2a is source pixel (cy - y1a + y1b, cx - x1a + x1b).
+ * Placements do not overlap (the first that holds a pixel gives it).  The canvas (canvas_h x canvas_w; 2s x 2s for a mosaic, the image itself
+ * for n_src = 1) is never materialised: a canvas pixel that no placement holds, and every pixel outside the canvas, is `border` (114).
+ * Per destination element (y, x) of image i, plane c, in this order:
+ *   1. flips: yw = flip_ud ? size - 1 - y : y, xw = flip_lr ? size - 1 - x : x (the reference flips after the warp: the flipped image's
+ *      pixel (y, x) is the warped image's pixel (yw, xw))
+ *   2. warp, with the inverse 2 x 3 matrix A in double (ops.affine_matrix inverts M as warpAffine does) and rn = round-half-even to int:
+ *        X = (rn(A[0] * xw * 1024) + rn((A[1] * yw + A[2]) * 1024) + 16) >> 5      (every product and sum rounded on its own: no fma;
+ *        Y = (rn(A[3] * xw * 1024) + rn((A[4] * yw + A[5]) * 1024) + 16) >> 5       >> is arithmetic)
+ *        sx = X >> 5, fx = X & 31, sy = Y >> 5, fy = Y & 31
+ *        level = ((32 - fx) * (32 - fy) * p00 + fx * (32 - fy) * p01 + (32 - fx) * fy * p10 + fx * fy * p11 + 512) >> 10
+ *      with p00 = canvas(sy, sx), p01 = canvas(sy, sx + 1), p10 = canvas(sy + 1, sx), p11 = canvas(sy + 1, sx + 1) per BGR channel, each
+ *      tap resolved by itself as above
+ *   3. lut != NULL (RandomHSV; the reference skips the stage when all three gains are 0): (b, g, r) -> (h, s, v) in integers,
+ *        v = max(b, g, r), d = v - min(b, g, r), sdiv[k] = rn((255 << 12) / (double)k), hdiv[k] = rn((180 << 12) / (6.0 * k)), sdiv[0] = hdiv[0] = 0
+ *        s = (d * sdiv[v] + (1 << 11)) >> 12
+ *        h = v == r ? g - b : v == g ? b - r + 2 * d : r - g + 4 * d;  h = (h * hdiv[d] + (1 << 11)) >> 12;  h < 0: h += 180
+ *      then h = lut[h], s = lut[256 + s], v = lut[512 + v] (three 256-byte tables the caller builds as RandomHSV does; hue entries stay
+ *      below 180, which is the caller's to see to: a larger one is read as hue 0), then back in
+ *      float32, every operation rounded on its own: H = h * (6.0f / 180.0f), S = s * (1.0f / 255.0f), V = v * (1.0f / 255.0f);
+ *        s == 0: b = g = r = V;  else k = floor(H), f = H - k,
+ *        t0 = V, t1 = V * (1 - S), t2 = V * (1 - S * f), t3 = V * (1 - S * (1 - f)),
+ *        (b, g, r) = (t1,t3,t0) (t1,t0,t2) (t3,t0,t1) (t0,t2,t1) (t0,t1,t3) (t2,t1,t0) for k = 0..5
+ *      and each is rn(t * 255.0f) clamped to [0, 255]
+ *   4. plane c takes channel 2 - c with bgr != 0 (BGR -> RGB), else channel c;  normalize != 0: dst = level / 255 rounded as
+ *      img.float() / 255 rounds; else dst = level */
+#define YMI_AUGMENT_MAX 32
+#define YMI_AUGMENT_MAX_SRC 4
+typedef struct ymi_augment_source {
+    const uint8_t* src;
+    int32_t h, w;
+    int32_t x1a, y1a, x2a, y2a, x1b, y1b;
+} ymi_augment_source;
+typedef struct ymi_augment_image {
+    ymi_augment_source s[YMI_AUGMENT_MAX_SRC];
+    double A[6];
+    const uint8_t* lut;
+    int32_t n_src, canvas_h, canvas_w, flip_ud, flip_lr, _pad;
+} ymi_augment_image;
+int ymi_augment_batch(const ymi_augment_image* table, const ymi_augment_image* table_d, int64_t n, float* dst, int64_t size, int32_t border,
+                      int32_t normalize, int32_t bgr, void* stream);
+/* ymi_augment_boxes: the labels of the same batch, one launch, one workgroup (a batch has a few thousand rows at most).
+ *   rows   : DEVICE float32 [n][7] = (image, source slot, cls, x, y, w, h), xywh normalised to the row's source image; image by image in
+ *            ascending order (a row that lies outside its image's [row_start, row_end), or names no image or slot, is dropped)
+ *   images : DEVICE array of `batch` ymi_augment_label_image
+ *   out    : batch_idx [n], cls [n] and bboxes [n][4] float32 hold the kept rows compacted in their original order (elements at and beyond
+ *            total are not written); keep [n] int32 is 1 for a kept row; count [batch] and total [1] int32.  The order is the rows': a
+ *            prefix sum over keep, no atomically claimed slots.
+ * Per row, in float32, every operation rounded on its own, in the reference's order (k: the row's slot):
+ *   1. xywh2xyxy: x1 = x - w / 2, y1 = y - h / 2, x2 = x + w / 2, y2 = y + h / 2
+ *   2. x *= src_w[k], y *= src_h[k] (denormalize); x *= ratio_w[k], y *= ratio_h[k] (LetterBox._update_labels; 1 in a mosaic);
+ *      x += padw[k], y += padh[k] (Mosaic._update_labels :809-813 / LetterBox._update_labels :1629-1632)
+ *   3. canvas > 0 (Mosaic._cat_labels :859-861): clip to [0, canvas]; a row with (x2 - x1) * (y2 - y1) <= 0 is dropped
+ *   4. apply_bboxes (:1100-1112): the corners (x1,y1) (x2,y2) (x1,y2) (x2,y1) through X = M[0] * x + M[1] * y + M[2], Y = M[3] * x + M[4] * y
+ *      + M[5], summed left to right (the reference's sum is a BLAS product whose order is not stated: agreement to a few ulp of the largest
+ *      term, not bit for bit), then min / max; clip X to [0, size_w], Y to [0, size_h]
+ *   5. box_candidates (:1297-1300) against the box of step 3 times `scale`: w1 = x2 * scale - x1 * scale, h1 likewise, w2, h2 of step 4;
+ *      kept when w2 > 2 and h2 > 2 and w2 * h2 / (w1 * h1 + 1e-16f) > area_thr and max(w2 / (h2 + 1e-16f), h2 / (w2 + 1e-16f)) < 100
+ *   6. xyxy2xywh: cx = (x1 + x2) / 2, cy = (y1 + y2) / 2, w2, h2; flip_ud: cy = size_h - cy; flip_lr: cx = size_w - cx
+ *   7. Format (:2072-2074): cx / size_w, cy / size_h, w2 / size_w, h2 / size_h, IEEE float32 quotients */
+typedef struct ymi_augment_label_image {
+    float src_w[YMI_AUGMENT_MAX_SRC], src_h[YMI_AUGMENT_MAX_SRC], ratio_w[YMI_AUGMENT_MAX_SRC], ratio_h[YMI_AUGMENT_MAX_SRC];
+    float padw[YMI_AUGMENT_MAX_SRC], padh[YMI_AUGMENT_MAX_SRC];
+    float M[6];
+    float scale, size_w, size_h, canvas;
+    int32_t flip_ud, flip_lr, row_start, row_end;
+} ymi_augment_label_image;
+int ymi_augment_boxes(const float* rows, int64_t n, const ymi_augment_label_image* images, int64_t batch, float area_thr, float* batch_idx,
+                      float* cls, float* bboxes, int32_t* keep, int32_t* count, int32_t* total, void* stream);
+
 /* ------------------------------------------------------------------------- optimizer step ---- */
 /* The update either side of backward, reference engine/trainer.py:614-622 (optimizer_step: clip_grad_norm_(10.0),
  * SGD-nesterov step, EMA update), :788-849 (three parameter groups) and utils/torch_utils.py:657-673 (ModelEMA.update),
