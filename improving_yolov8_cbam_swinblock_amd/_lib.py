@@ -135,6 +135,8 @@ _SIGNATURES = {
     "ymi_scale_boxes": (_c_i32, [_vp, _c_i64, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_i32, _c_i32, _vp, _c_i64, _vp]),
     "ymi_augment_batch": (_c_i32, [_vp, _vp, _c_i64, _vp, _c_i64, _c_i32, _c_i32, _c_i32, _vp]),
     "ymi_augment_boxes": (_c_i32, [_vp, _c_i64, _vp, _c_i64, _c_f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "ymi_val_match": (_c_i32, [_vp, _vp, _c_i64, _c_i64, _vp, _vp, _vp, _c_i64, _c_f32, _c_f32, _vp, ctypes.POINTER(_c_f32), _c_i32, _c_i32, _vp, _vp, _c_i64,
+                              _c_f32, _c_f32, _vp]),
     "ymi_opt_chunk_elems": (_c_i64, []),
     "ymi_opt_grad_norm": (_c_i32, [_vp, _vp, _c_i32, _c_i32, _c_i64, ctypes.POINTER(_vp), _vp, _vp, _c_i64, _c_i64, _vp, _c_i32, _vp]),
     "ymi_opt_update": (_c_i32, [_vp, _vp, _c_i32, _c_i32, _c_i64, ctypes.POINTER(_vp), _vp, _vp, _c_i32, _vp]),
@@ -148,6 +150,7 @@ class LetterboxImage(ctypes.Structure):  # ymi_letterbox_image
 
 
 AUGMENT_MAX_SRC = 4  # YMI_AUGMENT_MAX_SRC
+VALMATCH_CHUNK, VALMATCH_MAX_LEVELS, VALMATCH_MAX_DET = 1024, 16, 2048  # YMI_VALMATCH_CHUNK, YMI_VALMATCH_MAX_LEVELS; max_det of ymi_val_match
 
 
 class AugmentSource(ctypes.Structure):  # ymi_augment_source

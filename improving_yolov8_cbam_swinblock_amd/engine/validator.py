@@ -1,29 +1,47 @@
 """Validation of a detector: reference engine/validator.py:125-254 with models/yolo/detect/val.py:113-133,174-216,240-253,275-290.
 
-Per batch: the eval forward under autocast, ops.detect_nms on the device (multi_label, as val.py:123-133), one trip of (det, count)
-to the host, then per image the matching of at most max_det detections to the labels and the statistics lists - host code on a few
-hundred numbers.  There is no dataloader: batches arrive as engine.trainer.synthetic_batch makes them (img, batch_idx, cls, bboxes as
-normalised xywh).  A batch that also carries `ori_shape` and `ratio_pad` per image, as a letterboxing dataset attaches them, is matched
-in native space (val.py:135-172): the predictions go through ops.scale_boxes on the device before the one trip to the host, the labels
-through the same arithmetic on the host."""
+Per batch: the eval forward under autocast, ops.detect_nms on the device (multi_label, as val.py:123-133), ops.scale_boxes when the batch
+carries `ori_shape` and `ratio_pad` per image, as a letterboxing dataset attaches them (native-space matching, val.py:135-172), then the
+matching of at most max_det detections per image to the labels.  There is no dataloader: batches arrive as engine.trainer.synthetic_batch
+makes them (img, batch_idx, cls, bboxes as normalised xywh).
+
+match="device": the matching, the tp matrices and the confusion matrix are ONE launch per batch (ops.val_match); det, count and
+tp stay on the device, the batch loop copies nothing to the host and never synchronises, and one vectorised host step after the last batch
+builds `stats`, `detections`, `seen`, the matrix and the label counts.  Results are flushed to the host every FLUSH_EVERY batches.
+match="host" (the default): one trip of (det, count) to the host per batch, then per image box_iou, utils.metrics.match_predictions and
+ConfusionMatrix.process_batch in host code.  It stays the default because callers and tests/test_gpu_predict.py observe the label boxes
+through this module's box_iou, which the device path never calls.  Both paths give the same tp matrices and the same confusion matrix, bit for bit
+(tests/test_gpu_valmatch.py); tools/probes/val_match_probe.py times the two ("Validation statistics on the device")."""
 import numpy as np
 import torch
 
 from .. import ops
-from ..utils.metrics import DetMetrics, box_iou, match_predictions
+from ..utils.metrics import ConfusionMatrix, DetMetrics, box_iou, match_predictions
 from ..utils.ops import scale_boxes, xywh2xyxy
+
+# Device path: batches whose results are held on the device before one trip takes them to the host.  A batch holds det, count and tp:
+# max_det * (24 + 10) + 4 bytes per image, 0.33 MB at batch 32 / max_det 300, so 64 batches are 21 MB at most; a COCO-sized validation
+# (5000 images, 157 batches of 32) makes three trips instead of 157.
+FLUSH_EVERY = 64
 
 
 class DetectionValidator:
     """DetectionValidator(model)(batches) -> results_dict (metrics/precision(B), metrics/recall(B), metrics/mAP50(B), metrics/mAP50-95(B),
-    fitness).  `model` may be the trained model or TrainStep's `step.ema.ema`; its train / eval mode is restored."""
+    fitness; with loss=True also val/box_loss, val/cls_loss, val/dfl_loss: the mean over the batches of model.loss(batch, preds)[1],
+    reference engine/validator.py:219,235).  `model` may be the trained model or TrainStep's `step.ema.ema`; its train / eval mode is
+    restored.  After a call: `stats`, `detections` (per image [n, 6] host tensors as matched), `seen`, `confusion_matrix`
+    (utils.metrics.ConfusionMatrix), `nt_per_class` and `nt_per_image` (labels / images with a label per class, reference val.py:248-249)."""
 
-    def __init__(self, model, conf=0.001, iou=0.7, max_det=300, single_cls=False, agnostic_nms=False, dtype=torch.bfloat16, augment=False):
+    def __init__(self, model, conf=0.001, iou=0.7, max_det=300, single_cls=False, agnostic_nms=False, dtype=torch.bfloat16, augment=False, match="host",
+                 loss=False):
+        if match not in ("device", "host"):
+            raise ValueError(f"match is 'device' or 'host', got {match!r}")
         self.model = model
         self.augment = bool(augment)  # test-time augmentation: the forward is model.predict(img, augment=True) (reference engine/validator.py:214)
         self.conf, self.iou, self.max_det = conf, iou, max_det
         self.single_cls, self.agnostic_nms = single_cls, agnostic_nms
         self.dtype = dtype
+        self.match, self.with_loss = match, bool(loss)
         self.iouv = torch.linspace(0.5, 0.95, 10)
         self.nc = int(model.model[-1].nc)
         self.init_metrics()
@@ -33,6 +51,13 @@ class DetectionValidator:
         self.seen = 0
         self.stats = dict(tp=[], conf=[], pred_cls=[], target_cls=[])
         self.detections = []  # per image [n, 6] as matched (single_cls: class column 0), kept for callers that want the boxes
+        self.confusion_matrix = ConfusionMatrix(self.nc, conf=self.conf)
+        self.nt_per_class = np.zeros(self.nc, dtype=np.int64)
+        self.nt_per_image = np.zeros(self.nc, dtype=np.int64)
+        self.loss = None            # loss=True: the device sum of the batches' loss items
+        self._target_img = []       # per image (host path) or per flush (device path): the distinct classes labelled in an image
+        self._held, self._cm_dev = [], None
+        self._levels = [float(v) for v in self.iouv.tolist()]
 
     def postprocess(self, preds):
         """-> (det [B, max_det, 6], count [B]) on the device; reference val.py:113-133."""
@@ -60,6 +85,8 @@ class DetectionValidator:
                 pred[:, 5] = 0
                 cls = torch.zeros_like(cls)
             self.detections.append(pred)
+            self._target_img.append(cls.unique())
+            self.confusion_matrix.process_batch(pred, bbox, cls)
             if not len(pred):
                 if len(cls):
                     self._append(torch.zeros(0, len(self.iouv), dtype=torch.bool), pred[:, 4], pred[:, 5], cls)
@@ -73,11 +100,66 @@ class DetectionValidator:
         for k, v in zip(("tp", "conf", "pred_cls", "target_cls"), (tp, conf, pred_cls, target_cls)):
             self.stats[k].append(v)
 
+    def update_metrics_device(self, det, count, batch):
+        """det / count on the device: one launch, nothing crosses to the host.  The batch's results are held until the next flush."""
+        if self._cm_dev is None:
+            self._cm_dev = torch.zeros((self.nc + 1, self.nc + 1), dtype=torch.int32, device=det.device)
+        native = "ori_shape" in batch and "ratio_pad" in batch
+        tp = ops.val_match(det, count, batch["batch_idx"], batch["cls"], batch["bboxes"], tuple(batch["img"].shape[2:]), self._levels,
+                           ori_shapes=batch["ori_shape"] if native else None, ratio_pads=batch["ratio_pad"] if native else None,
+                           single_cls=self.single_cls, cm=self._cm_dev, cm_conf=self.confusion_matrix.conf, cm_iou=self.confusion_matrix.iou_thres)
+        self._held.append((det, count, tp, batch["batch_idx"].detach().reshape(-1), batch["cls"].detach().reshape(-1)))
+        if len(self._held) >= FLUSH_EVERY:
+            self._flush()
+
+    def _flush(self):
+        """the held batches -> host, five copies whatever their number, then the statistics of their images in one vectorised step."""
+        if not self._held:
+            return
+        dets, counts, tps, bidx, cls = zip(*self._held)
+        self._held = []
+        sizes = [int(d.shape[0]) for d in dets]                      # images per batch (shapes: host numbers)
+        first = np.concatenate(([0], np.cumsum(sizes)))[:-1]         # index of a batch's first image within this flush
+        n_lab = [int(b.numel()) for b in bidx]
+        det = torch.cat(dets, 0).cpu()
+        count = torch.cat(counts, 0).cpu().long()
+        tp = torch.cat(tps, 0).cpu()
+        lab_img = torch.cat([b.float() for b in bidx], 0).cpu().long()
+        lab_cls = torch.cat([c.float() for c in cls], 0).cpu()
+        in_batch = (lab_img >= 0) & (lab_img < torch.from_numpy(np.repeat(sizes, n_lab)))   # rows of image indices no image has belong to nobody
+        lab_img = lab_img + torch.from_numpy(np.repeat(first, n_lab))
+        lab_img, lab_cls = lab_img[in_batch], lab_cls[in_batch]
+        if self.single_cls:
+            det[:, :, 5] = 0
+            lab_cls = torch.zeros_like(lab_cls)
+        live = torch.arange(det.shape[1])[None, :] < count[:, None]  # [images, max_det]
+        rows = det[live]                                             # image by image, ranked order inside an image
+        self.seen += int(det.shape[0])
+        self.detections.extend(rows.split(count.tolist()))
+        order = torch.sort(lab_img, stable=True)[1]                  # image by image, table order inside an image
+        self._append(tp[live].bool(), rows[:, 4], rows[:, 5], lab_cls[order])
+        pairs = torch.unique(torch.stack((lab_img, lab_cls.long()), 1), dim=0) if len(lab_img) else torch.zeros(0, 2, dtype=torch.long)
+        self._target_img.append(pairs[:, 1].float())
+
     def get_stats(self):
         """reference val.py:240-253; with nothing accumulated (no labels and no detections anywhere) every metric is zero."""
         if self.stats["tp"]:
             self.metrics.process(**{k: torch.cat(v, 0).numpy() for k, v in self.stats.items()})
-        return self.metrics.results_dict
+        out = self.metrics.results_dict
+        if self.with_loss and self.loss is not None:
+            out.update(zip(("val/box_loss", "val/cls_loss", "val/dfl_loss"), self._loss_mean))
+        return out
+
+    def _finish(self, n_batches):
+        if self.match == "device":
+            self._flush()
+            if self._cm_dev is not None:
+                self.confusion_matrix.matrix = self._cm_dev.cpu().numpy().astype(np.int64)
+        count = lambda parts: np.bincount(torch.cat(parts).numpy().astype(int), minlength=self.nc) if parts else np.zeros(self.nc, dtype=np.int64)  # noqa: E731
+        self.nt_per_class = count(self.stats["target_cls"])
+        self.nt_per_image = count(self._target_img)
+        if self.with_loss and self.loss is not None:
+            self._loss_mean = [float(v) for v in (self.loss / n_batches).cpu()]
 
     def __call__(self, batches):
         if isinstance(batches, dict):
@@ -85,19 +167,31 @@ class DetectionValidator:
         was_training = self.model.training
         self.init_metrics()
         self.model.eval()
+        n_batches = 0
         try:
             for batch in batches:
+                n_batches += 1
                 with torch.no_grad():
                     kw = {"augment": True} if self.augment else {}  # (only then: any module that maps an image batch to predictions can be validated)
                     if self.dtype == torch.float32:
                         preds = self.model(batch["img"], **kw)
+                        if self.with_loss:
+                            items = self.model.loss(batch, preds)[1]
                     else:
                         with torch.autocast("cuda", dtype=self.dtype):
                             preds = self.model(batch["img"], **kw)
+                            if self.with_loss:
+                                items = self.model.loss(batch, preds)[1]
+                    if self.with_loss:
+                        self.loss = items.detach().clone() if self.loss is None else self.loss + items.detach()
                     det, count = self.postprocess(preds)
                     if "ori_shape" in batch and "ratio_pad" in batch:  # native-space predictions (val.py:157-172)
                         det = ops.scale_boxes(det, count, tuple(batch["img"].shape[2:]), batch["ori_shape"], batch["ratio_pad"], inplace=True)
-                self.update_metrics(det.cpu(), count.cpu(), batch)
+                    if self.match == "device":
+                        self.update_metrics_device(det, count, batch)
+                if self.match == "host":
+                    self.update_metrics(det.cpu(), count.cpu(), batch)
+            self._finish(n_batches)
         finally:
             self.model.train(was_training)
         return self.get_stats()

@@ -36,3 +36,4 @@ from .blocks import (  # noqa: F401
 )
 from .resize import letterbox, letterbox_geometry, scale_boxes, scale_boxes_params, scale_image, scale_rows, tta_clip_ranges, tta_merge  # noqa: F401
 from .augment import affine_matrix, augment_batch, hsv_luts, invert_affine, mosaic_placement  # noqa: F401
+from .validate import VAL_MATCH_LABEL_CHUNK, val_match  # noqa: F401

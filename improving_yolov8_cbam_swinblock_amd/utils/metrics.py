@@ -1,16 +1,22 @@
-"""Detection metrics under the reference's public names: box_iou, match_predictions, compute_ap, ap_per_class, Metric, DetMetrics.
+"""Detection metrics under the reference's public names: box_iou, match_predictions, ConfusionMatrix, compute_ap, ap_per_class, Metric, DetMetrics.
 
 The text of this module is the project's own, written from the definitions of the quantities.  What is shared with the reference
-(ultralytics/utils/metrics.py, engine/validator.py) is the interface - names, signatures, result keys - and the numbers: the tp matrices are
-equal and P, R, AP per class and the means agree within 1e-9 on the reference-generated fixtures (tests/test_host_nms_check.py).
+(ultralytics/utils/metrics.py, engine/validator.py) is the interface - names, signatures, result keys - and the numbers: the tp matrices and
+the confusion matrices are equal and P, R, AP per class and the means agree within 1e-9 on the reference-generated fixtures
+(tests/test_host_nms_check.py, tests/test_valmatch_ref_cpu.py).
 
 Definitions.  Detections are ranked by descending confidence.  At one IoU threshold a detection is *correct* when it claims a label of its own
 class that it overlaps by at least the threshold and no better-ranked detection claimed that label (a detection claims the label it overlaps
 most).  For one class, precision after k detections is (correct among the first k) / k and recall is (correct among the first k) / labels.
 AP is the area under the precision envelope (the largest precision at any recall at least as large) over recall in [0, 1], sampled at
 101 equally spaced recalls and integrated by the trapezoid rule.  P and R are read off the precision / recall-over-confidence curves at
-the confidence where the box-filtered class-mean F1 peaks.  Host code in numpy float64: after NMS an image carries at most max_det rows,
-so a kernel would buy nothing.  No plotting and no confusion matrix."""
+the confidence where the box-filtered class-mean F1 peaks.
+
+Where the work runs.  box_iou, match_predictions and ConfusionMatrix.process_batch here are HOST code: the statement of the quantities, and the
+validator's match="host" path.  The validator's match="device" path computes the same tp matrices and the same confusion matrix on the device with one
+launch per batch (ops.val_match, csrc/valmatch.hip) and crosses to the host once per validation; tools/probes/val_match_probe.py times the two
+paths ("Validation statistics on the device", says what has been measured).  ap_per_class and what follows it stay host numpy float64: they run once per validation on
+all rows.  No plotting."""
 import numpy as np
 import torch
 
@@ -49,6 +55,71 @@ def match_predictions(pred_classes, true_classes, iou, iouv):
                 owner[claim[d]] = d
                 out[d, t] = True
     return torch.from_numpy(out)
+
+
+class ConfusionMatrix:
+    """counts of (predicted class, labelled class) pairs of a detector, `matrix` [(nc + 1), (nc + 1)] int64: row = predicted class, column =
+    labelled class, index nc = background (a detection that holds no label / a label no detection claims).  Reference
+    utils/metrics.py:295-407 for task "detect", without the plots.
+
+    Rule (process_batch, one image).  Only detections with conf > `conf` take part; IoU is taken regardless of class.  A detection claims the
+    label it overlaps most, if that IoU exceeds `iou_thres` (both thresholds compared in float32, as a float32 tensor compares with a Python
+    number); a label goes to the claimant that overlaps it most.  The holder of a label counts at [its class, the label's class]; every other
+    detection - no claim, or a claim lost to a better one: it does not fall back to its next label - at [its class, nc]; a label nobody
+    claims at [nc, its class].  Equal IoUs (the reference leaves them to argsort): the lower label index for a detection's claim, then the
+    lower detection index for a label's holder - the rule of ymi_val_match, which fills the same matrix on the device.  Class ids are
+    truncated to integers; an update in which one lies outside [0, nc) is not counted."""
+
+    def __init__(self, nc, conf=0.25, iou_thres=0.45):
+        self.nc = int(nc)
+        self.conf = 0.25 if conf in {None, 0.001} else conf  # the validator's default confidence would count every stray: the reference substitutes 0.25
+        self.iou_thres = iou_thres
+        self.matrix = np.zeros((self.nc + 1, self.nc + 1), dtype=np.int64)
+
+    def _count(self, rows, cols):
+        rows, cols = np.asarray(rows, dtype=np.int64).reshape(-1), np.asarray(cols, dtype=np.int64).reshape(-1)
+        ok = (rows >= 0) & (rows <= self.nc) & (cols >= 0) & (cols <= self.nc)
+        np.add.at(self.matrix, (rows[ok], cols[ok]), 1)
+
+    def _class_ids(self, values):
+        """float class column -> int64 ids, truncated; outside [0, nc): -1"""
+        v = np.trunc(np.asarray(values, dtype=np.float64).reshape(-1))
+        return np.where((v >= 0) & (v < self.nc), v, -1).astype(np.int64)
+
+    def process_batch(self, detections, gt_bboxes, gt_cls):
+        """detections [n, 6] (x1, y1, x2, y2, conf, cls) or None, gt_bboxes [m, 4] xyxy, gt_cls [m]: one image."""
+        gt_cls = torch.as_tensor(gt_cls).detach().cpu().reshape(-1)
+        gc = self._class_ids(gt_cls.numpy())
+        det = torch.zeros(0, 6) if detections is None else torch.as_tensor(detections).detach().cpu().float().reshape(-1, 6)
+        det = det[(det[:, 4].numpy() > np.float32(self.conf)).nonzero()[0]]
+        dc = self._class_ids(det[:, 5].numpy())
+        n_lab, n_det = len(gc), len(dc)
+        background = np.full(1, self.nc, dtype=np.int64)
+        if n_lab == 0 or n_det == 0:
+            self._count(dc, np.broadcast_to(background, dc.shape))
+            self._count(np.broadcast_to(background, gc.shape), gc)
+            return
+        iou = box_iou(torch.as_tensor(gt_bboxes).detach().cpu().reshape(-1, 4), det[:, :4]).numpy()  # [labels, detections] float32
+        claim = iou.argmax(axis=0)                                 # first maximum: the lower label index
+        strength = iou[claim, np.arange(n_det)]
+        claims = strength > np.float32(self.iou_thres)
+        holder = np.full(n_lab, -1, dtype=np.int64)
+        for d in np.flatnonzero(claims):                           # ascending, strict: the lower detection index keeps an equal IoU
+            if holder[claim[d]] < 0 or strength[d] > strength[holder[claim[d]]]:
+                holder[claim[d]] = d
+        held = holder >= 0
+        holds = np.zeros(n_det, dtype=bool)
+        holds[holder[held]] = True
+        both = held & (gc >= 0) & (dc[np.where(held, holder, 0)] >= 0)
+        self._count(dc[holder[both]], gc[both])
+        self._count(np.broadcast_to(background, (int((~held).sum()),)), gc[~held])
+        self._count(dc[~holds], np.broadcast_to(background, (int((~holds).sum()),)))
+
+    def tp_fp(self):
+        """-> (true positives, false positives) per class, without the background row."""
+        tp = self.matrix.diagonal()
+        fp = self.matrix.sum(1) - tp
+        return tp[:-1], fp[:-1]
 
 
 def smooth(y, f=0.05):

@@ -539,6 +539,48 @@ typedef struct ymi_augment_label_image {
 int ymi_augment_boxes(const float* rows, int64_t n, const ymi_augment_label_image* images, int64_t batch, float area_thr, float* batch_idx,
                       float* cls, float* bboxes, int32_t* keep, int32_t* count, int32_t* total, void* stream);
 
+/* ------------------------------------------------------------------ validation statistics ---- */
+/* What the validator does per image after NMS (models/yolo/detect/val.py:135-155, :174-216; utils/metrics.py box_iou and
+ * ConfusionMatrix.process_batch :335-391; engine/validator.py match_predictions), csrc/valmatch.hip: ONE launch of `batch` workgroups, no
+ * workspace, no allocation, no synchronisation; it only enqueues on `stream`.
+ *   det, count : [batch][max_det][6] float32 rows (x1, y1, x2, y2, conf, cls) in ranked order and [batch] int32, as ymi_detect_nms /
+ *                ymi_scale_boxes leave them; max_det <= 2048; rows at or beyond count[b] are ignored whatever they hold
+ *   labels     : the batch's table of n_labels rows in the batch's own order: lab_img int32 (image of the row; rows of other values
+ *                belong to nobody), lab_cls float32, lab_box [n_labels][4] float32 normalised (cx, cy, w, h).  An image's rows need not be
+ *                contiguous; neither n_labels nor the rows per image are capped (the table is staged through LDS YMI_VALMATCH_CHUNK rows
+ *                at a time).  "Table order" below is the order of an image's rows in this table.  n_labels may be 0.
+ *   img_w, img_h : the network input's size;  native: DEVICE float32 [batch][5] = (gain, pad_x, pad_y, w0, h0), the table of
+ *                ymi_scale_boxes, or NULL (labels stay in the network input's pixels)
+ *   levels     : HOST array of n_levels <= YMI_VALMATCH_MAX_LEVELS float32 IoU levels; it travels in the kernel arguments
+ *   single_cls : != 0: every detection and every label counts as class 0, in tp and in the matrix
+ *   tp         : [batch][max_det][n_levels] uint8, every element written; zero at and beyond count[b]
+ *   cm         : NULL (no matrix) or int32 [(nc + 1) * (nc + 1)], row = predicted class, column = labelled class, index nc = background;
+ *                ADDED to with integer atomics (the caller zeroes it once per validation), so the result does not depend on any order
+ * Every step is one rounded float32 operation, in this order (the host path's torch statements; no fused multiply-add):
+ *   label box  : hw = w / 2, hh = h / 2; x1 = (cx - hw) * img_w, y1 = (cy - hh) * img_h, x2 = (cx + hw) * img_w, y2 = (cy + hh) * img_h;
+ *                with native: v = (v - pad) / gain (pad_x for x, pad_y for y; the IEEE quotient, as in ymi_scale_boxes), then
+ *                min(max(v, 0), w0) for x, min(max(v, 0), h0) for y
+ *   iou        : box_iou(label, detection): iw = max(min(lx2, px2) - max(lx1, px1), 0), ih likewise, inter = iw * ih,
+ *                area_l = (lx2 - lx1) * (ly2 - ly1), area_p likewise, iou = inter / (((area_l + area_p) - inter) + 1e-7f)
+ *   tp         : overlap = iou * (1 if the class columns are equal as floats, else 0).  Detection d claims the label of largest overlap,
+ *                the first maximum in table order (a detection that overlaps nothing claims the image's first row, as argmax does); s[d]
+ *                is that overlap.  m[d] = the largest s[e] over e < d with the same claim (-inf if there is none).
+ *                tp[d][t] = s[d] >= levels[t] and not (m[d] >= levels[t]).  An image without labels has tp = 0.
+ *   cm         : only detections with conf > cm_conf take part; iou is taken regardless of class.  A detection claims the label of largest
+ *                iou (first maximum in table order) if that iou > cm_iou (both thresholds compared in float32).  A claimed label goes to
+ *                the claimant of largest iou.  Then: the holder of a label adds 1 to cm[det_cls][gt_cls]; every other participating
+ *                detection - no claim, or its claim lost to a better one: it does not fall back to another label - adds 1 to
+ *                cm[det_cls][nc]; every label nobody claims adds 1 to cm[nc][gt_cls] (an image without detections: all of its labels; an
+ *                image without labels: all of its detections above cm_conf go to cm[det_cls][nc]).
+ *                Equal ious: the reference leaves them to argsort; the library's own rule is the lower table row for a detection's claim,
+ *                then the lower detection index for a label's holder.  Class ids are truncated to integers as .int() does; an update in
+ *                which a class id lies outside [0, nc) is not counted (a label held by such a detection is not counted as missed either). */
+#define YMI_VALMATCH_CHUNK 1024
+#define YMI_VALMATCH_MAX_LEVELS 16
+int ymi_val_match(const float* det, const int32_t* count, int64_t batch, int64_t max_det, const int32_t* lab_img, const float* lab_cls,
+                  const float* lab_box, int64_t n_labels, float img_w, float img_h, const float* native, const float* levels, int32_t n_levels,
+                  int32_t single_cls, uint8_t* tp, int32_t* cm, int64_t nc, float cm_conf, float cm_iou, void* stream);
+
 /* ------------------------------------------------------------------------- optimizer step ---- */
 /* The update either side of backward, reference engine/trainer.py:614-622 (optimizer_step: clip_grad_norm_(10.0),
  * SGD-nesterov step, EMA update), :788-849 (three parameter groups) and utils/torch_utils.py:657-673 (ModelEMA.update),
