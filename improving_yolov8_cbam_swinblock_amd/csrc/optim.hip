@@ -139,6 +139,32 @@ __global__ __launch_bounds__(256) void opt_finalize_kernel(const float* __restri
     }
 }
 
+// Gradient accumulation OUTSIDE autograd (reference trainer.py:305,397: nbs / batch backward passes per update): acc[i] += g[i] over the
+// same entry table and chunk map; ymi_opt_entry.acc is the tensor's slice of the optimizer's accumulation arena.  A pure stream: g and
+// acc read once, acc written once by the one thread that read it - no atomics, no flags, the same work on every replay of a graph.
+__global__ __launch_bounds__(256) void opt_accumulate_kernel(const ymi_opt_entry* __restrict__ tab, const int2* __restrict__ chunks, int first_tensor, GradPtrs gp) {
+    const int2 ch = chunks[blockIdx.x];
+    const ymi_opt_entry e = tab[ch.x];
+    const float* __restrict__ g = gp.g[ch.x - first_tensor];
+    float* __restrict__ acc = e.acc;
+    if (!g || !acc) return;  // no gradient this step: acc stays as it is
+    const int64_t base = (int64_t)ch.y * OPT_CHUNK;
+    const int64_t end = base + OPT_CHUNK < e.numel ? base + OPT_CHUNK : e.numel;
+    if (((((uintptr_t)g) | ((uintptr_t)acc)) & 15) == 0) {
+        for (int64_t i = base + threadIdx.x * 4; i < end; i += 1024) {
+            if (i + 3 < end) {
+                const f32x4 a = *reinterpret_cast<const f32x4*>(acc + i);
+                const f32x4 v = *reinterpret_cast<const f32x4*>(g + i);
+                *reinterpret_cast<f32x4*>(acc + i) = f32x4{a[0] + v[0], a[1] + v[1], a[2] + v[2], a[3] + v[3]};
+            } else {
+                for (int64_t j = i; j < end; ++j) acc[j] = acc[j] + g[j];
+            }
+        }
+    } else {
+        for (int64_t i = base + threadIdx.x; i < end; i += 256) acc[i] = acc[i] + g[i];
+    }
+}
+
 // MODE 0: parameters with gradients (update + EMA);  MODE 1: EMA only (buffers, frozen parameters)
 // RULE 0: SGD-momentum; 1: AdamW; 2: Adam; 3: Adamax; 4: NAdam; 5: RAdam; 6: RMSprop (a compile-time parameter: one straight-line body per rule)
 template <int MODE, int RULE>
@@ -323,5 +349,17 @@ extern "C" int ymi_opt_update(const ymi_opt_entry* table, const int32_t* chunk_m
         hipLaunchKernelGGL((opt_update_kernel<1, 0>), grid, block, 0, s, table, cm, first_tensor, gp, hyper, st);
     }
     YMI_CHECK_LAUNCH("opt_update");
+    return YMI_OK;
+}
+
+extern "C" int ymi_opt_grad_accumulate(const ymi_opt_entry* table, const int32_t* chunk_map, int32_t first_tensor, int32_t n_tensors, int64_t n_chunks,
+                                       const float* const* host_grads, void* stream) {
+    YMI_CHECK_ARG(table && chunk_map && host_grads, "opt_grad_accumulate: null argument");
+    YMI_CHECK_ARG(first_tensor >= 0 && n_tensors >= 1 && n_tensors <= OPT_GRADS, "opt_grad_accumulate: 1..%d tensors per launch", OPT_GRADS);
+    YMI_CHECK_ARG(n_chunks >= 1 && n_chunks < (1ll << 31), "opt_grad_accumulate: chunk count");
+    GradPtrs gp{};
+    for (int i = 0; i < n_tensors; ++i) gp.g[i] = host_grads[i];
+    hipLaunchKernelGGL(opt_accumulate_kernel, dim3((unsigned)n_chunks), dim3(256), 0, (hipStream_t)stream, table, reinterpret_cast<const int2*>(chunk_map), first_tensor, gp);
+    YMI_CHECK_LAUNCH("opt_grad_accumulate");
     return YMI_OK;
 }

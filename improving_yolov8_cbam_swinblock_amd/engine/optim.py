@@ -96,6 +96,11 @@ class FusedSGD:
         self._table = None
         self._hyper_host = None
         self._keep = []
+        # gradient accumulation (accumulate()): a float32 arena the parameters' gradients are folded into, allocated on first use
+        self._arena = None
+        self._acc = []       # per parameter: its slice of the arena
+        self._acc_seen = set()  # indices of the parameters that received a gradient since the arena was cleared
+        self.pending = 0     # folds since the last update
 
     # ---- device tables ---------------------------------------------------------------------------------------------
     def _build(self):
@@ -152,6 +157,9 @@ class FusedSGD:
                 b = min(a + OPT_MAX_GRADS, hi)
                 self.ranges.append((a, b - a, first_chunk_of[a], first_chunk_of[b] - first_chunk_of[a], has))
         self._entries = entries
+        self._tab_host = tab
+        self._arena, self._acc, self.pending = None, [], 0  # (a rebuild drops pending sums: the tensors they belonged to are gone)
+        self._acc_seen = set()
         self._table = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev)
         self._cmap = torch.tensor(cmap, dtype=torch.int32).reshape(-1, 2).contiguous().to(dev)
         self.n_grad_chunks = first_chunk_of[self.n_sgd] if self.sgd else len(cmap)
@@ -219,6 +227,9 @@ class FusedSGD:
     def step(self, grads_of=None):
         """grads_of: optional {param: gradient tensor} (default: p.grad).  Parameters without a gradient keep their
         value and momentum (torch.optim.SGD skips them) but still enter the EMA."""
+        if self.pending:
+            self.accumulate(grads_of)  # the updating step's own gradients join the sums ...
+            return self.step_pending()  # ... and the update reads the arena as "the gradient"
         if self._stale():
             self._build()
         self.sync_hyper()
@@ -257,9 +268,77 @@ class FusedSGD:
             self.ema.updates += 1
             self._dev_updates += 1
 
+    # ---- gradient accumulation outside autograd (reference trainer.py:305,397) -----------------------------------------
+    def _ensure_arena(self):
+        """the accumulation arena: one zeroed float32 buffer, every parameter's slice starting on a 16-byte boundary; its addresses go into
+        the entry table IN PLACE (graphs that captured step() hold the table's address)."""
+        if self._stale():
+            self._build()
+        if self._arena is not None:
+            return
+        offs, total = [], 0
+        for p in self.params:
+            offs.append(total)
+            total += (p.numel() + 3) // 4 * 4
+        dev = self._table.device
+        self._arena = torch.zeros(max(total, 4), dtype=torch.float32, device=dev)
+        self._acc = [self._arena[o : o + p.numel()].view_as(p) for o, p in zip(offs, self.params)]
+        for i, a in enumerate(self._acc):
+            self._tab_host[i].acc = a.data_ptr()
+        self._table.copy_(torch.frombuffer(bytearray(bytes(self._tab_host)), dtype=torch.uint8))
+
+    def accumulate(self, grads_of=None):
+        """fold p.grad (or grads_of[p]) into the arena: acc += g in float32, one launch per range of the entry table.  Autograd never
+        accumulates: the caller drops the gradients afterwards (zero_grad(set_to_none=True)), so every backward starts from p.grad is
+        None.  Sums form in call order.  Parameters without a gradient are skipped."""
+        self._ensure_arena()
+        L = _lib.lib()
+        tab = ctypes.c_void_p(self._table.data_ptr())
+        st = stream_ptr()
+        keep = []
+        for first, n, c0, nc, has in self.ranges:
+            if not (has and nc) or first >= self.n_sgd:
+                continue
+            arr = (ctypes.c_void_p * n)()
+            any_grad = False
+            for i in range(n):
+                p = self.params[first + i]
+                g = grads_of.get(p) if grads_of is not None else p.grad
+                if g is not None:
+                    if g.dtype != torch.float32 or not g.is_contiguous() or g.shape != p.shape:
+                        g = g.to(torch.float32).contiguous()
+                        keep.append(g)
+                    arr[i] = g.data_ptr()
+                    self._acc_seen.add(first + i)
+                    any_grad = True
+            if any_grad:
+                check(L.ymi_opt_grad_accumulate(tab, ctypes.c_void_p(self._cmap.data_ptr() + c0 * 8), first, n, nc, arr, st), "opt_grad_accumulate")
+        self.pending += 1
+
+    def step_pending(self):
+        """the update from the accumulated sums (clip on the total's norm, as the reference clips what AccumulateGrad summed), then the
+        arena is cleared - after the update has read it, on the same stream - and `pending` reset."""
+        if self._arena is None or not self._acc_seen:
+            raise RuntimeError("FusedSGD.step_pending(): nothing accumulated")
+        self.pending = 0
+        self.step({self.params[i]: self._acc[i] for i in sorted(self._acc_seen)})
+        self._arena.zero_()
+        self._acc_seen = set()
+
+    def discard_pending(self):
+        """drop the accumulated sums (the reference zeroes resumed gradients at trainer.py:346)."""
+        if self._arena is not None:
+            self._arena.zero_()
+        self._acc_seen = set()
+        self.pending = 0
+
     def grad_norm(self):
         """total gradient norm of the last step (before clipping), as clip_grad_norm_ returns it: one device->host read."""
         return float(self._state.view(torch.float32)[1])
+
+    def steps_taken(self):
+        """optimizer steps taken so far, counted on the device (one device->host read)."""
+        return int(self._state.view(torch.int64)[3]) if self._table is not None else 0
 
     def zero_grad(self, set_to_none=True):
         for grp in self.param_groups:
@@ -294,6 +373,37 @@ class FusedSGD:
             buf = st.get("momentum_buffer")
             if buf is not None:
                 self.momentum[int(idx)].copy_(buf.to(self.momentum[int(idx)].dtype))
+
+
+class FlatFold:
+    """dst[i] += src over flat float32 buffers through ymi_opt_grad_accumulate: a one-entry table per destination.  The split-graph schedule
+    of engine.trainer.TrainStep folds its flat gradient buckets into a flat arena of the same layout with it (one launch per bucket) and
+    adds the arena back into the buckets before the exchange of the updating step."""
+
+    def __init__(self, dsts):
+        for d in dsts:
+            if d.dtype != torch.float32 or not d.is_contiguous() or d.dim() != 1:
+                raise RuntimeError("FlatFold adds flat contiguous float32 buffers")
+        chunk = int(_lib.lib().ymi_opt_chunk_elems())
+        tab = (OptEntry * len(dsts))()
+        cmap, self._range = [], []
+        for i, d in enumerate(dsts):
+            tab[i] = OptEntry(None, None, None, d.numel(), 0, 0, None, d.data_ptr())
+            n = (d.numel() + chunk - 1) // chunk
+            self._range.append((len(cmap), n))
+            cmap.extend((i, c) for c in range(n))
+        self.dsts = list(dsts)
+        self._table = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dsts[0].device)
+        self._cmap = torch.tensor(cmap, dtype=torch.int32).reshape(-1, 2).contiguous().to(dsts[0].device)
+
+    def add(self, i, src):
+        if src.dtype != torch.float32 or not src.is_contiguous() or src.numel() != self.dsts[i].numel():
+            raise RuntimeError("FlatFold.add: a contiguous float32 buffer of the destination's length")
+        c0, nc = self._range[i]
+        if nc:
+            arr = (ctypes.c_void_p * 1)(src.data_ptr())
+            check(_lib.lib().ymi_opt_grad_accumulate(ctypes.c_void_p(self._table.data_ptr()), ctypes.c_void_p(self._cmap.data_ptr() + c0 * 8), i, 1, nc, arr,
+                                                     stream_ptr()), "opt_grad_accumulate")
 
 
 class FusedAdamW(FusedSGD):

@@ -1,16 +1,18 @@
 """Training step of the hot path (reference: ultralytics/engine/trainer.py:383-399,614-622,788-849 and
 models/yolo/detect/train.py:90-115), reduced to what the benchmark step needs: bf16 autocast forward,
 v8 detection loss, backward (+ RCCL gradient mean), gradient clip 10.0, SGD-nesterov step, EMA update."""
+import collections
 import math
 import os
 import random
 
+import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import _lib, ops
 from .ddp import GradientBuckets
-from .optim import FusedAdamax, FusedAdamW, FusedNAdam, FusedRAdam, FusedRMSprop, FusedSGD, ModelEMA
+from .optim import FlatFold, FusedAdamax, FusedAdamW, FusedNAdam, FusedRAdam, FusedRMSprop, FusedSGD, ModelEMA
 
 # weight-gradient GEMMs on a second stream during backward (ops.async_wgrad) in EAGER steps; YMI_WGRAD_STREAM=0 keeps
 # one stream.  Graph-replayed steps stay single-stream: measured no wall-time gain there, and concurrent kernels stretch
@@ -204,8 +206,16 @@ class TrainStep:
         self._shapes = {}  # image_shapes > 1: tuple(img.shape) -> _CapturedShape
         self._graph2 = self._graph3 = None
         self._comm_events = None  # time_exposed_communication(): [(event after the backward's last graph, event after the wait for the buckets)]
+        # gradient accumulation (update=False): nothing of it exists until a micro-step is asked for
+        self._micro = self._micro_items = self._update_graph = self._micro_table = None  # graph=True: forward + backward + fold; step from the arena + clear
+        self._flat_arena = self._flat_fold = None                    # split schedule: the buckets' sums over micro-steps
+        self._flat_pending = 0
 
-    def __call__(self, batch):
+    def __call__(self, batch, update=True):
+        """update=False: a micro-step - forward, loss, backward, the gradients folded into the optimizer's accumulation arena, zero_grad; no
+        gradient exchange, no optimizer step, no EMA update.  update=True with micro-steps pending completes the update from the sums."""
+        if not update or self.opt.pending or self._flat_pending:
+            return self._accumulating_call(batch, update)
         if not self.use_graph:
             return self.eager_step(batch)
         if self.image_shapes > 1:
@@ -215,8 +225,9 @@ class TrainStep:
         elif self._graph is None:
             if batch.get("max_boxes") is None:
                 raise ValueError("graph=True needs batch['max_boxes'] (static target shape)")
-            # The first batch's tensors become the graph's static inputs (later batches are copied into them).
-            self._static = dict(batch)
+            # The first batch's tensors become the graph's static inputs (later batches are copied into them).  A micro graph captured
+            # before this one already reads a static batch: this graph reads the same tensors.
+            self._adopt_static(batch)
             for _ in range(3):  # warm-up: allocator, lazy state (weight arena, optimizer tables), workspaces
                 self.eager_step(self._static)
             torch.cuda.synchronize()
@@ -240,6 +251,142 @@ class TrainStep:
         else:
             self._load_static(batch)
         return self._replay()
+
+    # ---- gradient accumulation (reference trainer.py:305,397) ------------------------------------------------------------------------
+    def _accumulating_call(self, batch, update):
+        if not update:
+            if self.use_graph and not (self.full_graph or self.overlap_graphs):
+                raise ValueError('update=False is not supported with graph="tail": gradient accumulation needs eager mode, graph=True or graph="split"')
+            if self.image_shapes > 1:
+                raise ValueError("update=False is not supported with image_shapes > 1: gradient accumulation keeps one static image shape")
+            if not self.use_graph and self.world > 1:
+                raise ValueError("update=False is not supported eagerly with world_size > 1: the overlapped bucket hooks would start an exchange "
+                                 'during micro-steps (use graph=True or graph="split")')
+        if not self.use_graph:
+            items = self._forward_backward(batch)
+            if update:
+                self.opt.step()  # micro-steps pending: folds these gradients too, steps from the arena, clears it
+            else:
+                self.opt.accumulate()
+            self.opt.zero_grad(set_to_none=True)
+            return items
+        if batch.get("max_boxes") is None:
+            raise ValueError("graph=True needs batch['max_boxes'] (static target shape)")
+        if self.overlap_graphs:
+            return self._accumulating_split(batch, update)
+        if self._micro is None:
+            return self._first_micro(batch)
+        if self.opt._table is not self._micro_table:
+            # FusedSGD._build() (parameters moved) replaced the entry table and dropped the arena: both graphs address the old ones
+            raise RuntimeError("the optimizer rebuilt its device tables after the micro and update graphs were captured: make a new TrainStep")
+        self._load_static(batch)
+        if update:
+            self.opt.sync_hyper()
+        self._micro.replay()
+        self.opt.pending += 1
+        if update:
+            # The update graph steps the parameters that had a gradient when it was captured (opt._acc_seen then, restored since and left
+            # alone by replays); the micro graph folds exactly those, every time: _first_micro checked that the two sets are one.
+            self._update_graph.replay()
+            self.opt.pending = 0
+            if self.ema is not None:
+                self.opt.count_updates(+1)
+        return self._micro_items
+
+    def _adopt_static(self, batch):
+        """the first batch's tensors become the static batch every graph of this step reads; once they exist - whichever graph was captured
+        first - later batches are copied into them, so no capture is left reading tensors nobody fills any more."""
+        if self._static is None:
+            self._static = dict(batch)
+        else:
+            self._load_static(batch)
+
+    def _build_lazy_state(self):
+        arena = self.model._state.arena
+        if arena is not None and not arena.built and arena.specs:
+            arena.build()
+        if self.opt._stale():
+            self.opt._build()
+        self.opt.sync_hyper()  # a capture must not stage the hyper-parameter array
+
+    def _first_micro(self, batch):
+        """graph=True, the first update=False call: the batch is applied exactly once, as an eager micro-step; after it the micro graph
+        (forward + backward + fold + zero_grad) and the shape-independent update graph (step from the arena + clear) are captured WITHOUT
+        being executed - the rule `_select_shape` follows for a new shape.  The full-step graph is not touched."""
+        self._adopt_static(batch)
+        items = self._forward_backward(self._static)
+        self.opt.accumulate()
+        self.opt.zero_grad(set_to_none=True)
+        self._build_lazy_state()
+        folded, self.opt._acc_seen = self.opt._acc_seen, set()  # (to see what the captured fold takes on its own)
+        torch.cuda.synchronize()
+        pool = self._graph.pool() if self._graph is not None else None
+        self._micro, self._micro_table = torch.cuda.CUDAGraph(), self.opt._table
+        with torch.cuda.graph(self._micro, pool=pool, capture_error_mode="global"):
+            self._micro_items = self._forward_backward(self._static)
+            self.opt.accumulate()
+            self.opt.zero_grad(set_to_none=True)
+        self._hold_captured()
+        pending, seen = self.opt.pending - 1, set(self.opt._acc_seen)  # the capture recorded a fold without running it
+        if seen != set(folded):  # (the update graph below steps `seen`; the micro graph folds what its backward produced)
+            raise RuntimeError("the captured backward produced gradients for other parameters than the eager micro-step before it")
+        self._update_graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self._update_graph, pool=self._micro.pool(), capture_error_mode="global"):
+            self.opt.step_pending()
+        if self.ema is not None:
+            self.opt.count_updates(-1)  # captured, not executed
+        self.opt.pending, self.opt._acc_seen = pending, seen
+        return items
+
+    def _accumulating_split(self, batch, update):
+        """the three-graph schedule: micro-steps replay G1 and G2 and fold each flat bucket into a flat arena of the same layout (one launch
+        per bucket, no all-reduce); the updating step adds the arena into the buckets BEFORE their all-reduce, so G3 reads the sums it
+        always reads."""
+        if self._flat_arena is None:
+            self._flat_arena = [torch.zeros_like(f) for f in self.buckets._flat]
+            self._flat_fold = FlatFold(self._flat_arena + list(self.buckets._flat))
+        nb = len(self._flat_arena)
+        if self._graph is None:  # nothing captured yet: the batch is applied once as an eager micro-step, then G1 .. G3 are captured unexecuted
+            self._adopt_static(batch)
+            items = self._forward_backward(self._static)
+            for bi in range(nb):
+                self._pack(bi, self.buckets.buckets[bi], [p.grad for p in self.buckets.buckets[bi]])
+                self._flat_fold.add(bi, self.buckets._flat[bi])
+            self.opt.zero_grad(set_to_none=True)
+            self._flat_pending += 1
+            self._build_lazy_state()
+            torch.cuda.synchronize()
+            self._graph = torch.cuda.CUDAGraph()
+            self._capture_overlap("global" if self.world == 1 else "thread_local")
+            return items
+        self._load_static(batch)
+        self.opt.sync_hyper()
+        for bi, g in enumerate((self._graph, self._graph2)):
+            g.replay()
+            if update:
+                self._flat_fold.add(nb + bi, self._flat_arena[bi])  # bucket += sums of the micro-steps
+                self.buckets.start(bi)
+            else:
+                self._flat_fold.add(bi, self.buckets._flat[bi])
+        if update:
+            self.buckets.wait_all(divide=False)
+            self._graph3.replay()
+            if self.ema is not None:
+                self.opt.count_updates(+1)
+            for a in self._flat_arena:
+                a.zero_()  # after the update has read the buckets the sums went into
+            self._flat_pending = 0
+        else:
+            self._flat_pending += 1
+        self.opt.zero_grad(set_to_none=True)
+        return self._static_items
+
+    def discard_pending(self):
+        """drop the sums of micro-steps not yet applied."""
+        self.opt.discard_pending()
+        for a in self._flat_arena or ():
+            a.zero_()
+        self._flat_pending = 0
 
     def _load_static(self, batch):
         """copy a batch into the static tensors the (selected) graphs read"""
@@ -466,3 +613,80 @@ class TrainStep:
         self._reduce_and_update()
         self.opt.zero_grad(set_to_none=True)
         return items
+
+
+ScheduleAt = collections.namedtuple("ScheduleAt", "ni accumulate lrs momentum update")
+
+
+class WarmupSchedule:
+    """the reference trainer's schedule arithmetic as host code, and nothing else (reference engine/trainer.py):
+      :305  accumulate = max(round(nbs / batch), 1)
+      :306  weight_decay *= batch * accumulate / nbs
+      :330  nw = max(round(warmup_epochs * nb), 100) if warmup_epochs > 0 else -1
+      :216 / :218  lf: one_cycle(1, lrf, epochs) with cos_lr, else the linear ramp max(1 - x / epochs, 0) * (1 - lrf) + lrf
+      :371-380  for ni <= nw: accumulate, the group learning rates (the bias group down from warmup_bias_lr, the others up from 0, towards
+                lr0 * lf(epoch)) and the momentum (from warmup_momentum) are np.interp'ed over [0, nw]; np.round: halves go to even
+      :397-399  an iteration updates when ni - last_opt_step >= accumulate.
+    Outside the warm-up the learning rates are LambdaLR's lr0 * lf(epoch) (:219, :352) and accumulate keeps its last warm-up value.
+    `last_opt_step` is the only state: `at()` reads it, `advance()` / `apply()` move it."""
+
+    def __init__(self, epochs, nb, batch, nbs=64, lr0=0.01, lrf=0.01, momentum=0.937, weight_decay=5e-4, warmup_epochs=3.0, warmup_momentum=0.8,
+                 warmup_bias_lr=0.1, cos_lr=False):
+        self.epochs, self.nb, self.batch, self.nbs = int(epochs), int(nb), batch, nbs
+        self.lr0, self.lrf, self.momentum, self.cos_lr = lr0, lrf, momentum, bool(cos_lr)
+        self.warmup_momentum, self.warmup_bias_lr = warmup_momentum, warmup_bias_lr
+        self.accumulate = max(round(nbs / batch), 1)
+        self.weight_decay = weight_decay * batch * self.accumulate / nbs
+        self.nw = max(round(warmup_epochs * nb), 100) if warmup_epochs > 0 else -1
+        self.last_opt_step = -1
+
+    def lf(self, x):
+        if self.cos_lr:
+            return max((1 - math.cos(x * math.pi / self.epochs)) / 2, 0) * (self.lrf - 1) + 1
+        return max(1 - x / self.epochs, 0) * (1.0 - self.lrf) + self.lrf
+
+    def at(self, epoch, i, warmup_bias_lr=None):
+        """-> ScheduleAt(ni, accumulate, [lr of the bias / weight / norm group], momentum, update) of iteration i of `epoch`."""
+        ni = i + self.nb * epoch
+        target = self.lr0 * self.lf(epoch)
+        if ni <= self.nw:
+            xi = [0, self.nw]
+            bias0 = self.warmup_bias_lr if warmup_bias_lr is None else warmup_bias_lr
+            accumulate = max(1, int(np.interp(ni, xi, [1, self.nbs / self.batch]).round()))
+            lrs = [float(np.interp(ni, xi, [bias0 if j == 0 else 0.0, target])) for j in range(3)]
+            momentum = float(np.interp(ni, xi, [self.warmup_momentum, self.momentum]))
+        else:
+            accumulate = max(1, int(np.float64(self.nbs / self.batch).round())) if self.nw >= 0 else self.accumulate
+            lrs, momentum = [target] * 3, self.momentum
+        return ScheduleAt(ni, accumulate, lrs, momentum, ni - self.last_opt_step >= accumulate)
+
+    def advance(self, rec):
+        """the iteration `rec` describes has run (:399)."""
+        if rec.update:
+            self.last_opt_step = rec.ni
+        return rec
+
+    def apply(self, opt, epoch, i):
+        """write iteration i's values into opt.param_groups and advance -> the ScheduleAt.  As in the reference only groups that have a
+        "momentum" key get the momentum; the Adam family (betas instead) warms its bias group up from 0, the reference's warmup_bias_lr for
+        the optimizer it picks itself (:816)."""
+        has_momentum = "momentum" in opt.param_groups[0]
+        rec = self.at(epoch, i, warmup_bias_lr=None if has_momentum else 0.0)
+        for j, grp in enumerate(opt.param_groups):
+            grp["lr"] = rec.lrs[j]
+            if "momentum" in grp:
+                grp["momentum"] = rec.momentum
+        opt.param_groups[1]["weight_decay"] = self.weight_decay  # (:306: the decayed group is built with the scaled value)
+        return self.advance(rec)
+
+
+def train_epoch(step, batches, schedule, epoch):
+    """the batch loop of the reference's epoch (trainer.py:367-399): schedule -> TrainStep(batch, update=...) -> running mean of the loss items
+    (:389-391), kept on the device: nothing is read back per iteration.  -> tloss (None for no batches).  Gradients pending when the epoch
+    ends stay pending, as in the reference."""
+    tloss = None
+    for i, batch in enumerate(batches):
+        rec = schedule.apply(step.opt, epoch, i)
+        items = step(batch, update=rec.update)
+        tloss = (tloss * i + items) / (i + 1) if tloss is not None else items.detach().clone()
+    return tloss

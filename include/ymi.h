@@ -608,7 +608,7 @@ typedef struct ymi_opt_entry {
     int32_t group;
     int32_t _pad;
     float* second;   /* Adam / AdamW / NAdam / RAdam: exp_avg_sq; Adamax: exp_inf; RMSprop: square_avg; NULL for SGD and EMA-only entries */
-    void* _pad2;
+    float* acc;      /* the tensor's slice of the accumulation arena (ymi_opt_grad_accumulate); NULL until gradients are accumulated */
 } ymi_opt_entry;
 int64_t ymi_opt_chunk_elems(void);
 /* partial sums of squares of (gradient * scale) into partials[partials_offset ..]; finalize != 0 (last launch of a step):
@@ -625,6 +625,12 @@ int ymi_opt_grad_norm(const ymi_opt_entry* table, const int32_t* chunk_map, int3
  * then ema = d*ema + (1-d)*p.  `rule` must equal hyper[14] (it selects the compiled kernel; pass 2 reads hyper[14] for the bias corrections).  host_grads == NULL: EMA-only pass over the given tensors (buffers, frozen parameters). */
 int ymi_opt_update(const ymi_opt_entry* table, const int32_t* chunk_map, int32_t first_tensor, int32_t n_tensors, int64_t n_chunks,
                    const float* const* host_grads, const float* hyper, const void* state, int32_t rule, void* stream);
+/* gradient accumulation outside autograd (reference trainer.py:305,397): table[t].acc[i] += host_grads[t - first_tensor][i] in float32 for
+ * every tensor of the launch, over the same table / chunk_map ranges as ymi_opt_grad_norm.  A tensor whose gradient pointer or acc is NULL
+ * is skipped (its acc stays as it is).  One read of g and acc, one write of acc per element, 16-byte accesses where both addresses allow;
+ * no atomics: sums form in call order, (g1 + g2) + g3, as AccumulateGrad forms them.  Only numel and acc of an entry are read. */
+int ymi_opt_grad_accumulate(const ymi_opt_entry* table, const int32_t* chunk_map, int32_t first_tensor, int32_t n_tensors, int64_t n_chunks,
+                            const float* const* host_grads, void* stream);
 
 /* SwinBlock MLP: Linear(C,4C) -> exact GELU -> Linear(4C,C) (+ skip).  Reference: ultralytics/nn/modules/swin_block.py:33 (definition)
  * and :53 (`x = x + self.mlp(self.norm2(x))`).  Token matrices are ymi_tensors with n = h = 1, w = tokens.
