@@ -2,6 +2,7 @@
 models/yolo/detect/train.py:90-115), reduced to what the benchmark step needs: bf16 autocast forward,
 v8 detection loss, backward (+ RCCL gradient mean), gradient clip 10.0, SGD-nesterov step, EMA update."""
 import collections
+import contextlib
 import math
 import os
 import random
@@ -126,12 +127,15 @@ def augment_batch(samples, imgsz, hyp=None, mosaic=True, transforms=None, device
 
 
 class _CapturedShape:
-    """what TrainStep keeps per captured image shape: the graphs, the static batch they read and the loss items they write."""
+    """what TrainStep keeps per image shape, and the only place it keeps it: the static batch (adopted from the first batch of the shape), and
+    - filled in by the capture - the loss items the graphs write, the shape's plain-step graphs (graph: the full step, or graph="tail"'s
+    forward + backward, or G1; graph2: G2) and, for graph="tail", the gradient tensors its graph rewrites in place."""
 
-    __slots__ = ("graph", "graph2", "static", "items")
+    __slots__ = ("static", "items", "graph", "graph2", "grads")
 
-    def __init__(self):
-        self.graph = self.graph2 = self.static = self.items = None
+    def __init__(self, static):
+        self.static = static
+        self.items = self.graph = self.graph2 = self.grads = None
 
 
 class TrainStep:
@@ -152,14 +156,19 @@ class TrainStep:
         The backward is split with torch.autograd.grad at the boundary tensors (BaseModel.boundary_layers); gradient joins of
         boundary tensors (ops.GradJoin) carry the head's contribution into the backbone's pass.
       * graph="tail": the round-3 multi-rank form (forward + backward as one graph, gradient mean and update eager behind it).
-    image_shapes=N > 1 (multi-scale training, preprocess_batch(multi_scale=True)): up to N distinct shapes of batch["img"] are captured, one
-    graph (three with the split schedule; the update graph G3 reads no activation and is shared) per shape, in a dict keyed by the shape.  A
+    Every captured call goes the same way: `_select` finds the record (_CapturedShape) of batch["img"]'s shape in `_shapes` and loads the
+    batch into its static tensors - or makes the record, which adopts the batch's tensors - and the record's graphs replay (`_replay`).  A
+    record without graphs gets them from `_capture`, the one capture routine, which expects the record's batch to have just been applied
+    eagerly (`_settle` behind it) and executes nothing.  Helpers are handed the record; nothing of a shape is kept on the step itself.
+    image_shapes=N (multi-scale training, preprocess_batch(multi_scale=True)) is how many records there may be: up to N distinct shapes of
+    batch["img"] are captured, one graph (two with the split schedule; the update graph G3 reads no activation and is shared) per shape.  A
     batch of a NEW shape is applied exactly once: as an eager step, after which that shape's graphs are captured WITHOUT being executed; later
     batches of the shape replay.  Everything that does not depend on the activation shape - parameters, optimizer state, the EMA, the weight
     arena, the gradient buckets - is shared by all shapes' graphs, which also share the first graph's memory pool.  Label tensors and
     max_boxes stay static across all shapes.  Scratch buffers are the hazard: `_lib.workspace` and the model's statistics arena REPLACE a
     buffer when a larger shape asks for more, while the smaller shape's graph still holds the old address, so every capture keeps what its
-    launches address alive (_hold_captured).  The default, image_shapes=1, is the single static shape described above.
+    launches address alive (_hold_captured).  The default, image_shapes=1, is the same path with one record and another warm-up policy: the
+    first plain call applies its batch with 3 eager steps (allocator, lazy state, workspaces), captures, and replays.
     Learning rates / momentum changed through `opt.param_groups` reach a replayed graph: they are read from a device
     array (`FusedSGD.sync_hyper`).
 
@@ -192,10 +201,6 @@ class TrainStep:
         self.buckets = GradientBuckets(model, world_size, bucket_bytes, overlap=not self.use_graph, groups=groups)
         # the buckets hold gradient SUMS over ranks; the fused step applies 1 / world (hyper[11]) - no divide launches
         self.opt.world = world_size
-        self._graph = None
-        self._static = None
-        self._static_items = None
-        self._graph_grads = None
         self._seed = None
         self._held = []  # model-side buffers the captured graphs write (_hold_captured)
         self.image_shapes = int(image_shapes)
@@ -203,8 +208,11 @@ class TrainStep:
             raise ValueError("image_shapes counts the image shapes a graph is kept for: at least 1")
         if self.image_shapes > 1 and self.use_graph and not (self.full_graph or self.overlap_graphs):
             raise ValueError('graph="tail" replays one static shape: image_shapes > 1 needs graph=True or graph="split"')
-        self._shapes = {}  # image_shapes > 1: tuple(img.shape) -> _CapturedShape
-        self._graph2 = self._graph3 = None
+        self._shapes = {}  # tuple(img.shape) -> _CapturedShape, at most image_shapes of them; the first one's graph owns the memory pool
+        self._graph3 = None  # the split schedule's update graph, shared by all shapes
+        # several ranks: the process group's watchdog thread polls its events while this thread captures; only this thread's calls may
+        # invalidate the capture
+        self._capture_mode = "global" if world_size == 1 else "thread_local"
         self._comm_events = None  # time_exposed_communication(): [(event after the backward's last graph, event after the wait for the buckets)]
         # gradient accumulation (update=False): nothing of it exists until a micro-step is asked for
         self._micro = self._micro_items = self._update_graph = self._micro_table = None  # graph=True: forward + backward + fold; step from the arena + clear
@@ -218,39 +226,133 @@ class TrainStep:
             return self._accumulating_call(batch, update)
         if not self.use_graph:
             return self.eager_step(batch)
-        if self.image_shapes > 1:
-            fresh = self._select_shape(batch)
-            if fresh is not None:
-                return fresh  # a new shape: applied by its eager step, its graphs are captured for the batches to come
-        elif self._graph is None:
-            if batch.get("max_boxes") is None:
-                raise ValueError("graph=True needs batch['max_boxes'] (static target shape)")
-            # The first batch's tensors become the graph's static inputs (later batches are copied into them).  A micro graph captured
-            # before this one already reads a static batch: this graph reads the same tensors.
-            self._adopt_static(batch)
-            for _ in range(3):  # warm-up: allocator, lazy state (weight arena, optimizer tables), workspaces
-                self.eager_step(self._static)
-            torch.cuda.synchronize()
-            self._graph = torch.cuda.CUDAGraph()
-            # several ranks: the process group's watchdog thread polls its events while this thread captures; only
-            # this thread's calls may invalidate the capture
-            mode = "global" if self.world == 1 else "thread_local"
-            if self.overlap_graphs:
-                self._capture_overlap(mode)
-            else:
-                with torch.cuda.graph(self._graph, capture_error_mode=mode):
-                    if self.full_graph:
-                        self._static_items = self.eager_step(self._static)
-                    else:
-                        self._static_items = self._forward_backward(self._static)
-                self._hold_captured()
-                if not self.full_graph:  # the gradients the replays rewrite in place
-                    self._graph_grads = {p: p.grad for p in self.params if p.grad is not None}
-                elif self.ema is not None:
-                    self.opt.count_updates(-1)  # the capture recorded the update without running it
+        rec = self._select(batch)
+        if rec.graph is not None:
+            return self._replay(rec)
+        # The first plain call of this shape.  image_shapes == 1: 3 warm-up steps (allocator, lazy state, workspaces), capture, replay - the
+        # batch is applied 4 times.  image_shapes > 1: the batch is applied exactly once, by the eager step; its graphs serve the batches to come.
+        once = self.image_shapes > 1
+        for _ in range(1 if once else 3):
+            items = self.eager_step(rec.static)
+        self._settle()
+        self._capture(rec)
+        return items if once else self._replay(rec)
+
+    def _replay(self, rec):
+        if self.overlap_graphs:
+            return self._replay_split(rec)
+        if self.full_graph:
+            self.opt.sync_hyper()  # scheduler changes reach the captured update through the device array
+            rec.graph.replay()
+            self.opt.count_updates(+1)  # the captured step advanced the device counter
         else:
-            self._load_static(batch)
-        return self._replay()
+            rec.graph.replay()
+            self._reduce_and_update(rec.grads)
+            self.opt.zero_grad(set_to_none=True)  # drops references only: the graph owns its gradient buffers
+        return rec.items
+
+    # ---- static batches and their records ---------------------------------------------------------------------------------------------
+    def _select(self, batch):
+        """-> the record whose static tensors now hold `batch`: the one of batch["img"]'s shape, loaded; or a new one that adopts the batch's
+        own tensors (rec.graph is None: the caller applies the batch eagerly and captures).  The first batch's tensors become the static
+        inputs of every graph of that shape, whichever is captured first - later batches are copied into them, so no capture is left
+        reading tensors nobody fills any more.  Only the image may change shape: labels and max_boxes are static across all shapes."""
+        if batch.get("max_boxes") is None:
+            raise ValueError("graph=True needs batch['max_boxes'] (static target shape)")
+        key = tuple(batch["img"].shape)
+        first = next(iter(self._shapes.values()), None)
+        # image_shapes == 1: the one record takes every batch - another image shape fails the static-shape check like any other tensor
+        rec = self._shapes.get(key) if self.image_shapes > 1 else first
+        if rec is not None:
+            self._match_static(rec.static, batch)
+            return rec
+        if len(self._shapes) >= self.image_shapes:
+            raise ValueError(f"graph=True with image_shapes={self.image_shapes}: batch['img'] has the new shape {key}, captured are {sorted(self._shapes)}")
+        if first is not None:
+            self._match_static(first.static, batch, skip=("img",), copy=False)
+        rec = self._shapes[key] = _CapturedShape(dict(batch))
+        return rec
+
+    @staticmethod
+    def _match_static(static, batch, skip=(), copy=True):
+        """check `batch` against the static batch a graph reads (keys in `skip` left out) and, with copy, load it into those tensors."""
+        for k, v in batch.items():
+            ref = static.get(k)
+            if k in skip or v is ref:
+                continue
+            if torch.is_tensor(v):
+                if not torch.is_tensor(ref) or v.shape != ref.shape:  # copy_ would broadcast silently (e.g. a shorter label tensor)
+                    raise ValueError(f"graph=True replays static shapes: batch['{k}'] is {tuple(v.shape)}, captured {tuple(ref.shape) if torch.is_tensor(ref) else ref!r}")
+                if copy:
+                    ref.copy_(v)
+            elif v != ref:
+                raise ValueError(f"graph=True: batch['{k}'] = {v!r} differs from the captured value {ref!r}")
+
+    # ---- capture ------------------------------------------------------------------------------------------------------------------------
+    def _settle(self):
+        """between the eager application of a batch and a capture: the lazy state a capture must find in place, because its construction
+        stages host tables - the weight arena (built from the uses the step recorded), the optimizer's tables, the hyper-parameter array -
+        and a synchronised device.  Behind a full eager_step only the arena can still be missing (after ONE step; the second forward
+        builds it otherwise): the optimizer built its tables in step(), and sync_hyper() behind a step that just called it stages nothing."""
+        arena = self.model._state.arena
+        if arena is not None and not arena.built and arena.specs:
+            arena.build()
+        if self.opt._stale():
+            self.opt._build()
+        self.opt.sync_hyper()  # a capture must not stage the hyper-parameter array
+        torch.cuda.synchronize()
+
+    def _hold_captured(self):
+        """a graph just captured launches that write the model's statistics arena, pack into its weight arena and stage the batched slab sum
+        in RUN.table, and they address the scratch buffers `_lib.workspace` handed out during the capture: keep all of them referenced for as
+        long as the graphs live, whatever the model, a later pass or a larger image shape replaces them with (a workspace is REPLACED when a
+        larger request arrives; a replay of the smaller shape's graph would otherwise write memory the allocator has given to someone else)."""
+        st = self.model._state
+        dev = next(iter(self.params)).device
+        self._held.append((st.stats, st.arena, ops.RUN.table, _lib.live_workspaces(dev)))
+
+    def _capture(self, rec):
+        """capture the plain step's graphs of rec's shape into rec, WITHOUT executing them: the full step, graph="tail"'s forward + backward,
+        or G1 and G2 (and G3, once).  The caller has just applied rec.static eagerly and called _settle().  The first record's graph starts
+        a fresh memory pool - also behind a micro graph - and every later shape's graphs share it."""
+        first = next(iter(self._shapes.values()))
+        pool = first.graph.pool() if first.graph is not None else None
+        rec.graph = torch.cuda.CUDAGraph()
+        if self.overlap_graphs:
+            return self._capture_split(rec, pool)
+        with torch.cuda.graph(rec.graph, pool=pool, capture_error_mode=self._capture_mode):
+            rec.items = self.eager_step(rec.static) if self.full_graph else self._forward_backward(rec.static)
+        self._hold_captured()
+        if self.full_graph:
+            self.opt.count_updates(-1)  # the capture recorded the update without running it
+        else:  # the gradients the replays rewrite in place
+            rec.grads = {p: p.grad for p in self.params if p.grad is not None}
+
+    def _capture_split(self, rec, pool):
+        """G1 and G2 of rec's shape; G3 reads the flat gradient buckets and the optimizer's own state only - nothing of an activation's
+        shape - so the first capture's is replayed for every shape."""
+        mode = self._capture_mode
+        # conv / linear weight gradients are written straight into the flat buckets (ops.grad_arena): only the small vectors (BatchNorm
+        # and LayerNorm parameters, biases, the paired Detect weights) are copied there
+        arena = {id(p): v for bi in range(len(self.buckets.buckets)) for p, v in zip(self.buckets.buckets[bi], self.buckets.flat_views(bi)) if p.dim() >= 2}
+        with torch.cuda.graph(rec.graph, pool=pool, capture_error_mode=mode), ops.grad_arena(arena):
+            rec.items, hg, pairs = self._head_pass(rec.static)
+            self._pack(0, self._head_params, hg)
+        self._hold_captured()
+        del hg
+        rec.graph2 = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(rec.graph2, pool=rec.graph.pool(), capture_error_mode=mode), ops.grad_arena(arena):
+            self._backbone_pass(pairs)
+            self._pack(1, self._back_params, [p.grad for p in self._back_params])
+        self._hold_captured()
+        del pairs
+        self.buckets.wait_all(divide=False)  # (nothing in flight: points .grad at the flat slices the update graph will read)
+        if self._graph3 is None:
+            self._graph3 = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(self._graph3, pool=rec.graph.pool(), capture_error_mode=mode):
+                self.opt.step(None)
+            self.opt.count_updates(-1)  # captured, not executed
+        self.opt.zero_grad(set_to_none=True)
 
     # ---- gradient accumulation (reference trainer.py:305,397) ------------------------------------------------------------------------
     def _accumulating_call(self, batch, update):
@@ -270,16 +372,19 @@ class TrainStep:
                 self.opt.accumulate()
             self.opt.zero_grad(set_to_none=True)
             return items
-        if batch.get("max_boxes") is None:
-            raise ValueError("graph=True needs batch['max_boxes'] (static target shape)")
+        rec = self._select(batch)
         if self.overlap_graphs:
-            return self._accumulating_split(batch, update)
+            if self._flat_arena is None:
+                self._flat_arena = [torch.zeros_like(f) for f in self.buckets._flat]
+                self._flat_fold = FlatFold(self._flat_arena + list(self.buckets._flat))
+            if rec.graph is None:
+                return self._first_split_micro(rec)
+            return self._replay_split(rec, update, arena=True)
         if self._micro is None:
-            return self._first_micro(batch)
+            return self._first_micro(rec)
         if self.opt._table is not self._micro_table:
             # FusedSGD._build() (parameters moved) replaced the entry table and dropped the arena: both graphs address the old ones
             raise RuntimeError("the optimizer rebuilt its device tables after the micro and update graphs were captured: make a new TrainStep")
-        self._load_static(batch)
         if update:
             self.opt.sync_hyper()
         self._micro.replay()
@@ -289,41 +394,23 @@ class TrainStep:
             # alone by replays); the micro graph folds exactly those, every time: _first_micro checked that the two sets are one.
             self._update_graph.replay()
             self.opt.pending = 0
-            if self.ema is not None:
-                self.opt.count_updates(+1)
+            self.opt.count_updates(+1)
         return self._micro_items
 
-    def _adopt_static(self, batch):
-        """the first batch's tensors become the static batch every graph of this step reads; once they exist - whichever graph was captured
-        first - later batches are copied into them, so no capture is left reading tensors nobody fills any more."""
-        if self._static is None:
-            self._static = dict(batch)
-        else:
-            self._load_static(batch)
-
-    def _build_lazy_state(self):
-        arena = self.model._state.arena
-        if arena is not None and not arena.built and arena.specs:
-            arena.build()
-        if self.opt._stale():
-            self.opt._build()
-        self.opt.sync_hyper()  # a capture must not stage the hyper-parameter array
-
-    def _first_micro(self, batch):
+    def _first_micro(self, rec):
         """graph=True, the first update=False call: the batch is applied exactly once, as an eager micro-step; after it the micro graph
         (forward + backward + fold + zero_grad) and the shape-independent update graph (step from the arena + clear) are captured WITHOUT
-        being executed - the rule `_select_shape` follows for a new shape.  The full-step graph is not touched."""
-        self._adopt_static(batch)
-        items = self._forward_backward(self._static)
+        being executed - the rule a new image shape follows.  The full-step graph is not touched; the micro graph shares its memory pool
+        when it exists."""
+        items = self._forward_backward(rec.static)
         self.opt.accumulate()
         self.opt.zero_grad(set_to_none=True)
-        self._build_lazy_state()
+        self._settle()
         folded, self.opt._acc_seen = self.opt._acc_seen, set()  # (to see what the captured fold takes on its own)
-        torch.cuda.synchronize()
-        pool = self._graph.pool() if self._graph is not None else None
+        pool = rec.graph.pool() if rec.graph is not None else None
         self._micro, self._micro_table = torch.cuda.CUDAGraph(), self.opt._table
         with torch.cuda.graph(self._micro, pool=pool, capture_error_mode="global"):
-            self._micro_items = self._forward_backward(self._static)
+            self._micro_items = self._forward_backward(rec.static)
             self.opt.accumulate()
             self.opt.zero_grad(set_to_none=True)
         self._hold_captured()
@@ -333,53 +420,22 @@ class TrainStep:
         self._update_graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self._update_graph, pool=self._micro.pool(), capture_error_mode="global"):
             self.opt.step_pending()
-        if self.ema is not None:
-            self.opt.count_updates(-1)  # captured, not executed
+        self.opt.count_updates(-1)  # captured, not executed
         self.opt.pending, self.opt._acc_seen = pending, seen
         return items
 
-    def _accumulating_split(self, batch, update):
-        """the three-graph schedule: micro-steps replay G1 and G2 and fold each flat bucket into a flat arena of the same layout (one launch
-        per bucket, no all-reduce); the updating step adds the arena into the buckets BEFORE their all-reduce, so G3 reads the sums it
-        always reads."""
-        if self._flat_arena is None:
-            self._flat_arena = [torch.zeros_like(f) for f in self.buckets._flat]
-            self._flat_fold = FlatFold(self._flat_arena + list(self.buckets._flat))
-        nb = len(self._flat_arena)
-        if self._graph is None:  # nothing captured yet: the batch is applied once as an eager micro-step, then G1 .. G3 are captured unexecuted
-            self._adopt_static(batch)
-            items = self._forward_backward(self._static)
-            for bi in range(nb):
-                self._pack(bi, self.buckets.buckets[bi], [p.grad for p in self.buckets.buckets[bi]])
-                self._flat_fold.add(bi, self.buckets._flat[bi])
-            self.opt.zero_grad(set_to_none=True)
-            self._flat_pending += 1
-            self._build_lazy_state()
-            torch.cuda.synchronize()
-            self._graph = torch.cuda.CUDAGraph()
-            self._capture_overlap("global" if self.world == 1 else "thread_local")
-            return items
-        self._load_static(batch)
-        self.opt.sync_hyper()
-        for bi, g in enumerate((self._graph, self._graph2)):
-            g.replay()
-            if update:
-                self._flat_fold.add(nb + bi, self._flat_arena[bi])  # bucket += sums of the micro-steps
-                self.buckets.start(bi)
-            else:
-                self._flat_fold.add(bi, self.buckets._flat[bi])
-        if update:
-            self.buckets.wait_all(divide=False)
-            self._graph3.replay()
-            if self.ema is not None:
-                self.opt.count_updates(+1)
-            for a in self._flat_arena:
-                a.zero_()  # after the update has read the buckets the sums went into
-            self._flat_pending = 0
-        else:
-            self._flat_pending += 1
+    def _first_split_micro(self, rec):
+        """the split schedule, update=False before anything was captured: the batch is applied once as an eager micro-step (each bucket
+        packed and folded into the flat arena), then G1 .. G3 are captured unexecuted."""
+        items = self._forward_backward(rec.static)
+        for bi, params in enumerate(self.buckets.buckets):
+            self._pack(bi, params, [p.grad for p in params])
+            self._flat_fold.add(bi, self.buckets._flat[bi])
         self.opt.zero_grad(set_to_none=True)
-        return self._static_items
+        self._flat_pending += 1
+        self._settle()
+        self._capture(rec)
+        return items
 
     def discard_pending(self):
         """drop the sums of micro-steps not yet applied."""
@@ -388,75 +444,23 @@ class TrainStep:
             a.zero_()
         self._flat_pending = 0
 
-    def _load_static(self, batch):
-        """copy a batch into the static tensors the (selected) graphs read"""
-        for k, v in batch.items():
-            if torch.is_tensor(v) and v is not self._static[k]:
-                if v.shape != self._static[k].shape:  # copy_ would broadcast silently (e.g. a shorter label tensor)
-                    raise ValueError(f"graph=True replays static shapes: batch['{k}'] is {tuple(v.shape)}, captured {tuple(self._static[k].shape)}")
-                self._static[k].copy_(v)
-            elif not torch.is_tensor(v) and v != self._static[k]:
-                raise ValueError(f"graph=True: batch['{k}'] = {v!r} differs from the captured value {self._static[k]!r}")
-
-    # ---- several image shapes (image_shapes > 1) ------------------------------------------------------------------------------------
-    def _select_shape(self, batch):
-        """make the graphs of batch["img"]'s shape the ones `_replay` runs and load the batch into their static tensors -> None; or, for a
-        shape not seen before, apply the batch with an eager step, capture the shape's graphs without executing them -> that step's loss items."""
-        if batch.get("max_boxes") is None:
-            raise ValueError("graph=True needs batch['max_boxes'] (static target shape)")
-        key = tuple(batch["img"].shape)
-        cap = self._shapes.get(key)
-        if cap is not None:
-            self._graph, self._graph2, self._static, self._static_items = cap.graph, cap.graph2, cap.static, cap.items
-            self._load_static(batch)
-            return None
-        if len(self._shapes) >= self.image_shapes:
-            raise ValueError(f"graph=True with image_shapes={self.image_shapes}: batch['img'] has the new shape {key}, captured are {sorted(self._shapes)}")
-        first = next(iter(self._shapes.values()), None)
-        if first is not None:  # only the image may change shape: labels and max_boxes are static across all shapes
-            for k, v in batch.items():
-                ref = first.static.get(k)
-                if k == "img":
-                    continue
-                if torch.is_tensor(v):
-                    if not torch.is_tensor(ref) or v.shape != ref.shape:
-                        raise ValueError(f"graph=True replays static shapes: batch['{k}'] is {tuple(v.shape)}, captured {tuple(ref.shape) if torch.is_tensor(ref) else ref!r}")
-                elif v != ref:
-                    raise ValueError(f"graph=True: batch['{k}'] = {v!r} differs from the captured value {ref!r}")
-        cap = _CapturedShape()
-        cap.static = dict(batch)
-        items = self.eager_step(cap.static)  # this batch's one application
-        # lazy state the capture must find in place (its construction stages host tables): the weight arena is built from the uses the step recorded
-        arena = self.model._state.arena
-        if arena is not None and not arena.built and arena.specs:
-            arena.build()
-        torch.cuda.synchronize()
-        pool = first.graph.pool() if first is not None else None
-        mode = "global" if self.world == 1 else "thread_local"
-        self._graph, self._static = torch.cuda.CUDAGraph(), cap.static
-        if self.overlap_graphs:
-            self._capture_overlap(mode, pool)
-        else:
-            with torch.cuda.graph(self._graph, pool=pool, capture_error_mode=mode):
-                self._static_items = self.eager_step(self._static)
-            self._hold_captured()
-            if self.ema is not None:
-                self.opt.count_updates(-1)  # the capture recorded the update without running it
-        cap.graph, cap.graph2, cap.items = self._graph, self._graph2, self._static_items
-        self._shapes[key] = cap
-        return items
-
-    def _replay(self):
-        if self.full_graph or self.overlap_graphs:
-            self.opt.sync_hyper()  # scheduler changes reach the captured update through the device array
-        self._graph.replay()
-        if self.full_graph:
-            if self.ema is not None:
-                self.opt.count_updates(+1)  # the captured step advanced the device counter
-        elif self.overlap_graphs:
-            self.buckets.start(0)       # the head's gradient sums travel ...
-            self._graph2.replay()       # ... while the backbone's backward runs
-            self.buckets.start(1)
+    # ---- the three-graph schedule -----------------------------------------------------------------------------------------------
+    def _replay_split(self, rec, update=True, arena=False):
+        """G1 -> all-reduce of bucket 0 starts -> G2 -> all-reduce of bucket 1 starts -> wait for both -> G3.  arena (gradient accumulation):
+        a micro-step (update=False) stops behind G2 and, instead of starting an all-reduce, folds each flat bucket into a flat arena of the
+        same layout (one launch per bucket); the updating step adds the arena into the buckets BEFORE their all-reduce, so G3 reads the sums
+        it always reads.  The plain step passes neither and touches nothing of the arena."""
+        self.opt.sync_hyper()  # scheduler changes reach the captured update through the device array
+        nb = len(self.buckets._flat)
+        for bi, g in enumerate((rec.graph, rec.graph2)):
+            g.replay()
+            if not update:
+                self._flat_fold.add(bi, self.buckets._flat[bi])
+                continue
+            if arena:
+                self._flat_fold.add(nb + bi, self._flat_arena[bi])  # bucket += sums of the micro-steps
+            self.buckets.start(bi)  # the head's gradient sums travel while the backbone's backward runs
+        if update:
             ev = self._comm_event_pair()
             if ev:
                 ev[0].record()          # (completes when the backbone's backward does)
@@ -464,35 +468,32 @@ class TrainStep:
             if ev:
                 ev[1].record()          # (completes once the compute stream may go on: the gap is communication nothing hid)
             self._graph3.replay()
-            if self.ema is not None:
-                self.opt.count_updates(+1)
-            self.opt.zero_grad(set_to_none=True)
+            self.opt.count_updates(+1)
+            if arena:
+                for a in self._flat_arena:
+                    a.zero_()  # after the update has read the buckets the sums went into
+                self._flat_pending = 0
         else:
-            self._reduce_and_update(self._graph_grads)
-            self.opt.zero_grad(set_to_none=True)  # drops references only: the graph owns its gradient buffers
-        return self._static_items
+            self._flat_pending += 1
+        self.opt.zero_grad(set_to_none=True)
+        return rec.items
 
-    # ---- the three-graph schedule -----------------------------------------------------------------------------------------------
     def _head_pass(self, batch):
         """forward + loss + the backward of everything behind the backbone / head boundary (the head reads detached leaves of the
         boundary tensors: BaseModel._predict_once) -> (loss items, head gradients aligned with self._head_params,
         [(boundary tensor, gradient the head formed for it)])."""
         model = self.model
-        model.train()
         model._taps = dict(self._boundary)
         try:
-            with torch.autocast("cuda", dtype=self.dtype, enabled=self.dtype != torch.float32):
-                loss, items = model(batch)
+            loss, items = self._forward(batch)
             taps = model._taps
         finally:
             model._taps = None
-        if self._seed is None or self._seed.device != loss.device:
-            self._seed = torch.full((3,), float(self.world), dtype=torch.float32, device=loss.device)
         pairs = [v for v in taps.values() if isinstance(v, tuple)]
         leaves = [leaf for _, leaf in pairs]
         # torch.autograd.grad, not backward(): the leaves are channel slices of concat buffers (not dense), and AccumulateGrad would
         # re-lay every gradient it stores for them out as NCHW-contiguous copies; captured gradients are handed over as they are
-        with ops.deferred_wgrad(True), ops.wgrad_riders(self.use_graph):
+        with self._wgrad_schedule():
             grads = torch.autograd.grad([loss], leaves + self._head_params, [self._seed], allow_unused=True)
         return items, list(grads[len(leaves):]), [(orig, g) for (orig, _), g in zip(pairs, grads[: len(leaves)])]
 
@@ -513,7 +514,7 @@ class TrainStep:
                 g = ops._accumulate(g, adds) if adds else g  # (no backbone consumer left to arrive: the head's gradient is the total)
             roots.append(orig)
             grads.append(g)
-        with ops.deferred_wgrad(True), ops.wgrad_riders(self.use_graph):
+        with self._wgrad_schedule():
             torch.autograd.backward(roots, grads)
 
     def _pack(self, bi, params, grads):
@@ -528,56 +529,32 @@ class TrainStep:
         if dst:
             torch._foreach_copy_(dst, src)
 
-    def _hold_captured(self):
-        """a graph just captured launches that write the model's statistics arena, pack into its weight arena and stage the batched slab sum
-        in RUN.table, and they address the scratch buffers `_lib.workspace` handed out during the capture: keep all of them referenced for as
-        long as the graphs live, whatever the model, a later pass or a larger image shape replaces them with (a workspace is REPLACED when a
-        larger request arrives; a replay of the smaller shape's graph would otherwise write memory the allocator has given to someone else)."""
-        st = self.model._state
-        dev = next(iter(self.params)).device
-        self._held.append((st.stats, st.arena, ops.RUN.table, _lib.live_workspaces(dev)))
-
-    def _capture_overlap(self, mode, pool=None):
-        """pool: the memory pool of an earlier shape's graphs (image_shapes > 1); G3 reads the flat gradient buckets and the optimizer's own
-        state only - nothing of an activation's shape - so the first capture's is replayed for every shape."""
-        b = self._static
-        # conv / linear weight gradients are written straight into the flat buckets (ops.grad_arena): only the small vectors (BatchNorm
-        # and LayerNorm parameters, biases, the paired Detect weights) are copied there
-        arena = {id(p): v for bi in range(len(self.buckets.buckets)) for p, v in zip(self.buckets.buckets[bi], self.buckets.flat_views(bi)) if p.dim() >= 2}
-        with torch.cuda.graph(self._graph, pool=pool, capture_error_mode=mode), ops.grad_arena(arena):
-            self._static_items, hg, pairs = self._head_pass(b)
-            self._pack(0, self._head_params, hg)
-        self._hold_captured()
-        del hg
-        self._graph2 = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(self._graph2, pool=self._graph.pool(), capture_error_mode=mode), ops.grad_arena(arena):
-            self._backbone_pass(pairs)
-            self._pack(1, self._back_params, [p.grad for p in self._back_params])
-        self._hold_captured()
-        del pairs
-        self.buckets.wait_all(divide=False)  # (nothing in flight: points .grad at the flat slices the update graph will read)
-        if self._graph3 is None:
-            self._graph3 = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(self._graph3, pool=self._graph.pool(), capture_error_mode=mode):
-                self.opt.step(None)
-            if self.ema is not None:
-                self.opt.count_updates(-1)  # captured, not executed
-        self.opt.zero_grad(set_to_none=True)
-
-    def _forward_backward(self, batch):
+    # ---- forward, backward, update ------------------------------------------------------------------------------------------------------
+    def _forward(self, batch):
+        """-> (loss, loss items); behind it self._seed is the backward's seed.  The backward of loss.sum() * world (reference
+        trainer.py:386-388, 394) is seeded directly with d(total)/d(loss) = world: the sum, the multiplication and their backward nodes
+        would be five one-element launches."""
         self.model.train()
         with torch.autocast("cuda", dtype=self.dtype, enabled=self.dtype != torch.float32):
             loss, items = self.model(batch)
-        # this step owns its gradients: zero_grad(set_to_none=True) after every update, so AccumulateGrad adopts the tensors
-        # the weight-gradient Functions return and nothing reads them before backward() is over - the condition under which
-        # their slab sums may be batched into one launch at the end of the pass (ops.deferred_wgrad; parameters that do hold a
-        # gradient or a hook - the overlapped DDP schedule - are detected there and reduced at once)
-        # backward of loss.sum() * world (reference trainer.py:386-388, 394) seeded directly with d(total)/d(loss) = world: the
-        # sum, the multiplication and their backward nodes would be five one-element launches
         if self._seed is None or self._seed.device != loss.device:
             self._seed = torch.full((3,), float(self.world), dtype=torch.float32, device=loss.device)
-        # (captured steps run on one stream: there the BatchNorm-backward final passes ride in the weight-gradient launches, ops.wgrad_riders)
-        with ops.deferred_wgrad(True), ops.async_wgrad(ASYNC_WGRAD and not self.use_graph), ops.wgrad_riders(self.use_graph):  # joins the side stream on exit
+        return loss, items
+
+    @contextlib.contextmanager
+    def _wgrad_schedule(self):
+        """around every backward pass of the step.  This step owns its gradients: zero_grad(set_to_none=True) after every update, so
+        AccumulateGrad adopts the tensors the weight-gradient Functions return and nothing reads them before the pass is over - the
+        condition under which their slab sums may be batched into one launch at the end of the pass (ops.deferred_wgrad; parameters that
+        do hold a gradient or a hook - the overlapped DDP schedule - are detected there and reduced at once).  Eager steps put the
+        weight-gradient GEMMs on a side stream, joined on exit (ops.async_wgrad); captured steps run on one stream, and there the
+        BatchNorm-backward final passes ride in the weight-gradient launches (ops.wgrad_riders)."""
+        with ops.deferred_wgrad(True), ops.async_wgrad(ASYNC_WGRAD and not self.use_graph), ops.wgrad_riders(self.use_graph):
+            yield
+
+    def _forward_backward(self, batch):
+        loss, items = self._forward(batch)
+        with self._wgrad_schedule():
             torch.autograd.backward([loss], [self._seed])
         return items
 
@@ -589,6 +566,12 @@ class TrainStep:
         if ev:
             ev[1].record()
         self.opt.step(grads_of if self.world == 1 else None)
+
+    def eager_step(self, batch):
+        items = self._forward_backward(batch)
+        self._reduce_and_update()
+        self.opt.zero_grad(set_to_none=True)
+        return items
 
     # ---- exposed-communication probe (bench.py's several-rank line) ---------------------------------------------------------------
     def time_exposed_communication(self, on=True):
@@ -607,12 +590,6 @@ class TrainStep:
         """mean milliseconds per step between the two events (call after a synchronize); None when nothing was timed"""
         ev = self._comm_events or []
         return sum(a.elapsed_time(b) for a, b in ev) / len(ev) if ev else None
-
-    def eager_step(self, batch):
-        items = self._forward_backward(batch)
-        self._reduce_and_update()
-        self.opt.zero_grad(set_to_none=True)
-        return items
 
 
 ScheduleAt = collections.namedtuple("ScheduleAt", "ni accumulate lrs momentum update")

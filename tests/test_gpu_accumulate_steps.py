@@ -97,7 +97,7 @@ def run_pattern(mode, pattern, warm_at=None):
                                     updates=step.ema.updates, steps=step.opt.steps_taken()))
     torch.cuda.synchronize()
     out.update(w0=model.model[0].conv.weight.detach().clone(), bn=head_bn_weight.detach().clone(), steps=step.opt.steps_taken(), updates=step.ema.updates,
-               pending=step.opt.pending + step._flat_pending, full_graph=step._graph is not None)
+               pending=step.opt.pending + step._flat_pending, full_graph=any(rec.graph is not None for rec in step._shapes.values()))
     _RUNS[key] = out
     return out
 
@@ -218,7 +218,7 @@ def test_train_epoch_follows_the_warmup_schedule(nbs, graph):
         assert [u for u, _ in seen] == [r.update for r in want[epoch * 6: epoch * 6 + 6]]
         assert torch.allclose(tloss, torch.stack([x for _, x in seen]).mean(0), rtol=1e-5, atol=0)
     assert step.ema.updates == n_updates + warmup_steps == step.opt.steps_taken() and step.opt.pending == trailing
-    assert (step._micro is not None) == (step._update_graph is not None) == (step._graph is not None) == graph
+    assert (step._micro is not None) == (step._update_graph is not None) == any(rec.graph is not None for rec in step._shapes.values()) == graph
     last = want[-1]
     assert [g["lr"] for g in step.opt.param_groups] == last.lrs and all(g["momentum"] == last.momentum for g in step.opt.param_groups)
     assert step.opt.param_groups[1]["weight_decay"] == sched.weight_decay and step.opt.param_groups[0]["weight_decay"] == 0.0

@@ -303,10 +303,12 @@ def _ddp_worker(rank, world, port, graph, q):
     ddp.broadcast_parameters(model)
     step = TrainStep(model, world_size=world, graph=graph)
     batch = synthetic_batch(2, 320, d, ddp.shard_seed(1, rank))
-    items = [step(batch).float().cpu() for _ in range(5)]
+    items = [step(batch).float().cpu() for _ in range(3)]
+    step.time_exposed_communication(True)  # the last two steps bracket their wait for the exchange with events
+    items += [step(batch).float().cpu() for _ in range(2)]
     torch.cuda.synchronize()
     flat = torch.cat([p.detach().float().reshape(-1).cpu() for p in model.parameters()])
-    q.put((rank, torch.stack(items).numpy(), flat.numpy()))
+    q.put((rank, torch.stack(items).numpy(), flat.numpy(), step.exposed_communication_ms()))
     dist.barrier()
     dist.destroy_process_group()
 
@@ -314,7 +316,7 @@ def _ddp_worker(rank, world, port, graph, q):
 @pytest.mark.parametrize("graph", [False, True, "tail"], ids=["eager_overlapped", "three_graphs_overlapped", "graph_plus_eager_tail"])
 def test_two_rank_training_keeps_replicas_identical(graph):
     """2 ranks (gloo over CUDA tensors, one GPU): after 5 steps on different shards the replicas hold identical
-    parameters (gradient mean applied on both) and the losses differ per shard."""
+    parameters (gradient mean applied on both) and the losses differ per shard; every schedule times its exposed communication."""
     import socket
 
     import numpy as np
@@ -335,6 +337,8 @@ def test_two_rank_training_keeps_replicas_identical(graph):
     assert np.isfinite(res[0][1]).all() and np.isfinite(res[1][1]).all()
     assert not np.allclose(res[0][1], res[1][1])  # different shards
     np.testing.assert_allclose(res[0][2], res[1][2], rtol=0, atol=0)
+    for r in res:
+        assert r[3] is not None and r[3] >= 0.0, r[3]
 
 
 def _rccl_worker(port, q):
