@@ -277,25 +277,136 @@ __device__ __forceinline__ bool ticket_is_last(unsigned* counter, unsigned last,
     __syncthreads();
     return *flag != 0;
 }
-// ---- a BatchNorm-backward final pass riding in a weight-gradient launch (round 5; wgrad.hip, reduce_bwd.hip) --------------------------
+// ---- the final pass of a BatchNorm backward: ONE body for its own launch and for the rider (reduce_bwd.hip, wgrad.hip) --------------------
+// gamma / beta of the channels >= split come from a second pair of arrays (two BatchNorms behind one convolution: Detect's sibling
+// branches run as one, head.py:71-72); split == 0: one pair
+struct GammaBeta2 {
+    const float* gamma;
+    const float* beta;
+    int split;
+};
+// coefficients of the BN backward apply pass, from the finished sums (one set per channel):
+//   z = x*a0 + a1 ;  draw = dy*act'(z)*c0 - x*c1 - c2
+struct BnCoefArgs {
+    const float* gamma;
+    const float* beta;
+    const float* mean;
+    const float* inv;
+    float inv_count;
+    float* coef;  // [5][C] or nullptr
+    GammaBeta2 g2;
+};
+// a final pass: sum `blocks` partial rows [block][2][C] per channel into out0 (dbeta) / out1 (dgamma), either may be null, and derive bn.coef
+struct BnFinal {
+    const float* part;
+    int blocks, C;
+    float* out0;
+    float* out1;
+    BnCoefArgs bn;
+};
+// the one statement of "channel >= split takes the second pair, a null pointer means 1 / 0"
+__device__ __forceinline__ void bn_affine_of(const float* gamma, const float* beta, const GammaBeta2& g2, int c, float& ga, float& be) {
+    const bool second = g2.split > 0 && c >= g2.split;
+    const float* gp = second ? g2.gamma : gamma;
+    const float* bp = second ? g2.beta : beta;
+    const int pc = second ? c - g2.split : c;
+    ga = gp ? gp[pc] : 1.0f;
+    be = bp ? bp[pc] : 0.0f;
+}
+// the per-channel parameters the coefficients need (fetched apart from the formulas: the final pass fetches them beside its partial rows)
+struct BnChan {
+    float ga, be, inv, mean;
+};
+__device__ __forceinline__ void bn_chan_fetch(const BnCoefArgs& bn, int c, BnChan& p) {
+    bn_affine_of(bn.gamma, bn.beta, bn.g2, c, p.ga, p.be);
+    p.inv = bn.inv[c];
+    p.mean = bn.mean[c];
+}
+// the one statement of the five coefficients
+__device__ __forceinline__ void bn_coef_write(const BnCoefArgs& bn, int C, int c, const BnChan& p, float s0, float s1) {
+    const float ga = p.ga, be = p.be;
+    const float p0 = p.inv, p1 = -p.mean * p0;
+    const float k1 = s0 * bn.inv_count, k2 = s1 * bn.inv_count;
+    bn.coef[0 * C + c] = p0 * ga;
+    bn.coef[1 * C + c] = p1 * ga + be;
+    bn.coef[2 * C + c] = ga * p0;
+    bn.coef[3 * C + c] = ga * p0 * p0 * k2;
+    bn.coef[4 * C + c] = ga * p0 * (k1 + p1 * k2);
+}
+// Workgroup w of NT threads (1024: chan_reduce_final_kernel; 256: a weight-gradient launch's rider workgroups) owns channels [32 w, 32 w + 32).
+// The partial rows go to 32 row slices (slice s: rows s, s + 32, ...); a thread plays 1024 / NT of them for its channel.  Per slice: four
+// float chains per output at rows b, b + 32, b + 64, b + 96 stepping 128 (loads in flight), the tail steps 32 into the first chain, combined
+// as ((a + b) + (c + d)) in double; the slice-0 threads sum the 32 slices in slice order in double and store floats.  The order is the same
+// for every NT, so a step gives the same gradients whether its final passes ride or not.  red: [2][32][33] doubles of LDS.
+// PREFETCH: the per-channel parameters of the coefficients are fetched before the partial rows, not behind the barrier (the pass is a chain
+// of load latencies: there they were a round trip of their own).  Moves no value.  The rider leaves it off: with it the weight-gradient kernels
+// with the fewest registers lose a wave per SIMD (profiles/bnfinal_refactor_ab.txt).
+constexpr int BN_FINAL_RED = 2 * 32 * 33;  // doubles
+template <int NT, bool PREFETCH = true> __device__ __forceinline__ void bn_final_block(const BnFinal& f, int w, double* red) {
+    static_assert(NT == 1024 || NT == 256, "32 channels x 32 or 8 thread rows");
+    constexpr int SPT = 1024 / NT;  // slices per thread
+    const int cl = threadIdx.x & 31, grp = threadIdx.x >> 5;
+    const int c = w * 32 + cl, C = f.C;
+    BnChan p{1.0f, 0.0f, 0.f, 0.f};
+    if (PREFETCH && grp == 0 && c < C && f.bn.coef) bn_chan_fetch(f.bn, c, p);
+    int es = 0;
+#pragma unroll
+    do {  // (a do loop: as a for loop the one-slice form came out of the compiler with two more VGPRs than the loop-free kernel it replaces)
+        const int slice = grp * SPT + es;
+        double s0 = 0.0, s1 = 0.0;
+        if (c < C) {
+            float a0 = 0.f, a1 = 0.f, b0 = 0.f, b1 = 0.f, c0 = 0.f, c1 = 0.f, d0 = 0.f, d1 = 0.f;
+            int b = slice;
+            for (; b + 96 < f.blocks; b += 128) {
+                a0 += f.part[((int64_t)b * 2 + 0) * C + c];
+                a1 += f.part[((int64_t)b * 2 + 1) * C + c];
+                b0 += f.part[((int64_t)(b + 32) * 2 + 0) * C + c];
+                b1 += f.part[((int64_t)(b + 32) * 2 + 1) * C + c];
+                c0 += f.part[((int64_t)(b + 64) * 2 + 0) * C + c];
+                c1 += f.part[((int64_t)(b + 64) * 2 + 1) * C + c];
+                d0 += f.part[((int64_t)(b + 96) * 2 + 0) * C + c];
+                d1 += f.part[((int64_t)(b + 96) * 2 + 1) * C + c];
+            }
+            for (; b < f.blocks; b += 32) {
+                a0 += f.part[((int64_t)b * 2 + 0) * C + c];
+                a1 += f.part[((int64_t)b * 2 + 1) * C + c];
+            }
+            s0 = ((double)a0 + (double)b0) + ((double)c0 + (double)d0);
+            s1 = ((double)a1 + (double)b1) + ((double)c1 + (double)d1);
+        }
+        red[(0 * 32 + slice) * 33 + cl] = s0;
+        red[(1 * 32 + slice) * 33 + cl] = s1;
+    } while (++es < SPT);
+    __syncthreads();
+    if (grp == 0 && c < C) {
+        double a0 = 0.0, a1 = 0.0;
+#pragma unroll
+        for (int q = 0; q < 32; ++q) {
+            a0 += red[(0 * 32 + q) * 33 + cl];
+            a1 += red[(1 * 32 + q) * 33 + cl];
+        }
+        if (f.out0) f.out0[c] = (float)a0;
+        if (f.out1) f.out1[c] = (float)a1;
+        if (f.bn.coef) {
+            if (!PREFETCH) bn_chan_fetch(f.bn, c, p);
+            bn_coef_write(f.bn, C, c, p, (float)a0, (float)a1);
+        }
+    }
+}
+// ---- ... riding in a weight-gradient launch (round 5; wgrad.hip, reduce_bwd.hip) -------------------------------------------------------------
 // The final pass of a BatchNorm backward (sum <= 512 partial rows per channel, derive the apply pass's coefficients) is a 1-16 workgroup
 // kernel at a dependent-launch latency (~5.4 us, 57 times a step), and it cannot move into its producer or its consumer (a hand-off level
 // costs ~2.5 us, profiles/r05_bn_tail_ab.txt).  But the weight-gradient GEMM of the PREVIOUS layer of the backward pass is independent of it
 // and sits right beside it in the stream: with ymi_wgrad_hold(1) a deferred weight-gradient launch is held back until the next BatchNorm
-// backward has issued its reduce pass and then launched with that layer's final pass as extra workgroups at the front of its grid.
-struct YmiBnRider {
-    const float* part;  // [blocks][2][C] partial rows of the reduce pass
-    int blocks, C;
-    int nwg;            // rider workgroups at the front of the grid (a multiple of 8: the XCD dealing of the rest is unchanged); 0: none
-    float* out0;        // dbeta
-    float* out1;        // dgamma
-    const float* gamma; const float* beta; const float* mean; const float* inv;
-    const float* gamma2; const float* beta2; int split;  // second parameter set of a convolution pair (channels >= split); split == 0: one
-    float inv_count;
-    float* coef;        // [5][C]
+// backward has issued its reduce pass and then launched with that layer's final pass - bn_final_block, the same function its own launch
+// calls - as extra workgroups at the front of its grid.
+struct BnRider {
+    BnFinal f;
+    int nwg;  // rider workgroups at the front of the grid (a multiple of 8: the XCD dealing of the rest is unchanged); 0: none
 };
-// issue the held weight-gradient launch of `stream` with `rider` in it -> true; false when nothing is held there (the caller launches its final pass itself)
-bool ymi_wgrad_issue_held(const YmiBnRider* rider, hipStream_t stream);
+// issue the weight-gradient launch held on `stream` (and the current device) with final pass `f` riding in it -> true; false when nothing is
+// held there (the caller launches its final pass itself)
+bool ymi_wgrad_issue_held(const BnFinal* f, hipStream_t stream);
 
 // ---- entry points one source file offers another (host) ---------------------------------------------------------------------------
 // profile.hip: per-launch roofline records of the GEMM families (igemm.hip, wgrad.hip)
@@ -307,6 +418,12 @@ struct IgemmArgs;
 int ymi_launch_igemm(const IgemmArgs& a, int dtype, bool stats, int* host_blocks, hipStream_t stream);
 int ymi_conv2d_fwd_statacc(const ymi_tensor* x, const void* w_packed, int64_t cout, int64_t kh, int64_t kw, int64_t stride, const ymi_tensor* y,
                            long long* stat_acc, void* stream);
+
+// reduce_bwd.hip: the final pass as its own launch - column sums (out0 / out1, either may be null) and a BatchNorm backward's whose first
+// stage ran elsewhere (first_conv.hip)
+int ymi_chan_reduce_final(const float* part, int blocks, int C, float* out0, float* out1, hipStream_t stream);
+int ymi_bn_bwd_final(const float* part, int blocks, int C, const float* gamma, const float* beta, const float* mean, const float* inv, float inv_count,
+                     float* dgamma, float* dbeta, float* coef, hipStream_t stream);
 
 // a slot of 64 ticket counters for one launch (host; round-robin over 1024 slots, zero between launches)
 unsigned* ymi_ticket_slot();

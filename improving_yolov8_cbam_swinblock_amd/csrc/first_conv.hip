@@ -24,9 +24,6 @@
 // float32 its 420 MB cost K3 more than K4 gained, 167 + 191 against 100 + 190 us.)
 #include "common.h"
 
-int ymi_bn_bwd_final(const float* part, int blocks, int C, const float* gamma, const float* beta, const float* mean, const float* inv, float inv_count,
-                     float* dgamma, float* dbeta, float* coef, hipStream_t stream);
-
 namespace {
 
 constexpr int FC_TH = 8, FC_TW = 64;                   // output tile: two rows per wave

@@ -15,38 +15,7 @@ struct RV {
 // FN: 0 colsum(a)            -> s0 = sum a
 //     1 bn-act backward      -> dz = a * act'(z), z = (b-mean)*inv*gamma+beta ; s0 = sum dz, s1 = sum dz*xhat
 //     2 layernorm param grads-> s0 = sum a (dbeta), s1 = sum a * (b - mean_row)*rstd_row (dgamma); mean/rstd per ROW
-// gamma / beta of the channels >= split come from a second pair of arrays (two BatchNorms behind one convolution: Detect's sibling
-// branches run as one, head.py:71-72); split == 0: one pair
-struct GammaBeta2 {
-    const float* gamma;
-    const float* beta;
-    int split;
-};
-// coefficients of the BN backward apply pass, from the finished sums (one set per channel):
-//   z = x*a0 + a1 ;  draw = dy*act'(z)*c0 - x*c1 - c2
-struct BnCoefArgs {
-    const float* gamma;
-    const float* beta;
-    const float* mean;
-    const float* inv;
-    float inv_count;
-    float* coef;  // [5][C] or nullptr
-    GammaBeta2 g2;
-};
-__device__ __forceinline__ void bn_coef_write(const BnCoefArgs& bn, int C, int c, float s0, float s1) {
-    const bool second = bn.g2.split > 0 && c >= bn.g2.split;
-    const float* gp = second ? bn.g2.gamma : bn.gamma;
-    const float* bp = second ? bn.g2.beta : bn.beta;
-    const int pc = second ? c - bn.g2.split : c;
-    const float ga = gp ? gp[pc] : 1.0f, be = bp ? bp[pc] : 0.0f;
-    const float p0 = bn.inv[c], p1 = -bn.mean[c] * p0;
-    const float k1 = s0 * bn.inv_count, k2 = s1 * bn.inv_count;
-    bn.coef[0 * C + c] = p0 * ga;
-    bn.coef[1 * C + c] = p1 * ga + be;
-    bn.coef[2 * C + c] = ga * p0;
-    bn.coef[3 * C + c] = ga * p0 * p0 * k2;
-    bn.coef[4 * C + c] = ga * p0 * (k1 + p1 * k2);
-}
+// gamma / beta of the channels >= split come from a second pair of arrays (common.h: GammaBeta2, bn_affine_of)
 // Tail of stage 1 (round 5): the workgroup that finishes LAST does stage 2 itself, so the separate final launch (a 1-16 workgroup kernel
 // at a dependent-launch latency, ~57 times a step) disappears.  Two levels, both deterministic (fixed rows in fixed order, whoever runs
 // them): the last workgroup of each of the 8 id classes (blockIdx.x & 7) sums that class's rows into xrows[class]; the last of those 8
@@ -85,12 +54,9 @@ __global__ void chan_reduce_kernel(RV a, RV b, int64_t P, int64_t span, int C, i
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int c = c0 + tx * 4 + r;
-            const bool second = g2.split > 0 && c >= g2.split;
-            const float* gp = second ? g2.gamma : gamma;
-            const float* bp = second ? g2.beta : beta;
-            const int pc = second ? c - g2.split : c;
-            g[r] = (FN == 1 && gp) ? gp[pc] : 1.0f;
-            be[r] = (FN == 1 && bp) ? bp[pc] : 0.0f;
+            g[r] = 1.0f;
+            be[r] = 0.0f;
+            if (FN == 1) bn_affine_of(gamma, beta, g2, c, g[r], be[r]);
             mu[r] = (FN == 1) ? mean[c] : 0.0f;
             iv[r] = (FN == 1) ? inv[c] : 1.0f;
         }
@@ -238,7 +204,11 @@ __global__ void chan_reduce_kernel(RV a, RV b, int64_t P, int64_t span, int C, i
         }
         if (tail.out0) tail.out0[c] = (float)sa;
         if (tail.out1) tail.out1[c] = (float)sb;
-        if (tail.bn.coef) bn_coef_write(tail.bn, C, c, (float)sa, (float)sb);
+        if (tail.bn.coef) {
+            BnChan p;
+            bn_chan_fetch(tail.bn, c, p);
+            bn_coef_write(tail.bn, C, c, p, (float)sa, (float)sb);
+        }
     }
 }
 
@@ -247,68 +217,16 @@ __global__ void chan_reduce_kernel(RV a, RV b, int64_t P, int64_t span, int C, i
 // with ticket counters behind __threadfence(), does stage 2 - parity-green and 12.85 -> 19.3 ms/step: a device-scope fence is an L2
 // write-back + invalidate on this 8-XCD part and every one of up to 1024 workgroups pays it (17.6 -> 148 us per reduce launch);
 // profiles/r04_bn_tail_ticket_ab.txt, code in git.)
-// 32 channels x 32 row slices per block, 4 independent accumulator pairs per thread (loads in flight)
-__global__ __launch_bounds__(1024) void chan_reduce_final_kernel(const float* __restrict__ part, int blocks, int C, float* __restrict__ out0, float* __restrict__ out1,
-                                                                 BnCoefArgs bn) {
-    __shared__ double red[2][32][33];
-    const int cl = threadIdx.x & 31, slice = threadIdx.x >> 5;
-    const int c = blockIdx.x * 32 + cl;
-    double s0 = 0.0, s1 = 0.0;
-    // the per-channel parameters of the coefficient pass are fetched FIRST, beside the partials (this kernel is a chain of load
-    // latencies: behind the barrier they were a round trip of their own)
-    float ga = 1.0f, be = 0.0f, p_inv = 0.f, p_mean = 0.f;
-    if (slice == 0 && c < C && bn.coef) {
-        const bool second = bn.g2.split > 0 && c >= bn.g2.split;
-        const float* gp = second ? bn.g2.gamma : bn.gamma;
-        const float* bp = second ? bn.g2.beta : bn.beta;
-        const int pc = second ? c - bn.g2.split : c;
-        ga = gp ? gp[pc] : 1.0f;
-        be = bp ? bp[pc] : 0.0f;
-        p_inv = bn.inv[c];
-        p_mean = bn.mean[c];
-    }
-    if (c < C) {
-        float a0 = 0.f, a1 = 0.f, b0 = 0.f, b1 = 0.f, c0 = 0.f, c1 = 0.f, d0 = 0.f, d1 = 0.f;
-        int b = slice;
-        for (; b + 96 < blocks; b += 128) {
-            a0 += part[((int64_t)b * 2 + 0) * C + c];
-            a1 += part[((int64_t)b * 2 + 1) * C + c];
-            b0 += part[((int64_t)(b + 32) * 2 + 0) * C + c];
-            b1 += part[((int64_t)(b + 32) * 2 + 1) * C + c];
-            c0 += part[((int64_t)(b + 64) * 2 + 0) * C + c];
-            c1 += part[((int64_t)(b + 64) * 2 + 1) * C + c];
-            d0 += part[((int64_t)(b + 96) * 2 + 0) * C + c];
-            d1 += part[((int64_t)(b + 96) * 2 + 1) * C + c];
-        }
-        for (; b < blocks; b += 32) {
-            a0 += part[((int64_t)b * 2 + 0) * C + c];
-            a1 += part[((int64_t)b * 2 + 1) * C + c];
-        }
-        s0 = ((double)a0 + (double)b0) + ((double)c0 + (double)d0);
-        s1 = ((double)a1 + (double)b1) + ((double)c1 + (double)d1);
-    }
-    red[0][slice][cl] = s0;
-    red[1][slice][cl] = s1;
-    __syncthreads();
-    if (slice == 0 && c < C) {
-        double a = 0.0, b2 = 0.0;
-#pragma unroll
-        for (int q = 0; q < 32; ++q) {
-            a += red[0][q][cl];
-            b2 += red[1][q][cl];
-        }
-        if (out0) out0[c] = (float)a;
-        if (out1) out1[c] = (float)b2;
-        if (bn.coef) {
-            const float p0 = p_inv, p1 = -p_mean * p0;
-            const float k1 = (float)a * bn.inv_count, k2 = (float)b2 * bn.inv_count;
-            bn.coef[0 * C + c] = p0 * ga;
-            bn.coef[1 * C + c] = p1 * ga + be;
-            bn.coef[2 * C + c] = ga * p0;
-            bn.coef[3 * C + c] = ga * p0 * p0 * k2;
-            bn.coef[4 * C + c] = ga * p0 * (k1 + p1 * k2);
-        }
-    }
+// The pass itself is common.h's bn_final_block - 32 channels x 32 row slices per workgroup, a slice per thread here - which a weight-gradient
+// launch's rider workgroups call as well (wgrad.hip).
+__global__ __launch_bounds__(1024) void chan_reduce_final_kernel(BnFinal f) {
+    __shared__ double red[BN_FINAL_RED];
+    bn_final_block<1024>(f, (int)blockIdx.x, red);
+}
+static int launch_final(const BnFinal& f, hipStream_t stream, const char* what) {
+    hipLaunchKernelGGL(chan_reduce_final_kernel, dim3((f.C + 31) / 32), dim3(1024), 0, stream, f);
+    YMI_CHECK_LAUNCH(what);
+    return YMI_OK;
 }
 
 // option bn_tail = 0: the final pass as its own launch (the "before" of profiles/r05_bn_tail_ab.txt)
@@ -368,19 +286,15 @@ static int launch_chan_reduce(const ymi_tensor* a, const ymi_tensor* b, const fl
 }
 
 int ymi_chan_reduce_final(const float* part, int blocks, int C, float* out0, float* out1, hipStream_t stream) {
-    hipLaunchKernelGGL(chan_reduce_final_kernel, dim3((C + 31) / 32), dim3(1024), 0, stream, part, blocks, C, out0, out1, BnCoefArgs{});  // (value-initialised: no coefficients)
-    YMI_CHECK_LAUNCH("chan_reduce_final");
-    return YMI_OK;
+    return launch_final(BnFinal{part, blocks, C, out0, out1, BnCoefArgs{}}, stream, "chan_reduce_final");  // (value-initialised: no coefficients)
 }
 
 // final pass of a BatchNorm + activation backward whose first stage ran elsewhere (csrc/first_conv.hip): sums `blocks` partial rows
 // [block][2][C] (dz, dz * xhat) into dbeta / dgamma and writes the apply pass's coefficients [a0 | a1 | c0 | c1 | c2][C]
 int ymi_bn_bwd_final(const float* part, int blocks, int C, const float* gamma, const float* beta, const float* mean, const float* inv, float inv_count,
                      float* dgamma, float* dbeta, float* coef, hipStream_t stream) {
-    hipLaunchKernelGGL(chan_reduce_final_kernel, dim3((C + 31) / 32), dim3(1024), 0, stream, part, blocks, C, dbeta, dgamma,
-                       BnCoefArgs{gamma, beta, mean, inv, inv_count, coef, GammaBeta2{nullptr, nullptr, 0}});
-    YMI_CHECK_LAUNCH("bn_bwd_final");
-    return YMI_OK;
+    return launch_final(BnFinal{part, blocks, C, dbeta, dgamma, BnCoefArgs{gamma, beta, mean, inv, inv_count, coef, GammaBeta2{nullptr, nullptr, 0}}}, stream,
+                        "bn_bwd_final");
 }
 
 extern "C" int ymi_colsum(const ymi_tensor* x, float* out, void* workspace, size_t workspace_bytes, void* stream) {
@@ -597,11 +511,11 @@ static int bn_act_bwd_impl(const ymi_tensor* dout, const ymi_tensor* raw, const 
     int blocks = 0;
     float* coef = (float*)workspace + (size_t)rblocks * 2 * C;
     double* xrows = reinterpret_cast<double*>(coef + 6 * (size_t)C);  // (8-byte aligned: the workspace is, and every term is a multiple of 8 bytes)
+    const BnCoefArgs bn{gamma, beta, save_mean, save_invstd, 1.0f / (float)P, coef, g2};
     if (bn_tail_on() && C <= 1024) {
         // dbeta = sum dz, dgamma = sum dz*xhat and the apply pass's coefficients from the reduce kernel's last workgroups
         unsigned* tickets = ymi_ticket_slot();
         YMI_CHECK_ARG(tickets, "bn_act_bwd: ticket counters");
-        const BnCoefArgs bn{gamma, beta, save_mean, save_invstd, 1.0f / (float)P, coef, g2};
         int rc = launch_chan_reduce<1>(dout, raw, gamma, beta, save_mean, save_invstd, act, (float*)workspace, &blocks, s, "bn_act_bwd(reduce)", g2,
                                        ReduceTail{tickets, rblocks % 32 == 0 ? 32 : 8, xrows, dbeta, dgamma, bn});
         if (rc) return rc;
@@ -609,17 +523,11 @@ static int bn_act_bwd_impl(const ymi_tensor* dout, const ymi_tensor* raw, const 
     }
     int rc = launch_chan_reduce<1>(dout, raw, gamma, beta, save_mean, save_invstd, act, (float*)workspace, &blocks, s, "bn_act_bwd(reduce)", g2);
     if (rc) return rc;
-    {   // the final pass rides in the weight-gradient launch held back for it, when there is one (common.h: YmiBnRider)
-        const YmiBnRider rider{(const float*)workspace, blocks, C, 0, dbeta, dgamma, gamma, beta, save_mean, save_invstd, g2.gamma, g2.beta, g2.split, 1.0f / (float)P, coef};
-        if (C <= 1024 && ymi_wgrad_issue_held(&rider, s)) {
-            YMI_CHECK_LAUNCH("bn_act_bwd(final, riding)");
-            return launch_bn_apply(dout, raw, draw, act, coef, s);
-        }
-    }
-    // dbeta = sum dz, dgamma = sum dz*xhat, and the apply pass's coefficients
-    hipLaunchKernelGGL(chan_reduce_final_kernel, dim3((C + 31) / 32), dim3(1024), 0, s, (const float*)workspace, blocks, C, dbeta, dgamma,
-                       BnCoefArgs{gamma, beta, save_mean, save_invstd, 1.0f / (float)P, coef, g2});
-    YMI_CHECK_LAUNCH("bn_act_bwd(final)");
+    // dbeta = sum dz, dgamma = sum dz*xhat, and the apply pass's coefficients: the final pass rides in the weight-gradient launch held back for it,
+    // when there is one (common.h: BnRider), or is its own launch - the same function either way
+    const BnFinal f{(const float*)workspace, blocks, C, dbeta, dgamma, bn};
+    if (C <= 1024 && ymi_wgrad_issue_held(&f, s)) YMI_CHECK_LAUNCH("bn_act_bwd(final, riding)");
+    else if ((rc = launch_final(f, s, "bn_act_bwd(final)")) != YMI_OK) return rc;
     return launch_bn_apply(dout, raw, draw, act, coef, s);
 }
 

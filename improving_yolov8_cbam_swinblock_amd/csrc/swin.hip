@@ -20,8 +20,6 @@
 
 #include "common.h"
 
-int ymi_chan_reduce_final(const float* part, int blocks, int C, float* out0, float* out1, hipStream_t stream);
-
 struct SV {
     const void* p;
     int64_t ld;

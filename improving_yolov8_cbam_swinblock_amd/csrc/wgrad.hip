@@ -18,8 +18,6 @@
 
 #include "common.h"
 
-int ymi_chan_reduce_final(const float* part, int blocks, int C, float* out0, float* out1, hipStream_t stream);
-
 struct WgradArgs {
     const void* x;
     const void* dy;
@@ -49,6 +47,9 @@ constexpr int WG_BN = 128;   // cols  ((tap, ci))
 constexpr int WG_BK = 32;    // pixels per K step (64 was measured 10-15 % slower: half as many resident workgroups per CU)
 constexpr int WG_NS = 2;     // LDS ring stages of the bf16 kernels (three and four: +9 %, profiles/r05_wgrad_patch_walk_ab.txt)
 constexpr int WG_WAVES = 5;  // waves per SIMD the 64-row tile's register allocation must allow (4 and 6: no better, profiles/r04_wgrad_targets_sweep.txt)
+
+// the LDS ring of a launch: WG_NS stages of a [WG_BK][BM] dY image and a [WG_BK][WG_BN] X image (the kernel asserts what else must fit in it)
+template <typename T, int BM> constexpr size_t wgrad_lds_bytes() { return (size_t)WG_NS * WG_BK * (BM + WG_BN) * sizeof(T); }
 
 // `buffer_load_dwordx4 ... lds`: 16 bytes per lane from base + voff + soff into LDS (lane-linear behind `dst`), zeros for lanes whose offset is
 // outside [0, bytes).  The resource is rebuilt from (base, bytes) at every call - four scalar moves - because a local of the resource type in a
@@ -172,70 +173,8 @@ template <> struct WFrag<float> {
 // (a 128x256 tile - 4 or 8 waves - measured 1.17-1.66x slower, profiles/r02_conv_bench_wgrad256.txt; removed in round 3)
 // BIAS: the instantiation that also forms the bias gradient's partials (its own code object: the 4 * TR accumulator registers and the branch
 // cost the bias-free launches 3-4 % when they were a run-time option of one kernel)
-// the final pass of a BatchNorm backward as a rider (common.h: YmiBnRider): workgroup w sums the partial rows of channels [32 w, 32 w + 32) - 8 row
-// slices x 32 channels per workgroup, eight loads in flight per lane, combined in double in a fixed order - and writes dbeta / dgamma and the apply
-// pass's coefficients (reduce_bwd.hip: chan_reduce_final_kernel is the same pass as its own launch)
-__device__ __forceinline__ void wgrad_rider_final(const YmiBnRider& r, int w, char* smem) {
-    // BIT FOR BIT chan_reduce_final_kernel's arithmetic (reduce_bwd.hip: 32 row slices per channel, four float chains each, combined in double in
-    // slice order), so a step gives the same gradients with the final passes riding or not: a thread plays four of the 32 slices
-    double* red = reinterpret_cast<double*>(smem);  // [2][32][33]
-    const int cl = threadIdx.x & 31, grp = threadIdx.x >> 5;
-    const int c = w * 32 + cl;
-    if (w * 32 >= r.C) return;  // (padding workgroups of the rider block: uniform)
-#pragma unroll
-    for (int es = 0; es < 4; ++es) {
-        const int slice = grp * 4 + es;
-        double s0 = 0.0, s1 = 0.0;
-        if (c < r.C) {
-            float a0 = 0.f, a1 = 0.f, b0 = 0.f, b1 = 0.f, c0 = 0.f, c1 = 0.f, d0 = 0.f, d1 = 0.f;
-            int b = slice;
-            for (; b + 96 < r.blocks; b += 128) {
-                a0 += r.part[((int64_t)b * 2 + 0) * r.C + c];
-                a1 += r.part[((int64_t)b * 2 + 1) * r.C + c];
-                b0 += r.part[((int64_t)(b + 32) * 2 + 0) * r.C + c];
-                b1 += r.part[((int64_t)(b + 32) * 2 + 1) * r.C + c];
-                c0 += r.part[((int64_t)(b + 64) * 2 + 0) * r.C + c];
-                c1 += r.part[((int64_t)(b + 64) * 2 + 1) * r.C + c];
-                d0 += r.part[((int64_t)(b + 96) * 2 + 0) * r.C + c];
-                d1 += r.part[((int64_t)(b + 96) * 2 + 1) * r.C + c];
-            }
-            for (; b < r.blocks; b += 32) {
-                a0 += r.part[((int64_t)b * 2 + 0) * r.C + c];
-                a1 += r.part[((int64_t)b * 2 + 1) * r.C + c];
-            }
-            s0 = ((double)a0 + (double)b0) + ((double)c0 + (double)d0);
-            s1 = ((double)a1 + (double)b1) + ((double)c1 + (double)d1);
-        }
-        red[(0 * 32 + slice) * 33 + cl] = s0;
-        red[(1 * 32 + slice) * 33 + cl] = s1;
-    }
-    __syncthreads();
-    if (grp == 0 && c < r.C) {
-        double a0 = 0.0, a1 = 0.0;
-#pragma unroll
-        for (int q = 0; q < 32; ++q) {
-            a0 += red[(0 * 32 + q) * 33 + cl];
-            a1 += red[(1 * 32 + q) * 33 + cl];
-        }
-        if (r.out0) r.out0[c] = (float)a0;
-        if (r.out1) r.out1[c] = (float)a1;
-        if (r.coef) {
-            const bool second = r.split > 0 && c >= r.split;
-            const float* gp = second ? r.gamma2 : r.gamma;
-            const float* bp = second ? r.beta2 : r.beta;
-            const int pc = second ? c - r.split : c;
-            const float ga = gp ? gp[pc] : 1.0f, be = bp ? bp[pc] : 0.0f;
-            const float p0 = r.inv[c], p1 = -r.mean[c] * p0;
-            const float k1 = (float)a0 * r.inv_count, k2 = (float)a1 * r.inv_count;
-            r.coef[0 * r.C + c] = p0 * ga;
-            r.coef[1 * r.C + c] = p1 * ga + be;
-            r.coef[2 * r.C + c] = ga * p0;
-            r.coef[3 * r.C + c] = ga * p0 * p0 * k2;
-            r.coef[4 * r.C + c] = ga * p0 * (k1 + p1 * k2);
-        }
-    }
-}
-
+// the final pass of a BatchNorm backward as a rider (common.h: BnRider): the first rider.nwg workgroups of the 1-D grid run bn_final_block, the function
+// chan_reduce_final_kernel runs as its own launch (reduce_bwd.hip), on the ring's LDS - a thread plays four of the 32 row slices - and leave.
 // PATCH (round 5): the K axis runs over the output pixels in PATCH order instead of raster order - step k is a ph x pw patch (ph * pw = 32, pw a power
 // of two dividing Wo, ph dividing Ho) whose origin (n, ho0, wo0) is SCALAR state.  A lane's row of the step is a fixed (pr, pc) inside the patch, so its
 // source offset is a per-thread constant plus a scalar: the pieces become `buffer_load_dwordx4 ... lds` with the constant in the vector offset and the
@@ -244,7 +183,7 @@ __device__ __forceinline__ void wgrad_rider_final(const YmiBnRider& r, int w, ch
 // r05_wgrad_patch_walk_ab.txt) - is five vector instructions per X piece and none per dY piece.  Any fixed order of the pixel sum is as good as raster order;
 // maps that do not tile into such patches (20 x 20) keep the raster walk.
 template <typename T, int NS, int BM, bool BIAS = false, bool PATCH = false>
-__global__ __launch_bounds__(256, (BM == 128 ? 3 : WG_WAVES)) void wgrad_kernel(WgradArgs a, YmiBnRider rider) {
+__global__ __launch_bounds__(256, (BM == 128 ? 3 : WG_WAVES)) void wgrad_kernel(WgradArgs a, BnRider rider) {
     constexpr int BNW = WG_BN, NT = 256;
     constexpr int CH = ElemTraits<T>::CH;
     constexpr int ES = (int)sizeof(T);
@@ -257,6 +196,13 @@ __global__ __launch_bounds__(256, (BM == 128 ? 3 : WG_WAVES)) void wgrad_kernel(
     constexpr int YBYTES = WG_BK * BM * ES, XBYTES = WG_BK * BNW * ES;
     constexpr int STAGE = YBYTES + XBYTES;
     static_assert(NY >= 1 && NX >= 1, "tile too small");
+    constexpr int LDS = (int)wgrad_lds_bytes<T, BM>();  // what the launcher gives
+    static_assert(LDS == NS * STAGE, "the launcher's LDS bytes are the ring");
+    // (the two staging images restate what the slab epilogues below define for themselves - RP and SROW = 144 of the bfloat16-slab epilogue,
+    // SROW = 272 of the float32-slab one: change them there and here together)
+    static_assert(LDS >= (NT / 64) * (BM / WROWS / 16 < 2 ? BM / WROWS / 16 : 2) * 16 * 144, "the bfloat16-slab epilogue stages RP 16-row tiles of 144-byte rows per wave in the ring");
+    static_assert(LDS >= (NT / 64) * 16 * 272, "the float32-slab epilogue stages a 16-row tile of 272-byte rows per wave in the ring");
+    static_assert(LDS >= BN_FINAL_RED * (int)sizeof(double), "a rider workgroup sums its slices in the ring");
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int tid = threadIdx.x, lane = tid & 63;
@@ -269,7 +215,7 @@ __global__ __launch_bounds__(256, (BM == 128 ? 3 : WG_WAVES)) void wgrad_kernel(
     // this XCD a launch ago (round 3 dealt z = 8 i + xcd: every split's rows came from the other seven L2s).
     int bx, by, bz;
     if (rider.nwg && (int)blockIdx.x < rider.nwg) {  // (only in the 1-D XCD-mapped grid; workgroup-uniform)
-        wgrad_rider_final(rider, (int)blockIdx.x, smem);
+        if ((int)blockIdx.x * 32 < rider.f.C) bn_final_block<NT, false>(rider.f, (int)blockIdx.x, reinterpret_cast<double*>(smem));  // (else: a padding workgroup of the rider block)
         return;
     }
     if (a.xcd_map) {
@@ -552,14 +498,6 @@ template <bool BF> __device__ __forceinline__ float slab_at(const void* slab, in
     if constexpr (BF) return (float)reinterpret_cast<const bf16_t*>(slab)[i];
     else return reinterpret_cast<const float*>(slab)[i];
 }
-template <bool BF> __device__ __forceinline__ f32x4 slab4_at(const void* slab, int64_t i) {  // i a multiple of 4
-    if constexpr (BF) {
-        const bf16x4 v = *reinterpret_cast<const bf16x4*>(reinterpret_cast<const bf16_t*>(slab) + i);
-        return f32x4{(float)v[0], (float)v[1], (float)v[2], (float)v[3]};
-    } else {
-        return *reinterpret_cast<const f32x4*>(reinterpret_cast<const float*>(slab) + i);
-    }
-}
 
 // Per-layer slab reduction (ymi_conv2d_bwd_weight, the non-deferred entry point), deterministic: one thread per output element,
 // coalesced along (tap, ci); four independent partial sums keep the split loads in flight, combined in a fixed order.
@@ -731,7 +669,7 @@ extern "C" size_t ymi_conv2d_bwd_weight_workspace(int64_t m_rows, int64_t cout, 
 static int wgrad_impl(const ymi_tensor* x, const ymi_tensor* dy, int64_t cout_real, int64_t cin_real, int64_t kh, int64_t kw, int64_t stride,
                       float* dw_oihw, float* dbias, void* workspace, size_t workspace_bytes, ymi_wgrad_pending* pending, void* stream);
 
-// ---- a launch, possibly held back (common.h: YmiBnRider) -------------------------------------------------------------------------------
+// ---- a launch, possibly held back (common.h: BnRider) ------------------------------------------------------------------------------------
 struct WgradLaunch {
     WgradArgs a;
     dim3 grid;
@@ -740,68 +678,77 @@ struct WgradLaunch {
     hipStream_t s;
     double flop, bytes;
 };
-static void wgrad_launch(const WgradLaunch& h, const YmiBnRider* rider) {
-    YmiBnRider r{};
+// one row tile: the BIAS instantiation where the launch forms the bias partials, the PATCH one where the map tiles into patches (bfloat16 only:
+// parity mode keeps the raster walk, pw_shift is -1 for float32 operands)
+template <typename T, int BM> static void wgrad_launch_tile(const WgradArgs& a, const BnRider& r, dim3 grid, hipStream_t s) {
+    constexpr size_t lds = wgrad_lds_bytes<T, BM>();
+    if constexpr (std::is_same<T, float>::value) {
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_kernel<T, WG_NS, BM, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_kernel<T, WG_NS, BM, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    } else if (a.pw_shift >= 0) {
+        if (a.bias_slab) hipLaunchKernelGGL((wgrad_kernel<T, WG_NS, BM, true, true>), grid, dim3(256), lds, s, a, r);
+        else hipLaunchKernelGGL((wgrad_kernel<T, WG_NS, BM, false, true>), grid, dim3(256), lds, s, a, r);
+        return;
+    }
+    if (a.bias_slab) hipLaunchKernelGGL((wgrad_kernel<T, WG_NS, BM, true>), grid, dim3(256), lds, s, a, r);
+    else hipLaunchKernelGGL((wgrad_kernel<T, WG_NS, BM, false>), grid, dim3(256), lds, s, a, r);
+}
+static void wgrad_launch(const WgradLaunch& h, const BnFinal* rider) {
+    BnRider r{};
     dim3 grid = h.grid;
     if (rider && h.a.xcd_map) {  // rider workgroups at the front of the 1-D grid
-        r = *rider;
+        r.f = *rider;
         r.nwg = ((rider->C + 31) / 32 + 7) / 8 * 8;
         grid.x += (unsigned)r.nwg;
     }
-    const WgradArgs& a = h.a;
-    hipStream_t s = h.s;
     int prof = -1;
-    if (ymi_prof_enabled()) prof = ymi_prof_start(s, 1, h.flop, h.bytes, h.bf16 ? 2500.0 : 157.3);
-#define YMI_WG_LAUNCH(T, BMV, LDS)                                                                                   \
-    do {                                                                                                            \
-        if (a.pw_shift >= 0) {                                                                                      \
-            if (a.bias_slab) hipLaunchKernelGGL((wgrad_kernel<T, WG_NS, BMV, true, true>), grid, dim3(256), (LDS), s, a, r);         \
-            else hipLaunchKernelGGL((wgrad_kernel<T, WG_NS, BMV, false, true>), grid, dim3(256), (LDS), s, a, r);               \
-        } else if (a.bias_slab) hipLaunchKernelGGL((wgrad_kernel<T, WG_NS, BMV, true>), grid, dim3(256), (LDS), s, a, r);         \
-        else hipLaunchKernelGGL((wgrad_kernel<T, WG_NS, BMV, false>), grid, dim3(256), (LDS), s, a, r);                         \
-    } while (0)
-    if (h.bf16) {
-        if (h.bm == 128) YMI_WG_LAUNCH(bf16_t, 128, (size_t)WG_NS * (WG_BK * (128 + WG_BN) * 2));
-        else if (h.bm == 32) YMI_WG_LAUNCH(bf16_t, 32, (size_t)WG_NS * (WG_BK * (32 + WG_BN) * 2));
-        else YMI_WG_LAUNCH(bf16_t, 64, (size_t)WG_NS * (WG_BK * (64 + WG_BN) * 2));
-    } else {
-        const size_t lds = 2 * (size_t)(WG_BK * (WG_BM + WG_BN) * 4);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_kernel<float, 2, 64, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_kernel<float, 2, 64, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        // (parity mode keeps the raster walk: pw_shift is -1 for float32 operands)
-        if (a.bias_slab) hipLaunchKernelGGL((wgrad_kernel<float, 2, 64, true>), grid, dim3(256), lds, s, a, r);
-        else hipLaunchKernelGGL((wgrad_kernel<float, 2, 64, false>), grid, dim3(256), lds, s, a, r);
-    }
-#undef YMI_WG_LAUNCH
-    ymi_prof_stop(s, prof);
+    if (ymi_prof_enabled()) prof = ymi_prof_start(h.s, 1, h.flop, h.bytes, h.bf16 ? 2500.0 : 157.3);
+    if (!h.bf16) wgrad_launch_tile<float, WG_BM>(h.a, r, grid, h.s);
+    else if (h.bm == 128) wgrad_launch_tile<bf16_t, 128>(h.a, r, grid, h.s);
+    else if (h.bm == 32) wgrad_launch_tile<bf16_t, 32>(h.a, r, grid, h.s);
+    else wgrad_launch_tile<bf16_t, 64>(h.a, r, grid, h.s);
+    ymi_prof_stop(h.s, prof);
 }
-static std::mutex g_hold_mu;
-static bool g_hold_on = false, g_held_valid = false;
-static WgradLaunch g_held;
-static void wgrad_flush_held_locked() {
-    if (g_held_valid) {
-        g_held_valid = false;
-        wgrad_launch(g_held, nullptr);
-    }
+// The held launch (ymi_wgrad_hold): at most one, always a deferred one with the 1-D XCD-mapped grid a rider can join, remembered with the device that
+// was current when it was held - it is issued there, whoever's call issues it.
+static struct WgradHeld {
+    std::mutex mu;
+    bool on = false;     // mode 1: deferred launches are held
+    bool valid = false;  // `launch` is waiting
+    WgradLaunch launch;
+    int device = 0;
+} g_held;
+static int wgrad_current_device() {
+    int d = 0;
+    (void)hipGetDevice(&d);
+    return d;
 }
-bool ymi_wgrad_issue_held(const YmiBnRider* rider, hipStream_t stream) {
-    std::lock_guard<std::mutex> lk(g_hold_mu);
-    if (!g_held_valid || g_held.s != stream || !g_held.a.xcd_map) return false;
-    g_held_valid = false;
-    wgrad_launch(g_held, rider);
+// (g_held.mu taken) issue the held launch, if any, on its device; the caller's device is current again afterwards
+static void wgrad_flush_held_locked(const BnFinal* rider = nullptr) {
+    if (!g_held.valid) return;
+    g_held.valid = false;
+    const int cur = wgrad_current_device();
+    if (cur != g_held.device) (void)hipSetDevice(g_held.device);
+    wgrad_launch(g_held.launch, rider);
+    if (cur != g_held.device) (void)hipSetDevice(cur);
+}
+bool ymi_wgrad_issue_held(const BnFinal* f, hipStream_t stream) {
+    std::lock_guard<std::mutex> lk(g_held.mu);
+    if (!g_held.valid || g_held.launch.s != stream || g_held.device != wgrad_current_device()) return false;
+    wgrad_flush_held_locked(f);
     return true;
 }
 // mode 1: hold deferred weight-gradient launches for riders; 0: stop holding (a held launch is issued as it is); 2: forget a held launch (after a
 // backward pass that raised: its operands are gone), the mode stays
 extern "C" int ymi_wgrad_hold(int32_t mode) {
-    std::lock_guard<std::mutex> lk(g_hold_mu);
+    std::lock_guard<std::mutex> lk(g_held.mu);
     if (mode == 2) {
-        g_held_valid = false;
+        g_held.valid = false;
         return YMI_OK;
     }
     YMI_CHECK_ARG(mode == 0 || mode == 1, "wgrad_hold: mode 0, 1 or 2");
     if (mode == 0) wgrad_flush_held_locked();
-    g_hold_on = mode == 1;
+    g_held.on = mode == 1;
     return hipGetLastError() == hipSuccess ? YMI_OK : YMI_ELAUNCH;
 }
 
@@ -833,7 +780,7 @@ extern "C" int ymi_wgrad_reduce_batch(const ymi_wgrad_pending* host_records, int
     YMI_CHECK_ARG(host_records && device_table && n > 0, "wgrad_reduce_batch: args");
     hipStream_t s = (hipStream_t)stream;
     {   // a launch still held back for a rider (ymi_wgrad_hold): its slabs are summed below
-        std::lock_guard<std::mutex> lk(g_hold_mu);
+        std::lock_guard<std::mutex> lk(g_held.mu);
         wgrad_flush_held_locked();
     }
     int64_t total = 0;
@@ -918,13 +865,14 @@ static int wgrad_impl(const ymi_tensor* x, const ymi_tensor* dy, int64_t cout_re
     WgradLaunch h{a, grid, bm, bf16, s, 2.0 * (double)mpix * (double)dy->c * (double)ng,
                   ((double)ymi_pixels(x) * x->c + (double)mpix * dy->c) * es + (double)dy->c * ng * 4.0};
     {
-        std::lock_guard<std::mutex> lk(g_hold_mu);
+        std::lock_guard<std::mutex> lk(g_held.mu);
         wgrad_flush_held_locked();  // (at most one launch is held)
-        if (pending && g_hold_on && a.xcd_map) {
+        if (pending && g_held.on && a.xcd_map) {
             // held back: the next BatchNorm backward of this stream issues it with its final pass riding along (or the next deferred call / the
             // batched slab sum / ymi_wgrad_hold(0) as it is).  The caller keeps operands and workspace alive until the slab sum anyway.
-            g_held = h;
-            g_held_valid = true;
+            g_held.launch = h;
+            g_held.device = wgrad_current_device();
+            g_held.valid = true;
         } else {
             wgrad_launch(h, nullptr);
         }

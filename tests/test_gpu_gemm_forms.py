@@ -676,7 +676,8 @@ WGRAD = [  # name, n, xc, cin_real, h, w, dyc, cout_real, k, s, wgrad_blocks (No
 ]
 
 
-def wgrad_case(dtype, spec, deferred, seed):
+def wgrad_case(dtype, spec, deferred, seed, ws_fill=None):
+    """ws_fill: a byte the workspace holds before the call (a caller that watches for the launch's first write: tests/test_gpu_bn_final.py)"""
     name, n, xc, cin_r, h, w, dyc, cout_r, k, s, blocks, patch = spec
     bf16 = dtype == BF
     if not bf16:
@@ -703,6 +704,8 @@ def wgrad_case(dtype, spec, deferred, seed):
     with options(**opts):
         need = L().ymi_conv2d_bwd_weight_workspace(mpix, dyc, xc, k, k)
         ws = torch.empty(int(need), dtype=torch.uint8, device=dev())
+        if ws_fill is not None:
+            ws.fill_(ws_fill)
         dw = torch.full((cout_r, cin_r, k, k), float("nan"), device=dev())
         db = torch.full((dyc,), float("nan"), device=dev())
         rec = WgradPending()

@@ -307,8 +307,9 @@ def test_weight_used_twice_in_one_pass_accumulates_both_gradients():
 
 def test_bn_backward_final_passes_riding_in_weight_gradient_launches():
     """ops.wgrad_riders: every deferred weight-gradient launch is held back until the next BatchNorm backward, whose final pass (dgamma / dbeta /
-    the apply pass's coefficients) then rides in it as extra workgroups.  The rider repeats chan_reduce_final_kernel's arithmetic bit for bit, so the
-    gradients are IDENTICAL to a pass with the final passes as their own launches; a raised pass leaves no launch behind."""
+    the apply pass's coefficients) then rides in it as extra workgroups.  The rider workgroups and chan_reduce_final_kernel call the same function
+    (csrc/common.h bn_final_block; tests/test_gpu_bn_final.py holds the two forms to each other word by word at the C ABI), so the gradients are
+    IDENTICAL to a pass with the final passes as their own launches; a raised pass leaves no launch behind."""
     from improving_yolov8_cbam_swinblock_amd import _lib as L, ops
 
     model, batch = _small_model()
