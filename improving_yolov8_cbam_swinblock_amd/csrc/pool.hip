@@ -1,31 +1,27 @@
 // SPPF max-pool cascade (k x k, stride 1, pad k/2 with -inf, three times chained) for NHWC tensors.
 //
-// Forward: one launch produces y1, y2, y3 from y0.  A workgroup owns a spatial tile x a 64-byte channel
-// slab (32 bf16 / 16 f32 channels), stages the tile plus a 3*(k/2) halo (clamped to the image) in LDS
-// once and runs the three pools as separable row-max / column-max passes between two LDS images, so
-// y0 is read from HBM once and y1..y3 are written once (the algorithmic minimum: 1 read + 3 writes).
-// Positions outside the image are -inf for every stage, which reproduces the chained semantics of
-// nn.MaxPool2d exactly (max is exact in any precision -> bit-identical to the f32 reference).
+// Two primitives, each written once: window_max() (maximum of the k positions around an LDS item along one axis) and
+// window_first_max() (the same with the offset of the FIRST maximum: PyTorch's tie rule).  Every pool is separable, a row pass
+// followed by a column pass, so the four forward passes are calls of the first and the four arg-max passes calls of the second.
 //
-// Backward: per stage, g_in[s] += sum over p in window(s) of [argmax_window(p) == s] * g_out[p], as a
-// GATHER (deterministic), with the arg-max of every window recomputed in LDS using PyTorch's tie rule
-// (first maximum in row-major scan order).
+// Forward, sppf_pool3_kernel<T, NCH, K>: one launch produces y1, y2, y3 from y0.  A workgroup owns a spatial tile x NCH 16-byte
+// channel chunks, stages the tile plus a 3*(k/2) halo (clamped to the image) in LDS once and runs the three pools between two
+// LDS images, so y0 is read from HBM once and y1..y3 are written once (the algorithmic minimum: 1 read + 3 writes).  Positions
+// outside the image are -inf for every stage, which reproduces the chained semantics of nn.MaxPool2d exactly (max is exact in
+// any precision -> bit-identical to the f32 reference).  Two forms are launched: the MAP form <T, 1, 5 | 7 | 0> where the whole
+// map of one chunk fits LDS (tile = image, no halo, up to 1024 threads; the model's 20x20 - 40x40 maps) and the TILED form
+// <T, 4, 0> (64-byte slabs, 256 threads) beyond.
+//
+// Backward: per stage, g_in[s] += sum over p in window(s) of [argmax_window(p) == s] * g_out[p], as a GATHER (deterministic),
+// with the arg-max of every window recomputed in LDS: sppf_bwd_map_kernel<T, K> (whole map, the three stages in one launch) and
+// maxpool_bwd_kernel<T> (tiled, one stage per launch).
 #include "common.h"
 
 struct PV {
     void* p;
     int64_t ld;
 };
-
-struct PoolArgs {
-    PV y0, y1, y2, y3;
-    int N, H, W, C;
-    int k, TH, TW;
-};
-
-template <typename T> struct SlabTraits;
-template <> struct SlabTraits<bf16_t> { static constexpr int CS = 32; };  // channels per 64-byte slab
-template <> struct SlabTraits<float> { static constexpr int CS = 16; };
+static PV pv(const ymi_tensor* t) { return PV{t->data, t->ld}; }
 
 // 16-byte chunk as floats
 template <typename T> struct Chunk;
@@ -42,82 +38,132 @@ template <> struct Chunk<float> {
 
 #define NEG_INF (-__builtin_inff())
 
-template <typename T>
-__global__ __launch_bounds__(256) void sppf_pool3_kernel(PoolArgs a) {
-    constexpr int CN = Chunk<T>::N;
-    constexpr int CS = SlabTraits<T>::CS;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int r = a.k / 2;
-    const int tiles_w = (a.W + a.TW - 1) / a.TW;
-    // unit order: channel slab fastest, then tile, then image; consecutive units on one XCD (neighbouring slabs share 128-byte lines)
-    const int unit = xcd_unit(flat_block_id(), gridDim.x * gridDim.y * gridDim.z);
-    const int bslab = unit % gridDim.y, btile = (unit / gridDim.y) % gridDim.x;
-    const int th0 = (btile / tiles_w) * a.TH, tw0 = (btile % tiles_w) * a.TW;
-    const int th1 = min(th0 + a.TH, a.H), tw1 = min(tw0 + a.TW, a.W);
-    const int c0 = bslab * CS;
-    const int n = unit / (gridDim.x * gridDim.y);
-    // staged region = tile + 3r halo, clamped to the image
-    const int rh0 = max(th0 - 3 * r, 0), rh1 = min(th1 + 3 * r, a.H);
-    const int rw0 = max(tw0 - 3 * r, 0), rw1 = min(tw1 + 3 * r, a.W);
-    const int RH = rh1 - rh0, RW = rw1 - rw0;
-    char* A = smem;
-    char* B = smem + (size_t)RH * RW * 64;
-    const int items = RH * RW * 4;  // (pixel, 16-byte chunk)
+// ---- the two window scans.  `base` is an LDS image of 16-byte items, `i` the centre item, `stride` the distance in items between
+// neighbours along the scanned axis, `pos` the centre's coordinate on that axis and `extent` the axis length; K is the compiled
+// window size (0: the run-time k).  Compiled K: the loop is unrolled over all K positions and one outside [0, extent) reads the
+// centre instead of being branched around, so the LDS reads of one item are issued together.  Run-time k: the loop is not unrolled
+// and visits the in-range positions only (the address select ahead of every read costs such a loop 13 % of the tiled forward).
+template <int K> __device__ __forceinline__ int window_begin(int pos, int r) { return K ? 0 : max(r - pos, 0); }
+template <int K> __device__ __forceinline__ int window_end(int pos, int r, int extent, int k) { return K ? K : min(k, extent + r - pos); }
 
-    const T* src = reinterpret_cast<const T*>(a.y0.p);
-    for (int i = threadIdx.x; i < items; i += 256) {
-        const int ch = i & 3, px = i >> 2;
-        const int h = rh0 + px / RW, w = rw0 + px % RW;
+// m = maximum over the window (the centre read again leaves a maximum unchanged)
+template <typename T, int K>
+__device__ __forceinline__ void window_max(const char* base, int i, int stride, int pos, int extent, int k, float (&m)[Chunk<T>::N]) {
+    constexpr int CN = Chunk<T>::N, UN = K ? K : 1;
+    const int r = k / 2;
+#pragma unroll
+    for (int e = 0; e < CN; ++e) m[e] = NEG_INF;
+#pragma unroll UN
+    for (int d = window_begin<K>(pos, r); d < window_end<K>(pos, r, extent, k); ++d) {
+        const int q = pos - r + d;
+        const bool ok = !K || (q >= 0 && q < extent);
         float v[CN];
-        if (c0 + ch * CN < a.C) {
-            Chunk<T>::load(src + (((int64_t)n * a.H + h) * a.W + w) * a.y0.ld + c0 + ch * CN, v);
-        } else {
+        Chunk<T>::load(base + (size_t)(ok ? i + (d - r) * stride : i) * 16, v);
+#pragma unroll
+        for (int e = 0; e < CN; ++e) m[e] = fmaxf(m[e], v[e]);
+    }
+}
+
+// best = maximum over the window, code = offset d (0..k-1, centre = k/2) of its FIRST occurrence.  This is the one statement of
+// the tie rule that makes gradients route like nn.MaxPool2d: the first in-range element initialises, then strictly greater wins.
+// Applied along rows and then along columns of the row maxima it selects the first maximum of the k x k window in row-major order.
+// (Run-time k: `ok` is the constant true, and it is the loop bounds that keep every visited position in range.)
+template <typename T, int K>
+__device__ __forceinline__ void window_first_max(const char* base, int i, int stride, int pos, int extent, int k, float (&best)[Chunk<T>::N],
+                                                 int (&code)[Chunk<T>::N]) {
+    constexpr int CN = Chunk<T>::N, UN = K ? K : 1;
+    const int r = k / 2;
+    float b[CN];  // (locals, copied out below: updated through the references the compare compiles to branches instead of selects)
+    int c[CN];
+#pragma unroll
+    for (int e = 0; e < CN; ++e) { b[e] = NEG_INF; c[e] = -1; }
+#pragma unroll UN
+    for (int d = window_begin<K>(pos, r); d < window_end<K>(pos, r, extent, k); ++d) {
+        const int q = pos - r + d;
+        const bool ok = !K || (q >= 0 && q < extent);
+        float v[CN];
+        Chunk<T>::load(base + (size_t)(ok ? i + (d - r) * stride : i) * 16, v);
+#pragma unroll
+        for (int e = 0; e < CN; ++e)
+            if (ok && (c[e] < 0 || v[e] > b[e])) {
+                b[e] = v[e];
+                c[e] = d;
+            }
+    }
+#pragma unroll
+    for (int e = 0; e < CN; ++e) { best[e] = b[e]; code[e] = c[e]; }
+}
+
+// ----------------------------------------------------------------------------------------- forward
+struct PoolArgs {
+    PV y[4];  // y0 (in), y1..y3 (out)
+    int N, H, W, C;
+    int k, TH, TW;  // TH x TW: the tile (tiled form; the map form's tile is the image)
+};
+
+// LDS of one forward workgroup: two images of the staged region (tile + 6r, clamped to the image; the map form: the image)
+static size_t sppf_fwd_lds(int H, int W, int r, int th, int tw, int nch) {
+    const int RH = (th + 6 * r < H) ? th + 6 * r : H, RW = (tw + 6 * r < W) ? tw + 6 * r : W;
+    return (size_t)RH * RW * nch * 16 * 2;
+}
+
+// grid: map form (chunks, images), tiled form (tiles, slabs, images); work units run chunk / slab fastest, then tile, then image
+// through xcd_unit(), so the workgroups that share a 128-byte line run on one XCD
+template <typename T, int NCH, int K>
+__global__ __launch_bounds__(NCH == 1 ? 1024 : 256) void sppf_pool3_kernel(PoolArgs a) {
+    constexpr int CN = Chunk<T>::N;
+    constexpr bool MAP = NCH == 1;  // launched with tile = image: one tile, no halo, C / CN chunks exactly, every staged item is emitted
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int k = K ? K : a.k, r = k / 2, halo = MAP ? 0 : 3 * r;
+    const int TH = MAP ? a.H : a.TH, TW = MAP ? a.W : a.TW;
+    const int slabs = MAP ? gridDim.x : gridDim.y, tiles = MAP ? 1 : gridDim.x, tiles_w = (a.W + TW - 1) / TW;
+    const int unit = xcd_unit(flat_block_id(), gridDim.x * gridDim.y * gridDim.z);
+    const int btile = (unit / slabs) % tiles, n = unit / (slabs * tiles);
+    const int c0 = (unit % slabs) * NCH * CN;
+    const int th0 = (btile / tiles_w) * TH, tw0 = (btile % tiles_w) * TW;
+    const int th1 = min(th0 + TH, a.H), tw1 = min(tw0 + TW, a.W);
+    // staged region = tile + 3r halo, clamped to the image
+    const int rh0 = max(th0 - halo, 0), rh1 = min(th1 + halo, a.H);
+    const int rw0 = max(tw0 - halo, 0), rw1 = min(tw1 + halo, a.W);
+    const int RH = rh1 - rh0, RW = rw1 - rw0;
+    const int items = RH * RW * NCH;  // (pixel, 16-byte chunk)
+    char* A = smem;                            // [RH][RW][NCH][16 B] input of the current stage
+    char* B = smem + (size_t)items * 16;       // [RH][RW][NCH][16 B] row maxima
+    const int64_t img = (int64_t)n * a.H * a.W;
+    const int org = rh0 * a.W + rw0, skip = a.W - RW;  // region pixel px is image pixel org + px + (px / RW) * skip (map form: px)
+
+    const T* src = reinterpret_cast<const T*>(a.y[0].p);
+    for (int i = threadIdx.x; i < items; i += blockDim.x) {
+        const int ch = i % NCH, px = i / NCH;
+        if (MAP || c0 + ch * CN < a.C) {
+            *reinterpret_cast<uint4*>(A + (size_t)i * 16) = *reinterpret_cast<const uint4*>(src + (img + org + px + px / RW * skip) * a.y[0].ld + c0 + ch * CN);
+        } else {  // the last slab overhangs C
+            float v[CN];
 #pragma unroll
             for (int e = 0; e < CN; ++e) v[e] = NEG_INF;
+            Chunk<T>::store(A + (size_t)i * 16, v);
         }
-        Chunk<T>::store(A + (size_t)i * 16, v);
     }
     __syncthreads();
-
-    PV outs[3] = {a.y1, a.y2, a.y3};
 #pragma unroll 1
-    for (int stage = 0; stage < 3; ++stage) {
-        // row max: B[h][w] = max_{|dx|<=r, inside region/image} A[h][w+dx]
-        for (int i = threadIdx.x; i < items; i += 256) {
-            const int ch = i & 3, px = i >> 2;
-            const int hh = px / RW, ww = px % RW;
+    for (int st = 1; st <= 3; ++st) {
+        // row max: B[h][w] = max_{|dx|<=r, inside the region} A[h][w+dx]
+        for (int i = threadIdx.x; i < items; i += blockDim.x) {
             float m[CN];
-#pragma unroll
-            for (int e = 0; e < CN; ++e) m[e] = NEG_INF;
-            const int lo = max(ww - r, 0), hi = min(ww + r, RW - 1);
-            for (int x = lo; x <= hi; ++x) {
-                float v[CN];
-                Chunk<T>::load(A + ((size_t)(hh * RW + x) * 4 + ch) * 16, v);
-#pragma unroll
-                for (int e = 0; e < CN; ++e) m[e] = fmaxf(m[e], v[e]);
-            }
+            window_max<T, K>(A, i, NCH, (i / NCH) % RW, RW, k, m);
             Chunk<T>::store(B + (size_t)i * 16, m);
         }
         __syncthreads();
-        // column max: A[h][w] = max_{|dy|<=r} B[h+dy][w]; then emit the tile interior
-        T* dst = reinterpret_cast<T*>(outs[stage].p);
-        for (int i = threadIdx.x; i < items; i += 256) {
-            const int ch = i & 3, px = i >> 2;
-            const int hh = px / RW, ww = px % RW;
+        // column max: A[h][w] = max_{|dy|<=r} B[h+dy][w] (A is only read by the row pass: free since the barrier above); emit the tile
+        T* dst = reinterpret_cast<T*>(a.y[st].p);
+        for (int i = threadIdx.x; i < items; i += blockDim.x) {
+            const int ch = i % NCH, px = i / NCH;
+            const int hh = px / RW, h = rh0 + hh, w = rw0 + px % RW;
             float m[CN];
-#pragma unroll
-            for (int e = 0; e < CN; ++e) m[e] = NEG_INF;
-            const int lo = max(hh - r, 0), hi = min(hh + r, RH - 1);
-            for (int y = lo; y <= hi; ++y) {
-                float v[CN];
-                Chunk<T>::load(B + ((size_t)(y * RW + ww) * 4 + ch) * 16, v);
-#pragma unroll
-                for (int e = 0; e < CN; ++e) m[e] = fmaxf(m[e], v[e]);
-            }
+            window_max<T, K>(B, i, RW * NCH, hh, RH, k, m);
             Chunk<T>::store(A + (size_t)i * 16, m);
-            const int h = rh0 + hh, w = rw0 + ww;
-            if (h >= th0 && h < th1 && w >= tw0 && w < tw1 && c0 + ch * CN < a.C)
-                Chunk<T>::store(dst + (((int64_t)n * a.H + h) * a.W + w) * outs[stage].ld + c0 + ch * CN, m);
+            if (MAP || (h >= th0 && h < th1 && w >= tw0 && w < tw1 && c0 + ch * CN < a.C))
+                Chunk<T>::store(dst + (img + org + px + hh * skip) * a.y[st].ld + c0 + ch * CN, m);
         }
         __syncthreads();
     }
@@ -126,24 +172,10 @@ __global__ __launch_bounds__(256) void sppf_pool3_kernel(PoolArgs a) {
     // inside every non-border edge, so all three emitted stages are exact.
 }
 
-static bool pool_geometry(int H, int W, int k, int es, int* TH, int* TW, size_t* lds) {
-    const int r = k / 2;
-    int th = H, tw = W;
-    auto bytes = [&](int t_h, int t_w) {
-        const int RH = (t_h + 6 * r < H) ? t_h + 6 * r : H, RW = (t_w + 6 * r < W) ? t_w + 6 * r : W;
-        return (size_t)RH * RW * 64 * 2;
-    };
-    while (bytes(th, tw) > 150 * 1024) {
-        if (th >= tw && th > 8) th = (th + 1) / 2;
-        else if (tw > 8) tw = (tw + 1) / 2;
-        else return false;
-    }
-    *TH = th; *TW = tw; *lds = bytes(th, tw);
-    (void)es;
-    return true;
-}
-
 // ---------------------------------------------------------------------------------------- backward
+// Two bodies over window_first_max(), on purpose: their gathers are different arithmetic.  The tiled kernel sums the k x k window
+// in row-major order and stores the running gradient in the tensor dtype between its three launches; the map kernel gathers
+// separably, column first, and keeps the running gradient in float32.  Merging them would change low bits of bf16 gradients.
 struct PoolBwdArgs {
     PV x, gout, gsrc, gin;  // gin = gsrc + route(gout | x)
     int N, H, W, C;
@@ -162,21 +194,25 @@ template <int CN> __device__ __forceinline__ uint64_t load_codes(const unsigned 
     return CN == 8 ? *reinterpret_cast<const uint64_t*>(p) : (uint64_t)*reinterpret_cast<const uint32_t*>(p);
 }
 
+// LDS of one tiled backward workgroup: x on tile + 4r, gout and the arg-max codes on tile + 2r, row maxima and their column codes
+// on (tile + 4r) x (tile + 2r), every extent clamped to the image; 64 value bytes and 4 * cn code bytes per pixel
+static size_t maxpool_bwd_lds(int H, int W, int r, int th, int tw, int cn) {
+    const int XH = (th + 4 * r < H) ? th + 4 * r : H, XW = (tw + 4 * r < W) ? tw + 4 * r : W;
+    const int GH = (th + 2 * r < H) ? th + 2 * r : H, GW = (tw + 2 * r < W) ? tw + 2 * r : W;
+    return (size_t)XH * XW * 64 + (size_t)GH * GW * (64 + 4 * cn) + (size_t)XH * GW * (64 + 4 * cn);
+}
+
 // one stage (maps too large for the whole-map kernel below): gin[s] = gsrc[s] + sum_{p in window(s)} [argmax(x, window(p)) == s] gout[p]
-// NCH = 16-byte channel chunks per pixel owned by one workgroup (4: a 64-byte slab, coalesced for large maps;
-// 1: four times as many workgroups, for the small SPPF maps where the launch would not fill the chip otherwise).
-// The arg-max is separable: first the row maximum (and its column code) over the k columns, then the first row
-// whose row maximum is the window maximum: 2k LDS reads per window instead of k*k, and the same element as a
-// row-major scan with "strictly greater wins" (PyTorch's tie rule).
-template <typename T, int NCH>
+// for a tile x a 64-byte channel slab.  The arg-max is separable: first the row maximum (and its column code) over the k columns, then
+// the first row whose row maximum is the window maximum: 2k LDS reads per window instead of k*k, and the same element as a row-major
+// scan.  (A window position is in the image exactly when it is in the staged region: the x region reaches r beyond the gout region.)
+template <typename T>
 __global__ __launch_bounds__(256) void maxpool_bwd_kernel(PoolBwdArgs a) {
-    constexpr int CN = Chunk<T>::N;
-    constexpr int CS = CN * NCH;
+    constexpr int CN = Chunk<T>::N, NCH = 4, CS = CN * NCH;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int r = a.k / 2, k = a.k;
     const int tiles_w = (a.W + a.TW - 1) / a.TW;
-    // unit order: channel chunk fastest, then tile, then image; consecutive units on one XCD: with one 16-byte chunk per workgroup
-    // eight workgroups share every 128-byte line, and dealt to eight XCDs they fetched it eight times (47 -> see profiles/r03 us)
+    // unit order: channel slab fastest, then tile, then image; consecutive units on one XCD (neighbouring slabs share 128-byte lines)
     const int unit = xcd_unit(flat_block_id(), gridDim.x * gridDim.y * gridDim.z);
     const int bslab = unit % gridDim.y, btile = (unit / gridDim.y) % gridDim.x;
     const int th0 = (btile / tiles_w) * a.TH, tw0 = (btile % tiles_w) * a.TW;
@@ -218,23 +254,10 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(PoolBwdArgs a) {
     // row pass: for every staged row and every G column, the maximum over the k columns and its column code
     for (int i = threadIdx.x; i < XH * GW * NCH; i += 256) {
         const int ch = i % NCH, px = i / NCH;
-        const int hh = px / GW, w = gw0 + px % GW;
+        const int hh = px / GW, wx = gw0 + px % GW - xw0;  // row and column in the x region
         float best[CN];
         int code[CN];
-#pragma unroll
-        for (int e = 0; e < CN; ++e) { best[e] = NEG_INF; code[e] = -1; }
-        for (int dx = 0; dx < k; ++dx) {
-            const int ww = w + dx - r;
-            if (ww < 0 || ww >= a.W) continue;
-            float v[CN];
-            Chunk<T>::load(X + ((size_t)(hh * XW + (ww - xw0)) * NCH + ch) * 16, v);
-#pragma unroll
-            for (int e = 0; e < CN; ++e)
-                if (code[e] < 0 || v[e] > best[e]) {  // first in-image element initialises; then strictly greater wins
-                    best[e] = v[e];
-                    code[e] = dx;
-                }
-        }
+        window_first_max<T, 0>(X, (hh * XW + wx) * NCH + ch, NCH, wx, XW, k, best, code);
         Chunk<T>::store(RM + (size_t)i * 16, best);
         store_codes<CN>(RC + (size_t)px * CS + ch * CN, code);
     }
@@ -242,25 +265,13 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(PoolBwdArgs a) {
     // column pass: arg-max code (dy*k + dx) of every window centred in the G region
     for (int i = threadIdx.x; i < GH * GW * NCH; i += 256) {
         const int ch = i % NCH, px = i / NCH;
-        const int h = gh0 + px / GW, wl = px % GW;
+        const int hx = gh0 + px / GW - xh0, wl = px % GW;  // row in the x region (the row maxima's), column in the G region
         float best[CN];
         int code[CN];
+        window_first_max<T, 0>(RM, (hx * GW + wl) * NCH + ch, GW * NCH, hx, XH, k, best, code);
 #pragma unroll
-        for (int e = 0; e < CN; ++e) { best[e] = NEG_INF; code[e] = -1; }
-        for (int dy = 0; dy < k; ++dy) {
-            const int hh = h + dy - r;
-            if (hh < 0 || hh >= a.H) continue;
-            const size_t rp = (size_t)(hh - xh0) * GW + wl;
-            float v[CN];
-            Chunk<T>::load(RM + (rp * NCH + ch) * 16, v);
-            const uint64_t rc = load_codes<CN>(RC + rp * CS + ch * CN);
-#pragma unroll
-            for (int e = 0; e < CN; ++e)
-                if (code[e] < 0 || v[e] > best[e]) {
-                    best[e] = v[e];
-                    code[e] = dy * k + (int)((rc >> (8 * e)) & 255);
-                }
-        }
+        for (int e = 0; e < CN; ++e)  // code = dy: fold in the column code of that row's maximum
+            code[e] = code[e] * k + RC[(size_t)((hx + code[e] - r) * GW + wl) * CS + ch * CN + e];
         store_codes<CN>(IDX + (size_t)px * CS + ch * CN, code);
     }
     __syncthreads();
@@ -293,57 +304,12 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(PoolBwdArgs a) {
     }
 }
 
-template <typename T, int NCH>
-static void launch_pool_bwd_t(const PoolBwdArgs& a, dim3 grid, size_t lds, hipStream_t stream) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(maxpool_bwd_kernel<T, NCH>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    hipLaunchKernelGGL((maxpool_bwd_kernel<T, NCH>), grid, dim3(256), lds, stream, a);
-}
-
-static int launch_pool_bwd(const ymi_tensor* x, int k, PV gout, const ymi_tensor* gsrc, PV gin, hipStream_t stream) {
-    PoolBwdArgs a{};
-    a.x = PV{x->data, x->ld}; a.gout = gout; a.gsrc = PV{gsrc->data, gsrc->ld}; a.gin = gin;
-    a.N = (int)x->n; a.H = (int)x->h; a.W = (int)x->w; a.C = (int)x->c; a.k = k;
-    const int r = k / 2;
-    const int cn = x->dtype == YMI_BF16 ? 8 : 4;
-    const int nch = (a.H * a.W <= 1024) ? 1 : 4;  // small maps: one chunk per workgroup so the grid fills the chip
-    const int cs = cn * nch;
-    int th = a.H, tw = a.W;
-    auto bytes = [&](int t_h, int t_w) {
-        const int XH = (t_h + 4 * r < a.H) ? t_h + 4 * r : a.H, XW = (t_w + 4 * r < a.W) ? t_w + 4 * r : a.W;
-        const int GH = (t_h + 2 * r < a.H) ? t_h + 2 * r : a.H, GW = (t_w + 2 * r < a.W) ? t_w + 2 * r : a.W;
-        return (size_t)XH * XW * nch * 16 + (size_t)GH * GW * (nch * 16 + cs) + (size_t)XH * GW * (nch * 16 + cs);
-    };
-    while (bytes(th, tw) > 150 * 1024) {
-        if (th >= tw && th > 8) th = (th + 1) / 2;
-        else if (tw > 8) tw = (tw + 1) / 2;
-        else {
-            ymi_set_error("sppf_pool3_bwd: tile does not fit LDS");
-            return YMI_EINVAL;
-        }
-    }
-    a.TH = th; a.TW = tw;
-    const size_t lds = bytes(th, tw);
-    dim3 grid(((a.H + th - 1) / th) * ((a.W + tw - 1) / tw), (a.C + cs - 1) / cs, a.N);
-    if (x->dtype == YMI_BF16) {
-        if (nch == 1) launch_pool_bwd_t<bf16_t, 1>(a, grid, lds, stream);
-        else launch_pool_bwd_t<bf16_t, 4>(a, grid, lds, stream);
-    } else {
-        if (nch == 1) launch_pool_bwd_t<float, 1>(a, grid, lds, stream);
-        else launch_pool_bwd_t<float, 4>(a, grid, lds, stream);
-    }
-    YMI_CHECK_LAUNCH("sppf_pool3_bwd");
-    return YMI_OK;
-}
-
-// ---- whole-map kernels: a workgroup owns ONE image x ONE 16-byte channel chunk and keeps the whole map in LDS --------------------
-// (the SPPF maps of the model are 20x20 - 40x40 at 1280 input.)  Work units are (chunk fastest, image) through xcd_unit(), so the
-// eight chunks of a 128-byte line run on one XCD.  One chunk per workgroup gives C/8 * N workgroups (1024 for the model) where the
-// tiled kernels' 64-byte slabs gave 256; loops over the K window positions are unrolled (K = 5, 7 compiled; 0: runtime k) with
-// out-of-image positions folded into the compare instead of branched around, so the LDS reads of one item are issued together.
-struct MapArgs {
-    PV y[4];    // forward: y0 (in), y1..y3 (out).  backward: y0, y1, y2 (y[3] unused)
-    PV dy[4];   // backward: dy0..dy3 (in)
-    PV dx;      // backward: out
+// ---- whole-map backward: a workgroup owns ONE image x ONE 16-byte channel chunk and keeps the whole map in LDS, as the forward's map
+// form does (grid (chunks, images), units chunk-fastest through xcd_unit(), window loops unrolled for K = 5, 7).
+struct MapBwdArgs {
+    PV y[3];    // y0, y1, y2
+    PV dy[4];   // dy0..dy3 (in)
+    PV dx;      // out
     int N, H, W, C, k;
 };
 
@@ -361,64 +327,6 @@ template <typename T> __device__ __forceinline__ void lds_store_f32(float* base,
         *reinterpret_cast<float4*>(base + (size_t)q * planes_stride + (size_t)i * 4) = make_float4(v[q * 4 + 0], v[q * 4 + 1], v[q * 4 + 2], v[q * 4 + 3]);
 }
 
-template <typename T, int K>
-__global__ __launch_bounds__(1024) void sppf_fwd_map_kernel(MapArgs a) {
-    constexpr int CN = Chunk<T>::N;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr int UN = K ? K : 1;  // unroll count of the window loops (runtime k: not unrolled)
-    const int HW = a.H * a.W, k = K ? K : a.k, r = k / 2;
-    const int unit = xcd_unit(flat_block_id(), gridDim.x * gridDim.y);
-    const int c0 = (unit % gridDim.x) * CN, n = unit / gridDim.x;
-    char* X = smem;                       // [HW][16 B] input of the current stage
-    char* RM = smem + (size_t)HW * 16;    // [HW][16 B] row maxima
-    const int64_t img = (int64_t)n * HW;
-    {
-        const T* src = reinterpret_cast<const T*>(a.y[0].p);
-        for (int i = threadIdx.x; i < HW; i += blockDim.x)
-            *reinterpret_cast<uint4*>(X + (size_t)i * 16) = *reinterpret_cast<const uint4*>(src + (img + i) * a.y[0].ld + c0);
-    }
-    __syncthreads();
-#pragma unroll 1
-    for (int st = 1; st <= 3; ++st) {
-        for (int i = threadIdx.x; i < HW; i += blockDim.x) {
-            const int h = i / a.W, w = i - h * a.W;
-            float m[CN];
-#pragma unroll
-            for (int e = 0; e < CN; ++e) m[e] = NEG_INF;
-#pragma unroll UN
-            for (int d = 0; d < k; ++d) {
-                const int ww = w - r + d;
-                const bool ok = ww >= 0 && ww < a.W;
-                float v[CN];
-                Chunk<T>::load(X + (size_t)(ok ? i - r + d : i) * 16, v);  // (an out-of-image column reads the centre: max unchanged)
-#pragma unroll
-                for (int e = 0; e < CN; ++e) m[e] = fmaxf(m[e], v[e]);
-            }
-            Chunk<T>::store(RM + (size_t)i * 16, m);
-        }
-        __syncthreads();
-        T* dst = reinterpret_cast<T*>(a.y[st].p);
-        for (int i = threadIdx.x; i < HW; i += blockDim.x) {
-            const int h = i / a.W;
-            float m[CN];
-#pragma unroll
-            for (int e = 0; e < CN; ++e) m[e] = NEG_INF;
-#pragma unroll UN
-            for (int d = 0; d < k; ++d) {
-                const int hh = h - r + d;
-                const bool ok = hh >= 0 && hh < a.H;
-                float v[CN];
-                Chunk<T>::load(RM + (size_t)(ok ? i + (d - r) * a.W : i) * 16, v);
-#pragma unroll
-                for (int e = 0; e < CN; ++e) m[e] = fmaxf(m[e], v[e]);
-            }
-            Chunk<T>::store(X + (size_t)i * 16, m);  // (X is only read by the row pass: free since the barrier above)
-            Chunk<T>::store(dst + (img + i) * a.y[st].ld + c0, m);
-        }
-        __syncthreads();
-    }
-}
-
 // Backward of the cascade in one launch:  g := dy3;  g := dy2 + route(g | y2);  g := dy1 + route(g | y1);  dx = dy0 + route(g | y0),
 // the running gradient in f32 in LDS.  route() is a deterministic gather with PyTorch's arg-max rule (first maximum in row-major
 // order), and it is SEPARABLE: the arg-max of window p is (first row whose row maximum is the window maximum, that row's first
@@ -426,7 +334,7 @@ __global__ __launch_bounds__(1024) void sppf_fwd_map_kernel(MapArgs a) {
 // V[hh][pw]  visits 2k positions per pixel instead of k*k (the sums associate column-first: exact for the dyadic tie fixtures,
 // within f32 rounding of the row-major order otherwise).
 template <typename T, int K>
-__global__ __launch_bounds__(1024) void sppf_bwd_map_kernel(MapArgs a) {
+__global__ __launch_bounds__(1024) void sppf_bwd_map_kernel(MapBwdArgs a) {
     constexpr int CN = Chunk<T>::N;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr int UN = K ? K : 1;  // unroll count of the window loops (runtime k: not unrolled)
@@ -460,48 +368,18 @@ __global__ __launch_bounds__(1024) void sppf_bwd_map_kernel(MapArgs a) {
         __syncthreads();
         // row pass: maximum over the k columns around every position and the code (0..k-1) of its first occurrence
         for (int i = threadIdx.x; i < HW; i += blockDim.x) {
-            const int h = i / a.W, w = i - h * a.W;
             float best[CN];
             int code[CN];
-#pragma unroll
-            for (int e = 0; e < CN; ++e) { best[e] = NEG_INF; code[e] = -1; }
-#pragma unroll UN
-            for (int d = 0; d < k; ++d) {
-                const int ww = w - r + d;
-                const bool ok = ww >= 0 && ww < a.W;
-                float v[CN];
-                Chunk<T>::load(X + (size_t)(ok ? i - r + d : i) * 16, v);
-#pragma unroll
-                for (int e = 0; e < CN; ++e)
-                    if (ok && (code[e] < 0 || v[e] > best[e])) {  // the first in-image element initialises; then strictly greater wins
-                        best[e] = v[e];
-                        code[e] = d;
-                    }
-            }
+            window_first_max<T, K>(X, i, 1, i % a.W, a.W, k, best, code);
             Chunk<T>::store(RM + (size_t)i * 16, best);
             store_codes<CN>(RC + (size_t)i * CN, code);
         }
         __syncthreads();
         // column pass: code (0..k-1) of the first row whose row maximum is the maximum of the window centred here
         for (int i = threadIdx.x; i < HW; i += blockDim.x) {
-            const int h = i / a.W;
             float best[CN];
             int code[CN];
-#pragma unroll
-            for (int e = 0; e < CN; ++e) { best[e] = NEG_INF; code[e] = -1; }
-#pragma unroll UN
-            for (int d = 0; d < k; ++d) {
-                const int hh = h - r + d;
-                const bool ok = hh >= 0 && hh < a.H;
-                float v[CN];
-                Chunk<T>::load(RM + (size_t)(ok ? i + (d - r) * a.W : i) * 16, v);
-#pragma unroll
-                for (int e = 0; e < CN; ++e)
-                    if (ok && (code[e] < 0 || v[e] > best[e])) {
-                        best[e] = v[e];
-                        code[e] = d;
-                    }
-            }
+            window_first_max<T, K>(RM, i, a.W, i / a.W, a.H, k, best, code);
             store_codes<CN>(RR + (size_t)i * CN, code);
         }
         __syncthreads();  // X and RM are dead from here: V takes their place
@@ -554,35 +432,77 @@ __global__ __launch_bounds__(1024) void sppf_bwd_map_kernel(MapArgs a) {
     }
 }
 
-// LDS of the whole-map kernels per pixel: forward 2 x 16 B; backward G (4 CN) + X|RM / V (32 B >= 4 CN) + RC + RR (2 CN)
-static size_t sppf_map_lds(int hw, int cn, bool bwd) { return (size_t)hw * (bwd ? 4 * cn + 32 + 2 * cn : 32); }
-static const size_t SPPF_MAP_LDS_MAX = 150 * 1024;
-static int sppf_map_threads(int hw) { const int t = (hw + 63) / 64 * 64; return t < 64 ? 64 : (t > 1024 ? 1024 : t); }
+// LDS of the whole-map backward per pixel: G (4 CN) + X|RM / V (32 B >= 4 CN) + RC + RR (2 CN)
+static size_t sppf_bwd_map_lds(int hw, int cn) { return (size_t)hw * (4 * cn + 32 + 2 * cn); }
 
-template <typename T>
-static void launch_sppf_map(bool bwd, const MapArgs& a, size_t lds, hipStream_t s) {
-    constexpr int CN = Chunk<T>::N;
-    const dim3 grid((unsigned)(a.C / CN), (unsigned)a.N), block((unsigned)sppf_map_threads(a.H * a.W));
-#define YMI_SPPF_MAP(KERN, KK)                                                                                                    \
-    do {                                                                                                                          \
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(KERN<T, KK>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-        hipLaunchKernelGGL((KERN<T, KK>), grid, block, lds, s, a);                                                                \
-    } while (0)
-    if (bwd) {
-        if (a.k == 5) YMI_SPPF_MAP(sppf_bwd_map_kernel, 5);
-        else if (a.k == 7) YMI_SPPF_MAP(sppf_bwd_map_kernel, 7);
-        else YMI_SPPF_MAP(sppf_bwd_map_kernel, 0);
-    } else {
-        if (a.k == 5) YMI_SPPF_MAP(sppf_fwd_map_kernel, 5);
-        else if (a.k == 7) YMI_SPPF_MAP(sppf_fwd_map_kernel, 7);
-        else YMI_SPPF_MAP(sppf_fwd_map_kernel, 0);
+// ------------------------------------------------------------------------------------------- host
+static const size_t POOL_LDS_MAX = 150 * 1024;  // the map forms run where the whole map fits this; the tiled forms halve their tile until it does
+static int sppf_map_threads(int hw) { const int t = (hw + 63) / 64 * 64; return t < 64 ? 64 : (t > 1024 ? 1024 : t); }
+static int cdiv(int a, int b) { return (a + b - 1) / b; }
+
+// tile of the tiled forms: the image, its longer side halved (down to 8) until bytes(th, tw) fits; false: it does not at 8 x 8
+template <typename F> static bool pool_fit_tile(int H, int W, F bytes, int* th, int* tw) {
+    *th = H; *tw = W;
+    while (bytes(*th, *tw) > POOL_LDS_MAX) {
+        if (*th >= *tw && *th > 8) *th = (*th + 1) / 2;
+        else if (*tw > 8) *tw = (*tw + 1) / 2;
+        else return false;
     }
-#undef YMI_SPPF_MAP
+    return true;
+}
+
+template <typename A> static void pool_launch(void (*kern)(A), dim3 grid, dim3 block, size_t lds, hipStream_t s, const A& a) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    hipLaunchKernelGGL(kern, grid, block, lds, s, a);
+}
+
+// f(Type<T>{}) for the tensor dtype (the tiled forms: they have the run-time k only); f(Form<T, K>{}) for the dtype and the compiled
+// window size K of the map forms (5, 7; 0 for every other k: the run-time one)
+template <typename T_> struct Type { using T = T_; };
+template <typename T_, int K_> struct Form {
+    using T = T_;
+    static constexpr int K = K_;
+};
+template <typename F> static void pool_dispatch_dtype(int dtype, F f) {
+    if (dtype == YMI_BF16) f(Type<bf16_t>{});
+    else f(Type<float>{});
+}
+template <typename F> static void pool_dispatch(int dtype, int k, F f) {
+    pool_dispatch_dtype(dtype, [&](auto t) {
+        using T = typename decltype(t)::T;
+        if (k == 5) f(Form<T, 5>{});
+        else if (k == 7) f(Form<T, 7>{});
+        else f(Form<T, 0>{});
+    });
+}
+
+// every tensor valid, of y0's shape and dtype, with c, ld and the base on 16-byte boundaries; k odd, at most 13
+static int pool_check_args(const char* who, std::initializer_list<const ymi_tensor*> ts, int64_t k) {
+    const ymi_tensor* y0 = *ts.begin();
+    const int cn = (y0 && y0->dtype == YMI_BF16) ? 8 : 4;
+    for (auto t : ts) {
+        YMI_CHECK_ARG(ymi_tensor_ok(t) && ymi_same_shape(t, y0) && t->dtype == y0->dtype, "%s: tensors must share shape and dtype", who);
+        YMI_CHECK_ARG(t->c % cn == 0 && t->ld % cn == 0 && ((uintptr_t)t->data & 15) == 0, "%s: channels/ld/base must be 16-byte aligned", who);
+    }
+    YMI_CHECK_ARG(k >= 1 && (k & 1) && k <= 13, "%s: odd k <= 13", who);
+    return YMI_OK;
+}
+
+static int launch_pool_bwd(const ymi_tensor* x, int k, PV gout, const ymi_tensor* gsrc, PV gin, hipStream_t stream) {
+    PoolBwdArgs a{};
+    a.x = pv(x); a.gout = gout; a.gsrc = pv(gsrc); a.gin = gin;
+    a.N = (int)x->n; a.H = (int)x->h; a.W = (int)x->w; a.C = (int)x->c; a.k = k;
+    const int cn = x->dtype == YMI_BF16 ? 8 : 4;
+    auto bytes = [&](int th, int tw) { return maxpool_bwd_lds(a.H, a.W, k / 2, th, tw, cn); };
+    YMI_CHECK_ARG(pool_fit_tile(a.H, a.W, bytes, &a.TH, &a.TW), "sppf_pool3_bwd: tile does not fit LDS");
+    const dim3 grid(cdiv(a.H, a.TH) * cdiv(a.W, a.TW), cdiv(a.C, 4 * cn), a.N);
+    pool_dispatch_dtype(x->dtype, [&](auto t) { pool_launch(maxpool_bwd_kernel<typename decltype(t)::T>, grid, dim3(256), bytes(a.TH, a.TW), stream, a); });
+    YMI_CHECK_LAUNCH("sppf_pool3_bwd");
+    return YMI_OK;
 }
 
 extern "C" int64_t ymi_sppf_pool3_bwd_workspace(int64_t n, int64_t h, int64_t w, int64_t c, int dtype) {
-    const int cn = dtype == YMI_BF16 ? 8 : 4;
-    if (sppf_map_lds((int)(h * w), cn, true) <= SPPF_MAP_LDS_MAX) return 0;
+    if (sppf_bwd_map_lds((int)(h * w), dtype == YMI_BF16 ? 8 : 4) <= POOL_LDS_MAX) return 0;
     return 2 * n * h * w * c * (int64_t)ymi_esize(dtype);  // the two intermediate gradients of the per-stage path
 }
 
@@ -590,71 +510,49 @@ extern "C" int64_t ymi_sppf_pool3_bwd_workspace(int64_t n, int64_t h, int64_t w,
 extern "C" int ymi_sppf_pool3_bwd(const ymi_tensor* y0, const ymi_tensor* y1, const ymi_tensor* y2, int64_t k, const ymi_tensor* dy0,
                                   const ymi_tensor* dy1, const ymi_tensor* dy2, const ymi_tensor* dy3, const ymi_tensor* dx, void* workspace,
                                   int64_t workspace_bytes, void* stream) {
-    const ymi_tensor* ts[8] = {y0, y1, y2, dy0, dy1, dy2, dy3, dx};
-    const int cn = (y0 && y0->dtype == YMI_BF16) ? 8 : 4;
-    for (auto t : ts) {
-        YMI_CHECK_ARG(ymi_tensor_ok(t) && ymi_same_shape(t, y0) && t->dtype == y0->dtype, "sppf_pool3_bwd: tensors must share shape and dtype");
-        YMI_CHECK_ARG(t->c % cn == 0 && t->ld % cn == 0 && ((uintptr_t)t->data & 15) == 0, "sppf_pool3_bwd: 16-byte alignment");
-    }
-    YMI_CHECK_ARG(k >= 1 && (k & 1) && k <= 13, "sppf_pool3_bwd: odd k <= 13");
+    if (int rc = pool_check_args("sppf_pool3_bwd", {y0, y1, y2, dy0, dy1, dy2, dy3, dx}, k)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    const int hw = (int)(y0->h * y0->w);
-    const size_t lds = sppf_map_lds(hw, cn, true);
-    if (lds <= SPPF_MAP_LDS_MAX) {
-        MapArgs a{};
-        a.y[0] = PV{y0->data, y0->ld}; a.y[1] = PV{y1->data, y1->ld}; a.y[2] = PV{y2->data, y2->ld};
-        a.dy[0] = PV{dy0->data, dy0->ld}; a.dy[1] = PV{dy1->data, dy1->ld}; a.dy[2] = PV{dy2->data, dy2->ld}; a.dy[3] = PV{dy3->data, dy3->ld};
-        a.dx = PV{dx->data, dx->ld};
-        a.N = (int)y0->n; a.H = (int)y0->h; a.W = (int)y0->w; a.C = (int)y0->c; a.k = (int)k;
-        if (y0->dtype == YMI_BF16) launch_sppf_map<bf16_t>(true, a, lds, s);
-        else launch_sppf_map<float>(true, a, lds, s);
+    const int cn = y0->dtype == YMI_BF16 ? 8 : 4, hw = (int)(y0->h * y0->w);
+    const size_t lds = sppf_bwd_map_lds(hw, cn);
+    if (lds <= POOL_LDS_MAX) {
+        MapBwdArgs a{{pv(y0), pv(y1), pv(y2)}, {pv(dy0), pv(dy1), pv(dy2), pv(dy3)}, pv(dx), (int)y0->n, (int)y0->h, (int)y0->w, (int)y0->c, (int)k};
+        const dim3 grid((unsigned)(a.C / cn), (unsigned)a.N), block((unsigned)sppf_map_threads(hw));
+        pool_dispatch(y0->dtype, a.k, [&](auto f) {
+            using F = decltype(f);
+            pool_launch(sppf_bwd_map_kernel<typename F::T, F::K>, grid, block, lds, s, a);
+        });
         YMI_CHECK_LAUNCH("sppf_pool3_bwd(map)");
         return YMI_OK;
     }
     const int64_t one = y0->n * y0->h * y0->w * y0->c * (int64_t)ymi_esize(y0->dtype);
     YMI_CHECK_ARG(workspace && workspace_bytes >= 2 * one && ((uintptr_t)workspace & 15) == 0, "sppf_pool3_bwd: workspace (see ymi_sppf_pool3_bwd_workspace)");
     const PV g2{workspace, y0->c}, g1{(char*)workspace + one, y0->c};
-    int rc = launch_pool_bwd(y2, (int)k, PV{dy3->data, dy3->ld}, dy2, g2, s);
+    int rc = launch_pool_bwd(y2, (int)k, pv(dy3), dy2, g2, s);
     if (rc) return rc;
     rc = launch_pool_bwd(y1, (int)k, g2, dy1, g1, s);
     if (rc) return rc;
-    return launch_pool_bwd(y0, (int)k, g1, dy0, PV{dx->data, dx->ld}, s);
+    return launch_pool_bwd(y0, (int)k, g1, dy0, pv(dx), s);
 }
 
 extern "C" int ymi_sppf_pool3_fwd(const ymi_tensor* y0, int64_t k, const ymi_tensor* y1, const ymi_tensor* y2, const ymi_tensor* y3, void* stream) {
-    YMI_CHECK_ARG(ymi_tensor_ok(y0) && ymi_tensor_ok(y1) && ymi_tensor_ok(y2) && ymi_tensor_ok(y3), "sppf_pool3_fwd: bad tensor");
-    YMI_CHECK_ARG(ymi_same_shape(y0, y1) && ymi_same_shape(y0, y2) && ymi_same_shape(y0, y3), "sppf_pool3_fwd: shapes");
-    YMI_CHECK_ARG(y0->dtype == y1->dtype && y0->dtype == y2->dtype && y0->dtype == y3->dtype, "sppf_pool3_fwd: dtypes");
-    YMI_CHECK_ARG(k >= 1 && (k & 1) && k <= 13, "sppf_pool3_fwd: odd k <= 13");
-    const int cn = y0->dtype == YMI_BF16 ? 8 : 4;
-    const ymi_tensor* ts[4] = {y0, y1, y2, y3};
-    for (auto t : ts)
-        YMI_CHECK_ARG(t->c % cn == 0 && t->ld % cn == 0 && ((uintptr_t)t->data & 15) == 0, "sppf_pool3_fwd: channels/ld/base must be 16-byte aligned");
-    if (sppf_map_lds((int)(y0->h * y0->w), cn, false) <= SPPF_MAP_LDS_MAX) {  // whole map per (image, 16-byte chunk) workgroup
-        MapArgs m{};
-        m.y[0] = PV{y0->data, y0->ld}; m.y[1] = PV{y1->data, y1->ld}; m.y[2] = PV{y2->data, y2->ld}; m.y[3] = PV{y3->data, y3->ld};
-        m.N = (int)y0->n; m.H = (int)y0->h; m.W = (int)y0->w; m.C = (int)y0->c; m.k = (int)k;
-        const size_t mlds = sppf_map_lds((int)(y0->h * y0->w), cn, false);
-        if (y0->dtype == YMI_BF16) launch_sppf_map<bf16_t>(false, m, mlds, (hipStream_t)stream);
-        else launch_sppf_map<float>(false, m, mlds, (hipStream_t)stream);
+    if (int rc = pool_check_args("sppf_pool3_fwd", {y0, y1, y2, y3}, k)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    PoolArgs a{{pv(y0), pv(y1), pv(y2), pv(y3)}, (int)y0->n, (int)y0->h, (int)y0->w, (int)y0->c, (int)k, (int)y0->h, (int)y0->w};
+    const int cn = y0->dtype == YMI_BF16 ? 8 : 4, r = a.k / 2;
+    const size_t map_lds = sppf_fwd_lds(a.H, a.W, r, a.H, a.W, 1);
+    if (map_lds <= POOL_LDS_MAX) {  // whole map per (image, 16-byte chunk) workgroup
+        const dim3 grid((unsigned)(a.C / cn), (unsigned)a.N), block((unsigned)sppf_map_threads(a.H * a.W));
+        pool_dispatch(y0->dtype, a.k, [&](auto f) {
+            using F = decltype(f);
+            pool_launch(sppf_pool3_kernel<typename F::T, 1, F::K>, grid, block, map_lds, s, a);
+        });
         YMI_CHECK_LAUNCH("sppf_pool3_fwd(map)");
         return YMI_OK;
     }
-    PoolArgs a{};
-    a.y0 = PV{y0->data, y0->ld}; a.y1 = PV{y1->data, y1->ld}; a.y2 = PV{y2->data, y2->ld}; a.y3 = PV{y3->data, y3->ld};
-    a.N = (int)y0->n; a.H = (int)y0->h; a.W = (int)y0->w; a.C = (int)y0->c; a.k = (int)k;
-    size_t lds = 0;
-    YMI_CHECK_ARG(pool_geometry(a.H, a.W, a.k, 0, &a.TH, &a.TW, &lds), "sppf_pool3_fwd: tile does not fit LDS");
-    const int cs = y0->dtype == YMI_BF16 ? 32 : 16;
-    dim3 grid(((a.H + a.TH - 1) / a.TH) * ((a.W + a.TW - 1) / a.TW), (a.C + cs - 1) / cs, a.N);
-    if (y0->dtype == YMI_BF16) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sppf_pool3_kernel<bf16_t>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipLaunchKernelGGL(sppf_pool3_kernel<bf16_t>, grid, dim3(256), lds, (hipStream_t)stream, a);
-    } else {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(sppf_pool3_kernel<float>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        hipLaunchKernelGGL(sppf_pool3_kernel<float>, grid, dim3(256), lds, (hipStream_t)stream, a);
-    }
+    auto bytes = [&](int th, int tw) { return sppf_fwd_lds(a.H, a.W, r, th, tw, 4); };
+    YMI_CHECK_ARG(pool_fit_tile(a.H, a.W, bytes, &a.TH, &a.TW), "sppf_pool3_fwd: tile does not fit LDS");
+    const dim3 grid(cdiv(a.H, a.TH) * cdiv(a.W, a.TW), cdiv(a.C, 4 * cn), a.N);
+    pool_dispatch_dtype(y0->dtype, [&](auto t) { pool_launch(sppf_pool3_kernel<typename decltype(t)::T, 4, 0>, grid, dim3(256), bytes(a.TH, a.TW), s, a); });
     YMI_CHECK_LAUNCH("sppf_pool3_fwd");
     return YMI_OK;
 }
-

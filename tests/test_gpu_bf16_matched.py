@@ -249,6 +249,14 @@ def test_maxpool_cascade_routes_ties_like_the_reference(k):
     (9, (2, 8, 13, 17), torch.float32),    # odd map, a window size without a compiled specialisation
     (3, (1, 16, 64, 64), torch.float32),   # backward too large for the whole-map kernel: stage by stage through the workspace
     (3, (1, 16, 96, 96), torch.float32),   # forward too: the tiled kernel
+    # The tiled kernels in bfloat16.  The tiled backward rounds the running gradient to bfloat16 between its three stages, and the
+    # equality below still holds EXACTLY, so it is not to be loosened: with these 16-level inputs every running gradient is a multiple
+    # of 1/8 below 32 in magnitude, which bfloat16 holds exactly (stage-by-stage rounding and one final rounding of the oracle's
+    # gradients give identical tensors for both shapes; largest magnitude 24.5 for the first row, 21.0 for the second).
+    (5, (1, 16, 48, 48), torch.bfloat16),  # 2304 px > 1920: tiled backward at the model's k (forward: map form); C = 16 is half a
+                                           # 32-channel slab (the overhang branch); 12 x 24 tiles, halos on both axes
+    (3, (1, 40, 72, 72), torch.bfloat16),  # 5184 px > 4800: tiled forward too; C = 40: one full slab and one of a single chunk
+    (9, (1, 8, 56, 56), torch.float32),    # tiled backward, run-time k, 4-pixel radius: 14 x 14 tiles of 149,120 LDS bytes, just under the limit
 ])
 def test_maxpool_cascade_ties_at_model_shapes(k, shape, dtype):
     """the same at the model's SPPF shapes against the oracle (whose tie rule the fixtures above pin to the reference); bf16: the
