@@ -114,10 +114,19 @@ def swin_mlp(u, fc1, fc2, residual=None):
     return _SwinMlp.apply(u, fc1.weight, fc1.bias, fc2.weight, fc2.bias, residual, join_of(u), join_of(residual) if residual is not None else None)
 
 
+# SwinBlock widths the model sends through the fused kernels.  The library supports 128, 256 and 384 (ymi_swin_ln_mlp_supported); a width is
+# listed here only where a SwinBlock forward + backward measured faster fused than unfused by more than the run-to-run spread
+# (profiles/swin_mlp_widths.txt, written by tools/probes/swin_mlp_widths.py): 256 is 5.0 % faster per block (spread 0.3 %); 384 measured 0.9 % SLOWER
+# (spread 0.3 %); 128 came out 12 % faster by the medians but inside a spread larger than the block's own time, which does not count as faster.
+# An unlisted width stays reachable through the C ABI and is tested there and through the module (tests/test_gpu_swin_mlp_widths.py).
+FUSED_SWIN_MLP_WIDTHS = (256,)
+
+
 def swin_ln_mlp_ok(x, fc1):
-    """SwinBlock's second half as the fused kernels of csrc/swin_mlp.hip: bfloat16 tokens of 256 channels (HOOKS["fused_swin_mlp"]: test / A-B hook)."""
+    """SwinBlock's second half as the fused kernels of csrc/swin_mlp.hip: bfloat16 tokens of a routed width (FUSED_SWIN_MLP_WIDTHS) whose hidden
+    width the library supports - a multiple of 32 within the width's LDS cap (HOOKS["fused_swin_mlp"]: test / A-B hook)."""
     return (HOOKS["fused_swin_mlp"] and x.dim() == 2 and x.is_cuda and x.dtype == torch.bfloat16 and x.stride(1) == 1 and x.stride(0) % 8 == 0
-            and bool(L().ymi_swin_ln_mlp_supported(x.shape[1], fc1.weight.shape[0], ymi_dtype(x.dtype))))
+            and x.shape[1] in FUSED_SWIN_MLP_WIDTHS and bool(L().ymi_swin_ln_mlp_supported(x.shape[1], fc1.weight.shape[0], ymi_dtype(x.dtype))))
 
 
 
@@ -160,7 +169,7 @@ class _SwinLnMlp(torch.autograd.Function):
         t, c = x.shape
         hidden = w1.shape[0]
         dout = grad_nhwc(dout, dtype)
-        # (the kernel stores whole 256-token tiles: post / dpre are the first t rows of padded buffers)
+        # (the kernel stores whole token tiles, 256 or 128 rows by width: post / dpre are the first t rows of buffers padded to 256)
         cap = L().ymi_swin_ln_mlp_pre_elems(t, hidden)
         post = torch.empty(cap, dtype=dtype, device=dev).view(-1, hidden)[:t]
         dpre = torch.empty(cap, dtype=dtype, device=dev).view(-1, hidden)[:t]

@@ -643,14 +643,22 @@ int ymi_swin_mlp_bwd_data(const ymi_tensor* dout, const void* w2_dgrad_packed, c
                           const void* w1_dgrad_packed, const ymi_tensor* add1, const ymi_tensor* add2, const ymi_tensor* du, void* stream);
 
 /* SwinBlock's second half as one kernel per direction: out = x + fc2(gelu(fc1(LayerNorm(x)))) - swin_block.py:53 with the modules of
- * swin_block.py:30-35 (norm2, mlp) - for bfloat16 tokens of 256 channels (csrc/swin_mlp.hip; `supported` says whether a shape takes this
- * path, anything else keeps ymi_layernorm_fwd + ymi_swin_mlp_fwd).  The [T, hidden] activations never reach HBM in the forward except, when
- * training, the bf16 pre-activations once, in a private register-order layout of ymi_swin_ln_mlp_pre_elems(T, hidden) elements.
- *   pack    : w1 [hidden][c], w2 [c][hidden] (float32, nn.Linear layouts) -> `packed`, ymi_swin_ln_mlp_pack_elems bfloat16 elements (four images)
+ * swin_block.py:30-35 (norm2, mlp) - for bfloat16 tokens of 128, 256 or 384 channels, the SwinBlock widths of the model files (csrc/swin_mlp.hip;
+ * `supported` says whether a shape takes this path, anything else keeps ymi_layernorm_fwd + ymi_swin_mlp_fwd).  The [T, hidden] activations
+ * never reach HBM in the forward except, when training, the bf16 pre-activations once, in a private register-order layout of
+ * ymi_swin_ln_mlp_pre_elems(T, hidden) elements.
+ *   supported: dtype bfloat16, c in {128, 256, 384}, hidden a multiple of 32 that leaves the fc1 bias room in LDS beside the weight ring:
+ *             hidden <= 8192 at c = 128 and 256, <= 4096 at c = 384
+ *   pack    : w1 [hidden][c], w2 [c][hidden] (float32, nn.Linear layouts) -> `packed`, ymi_swin_ln_mlp_pack_elems = 4 c hidden bfloat16 elements:
+ *             four images of c * hidden elements (fc1, fc2, fc2 transposed, fc1 transposed), each [hidden/32 chunks][32 c elements] with a chunk
+ *             laid out as the MFMA A fragments the kernels read - rows form [c/16 k-steps][64 lanes][8] (images 0, 2), cols form
+ *             [c/32 tiles][2 steps][64 lanes][8] (images 1, 3); a chunk image is 8 / 16 / 24 KB at c = 128 / 256 / 384
+ *   pre     : private, [tile][hidden/32 chunks][wave][2][64 lanes][8] bfloat16 with tiles of 256 tokens and 8 waves at c = 128 and 256, of 128
+ *             tokens and 4 waves at c = 384 (a wave = 32 tokens); pre_elems pads the token count to a multiple of 256, which both tiles divide
  *   fwd     : u / mean / rstd / pre non-null = training (u: LayerNorm output [T][c], saved for fc1's weight gradient and LayerNorm's backward)
  *   bwd_data: post = gelu(pre) and dpre = (dout W2) * gelu'(pre), both [T][hidden] row-major for the two weight-gradient GEMMs
  *             (ymi_conv2d_bwd_weight on (post, dout) and (u, dpre)); du = dpre W1 [T][c], LayerNorm's incoming gradient.  The kernel stores whole
- *             256-token tiles: post / dpre are dense (ld == hidden) views of the first T rows of buffers of ymi_swin_ln_mlp_pre_elems elements. */
+ *             token tiles (256 or 128 rows, as above): post / dpre are dense (ld == hidden) views of the first T rows of buffers of ymi_swin_ln_mlp_pre_elems elements. */
 int ymi_swin_ln_mlp_supported(int64_t c, int64_t hidden, int32_t dtype);
 int64_t ymi_swin_ln_mlp_pack_elems(int64_t c, int64_t hidden);
 int64_t ymi_swin_ln_mlp_pre_elems(int64_t tokens, int64_t hidden);
