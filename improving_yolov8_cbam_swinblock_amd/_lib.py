@@ -90,6 +90,12 @@ _SIGNATURES = {
     "ymi_bn_act_bwd_pair": (_c_i32, [_TP, _TP, _vp, _vp, _vp, _vp, _c_i64, _vp, _vp, _c_i32, _TP, _vp, _vp, _vp, _sz, _vp]),
     "ymi_conv2d_bwd_data": (_c_i32, [_TP, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _TP, _vp]),
     "ymi_conv2d_bwd_data_add": (_c_i32, [_TP, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _TP, _TP, _TP, _vp]),
+    "ymi_dwconv2d_fwd": (_c_i32, [_TP, _vp, _c_i64, _c_i64, _vp, _vp, _c_i32, _TP, _TP, _vp, ctypes.POINTER(_c_i64), _vp]),
+    "ymi_dwconv2d_stat_blocks": (_c_i64, [_c_i64, _c_i64, _c_i64, _c_i64]),
+    "ymi_dwconv2d_bn_act_fwd": (_c_i32, [_TP, _vp, _c_i64, _c_i64, _vp, _vp, _vp, _vp, _c_f32, _c_f32, _c_i32, _TP, _TP, _TP, _vp, _vp, _vp, _sz, _vp]),
+    "ymi_dwconv2d_bwd_data": (_c_i32, [_TP, _vp, _c_i64, _c_i64, _TP, _TP, _vp]),
+    "ymi_dwconv2d_bwd_weight": (_c_i32, [_TP, _TP, _c_i64, _c_i64, _vp, _vp, _sz, _vp]),
+    "ymi_dwconv2d_bwd_weight_workspace": (_sz, [_c_i64, _c_i64, _c_i64, _c_i64, _c_i64]),
     "ymi_swin_mlp_fwd": (_c_i32, [_TP, _vp, _vp, _c_i64, _vp, _vp, _TP, _TP, _TP, _TP, _vp]),
     "ymi_swin_ln_mlp_supported": (_c_i32, [_c_i64, _c_i64, _c_i32]),
     "ymi_swin_ln_mlp_pack_elems": (_c_i64, [_c_i64, _c_i64]),

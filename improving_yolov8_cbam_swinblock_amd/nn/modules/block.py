@@ -3,7 +3,7 @@ import torch
 import torch.nn as nn
 
 from ... import ops
-from .conv import Conv
+from .conv import Conv, DWConv, GhostConv
 
 
 class DFL(nn.Module):
@@ -110,3 +110,59 @@ class SPPF(nn.Module):
             cat = ops.empty_nhwc(n, 4 * c_, h, w, x.dtype, x.device)  # cv1 writes y0 straight into slice 0 of the concat buffer
         y0 = self.cv1(x, out=ops.OutSlot(cat, 0) if cat is not None else None)
         return self.cv2(ops.sppf_pool_cat(y0, self.m.kernel_size, cat), out=out)
+
+
+class C3(nn.Module):
+    """cv3(cat(m(cv1(x)), cv2(x))) with n Bottlenecks of kernels (1, 1), (3, 3) (reference block.py:314-338).  In train mode the last
+    Bottleneck and cv2 write their halves of the concat buffer."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__()
+        c_ = int(c2 * e)
+        self.cv1 = Conv(c1, c_, 1, 1)
+        self.cv2 = Conv(c1, c_, 1, 1)
+        self.cv3 = Conv(2 * c_, c2, 1)
+        self.m = nn.Sequential(*(Bottleneck(c_, c_, shortcut, g, k=((1, 1), (3, 3)), e=1.0) for _ in range(n)))
+
+    def forward(self, x):
+        x = ops.to_internal(x)
+        c_ = self.cv2.conv.out_channels
+        buf, slot = None, (lambda j: None)
+        if self.training and hasattr(self.cv2, "bn") and c_ % ops.chunk_elems(x.dtype) == 0:
+            n, _, h, w = x.shape
+            buf = ops.empty_nhwc(n, 2 * c_, h, w, x.dtype, x.device)
+            slot = lambda j: ops.OutSlot(buf, j * c_)  # noqa: E731
+        a = self.cv1(x)
+        for j, m in enumerate(self.m):
+            # (a Bottleneck takes an output slot; a GhostBottleneck's sum is its own launch and reaches the buffer through the concat's copy)
+            a = m(a, out=slot(0)) if (isinstance(m, Bottleneck) and j == len(self.m) - 1) else m(a)
+        b = self.cv2(x, out=slot(1))
+        return self.cv3(ops.concat([a, b], buf))
+
+
+class GhostBottleneck(nn.Module):
+    """conv(x) + shortcut(x): GhostConv -> (stride 2: depthwise) -> GhostConv without activation, beside an identity or a depthwise +
+    pointwise shortcut (reference block.py:426-452)."""
+
+    def __init__(self, c1, c2, k=3, s=1):
+        super().__init__()
+        c_ = c2 // 2
+        self.conv = nn.Sequential(
+            GhostConv(c1, c_, 1, 1),
+            DWConv(c_, c_, k, s, act=False) if s == 2 else nn.Identity(),
+            GhostConv(c_, c2, 1, 1, act=False),
+        )
+        self.shortcut = nn.Sequential(DWConv(c1, c1, k, s, act=False), Conv(c1, c2, 1, 1, act=False)) if s == 2 else nn.Identity()
+
+    def forward(self, x):
+        x = ops.to_internal(x)
+        return ops.add_residual(self.conv(x), self.shortcut(x))
+
+
+class C3Ghost(C3):
+    """C3 with GhostBottlenecks (reference block.py:406-423)."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        c_ = int(c2 * e)
+        self.m = nn.Sequential(*(GhostBottleneck(c_, c_) for _ in range(n)))

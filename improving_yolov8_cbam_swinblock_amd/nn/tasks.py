@@ -19,7 +19,7 @@ from .. import ops
 from ..utils.loss import DEFAULT_HYP, SplitPreds, v8DetectionLoss
 from ..utils.ops import make_divisible
 from ..utils.torch_utils import fuse_conv_and_bn, initialize_weights, intersect_dicts
-from .modules import C2f, CBAM, SPPF, Bottleneck, Concat, Conv, Detect, SwinBlock, Upsample
+from .modules import C2f, C3, CBAM, SPPF, Bottleneck, C3Ghost, Concat, Conv, Detect, DWConv, GhostBottleneck, GhostConv, SwinBlock, Upsample
 
 CFG_DIR = Path(__file__).resolve().parents[1] / "cfg" / "models" / "v8"
 
@@ -29,14 +29,19 @@ MODULES = {
     "C2f": C2f,
     "SPPF": SPPF,
     "Bottleneck": Bottleneck,
+    "DWConv": DWConv,
+    "GhostConv": GhostConv,
+    "GhostBottleneck": GhostBottleneck,
+    "C3": C3,
+    "C3Ghost": C3Ghost,
     "CBAM": CBAM,
     "SwinBlock": SwinBlock,
     "Concat": Concat,
     "Detect": Detect,
     "nn.Upsample": Upsample,  # the YAML's torch.nn.Upsample row runs as the HIP nearest-2x kernel
 }
-BASE_MODULES = frozenset({Conv, C2f, SPPF, Bottleneck})  # width-scaled (c1, c2, ...) constructors: tasks.py:1376-1413
-REPEAT_MODULES = frozenset({C2f})  # repeats passed as an argument: tasks.py:1414-1432
+BASE_MODULES = frozenset({Conv, C2f, SPPF, Bottleneck, DWConv, GhostConv, GhostBottleneck, C3, C3Ghost})  # width-scaled (c1, c2, ...) constructors: tasks.py:1376-1413
+REPEAT_MODULES = frozenset({C2f, C3, C3Ghost})  # repeats passed as an argument: tasks.py:1414-1432
 
 
 def guess_model_scale(model_path):
@@ -332,6 +337,13 @@ class DetectionModel(BaseModel):
                     src = (mod.conv.out_channels, src[1] * mod.conv.stride[0])
                 elif isinstance(mod, (C2f, SPPF)):
                     src = (mod.cv2.conv.out_channels, src[1])
+                elif isinstance(mod, C3):  # (C3Ghost too)
+                    src = (mod.cv3.conv.out_channels, src[1])
+                elif isinstance(mod, GhostConv):
+                    src = (2 * mod.cv1.conv.out_channels, src[1] * mod.cv1.conv.stride[0])
+                elif isinstance(mod, GhostBottleneck):
+                    dw = mod.conv[1]
+                    src = (2 * mod.conv[2].cv1.conv.out_channels, src[1] * (dw.conv.stride[0] if isinstance(dw, Conv) else 1))
                 elif isinstance(mod, Bottleneck):
                     src = (mod.cv2.conv.out_channels, src[1])
                 elif isinstance(mod, Upsample):

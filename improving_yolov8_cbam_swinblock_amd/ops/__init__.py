@@ -29,6 +29,7 @@ from .conv import (  # noqa: F401
     _dgrad_multi, _dgrad_prepare, _per_level, _width_class, chan_split2, conv_affine_act, conv_bn_act, conv_bn_act_pair, detect_train, detect_train_ok,
     first_conv_bn_act, first_conv_ok, linear, padded_grad_like,
 )
+from .dwconv import _DwConvAffineAct, _DwConvBnAct, dwconv_affine_act, dwconv_bn_act  # noqa: F401
 from .blocks import (  # noqa: F401
     _Act, _AddResidual, _C2fSplit, _Cbam, _Concat, _DetectLoss, _LayerNorm, _SppfPool, _SwinLnMlp, _SwinMlp, _Upsample2x, _WindowAttention,
     _WindowReverse, _map_array, add_residual, c2f_split, cbam, concat, detect_decode, detect_loss, detect_nms, detect_targets, gelu, layernorm, sppf_pool_cat,

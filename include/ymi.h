@@ -278,6 +278,37 @@ int ymi_first_conv_bn_act_bwd(const ymi_tensor* x4, const float* weight_oihw, in
                               const float* save_mean, const float* save_invstd, int32_t act, const ymi_tensor* dout, float* dgamma, float* dbeta,
                               float* dw_oihw, void* workspace, size_t workspace_bytes, ymi_wgrad_pending* pending, void* stream);
 
+/* ------------------------------------------------------------------ depthwise convolution ---- */
+/* Pure depthwise convolutions (groups == cin == cout), csrc/dwconv.hip: square k in {3, 5}, stride in {1, 2}, pad k/2, dilation 1, NHWC;
+ * channels in whole 16-byte chunks (C % 8 == 0 in YMI_BF16, C % 4 == 0 in YMI_F32); every tensor may be a channel slice of a wider buffer.
+ * w is the module's own [C][1][k][k] float32 weight and enters the arithmetic as float32 (no packed copy); accumulation is float32; every
+ * output is rounded once, on store.  Direct kernels on the vector ALUs (no reduction over channels: nothing for the matrix pipe).
+ *
+ * y = act(scale[c] * conv(x, w) + bias[c]) + residual; scale, bias, residual may be NULL.  With stat_partials != NULL (scale, bias, residual
+ * NULL, act none) the raw output plus per-workgroup rows [blocks][2][C] - sum and sum of squares of the ROUNDED outputs, the contract of
+ * ymi_conv2d_fwd, so ymi_bn_finalize reads them unchanged; *host_stat_blocks receives `blocks` <= ymi_dwconv2d_stat_blocks().
+ * Replaces the grouped F.conv2d of nn/modules/conv.py:79,91 as DWConv (conv.py:194-209) and GhostConv.cv2 (conv.py:357-358,370-371) call it. */
+int ymi_dwconv2d_fwd(const ymi_tensor* x, const float* w, int64_t k, int64_t stride, const float* scale, const float* bias, int32_t act,
+                     const ymi_tensor* residual, const ymi_tensor* y, float* stat_partials, int64_t* host_stat_blocks, void* stream);
+int64_t ymi_dwconv2d_stat_blocks(int64_t n, int64_t ho, int64_t wo, int64_t c);
+/* The train-mode depthwise Conv block in one call: the kernel above (raw, statistics rows) -> ymi_bn_finalize -> ymi_scale_shift_act (with the
+ * optional residual).  Arguments as ymi_conv2d_bn_silu_fwd; workspace >= (ymi_dwconv2d_stat_blocks * 2 * C + 2 * C) * 4 bytes.  raw, save_mean
+ * and save_invstd are what ymi_bn_act_bwd takes.  Replaces Conv.forward, nn/modules/conv.py:69-79, for g == c1 == c2. */
+int ymi_dwconv2d_bn_act_fwd(const ymi_tensor* x, const float* w, int64_t k, int64_t stride, const float* gamma, const float* beta,
+                            float* running_mean, float* running_var, float momentum, float eps, int32_t act, const ymi_tensor* residual,
+                            const ymi_tensor* raw, const ymi_tensor* out, float* save_mean, float* save_invstd, void* workspace,
+                            size_t workspace_bytes, void* stream);
+/* dx = conv_transpose(dy, w) (+ add); add may be NULL and may BE dx (in-place accumulation: a thread reads its addend before it stores).
+ * Stride 1: the forward body with the taps rotated; stride 2: a gather over the taps of matching parity (no atomics).  Adjoint of conv.py:79
+ * for g == c1 == c2; the addend forms the gradient sum of GhostConv's y (conv.py:370-371: y feeds the concat and cv2). */
+int ymi_dwconv2d_bwd_data(const ymi_tensor* dy, const float* w, int64_t k, int64_t stride, const ymi_tensor* add, const ymi_tensor* dx, void* stream);
+/* dw ([C][1][k][k] float32, overwritten) = sum over pixels of dy * x per tap and channel: every workgroup sums its pixels on chip and stores
+ * one row [k*k][C] in `workspace`; a second launch adds the rows in a fixed order.  No float atomics: bit-identical from run to run.
+ * workspace >= ymi_dwconv2d_bwd_weight_workspace(dy->n, dy->h, dy->w, C, k) bytes.  Weight gradient of conv.py:79 for g == c1 == c2. */
+int ymi_dwconv2d_bwd_weight(const ymi_tensor* x, const ymi_tensor* dy, int64_t k, int64_t stride, float* dw, void* workspace,
+                            size_t workspace_bytes, void* stream);
+size_t ymi_dwconv2d_bwd_weight_workspace(int64_t n, int64_t ho, int64_t wo, int64_t c, int64_t k);
+
 /* -------------------------------------------------------------------- SPPF pooling cascade ---- */
 
 /* y1 = maxpool_k(y0), y2 = maxpool_k(y1), y3 = maxpool_k(y2), stride 1, pad k/2 (-inf):
