@@ -4,6 +4,8 @@
 #include <stdint.h>
 #include <stdio.h>
 
+#include <type_traits>
+
 #include "../../include/ymi.h"
 
 typedef __bf16 bf16_t;
@@ -74,6 +76,36 @@ enum YmiOpt {
 int ymi_opt(int id);
 static inline int ew_ppt() { return ymi_opt(OPT_EW_PPT); }
 static inline int ew_cap() { return ymi_opt(OPT_EW_CAP); }
+// workgroups of a streaming pass from the uncapped count: the cap (default 512, runtime.hip), then the same number on every XCD
+static inline int64_t ew_capped(int64_t gb) {
+    if (gb > ew_cap()) gb = ew_cap();
+    return (gb + 7) / 8 * 8;
+}
+// ONE grid rule for the passes whose threads keep a channel group (affine: elementwise.hip, BatchNorm backward apply: reduce_bwd.hip); a workgroup
+// covers `rows` pixels at a time.  Every thread reloads its group's coefficients: give it ~ew_ppt pixels when the tensor allows.  Small maps
+// (<= 13 MB here) are pure latency: with 256 blocks a thread walked 3-6 pixels one dependent round trip after the other (10 us for 1.6 MB);
+// give them up to one resident round of blocks, i.e. 1-2 pixels per thread
+static inline int64_t ew_blocks(int64_t P, int rows) {
+    int64_t gb = (P + (int64_t)rows * ew_ppt() - 1) / ((int64_t)rows * ew_ppt());
+    if (gb < 1024) gb = (P + rows - 1) / rows < 1024 ? (P + rows - 1) / rows : 1024;
+    return ew_capped(gb);
+}
+// ONE place that turns a run-time dtype / activation into template arguments: f(TypeTag<T>{}) and f(TypeTag<T>{}, ActTag<ACT>{})
+template <typename T> struct TypeTag {
+    typedef T type;
+};
+template <int ACT> using ActTag = std::integral_constant<int, ACT>;
+template <typename F> static inline void dispatch_dtype(int dtype, F&& f) {
+    if (dtype == YMI_BF16) f(TypeTag<bf16_t>{});
+    else f(TypeTag<float>{});
+}
+template <typename F> static inline void dispatch_dtype_act(int dtype, int act, F&& f) {
+    dispatch_dtype(dtype, [&](auto t) {
+        if (act == YMI_ACT_SILU) f(t, ActTag<YMI_ACT_SILU>{});
+        else if (act == YMI_ACT_GELU) f(t, ActTag<YMI_ACT_GELU>{});
+        else f(t, ActTag<YMI_ACT_NONE>{});
+    });
+}
 // a 16-byte block of zeros in device memory (source of out-of-bounds im2col taps)
 const void* ymi_zero_page();
 
@@ -182,6 +214,53 @@ __device__ __forceinline__ XcdRange xcd_range(int64_t P, int64_t span_arg) {
 
 __device__ __forceinline__ int xcd_unit(int flat, int total) { return (total & 7) ? flat : (flat & 7) * (total >> 3) + (flat >> 3); }
 __device__ __forceinline__ int flat_block_id() { return blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z); }
+
+// ---- the pixel walk of the streaming BatchNorm passes (affine: elementwise.hip; backward reduce and apply: reduce_bwd.hip) ------------------------
+// A thread keeps the four channels at `coff` and visits the pixels p, p + step, ... < end of one or two rows (a; b when `two`: a template fact
+// in the reduce pass, which passes a constant that folds after inlining, a uniform run-time fact - is there a residual - in the affine pass).
+// U pixels per trip: 2 U independent 8/16-byte loads in flight per lane before the first use; the NEXT trip's loads are issued (raw, unconverted:
+// 2 VGPRs each in bf16) before this trip's arithmetic, so a workgroup with several trips does not pay one full memory round trip per trip (4 waves
+// per SIMD are not enough to hide it: the arithmetic of a trip is as long as its loads).  The leftover pixels go one at a time.
+// use(va, vb, p) gets pixel p's values as floats; vb is zero without a second row.
+template <int U, typename T, typename F>
+__device__ __forceinline__ void pixel_walk(const T* ap, int64_t lda, const T* bp, int64_t ldb, bool two, int coff, int64_t p, int64_t step, int64_t end, F&& use) {
+    typedef typename Raw4<T>::type R4;
+    R4 ra[U], rb[U];
+    bool have = p + (U - 1) * step < end;
+    if (have) {
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            ra[u] = *reinterpret_cast<const R4*>(ap + (p + u * step) * lda + coff);
+            if (two) rb[u] = *reinterpret_cast<const R4*>(bp + (p + u * step) * ldb + coff);
+        }
+    }
+    while (have) {
+        float va[U][4], vb[U][4] = {};
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            Raw4<T>::to_f32(ra[u], va[u]);
+            if (two) Raw4<T>::to_f32(rb[u], vb[u]);
+        }
+        const int64_t pc = p;
+        p += U * step;
+        have = p + (U - 1) * step < end;
+        if (have) {
+#pragma unroll
+            for (int u = 0; u < U; ++u) {
+                ra[u] = *reinterpret_cast<const R4*>(ap + (p + u * step) * lda + coff);
+                if (two) rb[u] = *reinterpret_cast<const R4*>(bp + (p + u * step) * ldb + coff);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) use(va[u], vb[u], pc + u * step);
+    }
+    for (; p < end; p += step) {
+        float va[4], vb[4] = {0.f, 0.f, 0.f, 0.f};
+        Pack<T, 4>::load(ap + p * lda + coff, va);
+        if (two) Pack<T, 4>::load(bp + p * ldb + coff, vb);
+        use(va, vb, p);
+    }
+}
 
 __device__ __forceinline__ float fast_exp(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
 // 1 / (1 + e^-x) with v_exp_f32 + v_rcp_f32 (each ~1 ulp) instead of the IEEE division sequence
@@ -332,6 +411,22 @@ __device__ __forceinline__ void bn_coef_write(const BnCoefArgs& bn, int C, int c
     bn.coef[2 * C + c] = ga * p0;
     bn.coef[3 * C + c] = ga * p0 * p0 * k2;
     bn.coef[4 * C + c] = ga * p0 * (k1 + p1 * k2);
+}
+// ---- the train-mode statistics rule (elementwise.hip: bn_finalize_kernel and the affine pass's prologue) -----------------------------------------
+// from the sums of x and x^2 over `count` pixels: mean, clamped variance, 1 / sqrt(var + eps), all in double.  (The momentum step of the running
+// statistics stays written out at both callers: under -ffp-contract=fast its two products and their sum come out fused for some channels and not for
+// others, differently for every shape of the code around them, and the stored words follow - profiles/bnstream_refactor_ab.txt.)
+struct BnStat {
+    double mean, var;
+    float inv;
+};
+__device__ __forceinline__ BnStat bn_stat_of(double sum, double sumsq, double count, float eps) {
+    BnStat s;
+    s.mean = sum / count;
+    s.var = sumsq / count - s.mean * s.mean;
+    if (s.var < 0.0) s.var = 0.0;
+    s.inv = (float)(1.0 / sqrt(s.var + (double)eps));
+    return s;
 }
 // Workgroup w of NT threads (1024: chan_reduce_final_kernel; 256: a weight-gradient launch's rider workgroups) owns channels [32 w, 32 w + 32).
 // The partial rows go to 32 row slices (slice s: rows s, s + 32, ...); a thread plays 1024 / NT of them for its channel.  Per slice: four

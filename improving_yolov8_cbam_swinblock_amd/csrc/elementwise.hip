@@ -362,19 +362,15 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float* __restri
             s1 += red[0][q][cl];
             s2 += red[1][q][cl];
         }
-        const double mean = s1 / count;
-        double var = s2 / count - mean * mean;
-        if (var < 0.0) var = 0.0;
-        const float inv = (float)(1.0 / sqrt(var + (double)eps));
-        const float g = g_, b = b_;
-        const float sc = g * inv;
+        const BnStat st = bn_stat_of(s1, s2, count, eps);
+        const float sc = g_ * st.inv;
         scale[c] = sc;
-        shift[c] = b - (float)mean * sc;
-        if (smean) smean[c] = (float)mean;
-        if (sinv) sinv[c] = inv;
-        if (rmean) rmean[pc] = (1.0f - momentum) * rm_ + momentum * (float)mean;
+        shift[c] = b_ - (float)st.mean * sc;
+        if (smean) smean[c] = (float)st.mean;
+        if (sinv) sinv[c] = st.inv;
+        if (rmean) rmean[pc] = (1.0f - momentum) * rm_ + momentum * (float)st.mean;
         if (rvar) {
-            const double unb = count > 1.0 ? var * count / (count - 1.0) : var;
+            const double unb = count > 1.0 ? st.var * count / (count - 1.0) : st.var;
             rvar[pc] = (1.0f - momentum) * rv_ + momentum * (float)unb;
         }
     }
@@ -486,7 +482,7 @@ __global__ void scale_shift_act_kernel(TV x, const float* __restrict__ scale, co
 // all its pixels and holds scale/shift in registers; 8-byte (bf16) / 16-byte (f32) accesses, coalesced along C.
 // BatchNorm finalize folded into the affine pass (round 5): `fin.acc` holds the statistics of this layer as fixed-point sums
 // [4 replicas][2][C] (igemm.hip's statistics epilogue).  Every thread derives scale / shift of ITS four channels in the prologue (eight
-// 16-byte loads, all in flight together, double arithmetic as bn_finalize_kernel); workgroup 0 also writes the saved mean / inverse
+// 16-byte loads, all in flight together, the statistics rule is common.h bn_stat_of as in bn_finalize_kernel); workgroup 0 also writes the saved mean / inverse
 // deviation and updates the running statistics (conv.py:66-67; torch_utils.py:468-470 sets eps / momentum).  nullptr: scale / shift arrays.
 struct BnFin {
     const long long* acc;
@@ -507,7 +503,6 @@ __global__ __launch_bounds__(256) void scale_shift_act_fixed_kernel(TV x, const 
     // pixels of this workgroup's XCD only (common.h, XCD ownership of the pixel axis): the GEMM that wrote `x` and the one that will read
     // `o` give this XCD the same eighth
     const XcdRange xr = xcd_range(Pall, span);
-    const int64_t P = xr.hi;
     const int g = threadIdx.x % groups;
     const int rows_per_block = 256 / groups;
     if ((int)threadIdx.x >= rows_per_block * groups) return;  // group counts that do not divide 256 (192 channels: 48 groups, 5 rows, 16 idle threads); no barriers below
@@ -533,17 +528,14 @@ __global__ __launch_bounds__(256) void scale_shift_act_fixed_kernel(TV x, const 
         for (int r = 0; r < 4; ++r) {
             const long long s1 = (q[0][0][r >> 1][r & 1] + q[1][0][r >> 1][r & 1]) + (q[2][0][r >> 1][r & 1] + q[3][0][r >> 1][r & 1]);
             const long long s2 = (q[0][1][r >> 1][r & 1] + q[1][1][r >> 1][r & 1]) + (q[2][1][r >> 1][r & 1] + q[3][1][r >> 1][r & 1]);
-            const double mean = (double)s1 * fin.inv_scale / fin.count;
-            double var = (double)s2 * fin.inv_scale / fin.count - mean * mean;
-            if (var < 0.0) var = 0.0;
-            const float inv = (float)(1.0 / sqrt(var + (double)fin.eps));
-            sc[r] = ga[r] * inv;
-            sh[r] = be[r] - (float)mean * sc[r];
-            mean4[r] = (float)mean;
-            inv4[r] = inv;
+            const BnStat st = bn_stat_of((double)s1 * fin.inv_scale, (double)s2 * fin.inv_scale, fin.count, fin.eps);
+            sc[r] = ga[r] * st.inv;
+            sh[r] = be[r] - (float)st.mean * sc[r];
+            mean4[r] = (float)st.mean;
+            inv4[r] = st.inv;
             if (writer) {
-                rm[r] = (1.0f - fin.momentum) * rm[r] + fin.momentum * (float)mean;
-                const double unb = fin.count > 1.0 ? var * fin.count / (fin.count - 1.0) : var;
+                rm[r] = (1.0f - fin.momentum) * rm[r] + fin.momentum * (float)st.mean;
+                const double unb = fin.count > 1.0 ? st.var * fin.count / (fin.count - 1.0) : st.var;
                 rv[r] = (1.0f - fin.momentum) * rv[r] + fin.momentum * (float)unb;
             }
         }
@@ -563,77 +555,28 @@ __global__ __launch_bounds__(256) void scale_shift_act_fixed_kernel(TV x, const 
     const T* xp = reinterpret_cast<const T*>(x.p);
     const T* rp = reinterpret_cast<const T*>(res.p);
     T* op = reinterpret_cast<T*>(o.p);
-    auto one = [&](float (&v)[4], const float (&rr)[4], int64_t p) {
+    // (a zero residual is added all the same: -0.0 leaves as +0.0 with or without one)
+    auto one = [&](const float (&v)[4], const float (&rr)[4], int64_t p) {
+        float y[4];
 #pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = apply_act<ACT>(v[r] * sc[r] + sh[r]) + rr[r];
-        Pack<T, 4>::store(op + p * o.ld + g * 4, v);
+        for (int r = 0; r < 4; ++r) y[r] = apply_act<ACT>(v[r] * sc[r] + sh[r]) + rr[r];
+        Pack<T, 4>::store(op + p * o.ld + g * 4, y);
     };
     const int64_t step = (int64_t)xr.nbx * rows_per_block;
-    int64_t p = xr.lo + (int64_t)xr.bi * rows_per_block + threadIdx.x / groups;
-    // 4 pixels per trip: the loads of all four are in flight before the first use, and the NEXT trip's (raw) loads are issued before this
-    // trip's arithmetic (as in the BatchNorm backward passes, csrc/reduce_bwd.hip)
-    typedef typename Raw4<T>::type R4;
-    constexpr int U = EW_U;  // pixels per trip
-    R4 rv[U], rres[U];
-    bool have = p + (U - 1) * step < P;
-    if (have) {
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            rv[u] = *reinterpret_cast<const R4*>(xp + (p + u * step) * x.ld + g * 4);
-            if (rp) rres[u] = *reinterpret_cast<const R4*>(rp + (p + u * step) * res.ld + g * 4);
-        }
-    }
-    while (have) {
-        float v[U][4], rr[U][4] = {};
-#pragma unroll
-        for (int u = 0; u < U; ++u) {
-            Raw4<T>::to_f32(rv[u], v[u]);
-            if (rp) Raw4<T>::to_f32(rres[u], rr[u]);
-        }
-        const int64_t pc = p;
-        p += U * step;
-        have = p + (U - 1) * step < P;
-        if (have) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                rv[u] = *reinterpret_cast<const R4*>(xp + (p + u * step) * x.ld + g * 4);
-                if (rp) rres[u] = *reinterpret_cast<const R4*>(rp + (p + u * step) * res.ld + g * 4);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < U; ++u) one(v[u], rr[u], pc + u * step);
-    }
-    for (; p < P; p += step) {
-        float v[4], rr[4] = {0.f, 0.f, 0.f, 0.f};
-        Pack<T, 4>::load(xp + p * x.ld + g * 4, v);
-        if (rp) Pack<T, 4>::load(rp + p * res.ld + g * 4, rr);
-        one(v, rr, p);
-    }
+    pixel_walk<EW_U>(xp, x.ld, rp, res.ld, rp != nullptr, g * 4, xr.lo + (int64_t)xr.bi * rows_per_block + threadIdx.x / groups, step, xr.hi, one);
 }
 
-template <typename T>
 static void launch_ssa_fixed(const ymi_tensor* raw, const float* scale, const float* shift, int act, TV r, const ymi_tensor* out, hipStream_t s, const BnFin* fin = nullptr) {
     const int groups = (int)raw->c / 4;
     const int64_t P = ymi_pixels(raw);
-    const int rows = 256 / groups;
-    // every thread reloads its group's scale/shift: give it ~8 pixels when the tensor allows.  Small maps (<= 13 MB here) are pure
-    // latency: with 256 blocks a thread walked 3-6 pixels one dependent round trip after the other (10 us for 1.6 MB); give them
-    // up to one resident round of blocks, i.e. 1-2 pixels per thread
-    int64_t gb = (P + (int64_t)rows * ew_ppt() - 1) / ((int64_t)rows * ew_ppt());
-    if (gb < 1024) gb = (P + rows - 1) / rows < 1024 ? (P + rows - 1) / rows : 1024;
-    if (gb > ew_cap()) gb = ew_cap();  // default 1024: four 256-thread workgroups per CU (runtime.hip)
-    gb = (gb + 7) / 8 * 8;             // the same number of workgroups on every XCD
     const int64_t span = ymi_xcd_span_arg(P);
-    dim3 g((unsigned)gb), b(256);
-    if (fin) {
-        if (act == YMI_ACT_SILU) hipLaunchKernelGGL((scale_shift_act_fixed_kernel<T, YMI_ACT_SILU, true>), g, b, 0, s, tv(raw), scale, shift, r, tv(out), groups, P, span, *fin);
-        else if (act == YMI_ACT_GELU) hipLaunchKernelGGL((scale_shift_act_fixed_kernel<T, YMI_ACT_GELU, true>), g, b, 0, s, tv(raw), scale, shift, r, tv(out), groups, P, span, *fin);
-        else hipLaunchKernelGGL((scale_shift_act_fixed_kernel<T, YMI_ACT_NONE, true>), g, b, 0, s, tv(raw), scale, shift, r, tv(out), groups, P, span, *fin);
-        return;
-    }
-    if (act == YMI_ACT_SILU) hipLaunchKernelGGL((scale_shift_act_fixed_kernel<T, YMI_ACT_SILU>), g, b, 0, s, tv(raw), scale, shift, r, tv(out), groups, P, span);
-    else if (act == YMI_ACT_GELU) hipLaunchKernelGGL((scale_shift_act_fixed_kernel<T, YMI_ACT_GELU>), g, b, 0, s, tv(raw), scale, shift, r, tv(out), groups, P, span);
-    else hipLaunchKernelGGL((scale_shift_act_fixed_kernel<T, YMI_ACT_NONE>), g, b, 0, s, tv(raw), scale, shift, r, tv(out), groups, P, span);
+    dim3 g((unsigned)ew_blocks(P, 256 / groups)), b(256);
+    dispatch_dtype_act(raw->dtype, act, [&](auto t, auto a) {
+        typedef typename decltype(t)::type T;
+        constexpr int ACT = decltype(a)::value;
+        if (fin) hipLaunchKernelGGL((scale_shift_act_fixed_kernel<T, ACT, true>), g, b, 0, s, tv(raw), scale, shift, r, tv(out), groups, P, span, *fin);
+        else hipLaunchKernelGGL((scale_shift_act_fixed_kernel<T, ACT>), g, b, 0, s, tv(raw), scale, shift, r, tv(out), groups, P, span);
+    });
 }
 
 extern "C" int ymi_scale_shift_act(const ymi_tensor* raw, const float* scale, const float* shift, int32_t act, const ymi_tensor* residual,
@@ -647,18 +590,15 @@ extern "C" int ymi_scale_shift_act(const ymi_tensor* raw, const float* scale, co
     dim3 g = ew_grid(total), b(256);
     hipStream_t s = (hipStream_t)stream;
     if (vec && raw->c / 4 <= 256) {
-        if (raw->dtype == YMI_BF16) launch_ssa_fixed<bf16_t>(raw, scale, shift, act, r, out, s);
-        else launch_ssa_fixed<float>(raw, scale, shift, act, r, out, s);
+        launch_ssa_fixed(raw, scale, shift, act, r, out, s);
         YMI_CHECK_LAUNCH("scale_shift_act");
         return YMI_OK;
     }
-    if (raw->dtype == YMI_BF16) {
-        if (vec) hipLaunchKernelGGL((scale_shift_act_kernel<bf16_t, true>), g, b, 0, s, tv(raw), scale, shift, act, r, tv(out));
-        else hipLaunchKernelGGL((scale_shift_act_kernel<bf16_t, false>), g, b, 0, s, tv(raw), scale, shift, act, r, tv(out));
-    } else {
-        if (vec) hipLaunchKernelGGL((scale_shift_act_kernel<float, true>), g, b, 0, s, tv(raw), scale, shift, act, r, tv(out));
-        else hipLaunchKernelGGL((scale_shift_act_kernel<float, false>), g, b, 0, s, tv(raw), scale, shift, act, r, tv(out));
-    }
+    dispatch_dtype(raw->dtype, [&](auto t) {
+        typedef typename decltype(t)::type T;
+        if (vec) hipLaunchKernelGGL((scale_shift_act_kernel<T, true>), g, b, 0, s, tv(raw), scale, shift, act, r, tv(out));
+        else hipLaunchKernelGGL((scale_shift_act_kernel<T, false>), g, b, 0, s, tv(raw), scale, shift, act, r, tv(out));
+    });
     YMI_CHECK_LAUNCH("scale_shift_act");
     return YMI_OK;
 }
@@ -737,8 +677,7 @@ extern "C" int ymi_conv2d_bn_silu_fwd_acc(const ymi_tensor* x, const void* w_pac
     const BnFin fin{(const long long*)stat_acc, gamma, beta, running_mean, running_var, save_mean, save_invstd, (double)ymi_pixels(raw),
                     ldexp(1.0, -ymi_stat_fixed_point_shift(ymi_pixels(raw))), momentum, eps};
     TV r = residual ? tv(residual) : TV{nullptr, 0, 0, 0, 0, 0};
-    if (raw->dtype == YMI_BF16) launch_ssa_fixed<bf16_t>(raw, nullptr, nullptr, act, r, out, (hipStream_t)stream, &fin);
-    else launch_ssa_fixed<float>(raw, nullptr, nullptr, act, r, out, (hipStream_t)stream, &fin);
+    launch_ssa_fixed(raw, nullptr, nullptr, act, r, out, (hipStream_t)stream, &fin);
     YMI_CHECK_LAUNCH("conv2d_bn_silu_fwd_acc");
     return YMI_OK;
 }

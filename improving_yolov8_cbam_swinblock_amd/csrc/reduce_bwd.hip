@@ -81,47 +81,7 @@ __global__ void chan_reduce_kernel(RV a, RV b, int64_t P, int64_t span, int C, i
                 }
             }
         };
-        int64_t p = p0 + ty;
-        // 4 pixels per trip: 8 independent 8/16-byte loads in flight per lane before the first use; the NEXT trip's loads are issued
-        // (raw, unconverted: 2 VGPRs each in bf16) before this trip's arithmetic, so a workgroup with several trips does not pay one
-        // full memory round trip per trip (4 waves per SIMD are not enough to hide it: the arithmetic of a trip is as long as its loads)
-        typedef typename Raw4<T>::type R4;
-        constexpr int U = RED_U;  // pixels per trip
-        R4 ra[U], rb[U];
-        bool have = p + (U - 1) * (int64_t)rows < p1;
-        if (have) {
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                ra[u] = *reinterpret_cast<const R4*>(ap + (p + u * (int64_t)rows) * a.ld + tx * 4);
-                if (FN != 0) rb[u] = *reinterpret_cast<const R4*>(bp + (p + u * (int64_t)rows) * b.ld + tx * 4);
-            }
-        }
-        while (have) {
-            float va[U][4], vb[U][4];
-#pragma unroll
-            for (int u = 0; u < U; ++u) {
-                Raw4<T>::to_f32(ra[u], va[u]);
-                if (FN != 0) Raw4<T>::to_f32(rb[u], vb[u]);
-            }
-            const int64_t pc = p;
-            p += U * (int64_t)rows;
-            have = p + (U - 1) * (int64_t)rows < p1;
-            if (have) {
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    ra[u] = *reinterpret_cast<const R4*>(ap + (p + u * (int64_t)rows) * a.ld + tx * 4);
-                    if (FN != 0) rb[u] = *reinterpret_cast<const R4*>(bp + (p + u * (int64_t)rows) * b.ld + tx * 4);
-                }
-            }
-#pragma unroll
-            for (int u = 0; u < U; ++u) accum(va[u], vb[u], pc + u * (int64_t)rows);
-        }
-        for (; p < p1; p += rows) {
-            float va[4], vb[4];
-            Pack<T, 4>::load(ap + p * a.ld + tx * 4, va);
-            if (FN != 0) Pack<T, 4>::load(bp + p * b.ld + tx * 4, vb);
-            accum(va, vb, p);
-        }
+        pixel_walk<RED_U>(ap, a.ld, bp, b.ld, FN != 0, tx * 4, p0 + ty, (int64_t)rows, p1, accum);
     }
     float* my = red + ((size_t)ty * TG + tx) * 8;
 #pragma unroll
@@ -269,17 +229,12 @@ static int launch_chan_reduce(const ymi_tensor* a, const ymi_tensor* b, const fl
     YMI_CHECK_ARG(!tail.tickets || crows == 1, "%s: the in-kernel final pass covers at most 1024 channels", what);
     const size_t lds = (size_t)256 * 8 * sizeof(float);
     RV ra{a->data, a->ld}, rb{b ? b->data : nullptr, b ? b->ld : 0};
-#define YMI_CR(T, A) hipLaunchKernelGGL((chan_reduce_kernel<T, FN, A>), dim3(blocks, crows), dim3(256), lds, stream, ra, rb, P, ymi_xcd_span_arg(P), C, TG, gamma, beta, mean, inv, part, g2, tail)
-#define YMI_CR_T(T)                                                      \
-    do {                                                                 \
-        if (FN != 1 || act == YMI_ACT_NONE) YMI_CR(T, YMI_ACT_NONE);     \
-        else if (act == YMI_ACT_SILU) YMI_CR(T, YMI_ACT_SILU);           \
-        else YMI_CR(T, YMI_ACT_GELU);                                    \
-    } while (0)
-    if (a->dtype == YMI_BF16) YMI_CR_T(bf16_t);
-    else YMI_CR_T(float);
-#undef YMI_CR_T
-#undef YMI_CR
+    dispatch_dtype_act(a->dtype, act, [&](auto t, auto ac) {
+        typedef typename decltype(t)::type T;
+        constexpr int ACT = FN == 1 ? decltype(ac)::value : YMI_ACT_NONE;  // only the BatchNorm backward has an activation: 10 kernels, not 18
+        hipLaunchKernelGGL((chan_reduce_kernel<T, FN, ACT>), dim3(blocks, crows), dim3(256), lds, stream, ra, rb, P, ymi_xcd_span_arg(P), C, TG, gamma, beta, mean,
+                           inv, part, g2, tail);
+    });
     YMI_CHECK_LAUNCH(what);
     *blocks_out = blocks;
     return YMI_OK;
@@ -326,12 +281,12 @@ int ymi_ln_param_grads(const ymi_tensor* dy, const ymi_tensor* x, const float* m
 
 // draw = gamma*inv*(dz - mean(dz) - xhat*mean(dz*xhat)), dz = dy*act'(z), written with the per-channel coefficients the
 // final-reduce kernel prepared:  z = x*a0 + a1 ;  draw = dz*c0 - x*c1 - c2   (coef = [a0|a1|c0|c1|c2][C])
-// FIXED: the number of G-channel groups divides 256, so a thread keeps one channel group and its coefficients in
-// registers for all of its pixels.  G = 4 (8-byte bf16 / 16-byte f32 accesses) or 8 (bf16 only, 16-byte accesses).
-template <typename T, int G, bool FIXED, int ACT>
+// FIXED: the number of 4-channel groups (8-byte bf16 / 16-byte f32 accesses) is at most 256, so a thread keeps one channel group and its
+// coefficients in registers for all of its pixels.
+template <typename T, bool FIXED, int ACT>
 __global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(RV dout, RV raw, RV draw, int64_t Pall, int64_t span, int C, const float* __restrict__ coef) {
+    constexpr int G = 4;
     const int groups = C / G;
-    int64_t P = Pall;
     const T* dp = reinterpret_cast<const T*>(dout.p);
     const T* rp = reinterpret_cast<const T*>(raw.p);
     T* op = reinterpret_cast<T*>(const_cast<void*>(draw.p));
@@ -357,64 +312,12 @@ __global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(RV dout, RV raw, 
             }
             Pack<T, G>::store(op + p * draw.ld + g * G, o);
         };
-        constexpr int U = G == 8 ? 2 : APPLY_U;  // pixels per trip: 2*U independent loads in flight per lane
         // the pixels of this workgroup's XCD (common.h, XCD ownership of the pixel axis; the grid is a multiple of 8)
         const XcdRange xr = xcd_range(Pall, span);
-        P = xr.hi;
         const int64_t step = (int64_t)xr.nbx * rows;
-        int64_t p = xr.lo + (int64_t)xr.bi * rows + threadIdx.x / groups;
-        if constexpr (G == 4) {
-            // as in chan_reduce_kernel: the next trip's (raw) loads are in flight while this trip's arithmetic runs
-            typedef typename Raw4<T>::type R4;
-            R4 rd[U], rx[U];
-            bool have = p + (U - 1) * step < P;
-            if (have) {
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    rd[u] = *reinterpret_cast<const R4*>(dp + (p + u * step) * dout.ld + g * G);
-                    rx[u] = *reinterpret_cast<const R4*>(rp + (p + u * step) * raw.ld + g * G);
-                }
-            }
-            while (have) {
-                float d[U][G], x[U][G];
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    Raw4<T>::to_f32(rd[u], d[u]);
-                    Raw4<T>::to_f32(rx[u], x[u]);
-                }
-                const int64_t pc = p;
-                p += U * step;
-                have = p + (U - 1) * step < P;
-                if (have) {
-#pragma unroll
-                    for (int u = 0; u < U; ++u) {
-                        rd[u] = *reinterpret_cast<const R4*>(dp + (p + u * step) * dout.ld + g * G);
-                        rx[u] = *reinterpret_cast<const R4*>(rp + (p + u * step) * raw.ld + g * G);
-                    }
-                }
-#pragma unroll
-                for (int u = 0; u < U; ++u) one(d[u], x[u], pc + u * step);
-            }
-        } else {
-            for (; p + (U - 1) * step < P; p += U * step) {
-                float d[U][G], x[U][G];
-#pragma unroll
-                for (int u = 0; u < U; ++u) {
-                    Pack<T, G>::load(dp + (p + u * step) * dout.ld + g * G, d[u]);
-                    Pack<T, G>::load(rp + (p + u * step) * raw.ld + g * G, x[u]);
-                }
-#pragma unroll
-                for (int u = 0; u < U; ++u) one(d[u], x[u], p + u * step);
-            }
-        }
-        for (; p < P; p += step) {
-            float d[G], x[G];
-            Pack<T, G>::load(dp + p * dout.ld + g * G, d);
-            Pack<T, G>::load(rp + p * raw.ld + g * G, x);
-            one(d, x, p);
-        }
+        pixel_walk<APPLY_U>(dp, dout.ld, rp, raw.ld, true, g * G, xr.lo + (int64_t)xr.bi * rows + threadIdx.x / groups, step, xr.hi, one);
     } else {
-        const uint32_t total = (uint32_t)(P * groups), ugroups = (uint32_t)groups;  // host: P * groups < 2^31
+        const uint32_t total = (uint32_t)(Pall * groups), ugroups = (uint32_t)groups;  // host: Pall * groups < 2^31
         for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
             const uint32_t pu = i / ugroups;
             const int g = (int)(i - pu * ugroups);
@@ -437,41 +340,19 @@ __global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(RV dout, RV raw, 
 static int launch_bn_apply(const ymi_tensor* dout, const ymi_tensor* raw, const ymi_tensor* draw, int act, const float* coef, hipStream_t s) {
     const int64_t P = ymi_pixels(dout);
     const int C = (int)dout->c;
-    const bool bf = dout->dtype == YMI_BF16;
-    const int G = 4;  // 8-byte (bf16) / 16-byte (f32) channel groups (16-byte groups for bf16 measured equal in round 2: removed)
-    const int groups = C / G;
+    const int groups = C / 4;
     const bool fixed = groups <= 256;
     const int64_t total = P * groups;
     YMI_CHECK_ARG(total < (1ll << 31), "bn_act_bwd: tensor too large for 32-bit indexing");
-    int64_t gb;
-    if (fixed) {
-        // every thread reloads its group's coefficients: give it at least ~8 pixels when the tensor allows
-        const int rows = 256 / groups;
-        gb = (P + (int64_t)rows * ew_ppt() - 1) / ((int64_t)rows * ew_ppt());
-        if (gb < 1024) gb = (P + rows - 1) / rows < 1024 ? (P + rows - 1) / rows : 1024;  // small maps: latency, not bandwidth (see launch_ssa_fixed)
-    } else {
-        gb = (total + 255) / 256;
-    }
-    if (gb > ew_cap()) gb = ew_cap();
-    gb = (gb + 7) / 8 * 8;
+    const dim3 gb((unsigned)(fixed ? ew_blocks(P, 256 / groups) : ew_capped((total + 255) / 256)));
     const int64_t span = ymi_xcd_span_arg(P);
     RV a{dout->data, dout->ld}, b{raw->data, raw->ld}, o{draw->data, draw->ld};
-#define YMI_BWD_APPLY(T, GG, F, A) hipLaunchKernelGGL((bn_act_bwd_apply_kernel<T, GG, F, A>), dim3((unsigned)gb), dim3(256), 0, s, a, b, o, P, span, C, coef)
-#define YMI_BWD_APPLY_A(T, GG, F)                                          \
-    do {                                                                   \
-        if (act == YMI_ACT_SILU) YMI_BWD_APPLY(T, GG, F, YMI_ACT_SILU);      \
-        else if (act == YMI_ACT_GELU) YMI_BWD_APPLY(T, GG, F, YMI_ACT_GELU); \
-        else YMI_BWD_APPLY(T, GG, F, YMI_ACT_NONE);                         \
-    } while (0)
-    if (bf) {
-        if (fixed) YMI_BWD_APPLY_A(bf16_t, 4, true);
-        else YMI_BWD_APPLY_A(bf16_t, 4, false);
-    } else {
-        if (fixed) YMI_BWD_APPLY_A(float, 4, true);
-        else YMI_BWD_APPLY_A(float, 4, false);
-    }
-#undef YMI_BWD_APPLY_A
-#undef YMI_BWD_APPLY
+    dispatch_dtype_act(dout->dtype, act, [&](auto t, auto ac) {
+        typedef typename decltype(t)::type T;
+        constexpr int ACT = decltype(ac)::value;
+        if (fixed) hipLaunchKernelGGL((bn_act_bwd_apply_kernel<T, true, ACT>), gb, dim3(256), 0, s, a, b, o, P, span, C, coef);
+        else hipLaunchKernelGGL((bn_act_bwd_apply_kernel<T, false, ACT>), gb, dim3(256), 0, s, a, b, o, P, span, C, coef);
+    });
     YMI_CHECK_LAUNCH("bn_act_bwd(apply)");
     return YMI_OK;
 }
@@ -560,10 +441,9 @@ extern "C" int ymi_gelu_bwd(const ymi_tensor* pre, const ymi_tensor* dy, const y
     int64_t gb = (total + 255) / 256;
     if (gb > 4096) gb = 4096;
     RV a{pre->data, pre->ld}, b{dy->data, dy->ld}, o{dx->data, dx->ld};
-    if (pre->dtype == YMI_BF16)
-        hipLaunchKernelGGL(gelu_bwd_kernel<bf16_t>, dim3((unsigned)gb), dim3(256), 0, (hipStream_t)stream, a, b, o, P, (int)pre->c);
-    else
-        hipLaunchKernelGGL(gelu_bwd_kernel<float>, dim3((unsigned)gb), dim3(256), 0, (hipStream_t)stream, a, b, o, P, (int)pre->c);
+    dispatch_dtype(pre->dtype, [&](auto t) {
+        hipLaunchKernelGGL(gelu_bwd_kernel<typename decltype(t)::type>, dim3((unsigned)gb), dim3(256), 0, (hipStream_t)stream, a, b, o, P, (int)pre->c);
+    });
     YMI_CHECK_LAUNCH("gelu_bwd");
     return YMI_OK;
 }
