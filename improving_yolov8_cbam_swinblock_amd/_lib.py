@@ -123,7 +123,9 @@ _SIGNATURES = {
     "ymi_layernorm_bwd_add": (_c_i32, [_TP, _c_i64, _TP, _vp, _vp, _vp, _TP, _TP, _vp, _vp, _vp, _sz, _vp]),
     "ymi_window_attention_fwd": (_c_i32, [_TP, _c_i64, _c_i64, _TP, _vp, _vp]),
     "ymi_window_attention_bwd": (_c_i32, [_TP, _TP, _TP, _vp, _c_i64, _c_i64, _TP, _vp]),
-    "ymi_colsum": (_c_i32, [_TP, _vp, _vp, _sz, _vp]),
+    "ymi_psa_attention_fwd": (_c_i32, [_TP, _c_i64, _c_i64, _c_i64, _TP, _TP, _vp, _vp]),
+    "ymi_psa_attention_bwd": (_c_i32, [_TP, _TP, _TP, _vp, _TP, _c_i64, _c_i64, _c_i64, _TP, _vp]),
+    "ymi_colsum":(_c_i32, [_TP, _vp, _vp, _sz, _vp]),
     "ymi_gelu_bwd": (_c_i32, [_TP, _TP, _TP, _vp]),
     "ymi_detect_targets": (_c_i32, [_vp, _vp, _vp, _c_i64, _c_i64, _c_i64, ctypes.c_float, ctypes.c_float, _vp, _vp]),
     "ymi_detect_loss_sizes": (_c_i32, [_c_i64, _c_i64, _c_i64, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]),

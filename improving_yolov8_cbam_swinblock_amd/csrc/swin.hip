@@ -13,6 +13,8 @@
 //    reads), float32 -> one-tile (both operands K-contiguous rows: V and, in backward, dO / Q / K
 //    are transposed on the way into LDS).  They share the LDS description (AttnLds), the row
 //    softmax, the tile stores and the launch helper.
+//    The tiled family also serves the PSA attention of C2PSA (ymi_psa_attention_*, end of file): full-map attention per image on qkv packed
+//    per head as [q | k | v] with keys narrower than values - AttnArgs carries the per-head addresses and the two widths.
 //    Token GEMMs (QKV, proj, MLP) are ymi_conv2d_fwd with a 1x1 "kernel".
 #include <stdlib.h>
 
@@ -435,10 +437,15 @@ __device__ __forceinline__ void lds_load_transposed(char* G, const T* src, int64
     }
 }
 
+// hd: width of a head in out / dout (and, in the one-tile and tr kernels, of Q, K and V: they read the nn.MultiheadAttention packing through C).
+// The tiled kernels take every qkv address from qo / ko / vo (channel of head 0's Q, K, V in a qkv row) and hs (channels between heads), contract the
+// scores over kd channels and the values over hd: the MultiheadAttention packing is (0, C, 2C, hd, kd = hd), the per-head [q | k | v] packing of the
+// PSA entry points (0, kd, 2 kd, 2 kd + hd).  vout: V compacted to [T, heads*hd] (forward); dvadd: added into dV (backward); either may be null.
 struct AttnArgs {
-    SV qkv, out, dout, dqkv;
+    SV qkv, out, dout, dqkv, vout, dvadd;
     float* lse;
     int L, heads, C, hd, hdp;
+    int qo, ko, vo, hs, kd;
     float scale;
 };
 
@@ -948,13 +955,24 @@ __global__ __launch_bounds__(256) void window_attn_tiled_fwd_kernel(AttnArgs a) 
     float* al = reinterpret_cast<float*>(smem + lds.floats());  // [64] rescale factor of this key tile / final 1/l
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int l15 = lane & 15, l4 = lane >> 4;
-    const int L = a.L, hd = a.hd;
+    const int L = a.L, hd = a.hd, kd = a.kd;
     const int head = blockIdx.y, co = head * hd;
+    const int qc = a.qo + head * a.hs, kc = a.ko + head * a.hs, vc = a.vo + head * a.hs;
     const int q0 = blockIdx.z * 64, qrows = (L - q0 < 64) ? L - q0 : 64;
     const int64_t t0 = (int64_t)blockIdx.x * L;
     const T* qkv = reinterpret_cast<const T*>(a.qkv.p) + t0 * a.qkv.ld;
     T* out = reinterpret_cast<T*>(const_cast<void*>(a.out.p)) + t0 * a.out.ld;
     const int ndt = (hd + 15) / 16;
+    if (a.vout.p) {  // V of this head, rows q0 .. q0 + qrows - 1, compacted: each (head, query tile) workgroup copies its own rows
+        T* vout = reinterpret_cast<T*>(const_cast<void*>(a.vout.p)) + (t0 + q0) * a.vout.ld + co;
+        const int g4 = hd / 4;
+        for (int i = threadIdx.x; i < qrows * g4; i += 256) {
+            const int r = i / g4, c = (i - r * g4) * 4;
+            float v[4];
+            Pack<T, 4>::load(qkv + (int64_t)(q0 + r) * a.qkv.ld + vc + c, v);
+            Pack<T, 4>::store(vout + (int64_t)r * a.vout.ld + c, v);
+        }
+    }
     f32x4 o[ATT_MAXDT];
 #pragma unroll
     for (int dt = 0; dt < ATT_MAXDT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -965,11 +983,11 @@ __global__ __launch_bounds__(256) void window_attn_tiled_fwd_kernel(AttnArgs a) 
         f32x4 s[4];
 #pragma unroll
         for (int t = 0; t < 4; ++t) s[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-        for (int d0 = 0; d0 < hd; d0 += ATT_HC) {
-            const int hc = (hd - d0 < ATT_HC) ? hd - d0 : ATT_HC, hcp = (hc + 31) / 32 * 32;
+        for (int d0 = 0; d0 < kd; d0 += ATT_HC) {
+            const int hc = (kd - d0 < ATT_HC) ? kd - d0 : ATT_HC, hcp = (hc + 31) / 32 * 32;
             __syncthreads();
-            lds_load_rows<T>(GA, qkv + (int64_t)q0 * a.qkv.ld + co + d0, a.qkv.ld, qrows, hc, hcp);
-            lds_load_rows<T>(GB, qkv + (int64_t)k0 * a.qkv.ld + a.C + co + d0, a.qkv.ld, krows, hc, hcp);
+            lds_load_rows<T>(GA, qkv + (int64_t)q0 * a.qkv.ld + qc + d0, a.qkv.ld, qrows, hc, hcp);
+            lds_load_rows<T>(GB, qkv + (int64_t)k0 * a.qkv.ld + kc + d0, a.qkv.ld, krows, hc, hcp);
             __syncthreads();
             const int rs = attn_row_bytes<T>(hcp);
 #pragma unroll
@@ -1000,7 +1018,7 @@ __global__ __launch_bounds__(256) void window_attn_tiled_fwd_kernel(AttnArgs a) 
         for (int d0 = 0; d0 < hd; d0 += ATT_HC) {
             const int hc = (hd - d0 < ATT_HC) ? hd - d0 : ATT_HC, hcp = (hc + 31) / 32 * 32;
             __syncthreads();
-            lds_load_transposed<T>(GA, qkv + (int64_t)k0 * a.qkv.ld + 2 * a.C + co + d0, a.qkv.ld, krows, hc, hcp);
+            lds_load_transposed<T>(GA, qkv + (int64_t)k0 * a.qkv.ld + vc + d0, a.qkv.ld, krows, hc, hcp);
             __syncthreads();
 #pragma unroll
             for (int dt = 0; dt < ATT_MAXDT; ++dt)
@@ -1031,28 +1049,37 @@ __device__ __forceinline__ void attn_tile_p_ds(const AttnArgs& a, char* GA, char
                                                int64_t trow0, int head, const float* delta, float (&p)[4][4], float (&ds)[4][4]) {
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int l15 = lane & 15, l4 = lane >> 4;
-    const int hd = a.hd;
+    const int hd = a.hd, kd = a.kd;
+    const int qc = a.qo + head * a.hs, kc = a.ko + head * a.hs, vc = a.vo + head * a.hs;
     f32x4 s[4], dp[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         s[t] = f32x4{0.f, 0.f, 0.f, 0.f};
         dp[t] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
-    for (int d0 = 0; d0 < hd; d0 += ATT_HC) {
-        const int hc = (hd - d0 < ATT_HC) ? hd - d0 : ATT_HC, hcp = (hc + 31) / 32 * 32;
-        const int rs = attn_row_bytes<T>(hcp);
-        __syncthreads();
-        lds_load_rows<T>(GA, qkv + (int64_t)q0 * a.qkv.ld + co + d0, a.qkv.ld, qrows, hc, hcp);          // Q
-        lds_load_rows<T>(GB, qkv + (int64_t)k0 * a.qkv.ld + a.C + co + d0, a.qkv.ld, krows, hc, hcp);  // K
-        __syncthreads();
+    // one walk over the chunks of the wider of the two contractions; a chunk past the end of the narrower one skips that product (d0, kd and hd
+    // are workgroup-uniform, so every wave meets the same barriers)
+    for (int d0 = 0; d0 < kd || d0 < hd; d0 += ATT_HC) {
+        if (d0 < kd) {
+            const int hc = (kd - d0 < ATT_HC) ? kd - d0 : ATT_HC, hcp = (hc + 31) / 32 * 32;
+            const int rs = attn_row_bytes<T>(hcp);
+            __syncthreads();
+            lds_load_rows<T>(GA, qkv + (int64_t)q0 * a.qkv.ld + qc + d0, a.qkv.ld, qrows, hc, hcp);  // Q
+            lds_load_rows<T>(GB, qkv + (int64_t)k0 * a.qkv.ld + kc + d0, a.qkv.ld, krows, hc, hcp);  // K
+            __syncthreads();
 #pragma unroll
-        for (int t = 0; t < 4; ++t) AT<T>::mma(GA, rs, wv * 16, GB, rs, t * 16, hcp, lane, s[t]);
-        __syncthreads();
-        lds_load_rows<T>(GA, dO + (int64_t)q0 * a.dout.ld + co + d0, a.dout.ld, qrows, hc, hcp);           // dO
-        lds_load_rows<T>(GB, qkv + (int64_t)k0 * a.qkv.ld + 2 * a.C + co + d0, a.qkv.ld, krows, hc, hcp);  // V
-        __syncthreads();
+            for (int t = 0; t < 4; ++t) AT<T>::mma(GA, rs, wv * 16, GB, rs, t * 16, hcp, lane, s[t]);
+        }
+        if (d0 < hd) {
+            const int hc = (hd - d0 < ATT_HC) ? hd - d0 : ATT_HC, hcp = (hc + 31) / 32 * 32;
+            const int rs = attn_row_bytes<T>(hcp);
+            __syncthreads();
+            lds_load_rows<T>(GA, dO + (int64_t)q0 * a.dout.ld + co + d0, a.dout.ld, qrows, hc, hcp);  // dO
+            lds_load_rows<T>(GB, qkv + (int64_t)k0 * a.qkv.ld + vc + d0, a.qkv.ld, krows, hc, hcp);   // V
+            __syncthreads();
 #pragma unroll
-        for (int t = 0; t < 4; ++t) AT<T>::mma(GA, rs, wv * 16, GB, rs, t * 16, hcp, lane, dp[t]);
+            for (int t = 0; t < 4; ++t) AT<T>::mma(GA, rs, wv * 16, GB, rs, t * 16, hcp, lane, dp[t]);
+        }
     }
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -1079,15 +1106,16 @@ __global__ __launch_bounds__(256) void window_attn_tiled_dq_kernel(AttnArgs a) {
     float* delta = reinterpret_cast<float*>(smem + lds.floats());  // [64]
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int l15 = lane & 15, l4 = lane >> 4;
-    const int L = a.L, hd = a.hd;
+    const int L = a.L, hd = a.hd, kd = a.kd;
     const int head = blockIdx.y, co = head * hd;
+    const int qc = a.qo + head * a.hs, kc = a.ko + head * a.hs;
     const int q0 = blockIdx.z * 64, qrows = (L - q0 < 64) ? L - q0 : 64;
     const int64_t t0 = (int64_t)blockIdx.x * L;
     const T* qkv = reinterpret_cast<const T*>(a.qkv.p) + t0 * a.qkv.ld;
     const T* ov = reinterpret_cast<const T*>(a.out.p) + t0 * a.out.ld;
     const T* dO = reinterpret_cast<const T*>(a.dout.p) + t0 * a.dout.ld;
     T* dqkv = reinterpret_cast<T*>(const_cast<void*>(a.dqkv.p)) + t0 * a.dqkv.ld;
-    const int ndt = (hd + 15) / 16;
+    const int ndt = (kd + 15) / 16;  // dQ is as wide as the score contraction
     attn_delta_rows<T>(delta, dO + (int64_t)q0 * a.dout.ld + co, a.dout.ld, ov + (int64_t)q0 * a.out.ld + co, a.out.ld, qrows, hd);
     f32x4 dq[ATT_MAXDT];
 #pragma unroll
@@ -1102,10 +1130,10 @@ __global__ __launch_bounds__(256) void window_attn_tiled_dq_kernel(AttnArgs a) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) reinterpret_cast<T*>(DS + (size_t)(16 * wv + 4 * l4 + r) * TS)[16 * t + l15] = from_f32<T>(ds[t][r]);
         // dQ[m][d] += sum_j dS[m][j] K^T[d][j]
-        for (int d0 = 0; d0 < hd; d0 += ATT_HC) {
-            const int hc = (hd - d0 < ATT_HC) ? hd - d0 : ATT_HC, hcp = (hc + 31) / 32 * 32;
+        for (int d0 = 0; d0 < kd; d0 += ATT_HC) {
+            const int hc = (kd - d0 < ATT_HC) ? kd - d0 : ATT_HC, hcp = (hc + 31) / 32 * 32;
             __syncthreads();
-            lds_load_transposed<T>(GA, qkv + (int64_t)k0 * a.qkv.ld + a.C + co + d0, a.qkv.ld, krows, hc, hcp);
+            lds_load_transposed<T>(GA, qkv + (int64_t)k0 * a.qkv.ld + kc + d0, a.qkv.ld, krows, hc, hcp);
             __syncthreads();
 #pragma unroll
             for (int dt = 0; dt < ATT_MAXDT; ++dt)
@@ -1114,7 +1142,7 @@ __global__ __launch_bounds__(256) void window_attn_tiled_dq_kernel(AttnArgs a) {
     }
 #pragma unroll
     for (int dt = 0; dt < ATT_MAXDT; ++dt)
-        if (dt < ndt) attn_store_tiles<T, 1>({dqkv + (int64_t)q0 * a.dqkv.ld + co}, a.dqkv.ld, {dq[dt]}, qrows, dt, hd);
+        if (dt < ndt) attn_store_tiles<T, 1>({dqkv + (int64_t)q0 * a.dqkv.ld + qc}, a.dqkv.ld, {dq[dt]}, qrows, dt, kd);
 }
 
 template <typename T>
@@ -1129,15 +1157,16 @@ __global__ __launch_bounds__(256) void window_attn_tiled_dkv_kernel(AttnArgs a) 
     float* delta = reinterpret_cast<float*>(smem + lds.floats());  // [64]
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     const int l15 = lane & 15, l4 = lane >> 4;
-    const int L = a.L, hd = a.hd;
+    const int L = a.L, hd = a.hd, kd = a.kd;
     const int head = blockIdx.y, co = head * hd;
+    const int qc = a.qo + head * a.hs, kc = a.ko + head * a.hs, vc = a.vo + head * a.hs;
     const int k0 = blockIdx.z * 64, krows = (L - k0 < 64) ? L - k0 : 64;
     const int64_t t0 = (int64_t)blockIdx.x * L;
     const T* qkv = reinterpret_cast<const T*>(a.qkv.p) + t0 * a.qkv.ld;
     const T* ov = reinterpret_cast<const T*>(a.out.p) + t0 * a.out.ld;
     const T* dO = reinterpret_cast<const T*>(a.dout.p) + t0 * a.dout.ld;
     T* dqkv = reinterpret_cast<T*>(const_cast<void*>(a.dqkv.p)) + t0 * a.dqkv.ld;
-    const int ndt = (hd + 15) / 16;
+    const int ndv = (hd + 15) / 16, ndk = (kd + 15) / 16;
     f32x4 dk[ATT_MAXDT], dv[ATT_MAXDT];
 #pragma unroll
     for (int dt = 0; dt < ATT_MAXDT; ++dt) {
@@ -1157,24 +1186,40 @@ __global__ __launch_bounds__(256) void window_attn_tiled_dkv_kernel(AttnArgs a) 
             Pack<T, 4>::store(reinterpret_cast<T*>(PT + (size_t)j * TS) + 16 * wv + 4 * l4, pv);
             Pack<T, 4>::store(reinterpret_cast<T*>(DST + (size_t)j * TS) + 16 * wv + 4 * l4, dv4);
         }
-        for (int d0 = 0; d0 < hd; d0 += ATT_HC) {
-            const int hc = (hd - d0 < ATT_HC) ? hd - d0 : ATT_HC, hcp = (hc + 31) / 32 * 32;
+        for (int d0 = 0; d0 < hd || d0 < kd; d0 += ATT_HC) {
+            // chunk widths of dO (value width) and of Q (score width); 0: that operand ends before this chunk (a zero-width load fills nothing)
+            const int hcv = d0 >= hd ? 0 : (hd - d0 < ATT_HC) ? hd - d0 : ATT_HC, hcvp = (hcv + 31) / 32 * 32;
+            const int hck = d0 >= kd ? 0 : (kd - d0 < ATT_HC) ? kd - d0 : ATT_HC, hckp = (hck + 31) / 32 * 32;
             __syncthreads();
-            lds_load_transposed<T>(GA, dO + (int64_t)q0 * a.dout.ld + co + d0, a.dout.ld, qrows, hc, hcp);  // dO^T [d][m]
-            lds_load_transposed<T>(GB, qkv + (int64_t)q0 * a.qkv.ld + co + d0, a.qkv.ld, qrows, hc, hcp);   // Q^T  [d][m]
+            lds_load_transposed<T>(GA, dO + (int64_t)q0 * a.dout.ld + co + d0, a.dout.ld, qrows, hcv, hcvp);  // dO^T [d][m]
+            lds_load_transposed<T>(GB, qkv + (int64_t)q0 * a.qkv.ld + qc + d0, a.qkv.ld, qrows, hck, hckp);   // Q^T  [d][m]
             __syncthreads();
 #pragma unroll
             for (int dt = 0; dt < ATT_MAXDT; ++dt)
-                if (dt < ndt && dt * 16 >= d0 && dt * 16 < d0 + ATT_HC) {
-                    AT<T>::mma(PT, TS, wv * 16, GA, TS, dt * 16 - d0, 64, lane, dv[dt]);   // dV[j][d] += sum_m P^T[j][m] dO^T[d][m]
-                    AT<T>::mma(DST, TS, wv * 16, GB, TS, dt * 16 - d0, 64, lane, dk[dt]);  // dK[j][d] += sum_m dS^T[j][m] Q^T[d][m]
+                if (dt * 16 >= d0 && dt * 16 < d0 + ATT_HC) {
+                    if (dt < ndv) AT<T>::mma(PT, TS, wv * 16, GA, TS, dt * 16 - d0, 64, lane, dv[dt]);   // dV[j][d] += sum_m P^T[j][m] dO^T[d][m]
+                    if (dt < ndk) AT<T>::mma(DST, TS, wv * 16, GB, TS, dt * 16 - d0, 64, lane, dk[dt]);  // dK[j][d] += sum_m dS^T[j][m] Q^T[d][m]
                 }
         }
     }
-    T* dst = dqkv + (int64_t)k0 * a.dqkv.ld + co;
+    if (a.dvadd.p) {  // the gradient V receives from its other consumer joins dV in float32, before the one rounding of the store
+        const T* add = reinterpret_cast<const T*>(a.dvadd.p) + (t0 + k0) * a.dvadd.ld + co;
+        const int col = lane & 15;
 #pragma unroll
-    for (int dt = 0; dt < ATT_MAXDT; ++dt)
-        if (dt < ndt) attn_store_tiles<T, 2>({dst + a.C, dst + 2 * a.C}, a.dqkv.ld, {dk[dt], dv[dt]}, krows, dt, hd);
+        for (int dt = 0; dt < ATT_MAXDT; ++dt)
+            if (dt < ndv && dt * 16 + col < hd)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int row = wv * 16 + 4 * l4 + r;
+                    if (row < krows) dv[dt][r] += to_f32(add[(int64_t)row * a.dvadd.ld + dt * 16 + col]);
+                }
+    }
+    T* dst = dqkv + (int64_t)k0 * a.dqkv.ld;
+#pragma unroll
+    for (int dt = 0; dt < ATT_MAXDT; ++dt) {
+        if (dt < ndk) attn_store_tiles<T, 1>({dst + kc}, a.dqkv.ld, {dk[dt]}, krows, dt, kd);
+        if (dt < ndv) attn_store_tiles<T, 1>({dst + vc}, a.dqkv.ld, {dv[dt]}, krows, dt, hd);
+    }
 }
 
 static int attn_common(const ymi_tensor* qkv, int64_t wlen, int64_t heads, AttnArgs* a, const char* what) {
@@ -1187,6 +1232,7 @@ static int attn_common(const ymi_tensor* qkv, int64_t wlen, int64_t heads, AttnA
     YMI_CHECK_ARG(ymi_pixels(qkv) % wlen == 0, "%s: token count not a multiple of the window length", what);
     a->L = (int)wlen; a->heads = (int)heads; a->C = (int)C; a->hd = (int)hd; a->hdp = attn_hdp(hd);
     a->scale = 1.0f / sqrtf((float)hd);
+    a->qo = 0; a->ko = (int)C; a->vo = 2 * (int)C; a->hs = (int)hd; a->kd = (int)hd;
     return YMI_OK;
 }
 
@@ -1253,5 +1299,64 @@ extern "C" int ymi_window_attention_bwd(const ymi_tensor* qkv, const ymi_tensor*
     a.lse = const_cast<float*>(lse);
     attn_run(true, qkv, wlen, a, stream);
     YMI_CHECK_LAUNCH("window_attention_bwd");
+    return YMI_OK;
+}
+
+// ---- PSA attention (reference block.py Attention): full-map self-attention per image, qkv packed per head as [q (kd) | k (kd) | v (hd)] ----
+// Always the tiled kernels: a map is any number of tokens (400 at 640^2, 1600 at 1280^2).  Scores contract over kd with scale kd^-0.5, values over hd.
+static int psa_common(const ymi_tensor* qkv, int64_t tokens, int64_t heads, int64_t kd, AttnArgs* a, const char* what) {
+    YMI_CHECK_ARG(ymi_tensor_ok(qkv) && tokens > 0 && heads > 0 && kd > 0, "%s: args", what);
+    YMI_CHECK_ARG(qkv->c % heads == 0 && qkv->c / heads > 2 * kd, "%s: qkv must have heads * (2 * key_dim + head_dim) channels", what);
+    const int64_t hs = qkv->c / heads, hd = hs - 2 * kd;
+    YMI_CHECK_ARG(kd % 4 == 0 && hd % 4 == 0 && kd <= 16 * ATT_MAXDT && hd <= 16 * ATT_MAXDT && qkv->ld % 4 == 0,
+                  "%s: key_dim and head_dim must be multiples of 4 and <= %d", what, 16 * ATT_MAXDT);
+    YMI_CHECK_ARG(ymi_pixels(qkv) % tokens == 0, "%s: token count not a multiple of the tokens per image", what);
+    YMI_CHECK_ARG(ymi_pixels(qkv) / tokens < (1ll << 31) && (tokens + 63) / 64 <= 65535 && heads <= 65535, "%s: grid too large", what);
+    a->L = (int)tokens; a->heads = (int)heads; a->C = (int)(heads * hd); a->hd = (int)hd; a->hdp = attn_hdp(hd);
+    a->qo = 0; a->ko = (int)kd; a->vo = 2 * (int)kd; a->hs = (int)hs; a->kd = (int)kd;
+    a->scale = 1.0f / sqrtf((float)kd);
+    return YMI_OK;
+}
+
+// a [T, heads * hd] companion of qkv (out, v_out, dout, dv_add)
+static bool psa_rows_ok(const ymi_tensor* t, const ymi_tensor* qkv, const AttnArgs& a) {
+    return ymi_tensor_ok(t) && t->c == a.C && ymi_pixels(t) == ymi_pixels(qkv) && t->dtype == qkv->dtype && t->ld % 4 == 0;
+}
+
+static void psa_run(bool bwd, const ymi_tensor* qkv, const AttnArgs& a, void* stream) {
+    const dim3 grid((unsigned)(ymi_pixels(qkv) / a.L), (unsigned)a.heads, (unsigned)((a.L + 63) / 64));
+    if (qkv->dtype == YMI_BF16) attn_launch_tiled<bf16_t>(bwd, grid, a, stream);
+    else attn_launch_tiled<float>(bwd, grid, a, stream);
+}
+
+extern "C" int ymi_psa_attention_fwd(const ymi_tensor* qkv, int64_t tokens, int64_t heads, int64_t kd, const ymi_tensor* out, const ymi_tensor* v_out,
+                                     float* lse, void* stream) {
+    AttnArgs a{};
+    int rc = psa_common(qkv, tokens, heads, kd, &a, "psa_attention_fwd");
+    if (rc) return rc;
+    YMI_CHECK_ARG(out && psa_rows_ok(out, qkv, a), "psa_attention_fwd: out must be [tokens, heads * head_dim] of qkv's dtype");
+    YMI_CHECK_ARG(!v_out || psa_rows_ok(v_out, qkv, a), "psa_attention_fwd: v_out must be [tokens, heads * head_dim] of qkv's dtype");
+    YMI_CHECK_ARG(lse, "psa_attention_fwd: lse");
+    a.qkv = SV{qkv->data, qkv->ld}; a.out = SV{out->data, out->ld}; a.lse = lse;
+    if (v_out) a.vout = SV{v_out->data, v_out->ld};
+    psa_run(false, qkv, a, stream);
+    YMI_CHECK_LAUNCH("psa_attention_fwd");
+    return YMI_OK;
+}
+
+extern "C" int ymi_psa_attention_bwd(const ymi_tensor* qkv, const ymi_tensor* out, const ymi_tensor* dout, const float* lse, const ymi_tensor* dv_add,
+                                     int64_t tokens, int64_t heads, int64_t kd, const ymi_tensor* dqkv, void* stream) {
+    AttnArgs a{};
+    int rc = psa_common(qkv, tokens, heads, kd, &a, "psa_attention_bwd");
+    if (rc) return rc;
+    YMI_CHECK_ARG(out && dout && lse && psa_rows_ok(out, qkv, a) && psa_rows_ok(dout, qkv, a), "psa_attention_bwd: out / dout must be [tokens, heads * head_dim] of qkv's dtype");
+    YMI_CHECK_ARG(!dv_add || psa_rows_ok(dv_add, qkv, a), "psa_attention_bwd: dv_add must be [tokens, heads * head_dim] of qkv's dtype");
+    YMI_CHECK_ARG(dqkv && ymi_tensor_ok(dqkv) && dqkv->c == qkv->c && ymi_pixels(dqkv) == ymi_pixels(qkv) && dqkv->dtype == qkv->dtype && dqkv->ld % 4 == 0,
+                  "psa_attention_bwd: dqkv must match qkv");
+    a.qkv = SV{qkv->data, qkv->ld}; a.out = SV{out->data, out->ld}; a.dout = SV{dout->data, dout->ld}; a.dqkv = SV{dqkv->data, dqkv->ld};
+    if (dv_add) a.dvadd = SV{dv_add->data, dv_add->ld};
+    a.lse = const_cast<float*>(lse);
+    psa_run(true, qkv, a, stream);
+    YMI_CHECK_LAUNCH("psa_attention_bwd");
     return YMI_OK;
 }

@@ -1,4 +1,4 @@
-"""Bottleneck / C2f / SPPF / DFL (reference: ultralytics/nn/modules/block.py)."""
+"""Bottleneck / C2f / SPPF / DFL / C3 family / PSA attention blocks (reference: ultralytics/nn/modules/block.py)."""
 import torch
 import torch.nn as nn
 
@@ -79,7 +79,7 @@ class C2f(nn.Module):
             # with or without the concat buffer - ops.concat is a join-aware consumer either way.  Other widths reach the
             # Bottleneck as padded copies: autograd sums their gradients and nothing is marked.
             if dense:
-                ops.mark_join(last, 1 + int(m.add) + int(j >= 1), force=(j == 0))
+                ops.mark_join(last, self._reads(m) + int(j >= 1), force=(j == 0))
                 if j == 0:
                     first_join = ops.join_of(last)
             last = m(last, out=slot(2 + j))
@@ -88,6 +88,11 @@ class C2f(nn.Module):
         return self.cv2(ops.concat(ys, buf, split_join=(first_join, self.c) if first_join is not None else None), out=out)
 
     forward_split = forward
+
+    @staticmethod
+    def _reads(m):
+        """how many join-aware ops of member block m read its input: a Bottleneck's cv1 and, with a shortcut, cv2's residual."""
+        return 1 + int(m.add)
 
 
 class SPPF(nn.Module):
@@ -124,7 +129,8 @@ class C3(nn.Module):
         self.cv3 = Conv(2 * c_, c2, 1)
         self.m = nn.Sequential(*(Bottleneck(c_, c_, shortcut, g, k=((1, 1), (3, 3)), e=1.0) for _ in range(n)))
 
-    def forward(self, x):
+    def forward(self, x, out=None):
+        """out: optional ops.OutSlot for the block's result (train mode), handed to cv3."""
         x = ops.to_internal(x)
         c_ = self.cv2.conv.out_channels
         buf, slot = None, (lambda j: None)
@@ -137,7 +143,7 @@ class C3(nn.Module):
             # (a Bottleneck takes an output slot; a GhostBottleneck's sum is its own launch and reaches the buffer through the concat's copy)
             a = m(a, out=slot(0)) if (isinstance(m, Bottleneck) and j == len(self.m) - 1) else m(a)
         b = self.cv2(x, out=slot(1))
-        return self.cv3(ops.concat([a, b], buf))
+        return self.cv3(ops.concat([a, b], buf), out=out)
 
 
 class GhostBottleneck(nn.Module):
@@ -166,3 +172,126 @@ class C3Ghost(C3):
         super().__init__(c1, c2, n, shortcut, g, e)
         c_ = int(c2 * e)
         self.m = nn.Sequential(*(GhostBottleneck(c_, c_) for _ in range(n)))
+
+
+class C3k(C3):
+    """C3 whose n Bottlenecks have two k x k kernels (reference block.py:1110-1129)."""
+
+    def __init__(self, c1, c2, n=1, shortcut=True, g=1, e=0.5, k=3):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        c_ = int(c2 * e)
+        self.m = nn.Sequential(*(Bottleneck(c_, c_, shortcut, g, k=(k, k), e=1.0) for _ in range(n)))
+
+
+class C3k2(C2f):
+    """C2f whose members are C3k(c, c, 2) blocks (c3k) or plain Bottlenecks with the default e = 0.5 (reference block.py:1088-1107)."""
+
+    def __init__(self, c1, c2, n=1, c3k=False, e=0.5, g=1, shortcut=True):
+        super().__init__(c1, c2, n, shortcut, g, e)
+        self.m = nn.ModuleList(C3k(self.c, self.c, 2, shortcut, g) if c3k else Bottleneck(self.c, self.c, shortcut, g) for _ in range(n))
+
+    @staticmethod
+    def _reads(m):
+        """a C3k reads its input with cv1 and cv2 and has no shortcut of its own."""
+        return 2 if isinstance(m, C3k) else 1 + int(m.add)
+
+
+class Attention(nn.Module):
+    """full-map self-attention with keys narrower than values and a depthwise positional term (reference block.py:1278-1338):
+    proj(attention(qkv(x)) + pe(v)).  qkv's output is packed per head as [q (key_dim) | k (key_dim) | v (head_dim)]; the attention core is
+    ops.psa_attention on the NHWC tensor's pixels as tokens, which also returns v compacted for `pe`; the sum rides in pe's kernel."""
+
+    def __init__(self, dim, num_heads=8, attn_ratio=0.5):
+        super().__init__()
+        self.num_heads = num_heads
+        self.head_dim = dim // num_heads
+        self.key_dim = int(self.head_dim * attn_ratio)
+        self.scale = self.key_dim**-0.5
+        nh_kd = self.key_dim * num_heads
+        h = dim + nh_kd * 2
+        self.qkv = Conv(dim, h, 1, act=False)
+        self.proj = Conv(dim, dim, 1, act=False)
+        self.pe = Conv(dim, dim, 3, 1, g=dim, act=False)
+
+    def forward(self, x, residual=None, out=None):
+        """residual: added to the result in proj's kernel (PSABlock's shortcut); out: optional ops.OutSlot (train mode)."""
+        x = ops.to_internal(x)
+        h, w = x.shape[2:]
+        o, v = ops.psa_attention(self.qkv(x), h * w, self.num_heads, self.key_dim)
+        y = self.pe(v, residual=o)
+        return self.proj(y, residual=residual, out=out)
+
+
+class PSABlock(nn.Module):
+    """x + attn(x), then + ffn of that (reference block.py:1341-1391); both shortcuts ride as residuals of the last convolution of their branch."""
+
+    def __init__(self, c, attn_ratio=0.5, num_heads=4, shortcut=True):
+        super().__init__()
+        self.attn = Attention(c, attn_ratio=attn_ratio, num_heads=num_heads)
+        self.ffn = nn.Sequential(Conv(c, c * 2, 1), Conv(c * 2, c, 1, act=False))
+        self.add = shortcut
+
+    def forward(self, x, out=None):
+        x = ops.to_internal(x)
+        return _psa_body(self.attn, self.ffn, x, self.add, self.training, out)
+
+
+def _psa_body(attn, ffn, x, add, training, out=None):
+    """the two residual branches PSABlock and PSA share.  A tensor read by a convolution and by a shortcut has two join-aware consumers: its
+    gradient sum forms in the convolution's data-gradient epilogue.  A caller that already attached a join to x has counted both."""
+    if add and training and ops.join_of(x) is None:
+        ops.mark_join(x, 2)  # attn.qkv and the shortcut (proj's residual)
+    y = attn(x, residual=x if add else None)
+    if add and training:
+        ops.mark_join(y, 2)  # ffn[0] and the shortcut (ffn[1]'s residual)
+    h = ffn[0](y)
+    return ffn[1](h, residual=y if add else None, out=out)
+
+
+def _split_for_psa(t, c, twice):
+    """(a, b) = channel halves of cv1's output; b is read by the first attention block - twice when that block has a shortcut."""
+    a, b = ops.chan_split2(t, c)
+    j = ops.join_of(b)
+    if j is not None and twice:
+        j.n = 2
+    return a, b
+
+
+class PSA(nn.Module):
+    """cv2(cat(a, b + attn(b) + ffn(..))) on the halves of cv1's output (reference block.py:1394-1449)."""
+
+    def __init__(self, c1, c2, e=0.5):
+        super().__init__()
+        assert c1 == c2
+        self.c = int(c1 * e)
+        self.cv1 = Conv(c1, 2 * self.c, 1, 1)
+        self.cv2 = Conv(2 * self.c, c1, 1)
+        self.attn = Attention(self.c, attn_ratio=0.5, num_heads=self.c // 64)
+        self.ffn = nn.Sequential(Conv(self.c, self.c * 2, 1), Conv(self.c * 2, self.c, 1, act=False))
+
+    def forward(self, x, out=None):
+        x = ops.to_internal(x)
+        a, b = _split_for_psa(self.cv1(x), self.c, self.training)
+        b = _psa_body(self.attn, self.ffn, b, True, self.training)
+        y = ops.concat([a, b])
+        return self.cv2(y, out=out)
+
+
+class C2PSA(nn.Module):
+    """PSA refactored to stack n PSABlocks on the second half of cv1's output (reference block.py:1452-1507)."""
+
+    def __init__(self, c1, c2, n=1, e=0.5):
+        super().__init__()
+        assert c1 == c2
+        self.c = int(c1 * e)
+        self.cv1 = Conv(c1, 2 * self.c, 1, 1)
+        self.cv2 = Conv(2 * self.c, c1, 1)
+        self.m = nn.Sequential(*(PSABlock(self.c, attn_ratio=0.5, num_heads=self.c // 64) for _ in range(n)))
+
+    def forward(self, x, out=None):
+        x = ops.to_internal(x)
+        a, b = _split_for_psa(self.cv1(x), self.c, self.training and len(self.m) > 0 and self.m[0].add)
+        for m in self.m:
+            b = m(b)
+        y = ops.concat([a, b])
+        return self.cv2(y, out=out)

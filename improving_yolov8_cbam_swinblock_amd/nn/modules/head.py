@@ -1,4 +1,4 @@
-"""Detect head (reference: ultralytics/nn/modules/head.py:23-183), legacy (v8) class branch."""
+"""Detect head (reference: ultralytics/nn/modules/head.py:23-183): the legacy (v8) class branch and the depthwise one of YOLO11."""
 import math
 import os
 
@@ -7,7 +7,7 @@ import torch.nn as nn
 
 from ... import ops
 from .block import DFL
-from .conv import Conv
+from .conv import Conv, DWConv
 
 
 def make_anchors(feats, strides, grid_cell_offset=0.5):
@@ -51,12 +51,11 @@ class Detect(nn.Module):
     shape = None
     anchors = torch.empty(0)
     strides = torch.empty(0)
-    legacy = True  # parse_model sets True for v8 YAMLs (reference tasks.py:1355,1488); only that branch is built
+    legacy = True  # parse_model clears it on the instance it builds after a C3k2 row (reference tasks.py:1355,1457-1458,1488)
 
     def __init__(self, nc=80, ch=()):
         super().__init__()
-        if not self.legacy:
-            raise NotImplementedError("only the legacy (YOLOv8) class branch of Detect is on the hot path")
+        self.legacy = bool(self.legacy)  # the instance keeps the branch it was built with, whatever the class attribute says later
         self.nc = nc
         self.nl = len(ch)
         self.reg_max = 16
@@ -64,11 +63,17 @@ class Detect(nn.Module):
         self.stride = torch.zeros(self.nl)
         c2, c3 = max((16, ch[0] // 4, self.reg_max * 4)), max(ch[0], min(self.nc, 100))
         self.cv2 = nn.ModuleList(nn.Sequential(Conv(x, c2, 3), Conv(c2, c2, 3), _Out1x1(c2, 4 * self.reg_max, 1)) for x in ch)
-        self.cv3 = nn.ModuleList(nn.Sequential(Conv(x, c3, 3), Conv(c3, c3, 3), _Out1x1(c3, self.nc, 1)) for x in ch)
+        if self.legacy:
+            self.cv3 = nn.ModuleList(nn.Sequential(Conv(x, c3, 3), Conv(c3, c3, 3), _Out1x1(c3, self.nc, 1)) for x in ch)
+        else:  # depthwise 3x3 -> pointwise, twice (reference head.py:51-58)
+            self.cv3 = nn.ModuleList(
+                nn.Sequential(nn.Sequential(DWConv(x, x, 3), Conv(x, c3, 1)), nn.Sequential(DWConv(c3, c3, 3), Conv(c3, c3, 1)), _Out1x1(c3, self.nc, 1))
+                for x in ch
+            )
         self.dfl = DFL(self.reg_max) if self.reg_max > 1 else nn.Identity()
 
     def _branch(self, seq, xi):
-        """Conv -> Conv -> biased 1x1 (head.py:45-59)."""
+        """Conv -> Conv -> biased 1x1, or the depthwise + pointwise pairs of the non-legacy class branch (head.py:45-59)."""
         h = xi
         for m in seq:
             h = m(h)
@@ -80,6 +85,8 @@ class Detect(nn.Module):
         convolution with c2 + c3 output channels (ops.conv_bn_act_pair).  A static property of the module (the model graph counts Detect as
         ONE consumer of each input when it holds): both are unfused Conv blocks with SiLU and widths in whole 16-byte bf16 chunks."""
         a, b = self.cv2[0][0], self.cv3[0][0]
+        if not self.legacy:  # the class branch opens with a depthwise convolution: no sibling to pair with; level by level through _branch
+            return False
         if not ops.HOOKS["detect_pair"]:  # test / A-B hook: the two branches as separate convolutions
             return False
         return (hasattr(a, "bn") and hasattr(b, "bn") and isinstance(a.act, nn.SiLU) and isinstance(b.act, nn.SiLU)

@@ -19,9 +19,10 @@ from .. import ops
 from ..utils.loss import DEFAULT_HYP, SplitPreds, v8DetectionLoss
 from ..utils.ops import make_divisible
 from ..utils.torch_utils import fuse_conv_and_bn, initialize_weights, intersect_dicts
-from .modules import C2f, C3, CBAM, SPPF, Bottleneck, C3Ghost, Concat, Conv, Detect, DWConv, GhostBottleneck, GhostConv, SwinBlock, Upsample
+from .modules import C2f, C2PSA, C3, C3k2, CBAM, PSA, SPPF, Bottleneck, C3Ghost, Concat, Conv, Detect, DWConv, GhostBottleneck, GhostConv, SwinBlock, Upsample
 
 CFG_DIR = Path(__file__).resolve().parents[1] / "cfg" / "models" / "v8"
+CFG_DIRS = (CFG_DIR, CFG_DIR.parent / "11")  # bare YAML names are looked up here, in this order
 
 # name lookup of reference tasks.py:1433-1439 (`globals()[m]`), restricted to what has kernels
 MODULES = {
@@ -34,14 +35,17 @@ MODULES = {
     "GhostBottleneck": GhostBottleneck,
     "C3": C3,
     "C3Ghost": C3Ghost,
+    "C3k2": C3k2,
+    "C2PSA": C2PSA,
+    "PSA": PSA,
     "CBAM": CBAM,
     "SwinBlock": SwinBlock,
     "Concat": Concat,
     "Detect": Detect,
     "nn.Upsample": Upsample,  # the YAML's torch.nn.Upsample row runs as the HIP nearest-2x kernel
 }
-BASE_MODULES = frozenset({Conv, C2f, SPPF, Bottleneck, DWConv, GhostConv, GhostBottleneck, C3, C3Ghost})  # width-scaled (c1, c2, ...) constructors: tasks.py:1376-1413
-REPEAT_MODULES = frozenset({C2f, C3, C3Ghost})  # repeats passed as an argument: tasks.py:1414-1432
+BASE_MODULES = frozenset({Conv, C2f, SPPF, Bottleneck, DWConv, GhostConv, GhostBottleneck, C3, C3Ghost, C3k2, C2PSA, PSA})  # width-scaled (c1, c2, ...) constructors: tasks.py:1376-1413
+REPEAT_MODULES = frozenset({C2f, C3, C3Ghost, C3k2, C2PSA})  # repeats passed as an argument: tasks.py:1414-1432
 
 
 def guess_model_scale(model_path):
@@ -52,15 +56,15 @@ def guess_model_scale(model_path):
 
 def yaml_model_load(path):
     """load a model YAML; 'yolov8s-x.yaml' resolves to 'yolov8-x.yaml' + scale 's' (reference tasks.py:1520-1541).
-    Bare names are looked up in this package's cfg/models/v8."""
+    Bare names are looked up in this package's cfg/models/v8 and cfg/models/11."""
     path = Path(path)
     unified = Path(re.sub(r"(\d+)([nslmx])(.+)?$", r"\1\3", str(path)))
-    for cand in (unified, CFG_DIR / unified.name, path, CFG_DIR / path.name):
+    for cand in (unified, *(d / unified.name for d in CFG_DIRS), path, *(d / path.name for d in CFG_DIRS)):
         if cand.is_file():
             d = yaml.safe_load(cand.read_text())
             break
     else:
-        raise FileNotFoundError(f"model YAML '{path}' not found (also looked in {CFG_DIR})")
+        raise FileNotFoundError(f"model YAML '{path}' not found (also looked in {', '.join(str(d) for d in CFG_DIRS)})")
     d["scale"] = guess_model_scale(path)
     d["yaml_file"] = str(path)
     return d
@@ -71,6 +75,8 @@ def parse_model(d, ch, verbose=False):
     nc, scales = d.get("nc"), d.get("scales")
     depth, width = d.get("depth_multiple", 1.0), d.get("width_multiple", 1.0)
     max_channels = float("inf")
+    legacy = True  # Detect's class branch: cleared by a C3k2 row (reference tasks.py:1355,1457-1458)
+    scale = ""
     if scales:
         scale = d.get("scale")
         if not scale:
@@ -105,14 +111,20 @@ def parse_model(d, ch, verbose=False):
             if m in REPEAT_MODULES:
                 args.insert(2, n)
                 n = 1
+            if m is C3k2:
+                legacy = False
+                if scale and scale in "mlx":  # C3k members at the wide scales, whatever the row says (tasks.py:1459-1460)
+                    args[3] = True
         elif m is Concat:
             c2 = sum(ch[x] for x in f)
         elif m is Detect:
             args.append([ch[x] for x in f])
-            m.legacy = True  # v8 YAMLs never reach the C3k2/A2C2f rows that clear it (tasks.py:1355,1457-1465,1488)
+            m.legacy = legacy  # read by the constructor below; v8 YAMLs have no C3k2 row and keep True (tasks.py:1355,1457-1465,1488)
         else:  # CBAM, SwinBlock, Upsample: arguments untouched, channels pass through (tasks.py:1503-1504)
             c2 = ch[f]
         m_ = nn.Sequential(*(m(*args) for _ in range(n))) if n > 1 else m(*args)
+        if m is Detect:  # (the instance keeps its branch) the class default goes back to the v8 one for Detects built outside parse_model
+            Detect.legacy = True
         t = str(m)[8:-2].replace("__main__.", "")
         m_.np = sum(x.numel() for x in m_.parameters())
         m_.i, m_.f, m_.type = i, f, t
@@ -221,8 +233,8 @@ class BaseModel(nn.Module):
             f = [m.f] if isinstance(m.f, int) else list(m.f)
             srcs.append([m.i - 1 if j == -1 else j for j in f])
         outs = self._channel_trace(self.yaml.get("ch", 3))
-        slot_ok = (Conv, C2f, SPPF, CBAM, SwinBlock, Upsample)
-        join_ok = (Conv, C2f, SPPF, SwinBlock, Upsample, Concat, Detect)
+        slot_ok = (Conv, C2f, SPPF, CBAM, SwinBlock, Upsample, C2PSA, PSA)  # forward(x, out=slot) hands the slot to the block's last convolution
+        join_ok = (Conv, C2f, SPPF, SwinBlock, Upsample, Concat, Detect, C2PSA, PSA)  # the block's input is read once, by a join-aware convolution
         slot, consumers, ok = {}, {}, {}
         for m in self.model:
             for j in srcs[m.i]:
@@ -335,7 +347,7 @@ class DetectionModel(BaseModel):
             for mod in mods:
                 if isinstance(mod, Conv):
                     src = (mod.conv.out_channels, src[1] * mod.conv.stride[0])
-                elif isinstance(mod, (C2f, SPPF)):
+                elif isinstance(mod, (C2f, SPPF, C2PSA, PSA)):  # (C3k2 is a C2f)
                     src = (mod.cv2.conv.out_channels, src[1])
                 elif isinstance(mod, C3):  # (C3Ghost too)
                     src = (mod.cv3.conv.out_channels, src[1])

@@ -31,8 +31,8 @@ from .conv import (  # noqa: F401
 )
 from .dwconv import _DwConvAffineAct, _DwConvBnAct, dwconv_affine_act, dwconv_bn_act  # noqa: F401
 from .blocks import (  # noqa: F401
-    _Act, _AddResidual, _C2fSplit, _Cbam, _Concat, _DetectLoss, _LayerNorm, _SppfPool, _SwinLnMlp, _SwinMlp, _Upsample2x, _WindowAttention,
-    _WindowReverse, _map_array, add_residual, c2f_split, cbam, concat, detect_decode, detect_loss, detect_nms, detect_targets, gelu, layernorm, sppf_pool_cat,
+    _Act, _AddResidual, _C2fSplit, _Cbam, _Concat, _DetectLoss, _LayerNorm, _PsaAttention, _SppfPool, _SwinLnMlp, _SwinMlp, _Upsample2x, _WindowAttention,
+    _WindowReverse, _map_array, add_residual, c2f_split, cbam, concat, detect_decode, detect_loss, detect_nms, detect_targets, gelu, layernorm, psa_attention, sppf_pool_cat,
     swin_ln_mlp, swin_ln_mlp_ok, swin_mlp, upsample2x, window_attention, window_pad, window_partition, window_partition_index, window_reverse,
 )
 from .resize import letterbox, letterbox_geometry, scale_boxes, scale_boxes_params, scale_image, scale_rows, tta_clip_ranges, tta_merge  # noqa: F401

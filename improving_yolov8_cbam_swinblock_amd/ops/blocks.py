@@ -530,6 +530,50 @@ def window_attention(qkv, wlen, heads):
     return _WindowAttention.apply(qkv, int(wlen), int(heads))
 
 
+class _PsaAttention(torch.autograd.Function):
+    """softmax(q^T k * kd^-0.5) v per (image, head) on qkv packed per head as [q (kd) | k (kd) | v (hd)]: the core of the reference's
+    block.py Attention (:1330-1336).  -> (out, v), both [.., heads * hd]: v is the compacted copy of the V columns that the depthwise `pe`
+    convolution reads; the gradient arriving for it is added into dV inside the backward kernel (dv_add), not by a launch of its own.
+    qkv: a [T, C] token matrix or an internal NHWC tensor (its pixels are the tokens, image after image)."""
+
+    @staticmethod
+    def forward(ctx, qkv, tokens, heads, kd):
+        c = qkv.shape[1] - 2 * kd * heads
+        if qkv.dim() == 4:
+            n, _, h, w = qkv.shape
+            out, v, t = empty_nhwc(n, c, h, w, qkv.dtype, qkv.device), empty_nhwc(n, c, h, w, qkv.dtype, qkv.device), n * h * w
+        else:
+            t = qkv.shape[0]
+            out, v = (torch.empty((t, c), dtype=qkv.dtype, device=qkv.device) for _ in range(2))
+        lse = torch.empty((t, heads), dtype=torch.float32, device=qkv.device)
+        check(L().ymi_psa_attention_fwd(_byref(as_ymi(qkv)), tokens, heads, kd, _byref(as_ymi(out)), _byref(as_ymi(v)), ptr(lse), stream_ptr()), "psa_attention_fwd")
+        ctx.save_for_backward(qkv, out, lse)
+        ctx.cfg = (tokens, heads, kd)
+        ctx.set_materialize_grads(False)  # (an unused output gets no zero tensor: None means "nothing to add")
+        return out, v
+
+    @staticmethod
+    def backward(ctx, g, gv):
+        qkv, out, lse = ctx.saved_tensors
+        tokens, heads, kd = ctx.cfg
+        if g is None:
+            g = torch.zeros_like(out)
+        g = grad_nhwc(g, qkv.dtype)
+        gv = grad_nhwc(gv, qkv.dtype) if gv is not None else None
+        dqkv = empty_nhwc(*qkv.shape, qkv.dtype, qkv.device) if qkv.dim() == 4 else torch.empty_like(qkv)
+        check(
+            L().ymi_psa_attention_bwd(_byref(as_ymi(qkv)), _byref(as_ymi(out)), _byref(as_ymi(g)), ptr(lse), _byref(as_ymi(gv)) if gv is not None else None,
+                                      tokens, heads, kd, _byref(as_ymi(dqkv)), stream_ptr()),
+            "psa_attention_bwd",
+        )
+        return dqkv, None, None, None
+
+
+def psa_attention(qkv, tokens, heads, kd):
+    """-> (out, v) of the PSA attention core; see _PsaAttention."""
+    return _PsaAttention.apply(qkv, int(tokens), int(heads), int(kd))
+
+
 class _WindowReverse(torch.autograd.Function):
     """tokens -> NHWC image with the padding cropped (window_reverse + rearrange + crop, swin_block.py:55-58)."""
 

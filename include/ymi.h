@@ -369,6 +369,16 @@ int ymi_layernorm_bwd_add(const ymi_tensor* x, int64_t ws, const ymi_tensor* dou
 int ymi_window_attention_fwd(const ymi_tensor* qkv, int64_t wlen, int64_t heads, const ymi_tensor* out, float* lse, void* stream);
 int ymi_window_attention_bwd(const ymi_tensor* qkv, const ymi_tensor* out, const ymi_tensor* dout, const float* lse, int64_t wlen,
                              int64_t heads, const ymi_tensor* dqkv, void* stream);
+/* Attention core of the reference's block.py Attention (C2PSA / PSABlock): full-map self-attention per image and head on
+ * qkv [T][heads * (2 kd + hd)], packed per head as [q (kd) | k (kd) | v (hd)]; T is a whole number of images of `tokens`
+ * tokens each (any positive count).  P = softmax(q k^T * kd^-0.5) over the image's tokens, o = P v; out [T][heads * hd];
+ * v_out (may be null) receives V compacted to [T][heads * hd]; lse [T][heads] saved.  Flash-style tiles: no atomics,
+ * run-to-run identical.  kd and hd: multiples of 4, at most 192. */
+int ymi_psa_attention_fwd(const ymi_tensor* qkv, int64_t tokens, int64_t heads, int64_t kd, const ymi_tensor* out, const ymi_tensor* v_out,
+                          float* lse, void* stream);
+/* dqkv [T][heads * (2 kd + hd)]; dv_add [T][heads * hd] (may be null) is added into the V columns in float32, before the store. */
+int ymi_psa_attention_bwd(const ymi_tensor* qkv, const ymi_tensor* out, const ymi_tensor* dout, const float* lse, const ymi_tensor* dv_add,
+                          int64_t tokens, int64_t heads, int64_t kd, const ymi_tensor* dqkv, void* stream);
 /* Generic token GEMM backward helpers (nn.Linear adjoint): column sums for bias gradients. */
 int ymi_colsum(const ymi_tensor* x, float* out /*[c]*/, void* workspace, size_t workspace_bytes, void* stream);
 /* dx = dy * gelu'(pre) (exact erf GELU, swin_block.py:33). */
