@@ -11,8 +11,9 @@
 //    families (attn_form): windows of more than 64 tokens (or the attn_tiled option) -> tiled,
 //    flash-style; otherwise bfloat16 -> tr (operands staged once row-major, transposed fragment
 //    reads), float32 -> one-tile (both operands K-contiguous rows: V and, in backward, dO / Q / K
-//    are transposed on the way into LDS).  They share the LDS description (AttnLds), the row
-//    softmax, the tile stores and the launch helper.
+//    are transposed on the way into LDS) up to head_dim 192 and tiled above, where the one-tile
+//    backward image no longer fits.  They share the LDS description (AttnLds), the row
+//    softmax, the tile stores and the launch helper.  head_dim: a multiple of 4 up to 256.
 //    The tiled family also serves the PSA attention of C2PSA (ymi_psa_attention_*, end of file): full-map attention per image on qkv packed
 //    per head as [q | k | v] with keys narrower than values - AttnArgs carries the per-head addresses and the two widths.
 //    Token GEMMs (QKV, proj, MLP) are ymi_conv2d_fwd with a 1x1 "kernel".
@@ -449,7 +450,12 @@ struct AttnArgs {
     float scale;
 };
 
-constexpr int ATT_MAXDT = 12;  // head_dim <= 192
+// Head-dimension tiles of 16 columns.  The kernels that keep a result tile per head-dimension tile in registers (the tr kernels, the tiled
+// kernels) take the tile count as a template parameter, so the guarded `dt < ndt` loops unroll over exactly as many tiles as the launch can need:
+// ATT_MAXDT serves every head up to 192 channels - every PSA launch (their bf16 occupancy is set by registers) and every window launch that wide -
+// ATT_MAXDT_WIN the window-attention heads of 196..256 channels (SwinBlock(512, 2): head_dim 256).
+constexpr int ATT_MAXDT = 12;      // PSA: key_dim, head_dim <= 192; the float32 one-tile kernels: head_dim <= 192
+constexpr int ATT_MAXDT_WIN = 16;  // window attention: head_dim <= 256
 constexpr int ATT_HC = 96;     // head_dim columns per staging round of the tiled kernels
 constexpr size_t ATT_LDS_MAX = 160 * 1024;  // LDS of a CU; every attention kernel is allowed all of it
 
@@ -483,11 +489,17 @@ template <typename T> constexpr AttnLds attn_tiled_lds(int nsq) {
     constexpr int rows = 64 * attn_row_bytes<T>(ATT_HC), cols = ATT_HC * attn_row_bytes<T>(64);
     return AttnLds{(size_t)(rows > cols ? rows : cols), 2, nsq, (size_t)64 * attn_row_bytes<T>(64), true};
 }
-// The launchers send every window of at most 64 tokens to a one-tile or tr kernel without looking at its LDS size: the largest images, at the
-// largest head_dim attn_common accepts, must fit.  (Raising ATT_MAXDT fails here, not at a launch.)
+// The launchers send a window of at most 64 tokens to a one-tile or tr kernel without looking at its LDS size: the largest image of each form, at
+// the largest head_dim attn_form sends to it, must fit.  (Raising ATT_MAXDT or ATT_MAXDT_WIN fails here, not at a launch.)
 static_assert(attn_one_tile_lds<float>(attn_hdp(16 * ATT_MAXDT), true).bytes() <= ATT_LDS_MAX, "one-tile float32 backward image exceeds the LDS");
 static_assert(attn_tr_lds(attn_hdp(16 * ATT_MAXDT), true).bytes() <= ATT_LDS_MAX, "tr backward image exceeds the LDS");
 static_assert(attn_one_tile_lds<float>(192, true).bytes() == 156928 && attn_tr_lds(192, true).bytes() == 120832, "tests/attn_exact.py attn_lds restates these");
+// above ATT_MAXDT tiles the float32 one-tile backward image does not fit (174,336 B at hdp 224, 191,744 B at 256): attn_form sends those to the tiled
+// kernels; the tr images fit at every width up to ATT_MAXDT_WIN tiles
+static_assert(attn_one_tile_lds<float>(224, true).bytes() == 174336 && attn_one_tile_lds<float>(256, true).bytes() == 191744, "float32 above head_dim 192 is tiled");
+static_assert(attn_tr_lds(attn_hdp(16 * ATT_MAXDT_WIN), true).bytes() <= ATT_LDS_MAX, "tr backward image exceeds the LDS");
+static_assert(attn_tr_lds(256, false).bytes() == 110592 && attn_tr_lds(256, true).bytes() == 153600, "tests/attn_exact.py attn_lds restates these");
+static_assert(attn_tr_lds(224, false).bytes() == 98304 && attn_tr_lds(224, true).bytes() == 137216, "tests/attn_exact.py attn_lds restates these");
 static_assert(attn_tiled_lds<float>(2).bytes() <= ATT_LDS_MAX, "tiled dK/dV image exceeds the LDS");
 
 // Row softmax of four transposed score tiles: the lane holds keys j = 16t + 4*l4 + r of ONE query, the other keys of that query are in the lanes
@@ -786,6 +798,7 @@ __device__ __forceinline__ void attn_stage_rows(const bf16_t* const (&srcs)[NM],
 }
 
 // bf16 forward: Q, K, V staged once row-major; O = P V takes V through transposed fragment reads
+template <int MAXDT>
 __global__ __launch_bounds__(256) void window_attn_fwd_tr_kernel(AttnArgs a) {
     typedef bf16_t T;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -835,7 +848,7 @@ __global__ __launch_bounds__(256) void window_attn_fwd_tr_kernel(AttnArgs a) {
     __syncthreads();
     // O[m][d] = sum_j P[m][j] V[j][d]: A = rows of P (k = j contiguous), B = transposed read of V
 #pragma unroll
-    for (int dt = 0; dt < ATT_MAXDT; ++dt)
+    for (int dt = 0; dt < MAXDT; ++dt)
         if (dt < ndt) {
             f32x4 o = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -850,6 +863,7 @@ __global__ __launch_bounds__(256) void window_attn_fwd_tr_kernel(AttnArgs a) {
         }
 }
 
+template <int MAXDT>
 __global__ __launch_bounds__(256) void window_attn_bwd_tr_kernel(AttnArgs a) {
     typedef bf16_t T;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -916,7 +930,7 @@ __global__ __launch_bounds__(256) void window_attn_bwd_tr_kernel(AttnArgs a) {
     }
     __syncthreads();
 #pragma unroll
-    for (int dt = 0; dt < ATT_MAXDT; ++dt)
+    for (int dt = 0; dt < MAXDT; ++dt)
         if (dt < ndt) {
             f32x4 dv = f32x4{0.f, 0.f, 0.f, 0.f}, dk = dv, dq = dv;
 #pragma unroll
@@ -944,7 +958,7 @@ __global__ __launch_bounds__(256) void window_attn_bwd_tr_kernel(AttnArgs a) {
 // The head dimension is walked in chunks of ATT_HC columns through two LDS staging buffers, so float32 at head_dim 192
 // fits the 160 KiB of a CU.  This path serves config 5's optional ws = 14 row (196 tokens); the 49-token windows of the
 // benchmark stay on the one-tile kernels above.
-template <typename T>
+template <typename T, int MAXDT>
 __global__ __launch_bounds__(256) void window_attn_tiled_fwd_kernel(AttnArgs a) {
     constexpr AttnLds lds = attn_tiled_lds<T>(1);
     constexpr int TS = attn_row_bytes<T>(64);  // row stride of a [chunk][64] / [64][64] image
@@ -973,9 +987,9 @@ __global__ __launch_bounds__(256) void window_attn_tiled_fwd_kernel(AttnArgs a) 
             Pack<T, 4>::store(vout + (int64_t)r * a.vout.ld + c, v);
         }
     }
-    f32x4 o[ATT_MAXDT];
+    f32x4 o[MAXDT];
 #pragma unroll
-    for (int dt = 0; dt < ATT_MAXDT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int dt = 0; dt < MAXDT; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
     float m_run = -__builtin_inff(), l_run = 0.f;  // of query q0 + 16*wv + l15 (replicated in the 4 lanes that share it)
     for (int k0 = 0; k0 < L; k0 += 64) {
         const int krows = (L - k0 < 64) ? L - k0 : 64;
@@ -1010,7 +1024,7 @@ __global__ __launch_bounds__(256) void window_attn_tiled_fwd_kernel(AttnArgs a) 
 #pragma unroll
         for (int r = 0; r < 4; ++r) ar[r] = al[16 * wv + 4 * l4 + r];
 #pragma unroll
-        for (int dt = 0; dt < ATT_MAXDT; ++dt)
+        for (int dt = 0; dt < MAXDT; ++dt)
             if (dt < ndt)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) o[dt][r] *= ar[r];
@@ -1021,7 +1035,7 @@ __global__ __launch_bounds__(256) void window_attn_tiled_fwd_kernel(AttnArgs a) 
             lds_load_transposed<T>(GA, qkv + (int64_t)k0 * a.qkv.ld + vc + d0, a.qkv.ld, krows, hc, hcp);
             __syncthreads();
 #pragma unroll
-            for (int dt = 0; dt < ATT_MAXDT; ++dt)
+            for (int dt = 0; dt < MAXDT; ++dt)
                 if (dt < ndt && dt * 16 >= d0 && dt * 16 < d0 + ATT_HC) AT<T>::mma(P, TS, wv * 16, GA, TS, dt * 16 - d0, 64, lane, o[dt]);
         }
         __syncthreads();  // P / al are rewritten by the next key tile
@@ -1033,7 +1047,7 @@ __global__ __launch_bounds__(256) void window_attn_tiled_fwd_kernel(AttnArgs a) 
     }
     __syncthreads();
 #pragma unroll
-    for (int dt = 0; dt < ATT_MAXDT; ++dt)
+    for (int dt = 0; dt < MAXDT; ++dt)
         if (dt < ndt) {
             f32x4 on;
 #pragma unroll
@@ -1095,7 +1109,7 @@ __device__ __forceinline__ void attn_tile_p_ds(const AttnArgs& a, char* GA, char
     }
 }
 
-template <typename T>
+template <typename T, int MAXDT>
 __global__ __launch_bounds__(256) void window_attn_tiled_dq_kernel(AttnArgs a) {
     constexpr AttnLds lds = attn_tiled_lds<T>(1);
     constexpr int TS = attn_row_bytes<T>(64);
@@ -1117,9 +1131,9 @@ __global__ __launch_bounds__(256) void window_attn_tiled_dq_kernel(AttnArgs a) {
     T* dqkv = reinterpret_cast<T*>(const_cast<void*>(a.dqkv.p)) + t0 * a.dqkv.ld;
     const int ndt = (kd + 15) / 16;  // dQ is as wide as the score contraction
     attn_delta_rows<T>(delta, dO + (int64_t)q0 * a.dout.ld + co, a.dout.ld, ov + (int64_t)q0 * a.out.ld + co, a.out.ld, qrows, hd);
-    f32x4 dq[ATT_MAXDT];
+    f32x4 dq[MAXDT];
 #pragma unroll
-    for (int dt = 0; dt < ATT_MAXDT; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+    for (int dt = 0; dt < MAXDT; ++dt) dq[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
     for (int k0 = 0; k0 < L; k0 += 64) {
         const int krows = (L - k0 < 64) ? L - k0 : 64;
         float p[4][4], ds[4][4];
@@ -1136,16 +1150,16 @@ __global__ __launch_bounds__(256) void window_attn_tiled_dq_kernel(AttnArgs a) {
             lds_load_transposed<T>(GA, qkv + (int64_t)k0 * a.qkv.ld + kc + d0, a.qkv.ld, krows, hc, hcp);
             __syncthreads();
 #pragma unroll
-            for (int dt = 0; dt < ATT_MAXDT; ++dt)
+            for (int dt = 0; dt < MAXDT; ++dt)
                 if (dt < ndt && dt * 16 >= d0 && dt * 16 < d0 + ATT_HC) AT<T>::mma(DS, TS, wv * 16, GA, TS, dt * 16 - d0, 64, lane, dq[dt]);
         }
     }
 #pragma unroll
-    for (int dt = 0; dt < ATT_MAXDT; ++dt)
+    for (int dt = 0; dt < MAXDT; ++dt)
         if (dt < ndt) attn_store_tiles<T, 1>({dqkv + (int64_t)q0 * a.dqkv.ld + qc}, a.dqkv.ld, {dq[dt]}, qrows, dt, kd);
 }
 
-template <typename T>
+template <typename T, int MAXDT>
 __global__ __launch_bounds__(256) void window_attn_tiled_dkv_kernel(AttnArgs a) {
     constexpr AttnLds lds = attn_tiled_lds<T>(2);
     constexpr int TS = attn_row_bytes<T>(64);
@@ -1167,9 +1181,9 @@ __global__ __launch_bounds__(256) void window_attn_tiled_dkv_kernel(AttnArgs a) 
     const T* dO = reinterpret_cast<const T*>(a.dout.p) + t0 * a.dout.ld;
     T* dqkv = reinterpret_cast<T*>(const_cast<void*>(a.dqkv.p)) + t0 * a.dqkv.ld;
     const int ndv = (hd + 15) / 16, ndk = (kd + 15) / 16;
-    f32x4 dk[ATT_MAXDT], dv[ATT_MAXDT];
+    f32x4 dk[MAXDT], dv[MAXDT];
 #pragma unroll
-    for (int dt = 0; dt < ATT_MAXDT; ++dt) {
+    for (int dt = 0; dt < MAXDT; ++dt) {
         dk[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
         dv[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
@@ -1195,7 +1209,7 @@ __global__ __launch_bounds__(256) void window_attn_tiled_dkv_kernel(AttnArgs a) 
             lds_load_transposed<T>(GB, qkv + (int64_t)q0 * a.qkv.ld + qc + d0, a.qkv.ld, qrows, hck, hckp);   // Q^T  [d][m]
             __syncthreads();
 #pragma unroll
-            for (int dt = 0; dt < ATT_MAXDT; ++dt)
+            for (int dt = 0; dt < MAXDT; ++dt)
                 if (dt * 16 >= d0 && dt * 16 < d0 + ATT_HC) {
                     if (dt < ndv) AT<T>::mma(PT, TS, wv * 16, GA, TS, dt * 16 - d0, 64, lane, dv[dt]);   // dV[j][d] += sum_m P^T[j][m] dO^T[d][m]
                     if (dt < ndk) AT<T>::mma(DST, TS, wv * 16, GB, TS, dt * 16 - d0, 64, lane, dk[dt]);  // dK[j][d] += sum_m dS^T[j][m] Q^T[d][m]
@@ -1206,7 +1220,7 @@ __global__ __launch_bounds__(256) void window_attn_tiled_dkv_kernel(AttnArgs a) 
         const T* add = reinterpret_cast<const T*>(a.dvadd.p) + (t0 + k0) * a.dvadd.ld + co;
         const int col = lane & 15;
 #pragma unroll
-        for (int dt = 0; dt < ATT_MAXDT; ++dt)
+        for (int dt = 0; dt < MAXDT; ++dt)
             if (dt < ndv && dt * 16 + col < hd)
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
@@ -1216,7 +1230,7 @@ __global__ __launch_bounds__(256) void window_attn_tiled_dkv_kernel(AttnArgs a) 
     }
     T* dst = dqkv + (int64_t)k0 * a.dqkv.ld;
 #pragma unroll
-    for (int dt = 0; dt < ATT_MAXDT; ++dt) {
+    for (int dt = 0; dt < MAXDT; ++dt) {
         if (dt < ndk) attn_store_tiles<T, 1>({dst + kc}, a.dqkv.ld, {dk[dt]}, krows, dt, kd);
         if (dt < ndv) attn_store_tiles<T, 1>({dst + vc}, a.dqkv.ld, {dv[dt]}, krows, dt, hd);
     }
@@ -1228,7 +1242,7 @@ static int attn_common(const ymi_tensor* qkv, int64_t wlen, int64_t heads, AttnA
     const int64_t C = qkv->c / 3;
     YMI_CHECK_ARG(C % heads == 0, "%s: C %% heads", what);
     const int64_t hd = C / heads;
-    YMI_CHECK_ARG(hd % 4 == 0 && hd <= 16 * ATT_MAXDT && qkv->ld % 4 == 0, "%s: head_dim must be a multiple of 4 and <= %d", what, 16 * ATT_MAXDT);
+    YMI_CHECK_ARG(hd % 4 == 0 && hd <= 16 * ATT_MAXDT_WIN && qkv->ld % 4 == 0, "%s: head_dim must be a multiple of 4 and <= %d", what, 16 * ATT_MAXDT_WIN);
     YMI_CHECK_ARG(ymi_pixels(qkv) % wlen == 0, "%s: token count not a multiple of the window length", what);
     a->L = (int)wlen; a->heads = (int)heads; a->C = (int)C; a->hd = (int)hd; a->hdp = attn_hdp(hd);
     a->scale = 1.0f / sqrtf((float)hd);
@@ -1237,11 +1251,13 @@ static int attn_common(const ymi_tensor* qkv, int64_t wlen, int64_t heads, AttnA
 }
 
 // Which kernels serve a launch.  More than one 64-token tile, or the attn_tiled option (tests): the tiled kernels; one tile: the tr kernels in
-// bfloat16, the generic one-tile kernels in float32.  (Every one-tile image fits the LDS: the static_asserts beside the size functions.)
+// bfloat16; in float32 the generic one-tile kernels up to ATT_MAXDT head-dimension tiles and the tiled kernels above (the one-tile backward
+// image no longer fits).  (Every image a form is chosen for fits the LDS: the static_asserts beside the size functions.)
 enum AttnForm { ATTN_TILED, ATTN_TR, ATTN_ONE_TILE };
-static AttnForm attn_form(int64_t wlen, int32_t dtype, int attn_tiled) {
+static AttnForm attn_form(int64_t wlen, int64_t hd, int32_t dtype, int attn_tiled) {
     if (wlen > 64 || attn_tiled) return ATTN_TILED;
-    return dtype == YMI_BF16 ? ATTN_TR : ATTN_ONE_TILE;
+    if (dtype == YMI_BF16) return ATTN_TR;
+    return hd <= 16 * ATT_MAXDT ? ATTN_ONE_TILE : ATTN_TILED;
 }
 
 static void attn_launch(void (*kernel)(AttnArgs), dim3 grid, const AttnLds& lds, const AttnArgs& a, void* stream) {
@@ -1249,30 +1265,36 @@ static void attn_launch(void (*kernel)(AttnArgs), dim3 grid, const AttnLds& lds,
     hipLaunchKernelGGL(kernel, grid, dim3(256), lds.bytes(), (hipStream_t)stream, a);
 }
 
-template <typename T>
+template <typename T, int MAXDT>
 static void attn_launch_tiled(bool bwd, dim3 grid, const AttnArgs& a, void* stream) {
-    if (!bwd) return attn_launch(window_attn_tiled_fwd_kernel<T>, grid, attn_tiled_lds<T>(1), a, stream);
-    attn_launch(window_attn_tiled_dq_kernel<T>, grid, attn_tiled_lds<T>(1), a, stream);
-    attn_launch(window_attn_tiled_dkv_kernel<T>, grid, attn_tiled_lds<T>(2), a, stream);
+    if (!bwd) return attn_launch(window_attn_tiled_fwd_kernel<T, MAXDT>, grid, attn_tiled_lds<T>(1), a, stream);
+    attn_launch(window_attn_tiled_dq_kernel<T, MAXDT>, grid, attn_tiled_lds<T>(1), a, stream);
+    attn_launch(window_attn_tiled_dkv_kernel<T, MAXDT>, grid, attn_tiled_lds<T>(2), a, stream);
 }
 
 // one workgroup per (window, head) and, in the tiled kernels, per 64-token tile of the window
-static void attn_run(bool bwd, const ymi_tensor* qkv, int64_t wlen, const AttnArgs& a, void* stream) {
+// MAXDT: the tile count of the instantiation (ATT_MAXDT for every head it covers: those launches run the code they always ran)
+template <int MAXDT>
+static void attn_run_width(bool bwd, const ymi_tensor* qkv, int64_t wlen, const AttnArgs& a, void* stream) {
     const dim3 grid((unsigned)(ymi_pixels(qkv) / wlen), (unsigned)a.heads);
-    switch (attn_form(wlen, qkv->dtype, ymi_opt(OPT_ATTN_TILED))) {
+    switch (attn_form(wlen, a.hd, qkv->dtype, ymi_opt(OPT_ATTN_TILED))) {
     case ATTN_TILED: {
         const dim3 tg(grid.x, grid.y, (unsigned)((wlen + 63) / 64));
-        if (qkv->dtype == YMI_BF16) attn_launch_tiled<bf16_t>(bwd, tg, a, stream);
-        else attn_launch_tiled<float>(bwd, tg, a, stream);
+        if (qkv->dtype == YMI_BF16) attn_launch_tiled<bf16_t, MAXDT>(bwd, tg, a, stream);
+        else attn_launch_tiled<float, MAXDT>(bwd, tg, a, stream);
         break;
     }
     case ATTN_TR:
-        attn_launch(bwd ? window_attn_bwd_tr_kernel : window_attn_fwd_tr_kernel, grid, attn_tr_lds(a.hdp, bwd), a, stream);
+        attn_launch(bwd ? window_attn_bwd_tr_kernel<MAXDT> : window_attn_fwd_tr_kernel<MAXDT>, grid, attn_tr_lds(a.hdp, bwd), a, stream);
         break;
     case ATTN_ONE_TILE:
         attn_launch(bwd ? window_attn_bwd_kernel<float> : window_attn_fwd_kernel<float>, grid, attn_one_tile_lds<float>(a.hdp, bwd), a, stream);
         break;
     }
+}
+static void attn_run(bool bwd, const ymi_tensor* qkv, int64_t wlen, const AttnArgs& a, void* stream) {
+    if (a.hd <= 16 * ATT_MAXDT) attn_run_width<ATT_MAXDT>(bwd, qkv, wlen, a, stream);
+    else attn_run_width<ATT_MAXDT_WIN>(bwd, qkv, wlen, a, stream);
 }
 
 extern "C" int ymi_window_attention_fwd(const ymi_tensor* qkv, int64_t wlen, int64_t heads, const ymi_tensor* out, float* lse, void* stream) {
@@ -1325,8 +1347,8 @@ static bool psa_rows_ok(const ymi_tensor* t, const ymi_tensor* qkv, const AttnAr
 
 static void psa_run(bool bwd, const ymi_tensor* qkv, const AttnArgs& a, void* stream) {
     const dim3 grid((unsigned)(ymi_pixels(qkv) / a.L), (unsigned)a.heads, (unsigned)((a.L + 63) / 64));
-    if (qkv->dtype == YMI_BF16) attn_launch_tiled<bf16_t>(bwd, grid, a, stream);
-    else attn_launch_tiled<float>(bwd, grid, a, stream);
+    if (qkv->dtype == YMI_BF16) attn_launch_tiled<bf16_t, ATT_MAXDT>(bwd, grid, a, stream);
+    else attn_launch_tiled<float, ATT_MAXDT>(bwd, grid, a, stream);
 }
 
 extern "C" int ymi_psa_attention_fwd(const ymi_tensor* qkv, int64_t tokens, int64_t heads, int64_t kd, const ymi_tensor* out, const ymi_tensor* v_out,

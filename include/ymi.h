@@ -365,7 +365,9 @@ int ymi_layernorm_bwd_add(const ymi_tensor* x, int64_t ws, const ymi_tensor* dou
                           void* stream);
 /* Window attention core of nn.MultiheadAttention as used at swin_block.py:29,51:
  * qkv [T][3C] (q pre-scaled is NOT assumed: the kernel scales by 1/sqrt(hd)); per (window, head)
- * P = softmax(q k^T / sqrt(hd)) over all `wlen` keys, o = P v; out [T][C].  lse [T][heads] saved. */
+ * P = softmax(q k^T / sqrt(hd)) over all `wlen` keys, o = P v; out [T][C].  lse [T][heads] saved.
+ * Any window length; hd = C / heads a multiple of 4, at most 256 (wider: YMI_EINVAL, nothing is launched).  No atomics,
+ * run-to-run identical.  (The PSA entry points below keep their own limit of 192.) */
 int ymi_window_attention_fwd(const ymi_tensor* qkv, int64_t wlen, int64_t heads, const ymi_tensor* out, float* lse, void* stream);
 int ymi_window_attention_bwd(const ymi_tensor* qkv, const ymi_tensor* out, const ymi_tensor* dout, const float* lse, int64_t wlen,
                              int64_t heads, const ymi_tensor* dqkv, void* stream);
