@@ -520,6 +520,12 @@ int ymi_chan_reduce_final(const float* part, int blocks, int C, float* out0, flo
 int ymi_bn_bwd_final(const float* part, int blocks, int C, const float* gamma, const float* beta, const float* mean, const float* inv, float inv_count,
                      float* dgamma, float* dbeta, float* coef, hipStream_t stream);
 
+// wgrad.hip: the record ymi_wgrad_reduce_batch sums the slabs of one launch from ([splits][elems] slabs, elems = padded Cout * ng, a multiple of 8;
+// first_block is filled in by the batched sum).  It sets the sum's geometry: more interleaved split chains per output element the more splits there are,
+// and one 16-byte load per lane and split - 8 elements of a bfloat16 slab, 4 of a float32 one.  (first_conv.hip's backward writes such slabs too.)
+ymi_wgrad_pending ymi_wgrad_record(const void* slab, float* dw, int64_t elems, int splits, int ng, int cin, int cout_real, int cin_real, int ntaps,
+                                   bool slab_bf16, const float* bias_slab, float* dbias);
+
 // a slot of 64 ticket counters for one launch (host; round-robin over 1024 slots, zero between launches)
 unsigned* ymi_ticket_slot();
 
@@ -527,6 +533,32 @@ unsigned* ymi_ticket_slot();
 // to LDS by LDS-DMA (global_load_lds) are readable by other waves only after BOTH (counted wait, then barrier).
 template <int N> __device__ __forceinline__ void wait_vmcnt_barrier() {
     asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(N) : "memory");
+}
+
+// ---- the swizzled [row][column] bfloat16 LDS image that ds_read_b64_tr_b16 reads transposed (wgrad.hip, first_conv.hip) ---------------------
+// A fragment = 8 consecutive ROWS (8g .. 8g + 7 of a 32-row block, g = lane / 16) of column c0 + lane % 16, by two transposed 8-byte reads.
+// The instruction is serviced per 32-lane half: 2 groups x (4 rows x 4 eight-byte units); the 8 rows of a half are {r0..r0+3, r0+8..r0+11}.
+// With 64-, 128- or 256-byte rows those rows share banks on the plain image, so the 8-byte unit index is XORed with a per-row value that
+// spreads them over the 32 unit slots of a 256-byte bank row: position (r, u ^ (tr_swz<SW>(r) << 2)) holds unit u of row r, for writers and
+// readers alike.  The XOR never touches bit 0 of the unit index: it permutes 16-byte chunks (chunk ^ (tr_swz << 1)) and can be applied to the
+// source address of an LDS-DMA piece.  Wider rows take mode 1 (the XOR stays inside each 256-byte bank row).
+// SW by the row width (tr_swz_mode): 0 = 128-byte rows (2 bits), 1 = 256-byte and wider rows (3 bits), 2 = 64-byte rows (rows r and r + 8 of a half share
+// banks, rows r .. r + 3 do not: one bit)
+constexpr int tr_swz_mode(int row_bytes) { return row_bytes >= 256 ? 1 : row_bytes == 64 ? 2 : 0; }
+template <int SW> __device__ __forceinline__ int tr_swz(int row) {
+    return SW == 1 ? ((row & 3) | (((row >> 3) & 1) << 2)) : SW == 2 ? ((row >> 3) & 1) : (((row >> 1) & 1) | (((row >> 3) & 1) << 1));
+}
+// the two read addresses (LDS) of a lane's fragment, rows r_lo and r_lo + 4, in an image with `rowb` bytes per row; each file reads them in
+// its own instruction form
+struct TrFragAddr {
+    lptr_t lo, hi;
+};
+template <int SW> __device__ __forceinline__ TrFragAddr tr_frag_addr(const char* img, int rowb, int c0, int lane) {
+    const int g = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
+    const int r_lo = 8 * g + q, r_hi = r_lo + 4;
+    const int u = (c0 >> 2) + p;  // logical 8-byte unit of this lane's 4 columns
+    const int u_lo = u ^ (tr_swz<SW>(r_lo) << 2), u_hi = u ^ (tr_swz<SW>(r_hi) << 2);
+    return TrFragAddr{(lptr_t)(img + r_lo * rowb + u_lo * 8), (lptr_t)(img + r_hi * rowb + u_hi * 8)};
 }
 
 // wave-level reductions (64 lanes)

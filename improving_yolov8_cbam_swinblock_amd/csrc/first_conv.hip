@@ -70,20 +70,14 @@ __device__ __forceinline__ uint32_t fc_pack2(float lo, float hi) {
     return __builtin_bit_cast(uint32_t, v);
 }
 
-// ---- transposed fragment read (as csrc/wgrad.hip's WFrag): 8 consecutive ROWS (pixels 8 l4 .. 8 l4 + 7 of a 32-row block) of column c0 + l15 of a
-// [row][column] bfloat16 image with `rowb` bytes per row, by two ds_read_b64_tr_b16.  The 8-byte unit index is XORed with a per-row value
-// (SW = 2: 64-byte rows, SW = 0: 128-byte rows) so that the 8 rows a 32-lane half addresses fall into different banks; writers store unit u
-// of row r at unit u ^ (fc_swz<SW>(r) << 2).
-template <int SW> __device__ __forceinline__ int fc_swz(int row) { return SW == 2 ? ((row >> 3) & 1) : (((row >> 1) & 1) | (((row >> 3) & 1) << 1)); }
+// ---- transposed fragment read of a swizzled image (common.h: tr_frag_addr; SW = 2: 64-byte rows, SW = 0: 128-byte rows) through the builtin:
+// the reads are ordered against this kernel's own plain LDS stores, which the compiler sees
 template <int SW> __device__ __forceinline__ bf16x8 fc_tr_load(const char* img, int rowb, int c0, int lane) {
     typedef __attribute__((ext_vector_type(4))) short s16x4;
     typedef __attribute__((ext_vector_type(8))) short s16x8;
-    const int g = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
-    const int r_lo = 8 * g + q, r_hi = r_lo + 4;
-    const int u = (c0 >> 2) + p;
-    const int u_lo = u ^ (fc_swz<SW>(r_lo) << 2), u_hi = u ^ (fc_swz<SW>(r_hi) << 2);
-    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(img + r_lo * rowb + u_lo * 8));
-    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)(img + r_hi * rowb + u_hi * 8));
+    const TrFragAddr ad = tr_frag_addr<SW>(img, rowb, c0, lane);
+    const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)ad.lo);
+    const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4*)ad.hi);
     const s16x8 v = {lo[0], lo[1], lo[2], lo[3], hi[0], hi[1], hi[2], hi[3]};
     return __builtin_bit_cast(bf16x8, v);
 }
@@ -196,7 +190,7 @@ __global__ __launch_bounds__(256, 4) void first_conv_kernel(FirstConvArgs a) {  
     constexpr int NCT = CO / 16;                       // channel tiles of 16
     constexpr int OUTB = FC_TW * CO * 2;               // bytes of one wave's output row segment
     constexpr int CPP = CO / 8;                        // 16-byte chunks per output pixel
-    constexpr int DROWB = CO <= 32 ? 64 : 128, DSW = CO <= 32 ? 2 : 0;  // FC_BWD_WGRAD: row bytes / swizzle mode of the wave's [pixel][channel] image of d(raw)
+    constexpr int DROWB = CO <= 32 ? 64 : 128, DSW = tr_swz_mode(DROWB);  // FC_BWD_WGRAD: row bytes / swizzle mode of the wave's [pixel][channel] image of d(raw)
     constexpr int STAGEB = MODE == FC_BWD_WGRAD ? FC_TW * DROWB : OUTB;
     __shared__ __attribute__((aligned(16))) char patch[FC_PR * FC_ROWB];
     __shared__ __attribute__((aligned(16))) char stage[(MODE == FC_APPLY || MODE == FC_BWD_WGRAD) ? 4 * STAGEB : 16];
@@ -337,7 +331,7 @@ __global__ __launch_bounds__(256, 4) void first_conv_kernel(FirstConvArgs a) {  
                             const float dz = (float)dy_cur[ct][r] * fc_act_grad(raw[r] * a0[r] + a1[r], a.act);
                             o[r] = (bf16_t)(ok ? dz * c0[r] - (raw[r] * c1[r] + c2[r]) : 0.f);
                         }
-                        *reinterpret_cast<bf16x4*>(my + owl * DROWB + ((ch0 >> 2) ^ (fc_swz<DSW>(owl) << 2)) * 8) = o;
+                        *reinterpret_cast<bf16x4*>(my + owl * DROWB + ((ch0 >> 2) ^ (tr_swz<DSW>(owl) << 2)) * 8) = o;
                     }
                 }
                 if constexpr (MODE == FC_BWD_REDUCE || MODE == FC_BWD_WGRAD) {
@@ -530,9 +524,7 @@ extern "C" int ymi_first_conv_bn_act_bwd(const ymi_tensor* x4, const float* weig
     a.v0 = coef; a.slab = slab;
     rc = fc_launch<FC_BWD_WGRAD>(a, cout, (unsigned)wgs, s);
     if (rc) return rc;
-    const int64_t elems = cout * 72;
-    const int lanes = wgs > 128 ? 32 : wgs > 32 ? 16 : wgs > 8 ? 8 : 4;
-    ymi_wgrad_pending rec{slab, dw_oihw, elems, (int32_t)wgs, 72, 8, (int32_t)cout, (int32_t)c, 9, lanes, 0, (int32_t)((elems / 4 + 256 / lanes - 1) / (256 / lanes)), 0};
+    const ymi_wgrad_pending rec = ymi_wgrad_record(slab, dw_oihw, cout * 72, (int)wgs, 72, 8, (int)cout, (int)c, 9, false, nullptr, nullptr);
     if (pending) {
         *pending = rec;
         return YMI_OK;

@@ -7,8 +7,8 @@
 // fragments are read TRANSPOSED with ds_read_b64_tr_b16 (bf16) or plain ds_read_b32 (f32 parity
 // mode, 16x16x4 MFMA).  The pixel axis is split across workgroups; each split writes a slab of partial
 // sums, a second kernel sums the slabs in float32 in a fixed order (deterministic, no atomics) and scatters
-// into the reference's OIHW layout.  Slabs are float32 in parity mode and bfloat16 in the bf16 path
-// (round 3): the first-level partials of a split - a sum over >= 256 pixels held in float32 registers -
+// into the reference's OIHW layout.  Slabs are float32 in parity mode and bfloat16 in the bf16 path:
+// the first-level partials of a split - a sum over >= 256 pixels held in float32 registers -
 // are rounded once on their way out, the second level stays float32.  That halves the slab traffic
 // (36 MB -> 18 MB written per launch at bs 32, and the batched reduce reads half as much).
 #include <stdlib.h>
@@ -40,10 +40,7 @@ struct WgradArgs {
 // (Granlund-Montgomery; exact also for d = 1 and powers of two, so the K loop needs no special case and no branch)
 __device__ __forceinline__ int wg_fast_div(int n, uint32_t mul, uint32_t shr) { return (int)((__umulhi((uint32_t)n, mul) + (uint32_t)n) >> shr); }
 
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-
-constexpr int WG_BM = 64;    // rows  (co)
-constexpr int WG_BN = 128;   // cols  ((tap, ci))
+constexpr int WG_BN = 128;   // tile columns ((tap, ci)); the rows (co) are the kernel's BM
 constexpr int WG_BK = 32;    // pixels per K step (64 was measured 10-15 % slower: half as many resident workgroups per CU)
 constexpr int WG_NS = 2;     // LDS ring stages of the bf16 kernels (three and four: +9 %, profiles/r05_wgrad_patch_walk_ab.txt)
 constexpr int WG_WAVES = 5;  // waves per SIMD the 64-row tile's register allocation must allow (4 and 6: no better, profiles/r04_wgrad_targets_sweep.txt)
@@ -59,58 +56,41 @@ __device__ __forceinline__ void wg_buffer_to_lds(const void* base, uint32_t byte
     __builtin_amdgcn_raw_ptr_buffer_load_lds(__builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, bytes, 0x00020000), dst, 16, voff, soff, 0, 0);
 #endif
 }
+// `global_load_lds_dwordx4`: 16 bytes per lane from each lane's own address.  Behind a device-only function for the same reason: called from a member
+// of a class template, the builtin makes the host pass drop the launch stub of every kernel instantiation but the first that uses that member.
+__device__ __forceinline__ void wg_global_to_lds(const void* src, lptr_t dst) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __builtin_amdgcn_global_load_lds((gptr_t)src, dst, 16, 0, 0);
+#endif
+}
 template <typename T> struct WFrag;
-// LDS bank swizzle for the transposed reads (bf16).  ds_read_b64_tr_b16 is serviced per 32-lane half: 2 groups x
-// (4 rows x 4 eight-byte units); the 8 rows of a half are {r0..r0+3, r0+8..r0+11}.  With 128-byte (dY) or 256-byte
-// (X) rows those rows share banks (4-way / 8-way conflict on the plain image), so the 8-byte unit index is XORed
-// with a per-row value that spreads the 8 rows over the 32 unit slots of a 256-byte bank row.  The XOR never touches
-// bit 0 of the unit index, so it is a permutation of 16-byte chunks and can be applied to the LDS-DMA SOURCE address.
-__device__ __forceinline__ int wg_swz_y(int row) { return ((row >> 1) & 1) | (((row >> 3) & 1) << 1); }        // 2 bits
-__device__ __forceinline__ int wg_swz_x(int row) { return (row & 3) | (((row >> 3) & 1) << 2); }                // 3 bits
-// 64-byte rows (the dY image of the 32-channel tile): rows r and r+8 of a half share banks, rows r..r+3 do not: one bit
-__device__ __forceinline__ int wg_swz_y32(int row) { return (row >> 3) & 1; }
-// swizzle mode of an LDS image by its row width: 0 = 128-byte rows, 1 = 256-byte (and wider) rows, 2 = 64-byte rows
-template <int SW> __device__ __forceinline__ int wg_swz(int row) { return SW == 1 ? wg_swz_x(row) : SW == 2 ? wg_swz_y32(row) : wg_swz_y(row); }
-template <int BM> struct YSwz { static constexpr int SW = BM == 128 ? 1 : BM == 32 ? 2 : 0; };
 
 template <> struct WFrag<bf16_t> {
-    // a fragment = 8 k-values (pixels 8g..8g+7) for column c0+i of a [pixel][col] LDS image with `rowb` bytes per row
-    // The reads are written as inline assembly (round 5).  Through the builtin the compiler sees LDS reads that may alias the LDS-DMA pieces
+    // a fragment = 8 k-values (pixels 8g..8g+7) for column c0+i of a [pixel][col] LDS image (common.h: tr_frag_addr)
+    // The reads are written as inline assembly.  Through the builtin the compiler sees LDS reads that may alias the LDS-DMA pieces
     // issued a few instructions earlier and puts `s_waitcnt vmcnt(0)` in front of them: every K step then waited for the pieces of the NEXT
-    // step before it read its own fragments - the whole load latency exposed in every wave, every step (found in the ISA while building
-    // the patch walk; it had been there since round 1).  The ring's protocol (counted wait + barrier at the top of a step, pieces only into
-    // the stage nobody reads) is what orders the two; the compiler cannot know and must not add to it.
-    struct Addr { uint32_t lo, hi; };
-    template <int SW>
-    static __device__ __forceinline__ Addr addr(const char* img, int rowb, int c0, int lane) {
-        const int g = lane >> 4, i = lane & 15, q = i >> 2, p = i & 3;
-        const int r_lo = 8 * g + q, r_hi = r_lo + 4;
-        const int u = (c0 >> 2) + p;  // logical 8-byte unit of this lane's 4 columns
-        const int u_lo = u ^ (wg_swz<SW>(r_lo) << 2);
-        const int u_hi = u ^ (wg_swz<SW>(r_hi) << 2);
-        return Addr{(uint32_t)(uintptr_t)(lptr_t)(img + r_lo * rowb + u_lo * 8), (uint32_t)(uintptr_t)(lptr_t)(img + r_hi * rowb + u_hi * 8)};
-    }
-    static __device__ __forceinline__ void read2(bf16x8& f, const Addr& ad) {  // two transposed 8-byte reads fill one 8-value fragment
+    // step before it read its own fragments - the whole load latency exposed in every wave, every step.  The ring's protocol (counted wait +
+    // barrier at the top of a step, pieces only into the stage nobody reads) is what orders the two; the compiler cannot know and must not
+    // add to it.
+    static __device__ __forceinline__ void read2(bf16x8& f, const TrFragAddr& ad) {  // two transposed 8-byte reads fill one 8-value fragment
         typedef __attribute__((ext_vector_type(2))) uint32_t u2;
         u2 lo, hi;
-        asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(lo) : "v"(ad.lo));
-        asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(hi) : "v"(ad.hi));
+        asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(lo) : "v"((uint32_t)(uintptr_t)ad.lo));
+        asm volatile("ds_read_b64_tr_b16 %0, %1" : "=v"(hi) : "v"((uint32_t)(uintptr_t)ad.hi));
         const u32x4 v = {lo[0], lo[1], hi[0], hi[1]};
         f = __builtin_bit_cast(bf16x8, v);
     }
-    template <int BM, int TR, int TC, int BNW = WG_BN, bool BIAS = false>
+    template <int BM, int TR, int TC, bool BIAS>
     static __device__ __forceinline__ void step(const char* Ys, const char* Xs, int r0, int c0, int lane, f32x4 (&acc)[TR][TC], bool bias, f32x4 (&accb)[BIAS ? TR : 1]) {
         static_assert(WG_BK == 32, "one 32-deep sub-step");
         bf16x8 af[TR], bfr[TC];
         // addresses first (plain arithmetic), then every read of the step back to back: X fragments, then the dY fragments in the
         // order the MFMA rows use them
-        Addr ay[TR], ax[TC];
+        TrFragAddr ay[TR], ax[TC];
 #pragma unroll
-        for (int t = 0; t < TR; ++t) ay[t] = addr<YSwz<BM>::SW>(Ys, BM * 2, r0 + t * 16, lane);  // by the dY image's row width
-        // (512-byte X rows of the 256-column tile: the XOR only touches the low five bits of the 8-byte unit index, i.e. it
-        // permutes units inside each 256-byte bank row exactly as for 256-byte rows)
+        for (int t = 0; t < TR; ++t) ay[t] = tr_frag_addr<tr_swz_mode(BM * 2)>(Ys, BM * 2, r0 + t * 16, lane);
 #pragma unroll
-        for (int t = 0; t < TC; ++t) ax[t] = addr<1>(Xs, BNW * 2, c0 + t * 16, lane);
+        for (int t = 0; t < TC; ++t) ax[t] = tr_frag_addr<tr_swz_mode(WG_BN * 2)>(Xs, WG_BN * 2, c0 + t * 16, lane);
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int t = 0; t < TC; ++t) read2(bfr[t], ax[t]);
@@ -143,9 +123,8 @@ template <> struct WFrag<bf16_t> {
     }
 };
 template <> struct WFrag<float> {
-    template <int BM, int TR, int TC, int BNW = WG_BN, bool BIAS = false>
+    template <int BM, int TR, int TC, bool BIAS>
     static __device__ __forceinline__ void step(const char* Ys, const char* Xs, int r0, int c0, int lane, f32x4 (&acc)[TR][TC], bool bias, f32x4 (&accb)[BIAS ? TR : 1]) {
-        static_assert(BNW == WG_BN, "f32 parity mode uses the 128-column tile");
         const int kq = lane >> 4, i = lane & 15;
 #pragma unroll
         for (int ks = 0; ks < WG_BK / 4; ++ks) {
@@ -166,53 +145,285 @@ template <> struct WFrag<float> {
     }
 };
 
+// ---- a workgroup's tile and its loader map ---------------------------------------------------------------------------------------------------
 // BM = output channels per workgroup tile: 64, or 128 for layers with >= 128 output channels (16 instead of 8 MFMAs per
 // wave and K step against the same address arithmetic: the K loop is instruction-issue-bound, not MFMA-bound), or 32 for the
 // layers with <= 32 output channels (the 320x320 / 160x160 maps: millions of pixels against a 32 x 72..288 weight matrix; the
 // 64-row tile spent half its MFMAs on padding rows)
-// (a 128x256 tile - 4 or 8 waves - measured 1.17-1.66x slower, profiles/r02_conv_bench_wgrad256.txt; removed in round 3)
+// (a 128x256 tile - 4 or 8 waves - measured 1.17-1.66x slower, profiles/r02_conv_bench_wgrad256.txt)
+// ... and what both pixel walks share: the thread -> (row, 16-byte chunk) map of the loader and the LDS slot of a piece.
+// A thread fetches the same chunk column of rows y_row(i), i < NY, of the dY image and of rows x_row(i), i < NX, of the X image.  bf16: LDS position
+// (row, chunk') holds source chunk chunk' ^ (swizzle(row) << 1); the row bits the swizzle uses are the same for all of a thread's rows.  The X chunk
+// column fixes the thread's tap and input channel.
+template <typename T, int BM> struct WgTile {
+    static constexpr int NT = 256;
+    static constexpr int CH = ElemTraits<T>::CH, ES = (int)sizeof(T);
+    static constexpr int YCW = BM * ES / 16, XCW = WG_BN * ES / 16;  // 16-byte chunks per tile row
+    // threads that cover one dY load of the workgroup (32-channel tile: 128 - the other two waves fetch the SAME chunks to the SAME LDS bytes, so every
+    // wave issues the same number of loads and the counted waits stay uniform)
+    static constexpr int YT = WG_BK * YCW < NT ? WG_BK * YCW : NT;
+    static constexpr int NY = (WG_BK * YCW + NT - 1) / NT, NX = WG_BK * XCW / NT;  // 16-byte pieces per thread per K step
+    static constexpr int WCOLS = WG_BN / 64, WROWS = (NT / 64) / WCOLS;            // wave grid: every wave owns a (BM / WROWS) x 64 tile ...
+    static constexpr int WM = BM / WROWS, TR = WM / 16, TC = 4;                    // ... of TR x TC MFMA tiles
+    static constexpr int YBYTES = WG_BK * BM * ES, XBYTES = WG_BK * WG_BN * ES, STAGE = YBYTES + XBYTES;  // a ring stage: the dY image, then the X image
+    static_assert(NY >= 1 && NX >= 1, "tile too small");
+    static constexpr bool SWZ = std::is_same<T, bf16_t>::value;
+    static_assert(NT / XCW >= 16 || !SWZ, "bf16: a block-wide load covers >= 16 rows, so a thread's rows share the row bits the swizzle uses");
+    int yrow0, ych;         // first dY row; output channel of the chunk
+    bool y_cok, x_cok;      // the chunk lies inside the padded channels / inside (tap, ci)
+    int xrow0, ci, dh, dw;  // first X row; input channel and tap shift of the chunk
+    __device__ __forceinline__ WgTile(const WgradArgs& a, int tid, int j0, int co0) {
+        const int ytid = tid % YT;
+        yrow0 = ytid / YCW;
+        const int ycc = SWZ ? ((ytid % YCW) ^ (tr_swz<tr_swz_mode(YCW * 16)>(yrow0) << 1)) : (ytid % YCW);
+        ych = co0 + ycc * CH;
+        y_cok = ych < a.CoutP;
+        xrow0 = tid / XCW;
+        const int xcc = SWZ ? ((tid % XCW) ^ (tr_swz<tr_swz_mode(XCW * 16)>(xrow0) << 1)) : (tid % XCW);
+        const int j = j0 + xcc * CH;
+        x_cok = j < a.NG;
+        const int tap = x_cok ? j / a.Cin : 0;
+        ci = x_cok ? j - tap * a.Cin : 0;
+        dh = tap / a.KW - a.pad;
+        dw = tap % a.KW - a.pad;
+    }
+    __device__ __forceinline__ int y_row(int i) const { return yrow0 + i * (NT / YCW); }
+    __device__ __forceinline__ int x_row(int i) const { return xrow0 + i * (NT / XCW); }
+    // LDS-DMA writes a wave's 64 pieces lane-linear behind a wave-uniform address
+    static __device__ __forceinline__ lptr_t y_slot(char* Ys, int i, int wave) { return (lptr_t)(Ys + (i * NT + (wave * 64) % YT) * 16); }
+    static __device__ __forceinline__ lptr_t x_slot(char* Xs, int i, int wave) { return (lptr_t)(Xs + (i * NT + wave * 64) * 16); }
+};
+
+// ---- the raster walk: the K axis runs over the output pixels m_begin, m_begin + 1, ... of the split -------------------------------------------
+// Address state of this thread's rows, advanced by WG_BK pixels per K step with adds and compares only (the pixel ->
+// (n, ho, wo) decomposition by two multiply-highs and five multiplies per piece and step cost ~160 cycles per piece: the
+// issue phase was half of a K step, stamps in profiles/r02_igemm_phase_stamps.txt section 6).  issue() is called for
+// consecutive steps m_begin, m_begin + WG_BK, ...: it uses the state and then moves it one step on.
+//   X row: ws = wo * stride, hs = ho * stride (input coordinates of the tap-(0,0) pixel), x_off = element offset of that pixel
+//          + this thread's tap shift and channel; a step adds (q, r) = divmod(WG_BK, Wo) rows / columns, then wraps.
+//   Y row: element offset m * ldy + channel.
+// Pieces outside the split, the map or the channels read the zero page.
+template <typename T, int BM> struct WgRasterWalk {
+    using G = WgTile<T, BM>;
+    const WgradArgs& a;
+    const G& ld;
+    const int wave, m_end;
+    const int s_ = a.stride, ldx32 = (int)a.ldx, ldy32 = (int)a.ldy;
+    const int q_ = WG_BK / a.Wo, r_ = WG_BK - q_ * a.Wo;                              // scalar
+    const uint32_t d_step = (uint32_t)((q_ * s_ * a.W + r_ * s_) * ldx32);            // offset change of (ho += q, wo += r)
+    const uint32_t d_wwrap = (uint32_t)((s_ * a.W - a.Wo * s_) * ldx32);              // ... of (wo -= Wo, ho += 1)
+    const uint32_t d_hwrap = (uint32_t)((a.H * a.W - a.Ho * s_ * a.W) * ldx32);       // ... of (ho -= Ho, n += 1)
+    const uint32_t y_step = (uint32_t)(WG_BK * ldy32);
+    const int ws_lim = a.Wo * s_, hs_lim = a.Ho * s_;
+    int x_ws[G::NX], x_hs[G::NX];
+    uint32_t x_off[G::NX], y_off[G::NY];
+    __device__ __forceinline__ WgRasterWalk(const WgradArgs& a_, const G& ld_, int wave_, int m_begin)
+        : a(a_), ld(ld_), wave(wave_), m_end(min(a_.Mpix, m_begin + a_.pix_per_split)) {
+#pragma unroll
+        for (int i = 0; i < G::NX; ++i) {
+            const int m = m_begin + ld.x_row(i);
+            const int t = wg_fast_div(m, a.wo_mul, a.wo_shr);
+            const int wo = m - t * a.Wo;
+            const int n = wg_fast_div(t, a.ho_mul, a.ho_shr);
+            const int ho = t - n * a.Ho;
+            x_ws[i] = wo * s_;
+            x_hs[i] = ho * s_;
+            x_off[i] = (uint32_t)(((n * a.H + ho * s_ + ld.dh) * a.W + wo * s_ + ld.dw) * ldx32 + ld.ci);
+        }
+#pragma unroll
+        for (int i = 0; i < G::NY; ++i) y_off[i] = (uint32_t)((m_begin + ld.y_row(i)) * ldy32 + ld.ych);
+    }
+    __device__ __forceinline__ void issue(char* Ys, int mk) {
+        const T* __restrict__ xg = reinterpret_cast<const T*>(a.x);
+        const T* __restrict__ yg = reinterpret_cast<const T*>(a.dy);
+        const T* zero = reinterpret_cast<const T*>(a.zero);
+        char* Xs = Ys + G::YBYTES;
+        const int left = m_end - mk;  // scalar: rows below it are inside this split
+#pragma unroll
+        for (int i = 0; i < G::NY; ++i) {
+            const bool ok = ld.y_cok && ld.y_row(i) < left;
+            const T* src = ok ? yg + y_off[i] : zero;
+            wg_global_to_lds(src, ld.y_slot(Ys, i, wave));
+            y_off[i] += y_step;
+        }
+#pragma unroll
+        for (int i = 0; i < G::NX; ++i) {
+            const bool ok = ld.x_cok && ld.x_row(i) < left && (unsigned)(x_hs[i] + ld.dh) < (unsigned)a.H && (unsigned)(x_ws[i] + ld.dw) < (unsigned)a.W;
+            const T* src = ok ? xg + x_off[i] : zero;
+            wg_global_to_lds(src, ld.x_slot(Xs, i, wave));
+            // one K step on
+            x_ws[i] += r_ * s_;
+            x_hs[i] += q_ * s_;
+            x_off[i] += d_step;
+            if (x_ws[i] >= ws_lim) {
+                x_ws[i] -= ws_lim;
+                x_hs[i] += s_;
+                x_off[i] += d_wwrap;
+            }
+            while (x_hs[i] >= hs_lim) {  // at most once unless the map has fewer rows than a K step covers
+                x_hs[i] -= hs_lim;
+                x_off[i] += d_hwrap;
+            }
+        }
+    }
+};
+
+// ---- the patch walk: the K axis runs over the output pixels in PATCH order instead of raster order --------------------------------------------
+// Step k is a ph x pw patch (ph * pw = 32, pw a power of two dividing Wo, ph dividing Ho) whose origin (n, ho0, wo0) is SCALAR state.  A lane's
+// row of the step is a fixed (pr, pc) inside the patch, so its source offset is a per-thread constant plus a scalar: the pieces become
+// `buffer_load_dwordx4 ... lds` with the constant in the vector offset and the patch origin in the scalar offset, padding taps are lanes whose
+// vector offset is pushed out of range (the buffer unit writes zeros to LDS for them: tools/probes/bar/buffer_lds_probe.hip), and the per-lane
+// (ho, wo) walk with its wraps - as many issue slots as the MFMAs (profiles/r05_wgrad_patch_walk_ab.txt) - is five vector instructions per X
+// piece and none per dY piece.  Any fixed order of the pixel sum is as good as raster order; maps that do not tile into such patches (20 x 20)
+// keep the raster walk.  Splits are whole patches (the launcher: Mpix % WG_BK == 0), so no piece is cut by the split's end.
+template <typename T, int BM> struct WgPatchWalk {
+    using G = WgTile<T, BM>;
+    static constexpr uint32_t OOR = 0x80000000u;  // a vector offset beyond any buffer of < 2^31 bytes (vector + scalar offset stays below 2^32)
+    static constexpr int ES = G::ES;
+    const WgradArgs& a;
+    const int wave;
+    const int s_ = a.stride, ldx32 = (int)a.ldx, ldy32 = (int)a.ldy;
+    const int pw = 1 << a.pw_shift, ph = WG_BK >> a.pw_shift;
+    const uint32_t xbias = (uint32_t)((a.W + 1) * ldx32 * ES);  // keeps the (dh, dw) = (-1, -1) offsets non-negative
+    uint32_t pvx[G::NX], pvy[G::NY];  // per-thread constants: vector byte offsets of the pieces inside a patch ...
+    int pch[G::NX], pcw[G::NX];       // ... and the X pieces' input row / column relative to the patch origin's
+    int p_wo, p_ho;                   // scalar: the next patch's origin
+    uint32_t p_sx, p_sy;              // scalar byte offsets of that origin in X (tap (0, 0), channel 0) and dY
+    __device__ __forceinline__ WgPatchWalk(const WgradArgs& a_, const G& ld, int wave_, int m_begin) : a(a_), wave(wave_) {
+#pragma unroll
+        for (int i = 0; i < G::NX; ++i) {
+            const int row = ld.x_row(i);
+            const int pr = row >> a.pw_shift, pc = row & (pw - 1);
+            pch[i] = pr * s_ + ld.dh;
+            pcw[i] = pc * s_ + ld.dw;
+            pvx[i] = ld.x_cok ? (uint32_t)(((pch[i] * a.W + pcw[i]) * ldx32 + ld.ci) * ES) + xbias : OOR;
+        }
+#pragma unroll
+        for (int i = 0; i < G::NY; ++i) {
+            const int row = ld.y_row(i);
+            const int pr = row >> a.pw_shift, pc = row & (pw - 1);
+            pvy[i] = ld.y_cok ? (uint32_t)(((pr * a.Wo + pc) * ldy32 + ld.ych) * ES) : OOR;
+        }
+        const int pidx = __builtin_amdgcn_readfirstlane(m_begin / WG_BK);  // first patch of this split
+        const int npw = a.Wo >> a.pw_shift, nph = a.Ho / ph;
+        const int t = pidx / npw, wp = pidx - t * npw;
+        const int n = t / nph, hp = t - n * nph;
+        p_wo = wp * pw;
+        p_ho = hp * ph;
+        p_sx = (uint32_t)(((n * a.H + p_ho * s_) * a.W + p_wo * s_) * ldx32 * ES);
+        p_sy = (uint32_t)(((n * a.Ho + p_ho) * a.Wo + p_wo) * ldy32 * ES);
+    }
+    __device__ __forceinline__ void issue(char* Ys, int) {
+        char* Xs = Ys + G::YBYTES;
+        const char* xbase = reinterpret_cast<const char*>(a.x) - xbias;
+        const uint32_t sx = __builtin_amdgcn_readfirstlane(p_sx), sy = __builtin_amdgcn_readfirstlane(p_sy);  // (scalar by construction; said so)
+#pragma unroll
+        for (int i = 0; i < G::NY; ++i) wg_buffer_to_lds(a.dy, a.y_bytes, G::y_slot(Ys, i, wave), pvy[i], sy);
+        const int hs0 = __builtin_amdgcn_readfirstlane(p_ho * s_), ws0 = __builtin_amdgcn_readfirstlane(p_wo * s_);
+#pragma unroll
+        for (int i = 0; i < G::NX; ++i) {
+            const bool ok = (unsigned)(hs0 + pch[i]) < (unsigned)a.H && (unsigned)(ws0 + pcw[i]) < (unsigned)a.W;
+            wg_buffer_to_lds(xbase, a.x_bytes + xbias, G::x_slot(Xs, i, wave), ok ? pvx[i] : OOR, sx);
+        }
+        // one patch on (scalar)
+        p_wo += pw;
+        p_sx += (uint32_t)(pw * s_ * ldx32 * ES);
+        p_sy += (uint32_t)(pw * ldy32 * ES);
+        if (p_wo == a.Wo) {
+            p_wo = 0;
+            p_ho += ph;
+            p_sx += (uint32_t)((ph * s_ * a.W - a.Wo * s_) * ldx32 * ES);
+            p_sy += (uint32_t)((ph * a.Wo - a.Wo) * ldy32 * ES);
+            if (p_ho == a.Ho) {
+                p_ho = 0;
+                p_sx += (uint32_t)((a.H * a.W - a.Ho * s_ * a.W) * ldx32 * ES);
+            }
+        }
+    }
+};
+
+// ---- the LDS-staged slab store of the bf16 kernels -----------------------------------------------------------------------------------------------
+// Written straight from the accumulators, a store instruction covers 16 rows x 32 bytes (bfloat16 slabs) - sixteen partial lines - and those stores
+// cost 8 % of the family's time (0.7 ms per step if nothing hid them: profiles/r05_wgrad_slab_stores_ab.txt).  Each wave drops RP 16-row tiles x 64
+// columns of its accumulators, converted to the slab's element type S, into a private padded image in the ring and stores it back as whole row
+// segments of 64 columns, 16 bytes per lane.  Same values, same rounding.
+template <typename S, int TR> struct SlabStage {
+    static constexpr int ES = (int)sizeof(S);
+    static constexpr int SROW = 64 * ES + 16;              // padded row: 16 rows hit 16 distinct bank groups
+    static constexpr int CPR = 64 * ES / 16;               // 16-byte chunks = lanes per row segment (128 bytes of bfloat16, 256 of float32)
+    static constexpr int RPI = 64 / CPR;                   // rows per store instruction: 8 / 4
+    static constexpr int RP = TR < 4 / ES ? TR : 4 / ES;   // 16-row tiles per pass: up to 32 rows x 128 bytes or 16 rows x 256 bytes
+    static constexpr int BYTES = RP * 16 * SROW;           // of the ring, per wave
+    static_assert(TR % RP == 0, "whole passes");
+};
+// slab: this split's [CoutP][NG] slab; (row0, col0): the wave's first output channel and (tap, ci) column.  NG is a multiple of 8.
+template <typename S, int TR, int TC>
+__device__ __forceinline__ void wg_store_slab_staged(char* ring, int wave, int lane, const f32x4 (&acc)[TR][TC], S* slab, int row0, int col0, int CoutP, int NG) {
+    using St = SlabStage<S, TR>;
+    constexpr int ES = St::ES, SROW = St::SROW, RP = St::RP;
+    static_assert(TC * 16 == 64, "a wave's tile is 64 columns wide");
+    __syncthreads();  // the other waves may still read the last K step's stage
+    // the lane is made opaque here: its pieces below use the lane bits the fragment addresses use, and formed once, ahead of the K loop, they hold a
+    // VGPR across it (the 64-row raster kernel then takes 82 VGPRs instead of 80 and loses its sixth wave per SIMD)
+    asm volatile("" : "+v"(lane));
+    char* st = ring + wave * St::BYTES;
+    const int l15 = lane & 15, l4 = lane >> 4;
+    const int srow = lane / St::CPR, sch = lane % St::CPR;
+    const int col = col0 + sch * (16 / ES);
+#pragma unroll
+    for (int r0 = 0; r0 < TR; r0 += RP) {
+#pragma unroll
+        for (int rr = 0; rr < RP; ++rr)
+#pragma unroll
+            for (int c = 0; c < TC; ++c) {
+                char* p = st + (rr * 16 + l15) * SROW + (c * 16 + 4 * l4) * ES;
+                if constexpr (std::is_same<S, float>::value) {
+                    *reinterpret_cast<f32x4*>(p) = acc[r0 + rr][c];
+                } else {
+                    const bf16x4 v = {(bf16_t)acc[r0 + rr][c][0], (bf16_t)acc[r0 + rr][c][1], (bf16_t)acc[r0 + rr][c][2], (bf16_t)acc[r0 + rr][c][3]};
+                    *reinterpret_cast<bf16x4*>(p) = v;
+                }
+            }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+#pragma unroll
+        for (int k = 0; k < RP * 16 / St::RPI; ++k) {
+            const int row = k * St::RPI + srow;
+            const u32x4 u = *reinterpret_cast<const u32x4*>(st + row * SROW + sch * 16);
+            const int co = row0 + r0 * 16 + row;
+            if (co < CoutP && col < NG) *reinterpret_cast<u32x4*>(slab + (int64_t)co * NG + col) = u;
+        }
+        __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    }
+}
+
+// ---- the kernel ------------------------------------------------------------------------------------------------------------------------------
 // BIAS: the instantiation that also forms the bias gradient's partials (its own code object: the 4 * TR accumulator registers and the branch
 // cost the bias-free launches 3-4 % when they were a run-time option of one kernel)
+// PATCH: the patch walk instead of the raster walk
 // the final pass of a BatchNorm backward as a rider (common.h: BnRider): the first rider.nwg workgroups of the 1-D grid run bn_final_block, the function
 // chan_reduce_final_kernel runs as its own launch (reduce_bwd.hip), on the ring's LDS - a thread plays four of the 32 row slices - and leave.
-// PATCH (round 5): the K axis runs over the output pixels in PATCH order instead of raster order - step k is a ph x pw patch (ph * pw = 32, pw a power
-// of two dividing Wo, ph dividing Ho) whose origin (n, ho0, wo0) is SCALAR state.  A lane's row of the step is a fixed (pr, pc) inside the patch, so its
-// source offset is a per-thread constant plus a scalar: the pieces become `buffer_load_dwordx4 ... lds` with the constant in the vector offset and the
-// patch origin in the scalar offset, padding taps are lanes whose vector offset is pushed out of range (the buffer unit writes zeros to LDS for them:
-// tools/probes/bar/buffer_lds_probe.hip), and the per-lane (ho, wo) walk with its wraps - as many issue slots as the MFMAs (profiles/
-// r05_wgrad_patch_walk_ab.txt) - is five vector instructions per X piece and none per dY piece.  Any fixed order of the pixel sum is as good as raster order;
-// maps that do not tile into such patches (20 x 20) keep the raster walk.
-template <typename T, int NS, int BM, bool BIAS = false, bool PATCH = false>
+template <typename T, int BM, bool BIAS, bool PATCH>
 __global__ __launch_bounds__(256, (BM == 128 ? 3 : WG_WAVES)) void wgrad_kernel(WgradArgs a, BnRider rider) {
-    constexpr int BNW = WG_BN, NT = 256;
-    constexpr int CH = ElemTraits<T>::CH;
-    constexpr int ES = (int)sizeof(T);
-    constexpr int YCW = BM * ES / 16, XCW = BNW * ES / 16;            // 16-byte chunks per tile row
-    constexpr int YT = WG_BK * YCW < NT ? WG_BK * YCW : NT;           // threads that cover one dY load of the workgroup (32-channel tile: 128 -
-                                                                      // the other two waves fetch the SAME chunks to the SAME LDS bytes, so every
-                                                                      // wave issues the same number of loads and the counted waits stay uniform)
-    constexpr int NY = (WG_BK * YCW + NT - 1) / NT, NX = WG_BK * XCW / NT;  // chunks per thread per K step
-    constexpr int WCOLS = BNW / 64, WROWS = (NT / 64) / WCOLS;        // wave grid: every wave owns a (BM / WROWS) x 64 tile
-    constexpr int YBYTES = WG_BK * BM * ES, XBYTES = WG_BK * BNW * ES;
-    constexpr int STAGE = YBYTES + XBYTES;
-    static_assert(NY >= 1 && NX >= 1, "tile too small");
+    using G = WgTile<T, BM>;
+    constexpr int NT = G::NT, TR = G::TR, TC = G::TC, WM = G::WM, STAGE = G::STAGE, NS = WG_NS;
     constexpr int LDS = (int)wgrad_lds_bytes<T, BM>();  // what the launcher gives
     static_assert(LDS == NS * STAGE, "the launcher's LDS bytes are the ring");
-    // (the two staging images restate what the slab epilogues below define for themselves - RP and SROW = 144 of the bfloat16-slab epilogue,
-    // SROW = 272 of the float32-slab one: change them there and here together)
-    static_assert(LDS >= (NT / 64) * (BM / WROWS / 16 < 2 ? BM / WROWS / 16 : 2) * 16 * 144, "the bfloat16-slab epilogue stages RP 16-row tiles of 144-byte rows per wave in the ring");
-    static_assert(LDS >= (NT / 64) * 16 * 272, "the float32-slab epilogue stages a 16-row tile of 272-byte rows per wave in the ring");
+    static_assert(LDS >= (NT / 64) * SlabStage<bf16_t, TR>::BYTES && LDS >= (NT / 64) * SlabStage<float, TR>::BYTES, "the staged slab stores use the ring");
     static_assert(LDS >= BN_FINAL_RED * (int)sizeof(double), "a rider workgroup sums its slices in the ring");
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wr = wave / WCOLS, wc = wave % WCOLS;
+    const int wr = wave / G::WCOLS, wc = wave % G::WCOLS;
     // XCD-aware order (xcd_map): workgroup ids are dealt round-robin to the 8 XCDs; all tiles of one pixel split read the
     // same dY / X rows (the nine taps are the same pixels, shifted), so a split's tiles are given to ONE XCD, back to
     // back, and its rows are fetched into that L2 once.  An XCD gets CONSECUTIVE splits, z = xcd * ceil(splits / 8) + i: its
     // eighth of the pixel order (common.h, XCD ownership of the pixel axis) - the BatchNorm apply pass wrote those dY rows from
-    // this XCD a launch ago (round 3 dealt z = 8 i + xcd: every split's rows came from the other seven L2s).
+    // this XCD a launch ago (dealt z = 8 i + xcd, every split's rows came from the other seven L2s).
     int bx, by, bz;
     if (rider.nwg && (int)blockIdx.x < rider.nwg) {  // (only in the 1-D XCD-mapped grid; workgroup-uniform)
         if ((int)blockIdx.x * 32 < rider.f.C) bn_final_block<NT, false>(rider.f, (int)blockIdx.x, reinterpret_cast<double*>(smem));  // (else: a padding workgroup of the rider block)
@@ -229,158 +440,12 @@ __global__ __launch_bounds__(256, (BM == 128 ? 3 : WG_WAVES)) void wgrad_kernel(
     } else {
         bx = blockIdx.x; by = blockIdx.y; bz = blockIdx.z;
     }
-    const int j0 = bx * BNW, co0 = by * BM;
+    const int j0 = bx * WG_BN, co0 = by * BM;
     const int m_begin = bz * a.pix_per_split;
     const int m_end = min(a.Mpix, m_begin + a.pix_per_split);
-    const T* __restrict__ xg = reinterpret_cast<const T*>(a.x);
-    const T* __restrict__ yg = reinterpret_cast<const T*>(a.dy);
-    const T* zero = reinterpret_cast<const T*>(a.zero);
+    const G ld(a, tid, j0, co0);
+    typename std::conditional<PATCH, WgPatchWalk<T, BM>, WgRasterWalk<T, BM>>::type walk(a, ld, wave, m_begin);
 
-    // dY loader: thread -> (row, chunk) ; chunk column fixed per thread.  bf16: LDS position (row, chunk') holds
-    // source chunk chunk' ^ (swizzle(row) << 1); the row bits the swizzle uses are the same for all of a thread's rows.
-    constexpr bool SWZ = std::is_same<T, bf16_t>::value;
-    const int ytid = tid % YT;
-    const int ycc = SWZ ? ((ytid % YCW) ^ (wg_swz<YSwz<BM>::SW>(ytid / YCW) << 1)) : (ytid % YCW);
-    const bool y_cok = co0 + ycc * CH < a.CoutP;
-    // X loader: column chunk fixed per thread -> fixed tap / input-channel offset
-    static_assert(NT / XCW >= 16 || !std::is_same<T, bf16_t>::value, "bf16: a block-wide load covers >= 16 rows, so a thread's rows share the row bits the swizzle uses");
-    const int xrow0 = tid / XCW;
-    const int xcc = SWZ ? ((tid % XCW) ^ (wg_swz_x(xrow0) << 1)) : (tid % XCW);
-    const int j = j0 + xcc * CH;
-    const bool x_cok = j < a.NG;
-    const int tap = x_cok ? j / a.Cin : 0;
-    const int ci = x_cok ? j - tap * a.Cin : 0;
-    const int dh = tap / a.KW - a.pad, dw = tap % a.KW - a.pad;
-    const int ldx32 = (int)a.ldx, ldy32 = (int)a.ldy;
-    // Address state of this thread's rows, advanced by WG_BK pixels per K step with adds and compares only (the pixel ->
-    // (n, ho, wo) decomposition by two multiply-highs and five multiplies per piece and step cost ~160 cycles per piece: the
-    // issue phase was half of a K step, stamps in profiles/r02_igemm_phase_stamps.txt section 6).  issue() is called for
-    // consecutive steps m_begin, m_begin + WG_BK, ...: it uses the state and then moves it one step on.
-    //   X row: ws = wo * stride, hs = ho * stride (input coordinates of the tap-(0,0) pixel), xo = element offset of that pixel
-    //          + this thread's tap shift and channel; a step adds (q, r) = divmod(WG_BK, Wo) rows / columns, then wraps.
-    //   Y row: element offset m * ldy + channel.
-    const int s_ = a.stride;
-    const int q_ = WG_BK / a.Wo, r_ = WG_BK - q_ * a.Wo;                   // scalar
-    const uint32_t d_step = (uint32_t)((q_ * s_ * a.W + r_ * s_) * ldx32);   // offset change of (ho += q, wo += r)
-    const uint32_t d_wwrap = (uint32_t)((s_ * a.W - a.Wo * s_) * ldx32);     // ... of (wo -= Wo, ho += 1)
-    const uint32_t d_hwrap = (uint32_t)((a.H * a.W - a.Ho * s_ * a.W) * ldx32);  // ... of (ho -= Ho, n += 1)
-    const int ws_lim = a.Wo * s_, hs_lim = a.Ho * s_;
-    int x_ws[NX], x_hs[NX], x_row[NX];
-    uint32_t x_off[NX];
-#pragma unroll
-    for (int i = 0; i < NX; ++i) {
-        const int row = tid / XCW + i * (NT / XCW);
-        const int m = m_begin + row;
-        const int t = wg_fast_div(m, a.wo_mul, a.wo_shr);
-        const int wo = m - t * a.Wo;
-        const int n = wg_fast_div(t, a.ho_mul, a.ho_shr);
-        const int ho = t - n * a.Ho;
-        x_row[i] = row;
-        x_ws[i] = wo * s_;
-        x_hs[i] = ho * s_;
-        x_off[i] = (uint32_t)(((n * a.H + ho * s_ + dh) * a.W + wo * s_ + dw) * ldx32 + ci);
-    }
-    int y_row[NY];
-    uint32_t y_off[NY];
-#pragma unroll
-    for (int i = 0; i < NY; ++i) {
-        y_row[i] = ytid / YCW + i * (NT / YCW);
-        y_off[i] = (uint32_t)((m_begin + y_row[i]) * ldy32 + co0 + ycc * CH);
-    }
-    const uint32_t y_step = (uint32_t)(WG_BK * ldy32);
-    // ---- PATCH: per-thread constants and the scalar patch walk
-    constexpr uint32_t OOR = 0x80000000u;  // a vector offset beyond any buffer of < 2^31 bytes (vector + scalar offset stays below 2^32)
-    const int pw = 1 << a.pw_shift, ph = WG_BK >> a.pw_shift;
-    const uint32_t xbias = PATCH ? (uint32_t)((a.W + 1) * ldx32 * ES) : 0u;  // keeps the (dh, dw) = (-1, -1) offsets non-negative
-    const char* xbase = reinterpret_cast<const char*>(xg) - xbias;
-    uint32_t pvx[NX], pvy[NY];
-    int pch[NX], pcw[NX];
-    int p_wo = 0, p_ho = 0;            // scalar: the next patch's origin
-    uint32_t p_sx = 0, p_sy = 0;       // scalar byte offsets of that origin in X (tap (0, 0), channel 0) and dY
-    if constexpr (PATCH) {
-#pragma unroll
-        for (int i = 0; i < NX; ++i) {
-            const int row = tid / XCW + i * (NT / XCW);
-            const int pr = row >> a.pw_shift, pc = row & (pw - 1);
-            pch[i] = pr * s_ + dh;
-            pcw[i] = pc * s_ + dw;
-            pvx[i] = x_cok ? (uint32_t)(((pch[i] * a.W + pcw[i]) * ldx32 + ci) * ES) + xbias : OOR;
-        }
-#pragma unroll
-        for (int i = 0; i < NY; ++i) {
-            const int row = ytid / YCW + i * (NT / YCW);
-            const int pr = row >> a.pw_shift, pc = row & (pw - 1);
-            pvy[i] = y_cok ? (uint32_t)(((pr * a.Wo + pc) * ldy32 + co0 + ycc * CH) * ES) : OOR;
-        }
-        const int pidx = __builtin_amdgcn_readfirstlane(m_begin / WG_BK);  // first patch of this split
-        const int npw = a.Wo >> a.pw_shift, nph = a.Ho / ph;
-        const int t = pidx / npw, wp = pidx - t * npw;
-        const int n = t / nph, hp = t - n * nph;
-        p_wo = wp * pw;
-        p_ho = hp * ph;
-        p_sx = (uint32_t)(((n * a.H + p_ho * s_) * a.W + p_wo * s_) * ldx32 * ES);
-        p_sy = (uint32_t)(((n * a.Ho + p_ho) * a.Wo + p_wo) * ldy32 * ES);
-    }
-    auto issue = [&](int s, int mk) {
-        char* Ys = smem + s * STAGE;
-        char* Xs = Ys + YBYTES;
-        if constexpr (PATCH) {
-            const uint32_t sx = __builtin_amdgcn_readfirstlane(p_sx), sy = __builtin_amdgcn_readfirstlane(p_sy);  // (scalar by construction; said so)
-#pragma unroll
-            for (int i = 0; i < NY; ++i)
-                wg_buffer_to_lds(yg, a.y_bytes, (lptr_t)(Ys + (i * NT + (wave * 64) % YT) * 16), pvy[i], sy);
-            const int hs0 = __builtin_amdgcn_readfirstlane(p_ho * s_), ws0 = __builtin_amdgcn_readfirstlane(p_wo * s_);
-#pragma unroll
-            for (int i = 0; i < NX; ++i) {
-                const bool ok = (unsigned)(hs0 + pch[i]) < (unsigned)a.H && (unsigned)(ws0 + pcw[i]) < (unsigned)a.W;
-                wg_buffer_to_lds(xbase, a.x_bytes + xbias, (lptr_t)(Xs + (i * NT + wave * 64) * 16), ok ? pvx[i] : OOR, sx);
-            }
-            // one patch on (scalar)
-            p_wo += pw;
-            p_sx += (uint32_t)(pw * s_ * ldx32 * ES);
-            p_sy += (uint32_t)(pw * ldy32 * ES);
-            if (p_wo == a.Wo) {
-                p_wo = 0;
-                p_ho += ph;
-                p_sx += (uint32_t)((ph * s_ * a.W - a.Wo * s_) * ldx32 * ES);
-                p_sy += (uint32_t)((ph * a.Wo - a.Wo) * ldy32 * ES);
-                if (p_ho == a.Ho) {
-                    p_ho = 0;
-                    p_sx += (uint32_t)((a.H * a.W - a.Ho * s_ * a.W) * ldx32 * ES);
-                }
-            }
-            return;
-        }
-        const int left = m_end - mk;  // scalar: rows below it are inside this split
-#pragma unroll
-        for (int i = 0; i < NY; ++i) {
-            const bool ok = y_cok && y_row[i] < left;
-            const T* src = ok ? yg + y_off[i] : zero;
-            __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(Ys + (i * NT + (wave * 64) % YT) * 16), 16, 0, 0);
-            y_off[i] += y_step;
-        }
-#pragma unroll
-        for (int i = 0; i < NX; ++i) {
-            const bool ok = x_cok && x_row[i] < left && (unsigned)(x_hs[i] + dh) < (unsigned)a.H && (unsigned)(x_ws[i] + dw) < (unsigned)a.W;
-            const T* src = ok ? xg + x_off[i] : zero;
-            __builtin_amdgcn_global_load_lds((gptr_t)src, (lptr_t)(Xs + (i * NT + wave * 64) * 16), 16, 0, 0);
-            // one K step on
-            x_ws[i] += r_ * s_;
-            x_hs[i] += q_ * s_;
-            x_off[i] += d_step;
-            if (x_ws[i] >= ws_lim) {
-                x_ws[i] -= ws_lim;
-                x_hs[i] += s_;
-                x_off[i] += d_wwrap;
-            }
-            while (x_hs[i] >= hs_lim) {  // at most once unless the map has fewer rows than a K step covers
-                x_hs[i] -= hs_lim;
-                x_off[i] += d_hwrap;
-            }
-        }
-    };
-
-    constexpr int TR = BM / WROWS / 16, TC = 4;  // per wave: BM / WROWS rows x 64 cols
     f32x4 acc[TR][TC];
 #pragma unroll
     for (int r = 0; r < TR; ++r)
@@ -392,22 +457,23 @@ __global__ __launch_bounds__(256, (BM == 128 ? 3 : WG_WAVES)) void wgrad_kernel(
     f32x4 accb[BIAS ? TR : 1];
 #pragma unroll
     for (int r = 0; r < (BIAS ? TR : 1); ++r) accb[r] = f32x4{0.f, 0.f, 0.f, 0.f};
-    // NS-stage LDS ring, one raw barrier per K step, loads of NS-2 younger steps stay in flight (see igemm.hip)
+    // NS-stage LDS ring, one raw barrier per K step, loads of NS-2 younger steps stay in flight (see igemm.hip); every wave issues NY + NX
+    // pieces per step in both walks - the counted wait depends on it
     const int nk = (m_end - m_begin + WG_BK - 1) / WG_BK;
-    constexpr int LPT = NY + NX;
+    constexpr int LPT = G::NY + G::NX;
 #pragma unroll
     for (int s = 0; s < NS - 1; ++s)
-        if (s < nk) issue(s, m_begin + s * WG_BK);
+        if (s < nk) walk.issue(smem + s * STAGE, m_begin + s * WG_BK);
     for (int kt = 0; kt < nk; ++kt) {
         if (kt + NS - 2 < nk) wait_vmcnt_barrier<LPT * (NS - 2)>();
         else wait_vmcnt_barrier<0>();
-        if (kt + NS - 1 < nk) issue((kt + NS - 1) % NS, m_begin + (kt + NS - 1) * WG_BK);
+        if (kt + NS - 1 < nk) walk.issue(smem + ((kt + NS - 1) % NS) * STAGE, m_begin + (kt + NS - 1) * WG_BK);
         const char* Ys = smem + (kt % NS) * STAGE;
-        if constexpr (BIAS) WFrag<T>::template step<BM, TR, TC, BNW, true>(Ys, Ys + YBYTES, wr * (BM / WROWS), wc * 64, lane, acc, do_bias, accb);
-        else WFrag<T>::template step<BM, TR, TC, BNW, false>(Ys, Ys + YBYTES, wr * (BM / WROWS), wc * 64, lane, acc, false, accb);
+        WFrag<T>::template step<BM, TR, TC, BIAS>(Ys, Ys + G::YBYTES, wr * WM, wc * 64, lane, acc, do_bias, accb);
     }
 
     const int64_t slab_off = (int64_t)bz * a.CoutP * a.NG;
+    const int row0 = co0 + wr * WM, col0 = j0 + wc * 64;  // of this wave's tile
     // The MFMA operands are swapped (A = the X fragment, B = the dY fragment), so a lane's four accumulator values are four
     // CONSECUTIVE (tap, ci) columns of one output channel: one 16-byte store instead of four 4-byte stores to four rows
     // (stores are issue-bound on this chip: 8 / 16 instructions per lane instead of 32 / 64).  NG is a multiple of 4.
@@ -415,96 +481,49 @@ __global__ __launch_bounds__(256, (BM == 128 ? 3 : WG_WAVES)) void wgrad_kernel(
     if (BIAS && do_bias && l4 == 0) {  // every row of the ones product holds the same sums: lanes 0-15 write their output channel's
 #pragma unroll
         for (int r = 0; r < (BIAS ? TR : 1); ++r) {
-            const int co = co0 + wr * (BM / WROWS) + r * 16 + l15;
+            const int co = row0 + r * 16 + l15;
             if (co < a.CoutP) a.bias_slab[(int64_t)bz * a.CoutP + co] = accb[r][0];
         }
     }
-    if (std::is_same<T, bf16_t>::value && a.slab_bf16) {
-        // bfloat16 slabs leave through LDS (round 5): written straight from the accumulators, a store instruction covers 16 rows x 32 bytes -
-        // sixteen partial lines - and those stores cost 8 % of the family's time (0.7 ms per step if nothing hid them: profiles/
-        // r05_wgrad_slab_stores_ab.txt).  Each wave drops 32 rows x 64 columns of its tile into a private padded image and stores it back as whole
-        // 128-byte row segments, eight rows per instruction.  Same values, same rounding.
-        __syncthreads();  // the other waves may still read the last K step's stage
-        constexpr int SROW = 144;                 // padded row: 16 rows hit 16 distinct bank groups
-        constexpr int RP = TR < 2 ? TR : 2;       // 16-row tiles per pass
-        char* st = smem + wave * (RP * 16 * SROW);
-        bf16_t* slab = reinterpret_cast<bf16_t*>(a.slab) + slab_off;
-        const int srow = lane >> 3, sch = lane & 7;
-        const int col = j0 + wc * 64 + sch * 8;
-#pragma unroll
-        for (int r0 = 0; r0 < TR; r0 += RP) {
-#pragma unroll
-            for (int rr = 0; rr < RP; ++rr)
-#pragma unroll
-                for (int c = 0; c < TC; ++c) {
-                    const bf16x4 v = {(bf16_t)acc[r0 + rr][c][0], (bf16_t)acc[r0 + rr][c][1], (bf16_t)acc[r0 + rr][c][2], (bf16_t)acc[r0 + rr][c][3]};
-                    *reinterpret_cast<bf16x4*>(st + (rr * 16 + l15) * SROW + (c * 16 + 4 * l4) * 2) = v;
-                }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-            for (int k = 0; k < RP * 2; ++k) {
-                const int row = k * 8 + srow;
-                const uint4 u = *reinterpret_cast<const uint4*>(st + row * SROW + sch * 16);
-                const int co = co0 + wr * (BM / WROWS) + r0 * 16 + row;
-                if (co < a.CoutP && col < a.NG) *reinterpret_cast<uint4*>(slab + (int64_t)co * a.NG + col) = u;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        }
-    } else if (std::is_same<T, bf16_t>::value) {
-        // float32 slabs of the bf16 path (fewer than 16 splits): the same, 16 rows x 64 columns per pass, 256-byte row segments, four rows per instruction
-        __syncthreads();
-        constexpr int SROW = 272;
-        char* st = smem + wave * (16 * SROW);
-        float* slab = reinterpret_cast<float*>(a.slab) + slab_off;
-        const int srow = lane >> 4, sch = lane & 15;
-        const int col = j0 + wc * 64 + sch * 4;
-#pragma unroll
-        for (int r = 0; r < TR; ++r) {
-#pragma unroll
-            for (int c = 0; c < TC; ++c) *reinterpret_cast<f32x4*>(st + l15 * SROW + (c * 16 + 4 * l4) * 4) = acc[r][c];
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const int row = k * 4 + srow;
-                const f32x4 u = *reinterpret_cast<const f32x4*>(st + row * SROW + sch * 16);
-                const int co = co0 + wr * (BM / WROWS) + r * 16 + row;
-                if (co < a.CoutP && col < a.NG) *reinterpret_cast<f32x4*>(slab + (int64_t)co * a.NG + col) = u;
-            }
-            __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-            __builtin_amdgcn_wave_barrier();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-        }
+    if constexpr (std::is_same<T, bf16_t>::value) {  // bfloat16 slabs from 16 splits up (the launcher), float32 slabs below
+        if (a.slab_bf16) wg_store_slab_staged<bf16_t>(smem, wave, lane, acc, reinterpret_cast<bf16_t*>(a.slab) + slab_off, row0, col0, a.CoutP, a.NG);
+        else wg_store_slab_staged<float>(smem, wave, lane, acc, reinterpret_cast<float*>(a.slab) + slab_off, row0, col0, a.CoutP, a.NG);
     } else {  // f32 parity mode: float32 slabs straight from the accumulators
 #pragma unroll
         for (int r = 0; r < TR; ++r) {
-            const int co = co0 + wr * (BM / WROWS) + r * 16 + l15;
+            const int co = row0 + r * 16 + l15;
 #pragma unroll
             for (int c = 0; c < TC; ++c) {
-                const int col = j0 + wc * 64 + c * 16 + 4 * l4;
+                const int col = col0 + c * 16 + 4 * l4;
                 if (co < a.CoutP && col < a.NG) *reinterpret_cast<f32x4*>(reinterpret_cast<float*>(a.slab) + slab_off + (int64_t)co * a.NG + col) = acc[r][c];
             }
         }
     }
 }
 
-// a slab element as float (slabs are float32, or bfloat16 in the bf16 path)
-template <bool BF> __device__ __forceinline__ float slab_at(const void* slab, int64_t i) {
-    if constexpr (BF) return (float)reinterpret_cast<const bf16_t*>(slab)[i];
-    else return reinterpret_cast<const float*>(slab)[i];
+
+// ---- the slab sums -----------------------------------------------------------------------------------------------------------------------------
+// the sum of the `splits` values p[e], p[e + stride], ... in a fixed order (deterministic): four independent chains keep the split loads in flight,
+// the tail goes into chain 0, combined as (s0 + s1) + (s2 + s3)
+template <typename S> __device__ __forceinline__ float wg_split_sum(const S* __restrict__ p, int64_t e, int64_t stride, int splits) {
+    float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    int k = 0;
+    for (; k + 3 < splits; k += 4) {
+        s0 += (float)p[e + (int64_t)k * stride];
+        s1 += (float)p[e + (int64_t)(k + 1) * stride];
+        s2 += (float)p[e + (int64_t)(k + 2) * stride];
+        s3 += (float)p[e + (int64_t)(k + 3) * stride];
+    }
+    for (; k < splits; ++k) s0 += (float)p[e + (int64_t)k * stride];
+    return (s0 + s1) + (s2 + s3);
 }
 
-// Per-layer slab reduction (ymi_conv2d_bwd_weight, the non-deferred entry point), deterministic: one thread per output element,
-// coalesced along (tap, ci); four independent partial sums keep the split loads in flight, combined in a fixed order.
-// dw[co][ci][kh][kw] = sum_s slab[s][co][tap*Cin + ci]  (scatter into OIHW).
+// Per-layer slab reduction (ymi_conv2d_bwd_weight, the non-deferred entry point): one thread per output element, coalesced along (tap, ci).
+// dw[co][ci][kh][kw] = sum_s slab[s][co][tap*Cin + ci]  (scatter into OIHW).  BF: bfloat16 slabs, else float32.
 template <bool BF>
 __global__ void wgrad_reduce_kernel(const void* __restrict__ slab, int splits, int CoutP, int NG, int Cin, int cout_real, int cin_real, int ntaps,
                                     float* __restrict__ dw) {
+    typedef typename std::conditional<BF, bf16_t, float>::type S;
     // 32-bit index arithmetic (a weight tensor has < 2^31 elements)
     const uint32_t total = (uint32_t)cout_real * (uint32_t)ntaps * (uint32_t)cin_real;
     const int64_t sstride = (int64_t)CoutP * NG;
@@ -514,41 +533,21 @@ __global__ void wgrad_reduce_kernel(const void* __restrict__ slab, int splits, i
         const uint32_t co = t / (uint32_t)ntaps;
         const uint32_t tap = t - co * (uint32_t)ntaps;
         const int64_t e = (int64_t)co * NG + tap * Cin + ci;
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-        int k = 0;
-        for (; k + 3 < splits; k += 4) {
-            s0 += slab_at<BF>(slab, e + (int64_t)k * sstride);
-            s1 += slab_at<BF>(slab, e + (int64_t)(k + 1) * sstride);
-            s2 += slab_at<BF>(slab, e + (int64_t)(k + 2) * sstride);
-            s3 += slab_at<BF>(slab, e + (int64_t)(k + 3) * sstride);
-        }
-        for (; k < splits; ++k) s0 += slab_at<BF>(slab, e + (int64_t)k * sstride);
-        dw[((int64_t)co * cin_real + ci) * ntaps + tap] = (s0 + s1) + (s2 + s3);
+        dw[((int64_t)co * cin_real + ci) * ntaps + tap] = wg_split_sum(reinterpret_cast<const S*>(slab), e, sstride, splits);
     }
 }
 
-// All pending slab reductions of a backward pass in ONE launch (ymi_wgrad_reduce_batch): a 256-thread workgroup finds its
-// tensor by binary search over the table's first_block column, then sums `lanes` interleaved split chains per output
-// element in a fixed order (deterministic) and scatters into OIHW.  By the end of the backward pass the slabs have left the
-// caches: this kernel streams them from HBM, 4 elements per lane and load, four split chains in flight per lane.
-// dbias[co] = sum over the splits of the bias partials [split][coutp], four chains in flight, fixed order
+// dbias[co] = sum over the splits of the bias partials [split][coutp]
 __device__ __forceinline__ void bias_slab_sum(const float* __restrict__ bs, int splits, int coutp, float* __restrict__ db, int tid, int nthr) {
-    for (int co = tid; co < coutp; co += nthr) {
-        float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
-        int k = 0;
-        for (; k + 3 < splits; k += 4) {
-            s0 += bs[(int64_t)k * coutp + co];
-            s1 += bs[(int64_t)(k + 1) * coutp + co];
-            s2 += bs[(int64_t)(k + 2) * coutp + co];
-            s3 += bs[(int64_t)(k + 3) * coutp + co];
-        }
-        for (; k < splits; ++k) s0 += bs[(int64_t)k * coutp + co];
-        db[co] = (s0 + s1) + (s2 + s3);
-    }
+    for (int co = tid; co < coutp; co += nthr) db[co] = wg_split_sum(bs, co, coutp, splits);
 }
 __global__ void wgrad_bias_reduce_kernel(const float* __restrict__ bs, int splits, int coutp, float* __restrict__ db) {
     bias_slab_sum(bs, splits, coutp, db, (int)(blockIdx.x * blockDim.x + threadIdx.x), (int)(gridDim.x * blockDim.x));
 }
+// All pending slab reductions of a backward pass in ONE launch (ymi_wgrad_reduce_batch): a 256-thread workgroup finds its
+// tensor by binary search over the table's first_block column, then sums `lanes` interleaved split chains per output
+// element in a fixed order (deterministic) and scatters into OIHW.  By the end of the backward pass the slabs have left the
+// caches: this kernel streams them from HBM, 4 elements per lane and load, four split chains in flight per lane.
 template <bool BF> __device__ __forceinline__ void reduce_batch_body(const ymi_wgrad_pending& e, f32x4* red) {
     // the record's first workgroup also sums the bias partials (a few KB)
     if (e.bias_slab && (int)blockIdx.x == e.first_block) bias_slab_sum(e.bias_slab, e.splits, (int)(e.elems / e.ng), e.dbias, (int)threadIdx.x, 256);
@@ -624,7 +623,7 @@ struct WgradPlan {
     int splits, pix_per_split;
     size_t slab_bytes;
 };
-// row-tile choice.  Measured (round 1): with the same workgroup target as the 64-row tile the 128-row tile is 5-45 % SLOWER (the
+// row-tile choice.  Measured: with the same workgroup target as the 64-row tile the 128-row tile is 5-45 % SLOWER (the
 // pixel axis is split twice as often, doubling the slab traffic); with HALF the workgroups (same split count, 16 MFMAs
 // per wave and K step) it is 7-12 % faster on every layer with >= 128 output channels.
 static int wgrad_bm(int64_t coutp, bool bf16) {
@@ -634,8 +633,8 @@ static int wgrad_bm(int64_t coutp, bool bf16) {
 }
 static WgradPlan wgrad_plan(int64_t mpix, int64_t coutp, int64_t ng, int bm, size_t slab_esize) {
     const int64_t tiles = ((ng + WG_BN - 1) / WG_BN) * ((coutp + bm - 1) / bm);
-    // workgroups to aim for (tuning knobs; the in-situ optimum differs from the isolated one: see profiles/r03_wgrad_targets.txt).  Round 4,
-    // swept inside the step again (profiles/r04_wgrad_targets_sweep.txt): ONE RESIDENT ROUND - 5 workgroups per CU for the 64-row tile
+    // workgroups to aim for (tuning knobs; the in-situ optimum differs from the isolated one: see profiles/r03_wgrad_targets.txt).
+    // Swept inside the step (profiles/r04_wgrad_targets_sweep.txt): ONE RESIDENT ROUND - 5 workgroups per CU for the 64-row tile
     // (its launch bounds), 3 for the 128-row tile - is 0.09 ms/step faster than 1024 / 640; a fourth 128-row workgroup per CU costs 0.3 ms
     const int target64 = ymi_opt(OPT_WGRAD_BLOCKS);
     const int target128 = ymi_opt(OPT_WGRAD_BLOCKS128);
@@ -656,6 +655,8 @@ static WgradPlan wgrad_plan(int64_t mpix, int64_t coutp, int64_t ng, int bm, siz
 }
 
 static int64_t pad_to(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
+// rows [padded Cout] of bias partials the workspace has room for behind the slabs: a launch with a bias gradient has at most that many splits
+constexpr int64_t WG_BIAS_ROWS = 2048 * 2 + 1;
 
 extern "C" size_t ymi_conv2d_bwd_weight_workspace(int64_t m_rows, int64_t cout, int64_t cin, int64_t kh, int64_t kw) {
     // upper bound over both dtypes' channel padding (8), plus room for the bias-gradient partials
@@ -663,7 +664,7 @@ extern "C" size_t ymi_conv2d_bwd_weight_workspace(int64_t m_rows, int64_t cout, 
     WgradPlan p = wgrad_plan(m_rows, coutp, kh * kw * cinp, 64, 4);  // (float32 slabs: the larger of the two dtypes' needs)
     const WgradPlan p128 = wgrad_plan(m_rows, coutp, kh * kw * cinp, 128, 4);  // the 128-row tile splits the pixel axis further
     if (p128.slab_bytes > p.slab_bytes) p = p128;
-    return p.slab_bytes + (size_t)(2048 * 2 + 1) * coutp * sizeof(float) + 256;
+    return p.slab_bytes + (size_t)WG_BIAS_ROWS * coutp * sizeof(float) + 256;
 }
 
 static int wgrad_impl(const ymi_tensor* x, const ymi_tensor* dy, int64_t cout_real, int64_t cin_real, int64_t kh, int64_t kw, int64_t stride,
@@ -680,18 +681,15 @@ struct WgradLaunch {
 };
 // one row tile: the BIAS instantiation where the launch forms the bias partials, the PATCH one where the map tiles into patches (bfloat16 only:
 // parity mode keeps the raster walk, pw_shift is -1 for float32 operands)
+// (the ring is at most 48 KB: no launch needs the opt-in for more than 64 KB of dynamic LDS)
 template <typename T, int BM> static void wgrad_launch_tile(const WgradArgs& a, const BnRider& r, dim3 grid, hipStream_t s) {
     constexpr size_t lds = wgrad_lds_bytes<T, BM>();
-    if constexpr (std::is_same<T, float>::value) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_kernel<T, WG_NS, BM, false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(wgrad_kernel<T, WG_NS, BM, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    } else if (a.pw_shift >= 0) {
-        if (a.bias_slab) hipLaunchKernelGGL((wgrad_kernel<T, WG_NS, BM, true, true>), grid, dim3(256), lds, s, a, r);
-        else hipLaunchKernelGGL((wgrad_kernel<T, WG_NS, BM, false, true>), grid, dim3(256), lds, s, a, r);
-        return;
+    static_assert(lds <= 64 * 1024, "a larger ring needs hipFuncAttributeMaxDynamicSharedMemorySize");
+    void (*kernel)(WgradArgs, BnRider) = a.bias_slab ? wgrad_kernel<T, BM, true, false> : wgrad_kernel<T, BM, false, false>;
+    if constexpr (std::is_same<T, bf16_t>::value) {
+        if (a.pw_shift >= 0) kernel = a.bias_slab ? wgrad_kernel<T, BM, true, true> : wgrad_kernel<T, BM, false, true>;
     }
-    if (a.bias_slab) hipLaunchKernelGGL((wgrad_kernel<T, WG_NS, BM, true>), grid, dim3(256), lds, s, a, r);
-    else hipLaunchKernelGGL((wgrad_kernel<T, WG_NS, BM, false>), grid, dim3(256), lds, s, a, r);
+    hipLaunchKernelGGL(kernel, grid, dim3(256), lds, s, a, r);
 }
 static void wgrad_launch(const WgradLaunch& h, const BnFinal* rider) {
     BnRider r{};
@@ -703,7 +701,7 @@ static void wgrad_launch(const WgradLaunch& h, const BnFinal* rider) {
     }
     int prof = -1;
     if (ymi_prof_enabled()) prof = ymi_prof_start(h.s, 1, h.flop, h.bytes, h.bf16 ? 2500.0 : 157.3);
-    if (!h.bf16) wgrad_launch_tile<float, WG_BM>(h.a, r, grid, h.s);
+    if (!h.bf16) wgrad_launch_tile<float, 64>(h.a, r, grid, h.s);  // (wgrad_bm: parity mode has the 64-row tile only)
     else if (h.bm == 128) wgrad_launch_tile<bf16_t, 128>(h.a, r, grid, h.s);
     else if (h.bm == 32) wgrad_launch_tile<bf16_t, 32>(h.a, r, grid, h.s);
     else wgrad_launch_tile<bf16_t, 64>(h.a, r, grid, h.s);
@@ -762,6 +760,14 @@ extern "C" int ymi_conv2d_bwd_weight_deferred(const ymi_tensor* x, const ymi_ten
                                               ymi_wgrad_pending* pending, void* stream) {
     YMI_CHECK_ARG(pending, "conv2d_bwd_weight_deferred: null pending record");
     return wgrad_impl(x, dy, cout_real, cin_real, kh, kw, stride, dw_oihw, dbias, workspace, workspace_bytes, pending, stream);
+}
+
+ymi_wgrad_pending ymi_wgrad_record(const void* slab, float* dw, int64_t elems, int splits, int ng, int cin, int cout_real, int cin_real, int ntaps,
+                                   bool slab_bf16, const float* bias_slab, float* dbias) {
+    const int lanes = splits > 128 ? 32 : splits > 32 ? 16 : splits > 8 ? 8 : 4;
+    const int outs = 256 / lanes, ept = slab_bf16 ? 8 : 4;  // a workgroup sums `outs` groups of `ept` consecutive elements
+    return ymi_wgrad_pending{slab, dw, elems, splits, ng, cin, cout_real, cin_real, ntaps, lanes, 0, (int32_t)((elems / ept + outs - 1) / outs), slab_bf16 ? 1 : 0,
+                             bias_slab, dbias};
 }
 
 // the records travel to the device table in kernel ARGUMENTS (by value): no host staging buffer, so the launches are
@@ -823,7 +829,7 @@ static int wgrad_impl(const ymi_tensor* x, const ymi_tensor* dy, int64_t cout_re
     // out (<= 2e-3 asserted at the bs-32 shapes), and launches with few splits write little slab traffic to save anyway
     const bool slab_bf16 = bf16 && p.splits >= 16;
     if (bf16 && !slab_bf16) p = wgrad_plan(mpix, dy->c, ng, bm, 4);
-    size_t need = p.slab_bytes + (dbias ? (size_t)(2048 * 2 + 1) * dy->c * sizeof(float) : 0);
+    size_t need = p.slab_bytes + (dbias ? (size_t)WG_BIAS_ROWS * dy->c * sizeof(float) : 0);
     if (workspace_bytes < need) {
         ymi_set_error("conv2d_bwd_weight: workspace %zu < %zu bytes", workspace_bytes, need);
         return YMI_EWORKSPACE;
@@ -832,7 +838,7 @@ static int wgrad_impl(const ymi_tensor* x, const ymi_tensor* dy, int64_t cout_re
     a.x = x->data; a.dy = dy->data; a.slab = workspace; a.slab_bf16 = slab_bf16 ? 1 : 0; a.zero = ymi_zero_page();
     // bias gradient: per-split column sums of dY come out of the GEMM itself (a ones row against the dY fragments), behind the slabs
     a.bias_slab = dbias ? reinterpret_cast<float*>(reinterpret_cast<char*>(workspace) + p.slab_bytes) : nullptr;
-    YMI_CHECK_ARG(!dbias || (size_t)p.splits * dy->c <= (size_t)(2048 * 2 + 1) * dy->c, "conv2d_bwd_weight: too many splits for the bias partials");
+    YMI_CHECK_ARG(!dbias || p.splits <= WG_BIAS_ROWS, "conv2d_bwd_weight: too many splits for the bias partials");
     a.ldx = x->ld; a.ldy = dy->ld;
     a.Mpix = (int)mpix; a.H = (int)x->h; a.W = (int)x->w; a.Ho = (int)dy->h; a.Wo = (int)dy->w;
     a.stride = (int)stride; a.pad = (int)pad; a.KW = (int)kw;
@@ -857,7 +863,7 @@ static int wgrad_impl(const ymi_tensor* x, const ymi_tensor* dy, int64_t cout_re
             a.y_bytes = (uint32_t)yb;
         }
     }
-    a.xcd_map = p.splits >= 8 ? 1 : 0;  // (all tiles of a pixel split on one XCD: 275 -> 105 MB of HBM reads per launch, round 1)
+    a.xcd_map = p.splits >= 8 ? 1 : 0;  // (all tiles of a pixel split on one XCD: 275 -> 105 MB of HBM reads per launch)
     dim3 grid((unsigned)a.nx, (unsigned)a.ny, (unsigned)p.splits);
     if (a.xcd_map) grid = dim3((unsigned)(8 * ((p.splits + 7) / 8) * a.nx * a.ny), 1, 1);
     hipStream_t s = (hipStream_t)stream;
@@ -878,20 +884,15 @@ static int wgrad_impl(const ymi_tensor* x, const ymi_tensor* dy, int64_t cout_re
         }
     }
     YMI_CHECK_LAUNCH("wgrad");
-    const int64_t elems = (int64_t)a.CoutP * a.NG;
     if (pending) {  // the slab sum is left to ymi_wgrad_reduce_batch (one launch for every layer of the backward pass)
-        const int lanes = p.splits > 128 ? 32 : p.splits > 32 ? 16 : p.splits > 8 ? 8 : 4;
-        const int ept = a.slab_bf16 ? 8 : 4;  // elements per lane of the batched sum (one 16-byte load per split)
-        *pending = ymi_wgrad_pending{a.slab, dw_oihw, elems, p.splits, a.NG, a.Cin, (int32_t)cout_real, (int32_t)cin_real, (int32_t)(kh * kw), lanes, 0,
-                                     (int32_t)((elems / ept + 256 / lanes - 1) / (256 / lanes)), a.slab_bf16, a.bias_slab, dbias};
+        *pending = ymi_wgrad_record(a.slab, dw_oihw, (int64_t)a.CoutP * a.NG, p.splits, a.NG, a.Cin, (int)cout_real, (int)cin_real, (int)(kh * kw), slab_bf16,
+                                    a.bias_slab, dbias);
     } else {
         const int64_t total = cout_real * kh * kw * cin_real;
         int64_t gb = (total + 255) / 256;
         if (gb > 2048) gb = 2048;
-        if (slab_bf16) hipLaunchKernelGGL(wgrad_reduce_kernel<true>, dim3((unsigned)gb), dim3(256), 0, s, (const void*)a.slab, p.splits, a.CoutP, a.NG, a.Cin,
-                                     (int)cout_real, (int)cin_real, (int)(kh * kw), dw_oihw);
-        else hipLaunchKernelGGL(wgrad_reduce_kernel<false>, dim3((unsigned)gb), dim3(256), 0, s, (const void*)a.slab, p.splits, a.CoutP, a.NG, a.Cin,
-                                (int)cout_real, (int)cin_real, (int)(kh * kw), dw_oihw);
+        hipLaunchKernelGGL(slab_bf16 ? wgrad_reduce_kernel<true> : wgrad_reduce_kernel<false>, dim3((unsigned)gb), dim3(256), 0, s, (const void*)a.slab, p.splits,
+                           a.CoutP, a.NG, a.Cin, (int)cout_real, (int)cin_real, (int)(kh * kw), dw_oihw);
     }
     YMI_CHECK_LAUNCH("wgrad_reduce");
     if (dbias && !pending) {

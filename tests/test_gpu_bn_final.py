@@ -46,7 +46,7 @@ CARRIERS = [(BF, "8-15 splits", 32, False), (BF, ">=16 splits", 64, True), (BF, 
 
 
 def _carrier_spec(name):
-    (spec,) = [s for s in WGRAD if s[0].startswith(name)]
+    (spec,) = [s for s in WGRAD if s[0] == name] or [s for s in WGRAD if s[0].startswith(name)]  # the row of that name, else the one it begins
     return spec
 
 

@@ -673,6 +673,10 @@ WGRAD = [  # name, n, xc, cin_real, h, w, dyc, cout_real, k, s, wgrad_blocks (No
     ("raster (20x20 does not tile)", 2, 16, 16, 20, 20, 32, 32, 3, 1, None, 1),
     ("raster (patch off)", 2, 16, 16, 32, 32, 32, 32, 3, 1, None, 0),
     ("padded channels", 2, 24, 19, 12, 16, 40, 33, 1, 1, None, 1),
+    ("row tile 128, bf16 slabs", 2, 16, 16, 64, 64, 128, 128, 3, 1, None, 1),
+    ("row tile 128, bf16 slabs, ragged rows", 2, 16, 16, 64, 64, 264, 260, 3, 1, None, 1),
+    ("row tile 128, f32 slabs, ragged rows", 2, 16, 16, 32, 32, 264, 260, 3, 1, None, 1),
+    ("row tile 128, raster", 2, 16, 16, 64, 64, 128, 128, 3, 1, None, 0),
 ]
 
 
