@@ -51,6 +51,9 @@ static inline int ymi_stat_fixed_point_shift(int64_t count) {
     const int sh = 37 - lg;
     return sh < 8 ? 8 : sh > 40 ? 40 : sh;
 }
+// rows that ymi_bn_finalize (elementwise.hip) may stage behind the partial rows it is given when there are many: every caller sizes
+// its partials with this many rows more than it writes (the conv block's statistics, first_conv.hip's forward workspace)
+constexpr int BN_STAGE_ROWS = 64;
 static inline size_t ymi_esize(int dtype) { return dtype == YMI_BF16 ? 2 : 4; }
 static inline bool ymi_same_shape(const ymi_tensor* a, const ymi_tensor* b) {
     return a->n == b->n && a->h == b->h && a->w == b->w && a->c == b->c;
@@ -559,6 +562,26 @@ template <int SW> __device__ __forceinline__ TrFragAddr tr_frag_addr(const char*
     const int u = (c0 >> 2) + p;  // logical 8-byte unit of this lane's 4 columns
     const int u_lo = u ^ (tr_swz<SW>(r_lo) << 2), u_hi = u ^ (tr_swz<SW>(r_hi) << 2);
     return TrFragAddr{(lptr_t)(img + r_lo * rowb + u_lo * 8), (lptr_t)(img + r_hi * rowb + u_hi * 8)};
+}
+
+// sum of a value over the 16 lanes of its DPP row, result in every lane: xor-1 and xor-2 quad permutes, then the half-row and
+// row mirrors (each lane already holds its quad's / half-row's total, so the mirrored partner supplies the other one)
+// (igemm.hip's statistics epilogue, first_conv.hip's reducing passes)
+template <int CTRL> __device__ __forceinline__ float dpp_add(float v) {
+    return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
+}
+__device__ __forceinline__ float row16_sum(float v) {
+    v = dpp_add<0xB1>(v);   // quad_perm [1,0,3,2]
+    v = dpp_add<0x4E>(v);   // quad_perm [2,3,0,1]
+    v = dpp_add<0x141>(v);  // row_half_mirror
+    v = dpp_add<0x140>(v);  // row_mirror
+    return v;
+}
+// two floats rounded to bfloat16 in one word, the first in the low half (v_cvt_pk_bf16_f32; swin_mlp.hip, first_conv.hip)
+__device__ __forceinline__ uint32_t pack_bf16x2(float a, float b) {
+    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
+    const bf16x2 v = {(bf16_t)a, (bf16_t)b};
+    return __builtin_bit_cast(uint32_t, v);
 }
 
 // wave-level reductions (64 lanes)

@@ -408,8 +408,6 @@ __global__ __launch_bounds__(256) void stat_rows_reduce_kernel(const float* __re
     }
 }
 
-constexpr int BN_STAGE_ROWS = 64;
-
 // `part` may be overwritten beyond row `blocks` (callers size it with ymi_conv2d_stat_blocks + BN_STAGE_ROWS rows).
 static int bn_finalize_impl(const float* part, int64_t blocks, int64_t count, int64_t c, const float* gamma, const float* beta,
                             float* rmean, float* rvar, float momentum, float eps, float* scale, float* shift, float* smean,

@@ -22,6 +22,14 @@
 // what the generic path computes and stores, so every consumer of the recomputed value sees the stored value's bits.
 // (Handing dz from K3 to K4 instead of recomputing SiLU' there was measured: as bfloat16 it puts 2e-2 on dW - d(raw) cancels - and as
 // float32 its 420 MB cost K3 more than K4 gained, 167 + 191 against 100 + 190 us.)
+//
+// K1..K4 are ONE tile walk (first_conv_kernel: weight fragments, tiles, patch, rows, 16-pixel groups, the convolution) around four pass
+// types (FcStats, FcApply, FcBwdReduce, FcBwdWgrad).  A pass owns its arguments, its per-lane state, its rows of the constant table, its
+// share of LDS and its hooks: per 16-pixel group and channel tile, per wave row, per tile, per workgroup.  The walk reads the pass's rows of
+// the constant table itself and hands `red` over as the array it is: through a pointer the compiler assumed 16-byte alignment for the
+// table reads and paired the `red` accesses otherwise (other instructions than these kernels had, profiles/first_conv_refactor_ab.txt).
+// The split costs 87 code lines against the one-body kernel (profiles/first_conv_refactor_ab.txt: four argument structs where one served, a
+// signature and the constants of every hook).
 #include "common.h"
 
 namespace {
@@ -31,44 +39,67 @@ constexpr int FC_PR = 2 * FC_TH + 1;                   // patch rows
 constexpr int FC_ROWB = (2 * FC_TW + 2) * 8;           // bytes per patch row: 8 bytes per pixel; col 0 unused, col 1 = left halo, cols 2.. = the tile's 2 TW columns
                                                        // (so that the aligned groups of the interior start on 16-byte boundaries)
 constexpr int FC_WG_TILES = 4;                         // tiles per workgroup of the weight-gradient kernel, one slab each (2 and 8: slower, profiles/r04_first_conv_ab.txt)
+constexpr int FC_CROWS = 5;                            // rows of the per-channel constant table [FC_CROWS][CO]; a pass names and fills the ones it reads
 
-enum { FC_STATS = 0, FC_APPLY = 1, FC_BWD_REDUCE = 2, FC_BWD_WGRAD = 3 };
-
-struct FirstConvArgs {
-    const float* img;      // FC_STATS: float32 NCHW image
-    const float* w;        // float32 OIHW weight
-    void* x4;              // NHWC bfloat16, 4 channels: written by FC_STATS, read by the others
-    void* out;             // FC_APPLY: block output; FC_BWD_*: dout (read)
-    int64_t ldout;
-    float* partials;       // FC_STATS / FC_BWD_REDUCE: [unit][2][CO]
-    const float* v0;       // FC_APPLY: scale          FC_BWD_REDUCE: gamma   FC_BWD_WGRAD: coef [5][CO]
-    const float* v1;       // FC_APPLY: shift          FC_BWD_REDUCE: beta
-    const float* v2;       //                          FC_BWD_REDUCE: mean
-    const float* v3;       //                          FC_BWD_REDUCE: inv-std
-    float* slab;           // FC_BWD_WGRAD: [workgroup][CO][72] float32
-    int act;
+struct FcGeom {            // the same in every pass of a call (fc_geometry)
     int N, C, H, W, Ho, Wo;
     int tiles_h, tiles_w, total;
 };
+struct FcStatsArgs {
+    FcGeom g;
+    const float* img;      // float32 NCHW image
+    const float* w;        // float32 OIHW weight (every pass)
+    bf16_t* x4;            // NHWC bfloat16, 4 channels: written here, read by the other passes
+    float* partials;       // [unit][2][CO]
+};
+struct FcApplyArgs {
+    FcGeom g;
+    const float* w;
+    const bf16_t* x4;
+    bf16_t* out;           // the block's output, NHWC with `ldout` elements per pixel
+    int64_t ldout;
+    const float* scale;    // [CO] each
+    const float* shift;
+    int act;
+};
+struct FcBwdReduceArgs {
+    FcGeom g;
+    const float* w;
+    const bf16_t* x4;
+    const bf16_t* dout;    // NHWC with `ldout` elements per pixel
+    int64_t ldout;
+    float* partials;       // [unit][2][CO]
+    const float* gamma;    // [CO] each; gamma / beta may be null (1 / 0)
+    const float* beta;
+    const float* mean;
+    const float* invstd;
+    int act;
+};
+struct FcBwdWgradArgs {
+    FcGeom g;
+    const float* w;
+    const bf16_t* x4;
+    const bf16_t* dout;
+    int64_t ldout;
+    const float* coef;     // [5][CO] of ymi_bn_bwd_final: a0 | a1 | c0 | c1 | c2
+    float* slab;           // [workgroup][CO][72] float32
+    int act;
+};
 
-template <int CTRL> __device__ __forceinline__ float fc_dpp_add(float v) {
-    return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float fc_row16_sum(float v) {  // sum over the 16 lanes of a DPP row, in every lane (as igemm.hip)
-    v = fc_dpp_add<0xB1>(v);
-    v = fc_dpp_add<0x4E>(v);
-    v = fc_dpp_add<0x141>(v);
-    v = fc_dpp_add<0x140>(v);
-    return v;
-}
+struct FcLane {            // a thread's places in its workgroup, wave and MFMA fragments; the LDS its hooks reach
+    int tid, lane, wave, l15, l4;
+    const char* patch;
+    char* my;              // this wave's staging bytes
+};
+struct FcRow {             // a wave's output row of a tile
+    int ohl, ow0;          // row within the tile; the tile's first column
+    bool ok;               // inside the map
+    int64_t pix;           // pixel index of (n, row, ow0) in the NHWC output map
+};
+
 // SiLU or identity (the host refuses other activations: GELU's erf would double these kernels' code for a case no model has)
 __device__ __forceinline__ float fc_act(float x, int act) { return act == YMI_ACT_SILU ? silu_f(x) : x; }
 __device__ __forceinline__ float fc_act_grad(float x, int act) { return act == YMI_ACT_SILU ? silu_grad_f(x) : 1.0f; }
-__device__ __forceinline__ uint32_t fc_pack2(float lo, float hi) {
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-    const bf16x2 v = {(bf16_t)lo, (bf16_t)hi};
-    return __builtin_bit_cast(uint32_t, v);
-}
 
 // ---- transposed fragment read of a swizzled image (common.h: tr_frag_addr; SW = 2: 64-byte rows, SW = 0: 128-byte rows) through the builtin:
 // the reads are ordered against this kernel's own plain LDS stores, which the compiler sees
@@ -84,9 +115,10 @@ template <int SW> __device__ __forceinline__ bf16x8 fc_tr_load(const char* img, 
 
 // ---- the input patch of tile (n, oh0, ow0) into LDS -----------------------------------------------------------------------------------
 // from the float32 NCHW image (and, by the way, the tile's own pixels out to x4) ...
-__device__ __forceinline__ void fc_patch_from_image(const FirstConvArgs& a, char* patch, int n, int oh0, int ow0, int tid) {
-    const float* src = a.img + (int64_t)n * a.C * a.H * a.W;
-    const int64_t plane = (int64_t)a.H * a.W;
+__device__ __forceinline__ void fc_load_patch(const FcStatsArgs& a, char* patch, int n, int oh0, int ow0, int tid) {
+    const FcGeom& g = a.g;
+    const float* src = a.img + (int64_t)n * g.C * g.H * g.W;
+    const int64_t plane = (int64_t)g.H * g.W;
     const int ih0 = 2 * oh0 - 1;
     constexpr int ITEMS = FC_PR * (2 * FC_TW / 4);     // an item = one patch row x 4 consecutive image columns (16-byte aligned in the planes)
     constexpr int PASSES = (ITEMS + 255) / 256;
@@ -94,50 +126,49 @@ __device__ __forceinline__ void fc_patch_from_image(const FirstConvArgs& a, char
 #pragma unroll
     for (int p = 0; p < PASSES; ++p) {
         const int it = tid + 256 * p;
-        const int r = it / (2 * FC_TW / 4), g = it % (2 * FC_TW / 4);
-        const int ih = ih0 + r, iw = 2 * ow0 + 4 * g;
-        const bool ok = it < ITEMS && (unsigned)ih < (unsigned)a.H && iw < a.W;
+        const int r = it / (2 * FC_TW / 4), gr = it % (2 * FC_TW / 4);
+        const int ih = ih0 + r, iw = 2 * ow0 + 4 * gr;
+        const bool ok = it < ITEMS && (unsigned)ih < (unsigned)g.H && iw < g.W;
 #pragma unroll
-        for (int c = 0; c < 3; ++c) v[p][c] = (ok && c < a.C) ? *reinterpret_cast<const f32x4*>(src + c * plane + (int64_t)ih * a.W + iw) : f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int c = 0; c < 3; ++c) v[p][c] = (ok && c < g.C) ? *reinterpret_cast<const f32x4*>(src + c * plane + (int64_t)ih * g.W + iw) : f32x4{0.f, 0.f, 0.f, 0.f};
     }
     float halo = 0.f;                                  // left halo column (iw = 2 ow0 - 1): scalar loads by the first threads
     const int hr = tid / 4, hc = tid % 4;
     if (tid < FC_PR * 4) {
         const int ih = ih0 + hr, iw = 2 * ow0 - 1;
-        if (hc < a.C && (unsigned)ih < (unsigned)a.H && iw >= 0) halo = src[hc * plane + (int64_t)ih * a.W + iw];
+        if (hc < g.C && (unsigned)ih < (unsigned)g.H && iw >= 0) halo = src[hc * plane + (int64_t)ih * g.W + iw];
     }
 #pragma unroll
     for (int p = 0; p < PASSES; ++p) {
         const int it = tid + 256 * p;
         if (it < ITEMS) {
-            const int r = it / (2 * FC_TW / 4), g = it % (2 * FC_TW / 4);
-            char* dst = patch + r * FC_ROWB + (4 * g + 2) * 8;
-            *reinterpret_cast<u32x4*>(dst) = u32x4{fc_pack2(v[p][0][0], v[p][1][0]), fc_pack2(v[p][2][0], 0.f), fc_pack2(v[p][0][1], v[p][1][1]), fc_pack2(v[p][2][1], 0.f)};
-            *reinterpret_cast<u32x4*>(dst + 16) = u32x4{fc_pack2(v[p][0][2], v[p][1][2]), fc_pack2(v[p][2][2], 0.f), fc_pack2(v[p][0][3], v[p][1][3]), fc_pack2(v[p][2][3], 0.f)};
+            const int r = it / (2 * FC_TW / 4), gr = it % (2 * FC_TW / 4);
+            char* dst = patch + r * FC_ROWB + (4 * gr + 2) * 8;
+            *reinterpret_cast<u32x4*>(dst) = u32x4{pack_bf16x2(v[p][0][0], v[p][1][0]), pack_bf16x2(v[p][2][0], 0.f), pack_bf16x2(v[p][0][1], v[p][1][1]), pack_bf16x2(v[p][2][1], 0.f)};
+            *reinterpret_cast<u32x4*>(dst + 16) = u32x4{pack_bf16x2(v[p][0][2], v[p][1][2]), pack_bf16x2(v[p][2][2], 0.f), pack_bf16x2(v[p][0][3], v[p][1][3]), pack_bf16x2(v[p][2][3], 0.f)};
         }
     }
     if (tid < FC_PR * 4) *reinterpret_cast<bf16_t*>(patch + hr * FC_ROWB + 1 * 8 + hc * 2) = (bf16_t)halo;
-    if (a.C == 4) {  // (rare: a fourth input channel - filled in with scalar loads; the 16-byte stores above wrote zeros there)
+    if (g.C == 4) {  // (rare: a fourth input channel - filled in with scalar loads; the 16-byte stores above wrote zeros there)
         __syncthreads();
         for (int e = tid; e < FC_PR * 2 * FC_TW; e += 256) {
             const int r = e / (2 * FC_TW), cc = e % (2 * FC_TW);
             const int ih = ih0 + r, iw = 2 * ow0 + cc;
-            if ((unsigned)ih < (unsigned)a.H && iw < a.W) *reinterpret_cast<bf16_t*>(patch + r * FC_ROWB + (cc + 2) * 8 + 6) = (bf16_t)src[3 * plane + (int64_t)ih * a.W + iw];
+            if ((unsigned)ih < (unsigned)g.H && iw < g.W) *reinterpret_cast<bf16_t*>(patch + r * FC_ROWB + (cc + 2) * 8 + 6) = (bf16_t)src[3 * plane + (int64_t)ih * g.W + iw];
         }
     }
     __syncthreads();
     // x4: the image pixels this tile owns (rows 2 oh0 .. 2 oh0 + 2 TH - 1, cols 2 ow0 .. 2 ow0 + 2 TW - 1), two pixels per 16-byte store
-    bf16_t* x4 = reinterpret_cast<bf16_t*>(a.x4);
 #pragma unroll 4
     for (int e = tid; e < 2 * FC_TH * FC_TW; e += 256) {
         const int r = e / FC_TW, cc = 2 * (e - r * FC_TW);
         const int ih = 2 * oh0 + r, iw = 2 * ow0 + cc;
-        if (ih < a.H && iw < a.W) *reinterpret_cast<u32x4*>(x4 + (((int64_t)n * a.H + ih) * a.W + iw) * 4) = *reinterpret_cast<const u32x4*>(patch + (r + 1) * FC_ROWB + (cc + 2) * 8);
+        if (ih < g.H && iw < g.W) *reinterpret_cast<u32x4*>(a.x4 + (((int64_t)n * g.H + ih) * g.W + iw) * 4) = *reinterpret_cast<const u32x4*>(patch + (r + 1) * FC_ROWB + (cc + 2) * 8);
     }
 }
 // ... or from x4 (already in the patch's own form: 8 bytes per pixel)
-__device__ __forceinline__ void fc_patch_from_x4(const FirstConvArgs& a, char* patch, int n, int oh0, int ow0, int tid) {
-    const bf16_t* x4 = reinterpret_cast<const bf16_t*>(a.x4);
+template <typename Args> __device__ __forceinline__ void fc_load_patch(const Args& a, char* patch, int n, int oh0, int ow0, int tid) {
+    const FcGeom& g = a.g;
     const int ih0 = 2 * oh0 - 1;
     constexpr int ITEMS = FC_PR * FC_TW;               // an item = one patch row x 2 consecutive image columns (16 bytes)
     constexpr int PASSES = (ITEMS + 255) / 256;
@@ -145,15 +176,15 @@ __device__ __forceinline__ void fc_patch_from_x4(const FirstConvArgs& a, char* p
 #pragma unroll
     for (int p = 0; p < PASSES; ++p) {
         const int it = tid + 256 * p;
-        const int r = it / FC_TW, g = it % FC_TW;
-        const int ih = ih0 + r, iw = 2 * ow0 + 2 * g;
-        const bool ok = it < ITEMS && (unsigned)ih < (unsigned)a.H && iw < a.W;
-        v[p] = ok ? *reinterpret_cast<const u32x4*>(x4 + (((int64_t)n * a.H + ih) * a.W + iw) * 4) : u32x4{0u, 0u, 0u, 0u};
+        const int r = it / FC_TW, gr = it % FC_TW;
+        const int ih = ih0 + r, iw = 2 * ow0 + 2 * gr;
+        const bool ok = it < ITEMS && (unsigned)ih < (unsigned)g.H && iw < g.W;
+        v[p] = ok ? *reinterpret_cast<const u32x4*>(a.x4 + (((int64_t)n * g.H + ih) * g.W + iw) * 4) : u32x4{0u, 0u, 0u, 0u};
     }
     u32x2 halo = u32x2{0u, 0u};
     if (tid < FC_PR) {
         const int ih = ih0 + tid, iw = 2 * ow0 - 1;
-        if ((unsigned)ih < (unsigned)a.H && iw >= 0) halo = *reinterpret_cast<const u32x2*>(x4 + (((int64_t)n * a.H + ih) * a.W + iw) * 4);
+        if ((unsigned)ih < (unsigned)g.H && iw >= 0) halo = *reinterpret_cast<const u32x2*>(a.x4 + (((int64_t)n * g.H + ih) * g.W + iw) * 4);
     }
 #pragma unroll
     for (int p = 0; p < PASSES; ++p) {
@@ -185,47 +216,256 @@ __device__ __forceinline__ void fc_conv_group(const char* patch, int ohl, int mt
     }
 }
 
-template <int CO, int MODE>
-__global__ __launch_bounds__(256, 4) void first_conv_kernel(FirstConvArgs a) {  // (4 waves per SIMD where LDS allows: these kernels live on latency hiding)
+// ---- pieces that two passes share ---------------------------------------------------------------------------------------------------------
+// what a pass says of itself unless it says otherwise, and the hooks it leaves empty
+struct FcPass {
+    static constexpr int TILES = 1;                    // tiles per workgroup
+    static constexpr int STAGE_WAVE_BYTES = 0;         // LDS staging bytes of a wave
+    static constexpr int RED_FLOATS = 0;               // floats of LDS the waves combine through
+    static constexpr bool READS_DOUT = false;
+    static constexpr int CROWS = 0;                    // rows of the constant table it reads
+    template <typename Args> static __device__ __forceinline__ void constants(const Args&, int, float (&)[FC_CROWS]) {}
+    template <typename Args> __device__ __forceinline__ void wave_row(const Args&, const FcLane&, const FcRow&) {}
+    template <typename Args, int N> __device__ __forceinline__ void tile(const Args&, const FcLane&, float (&)[N], int) {}
+    template <typename Args, int N> __device__ __forceinline__ void workgroup(const Args&, const FcLane&, float (&)[N], int) {}
+};
+constexpr int fc_lds_len(int n) { return n > 0 ? n : 1; }  // (an array a pass does not use still needs a length; the compiler drops it)
+
+// the two backward passes: dout of a 16-pixel group (8-byte pieces: this lane's 4 channels of its pixel, per channel tile) is requested
+// one group ahead of its use; zero outside the map
+template <int NCT> struct FcDoutAhead {
+    bf16x4 cur[NCT], nxt[NCT];
+    template <typename Args> __device__ __forceinline__ void request(const Args& a, const FcLane& ln, const FcRow& row, int mt, bf16x4 (&dst)[NCT]) {
+        const int owl = mt * 16 + ln.l15;
+        const bool ok = row.ok && row.ow0 + owl < a.g.Wo;
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct)
+            dst[ct] = ok ? *reinterpret_cast<const bf16x4*>(a.dout + row.pix * a.ldout + (int64_t)owl * a.ldout + ct * 16 + 4 * ln.l4) : bf16x4{(bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f};
+    }
+    __device__ __forceinline__ void advance() {
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct) cur[ct] = nxt[ct];
+    }
+};
+
+// the two reducing passes: a lane's two partial sums per channel, and their way out after a tile - over the 16 pixels of a DPP row,
+// the four waves through `red`, one row of partials[unit][2][CO]
+template <int CO> struct FcSums {
+    static constexpr int NCT = CO / 16;
+    // [channel tile][r], as vectors like the accumulator fragment.  As float[NCT][4] members the compiler paired these additions otherwise
+    // than for the arrays the kernel used to declare itself, and with the pairing changed which dz * xh products are fused into s2:
+    // other last bits in dgamma / dbeta at 48 channels (profiles/first_conv_refactor_ab.txt)
+    f32x4 s1[NCT], s2[NCT];
+    __device__ __forceinline__ FcSums() {
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct) s1[ct] = s2[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    __device__ __forceinline__ void store(float* partials, const FcLane& ln, float (&red)[4 * 2 * CO], int unit) {
+#pragma unroll
+        for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float t1 = row16_sum(s1[ct][r]), t2s = row16_sum(s2[ct][r]);
+                if (ln.l15 == 0) {
+                    float* dst = &red[ln.wave * 2 * CO + ct * 16 + 4 * ln.l4 + r];  // (one address, two offsets: the pair leaves as one ds_write2_b32)
+                    dst[0] = t1;
+                    dst[CO] = t2s;
+                }
+            }
+        __syncthreads();
+        if (ln.tid < 2 * CO) {
+            const int which = ln.tid / CO, ch = ln.tid % CO;
+            partials[((int64_t)unit * 2 + which) * CO + ch] = (red[(0 * 2 + which) * CO + ch] + red[(1 * 2 + which) * CO + ch]) + (red[(2 * 2 + which) * CO + ch] + red[(3 * 2 + which) * CO + ch]);
+        }
+    }
+};
+
+// ---- the four passes.  group(): channels ch0 .. ch0 + 3 (channel tile ct) of pixel owl of the wave's row; raw = the convolution rounded to
+// bfloat16, ok = the pixel is inside the map, k = the pass's CROWS rows of the constant table at ch0 (one unused row for a pass that has
+// none), dy = its dout (passes that read it) -----------------------------------------------------------------------------------------------
+// K1: sums of raw and raw^2
+template <int CO> struct FcStats : FcPass {
+    typedef FcStatsArgs Args;
+    static constexpr int RED_FLOATS = 4 * 2 * CO;
+    FcSums<CO> sums;
+    __device__ __forceinline__ void group(const Args&, const FcLane&, int ct, int, int, bool ok, const float (&raw)[4], const f32x4 (&)[1], const bf16x4&) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float v = ok ? raw[r] : 0.f;
+            sums.s1[ct][r] += v;
+            sums.s2[ct][r] += v * v;
+        }
+    }
+    __device__ __forceinline__ void tile(const Args& a, const FcLane& ln, float (&red)[RED_FLOATS], int unit) { sums.store(a.partials, ln, red, unit); }
+};
+
+// K2: act(raw * scale + shift) -> the block's output
+template <int CO> struct FcApply : FcPass {
+    typedef FcApplyArgs Args;
+    enum { SCALE, SHIFT, CROWS };                      // rows of the constant table
+    static constexpr int CPP = CO / 8;                 // 16-byte chunks per output pixel
+    static constexpr int STAGE_WAVE_BYTES = FC_TW * CO * 2;  // one wave's output row segment
+    static __device__ __forceinline__ void constants(const Args& a, int ch, float (&c)[FC_CROWS]) {
+        c[SCALE] = a.scale[ch];
+        c[SHIFT] = a.shift[ch];
+    }
+    __device__ __forceinline__ void group(const Args& a, const FcLane& ln, int, int ch0, int owl, bool, const float (&raw)[4], const f32x4 (&k)[CROWS], const bf16x4&) {
+        bf16x4 o;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) o[r] = (bf16_t)fc_act(raw[r] * k[SCALE][r] + k[SHIFT][r], a.act);
+        *reinterpret_cast<bf16x4*>(ln.my + (owl * CO + ch0) * 2) = o;
+    }
+    // the wave's 64 pixels x CO channels leave as 16-byte chunks: consecutive lanes, consecutive bytes of the NHWC row
+    // (the staging area is this wave's own: its LDS writes and reads are ordered by the wave's program order)
+    __device__ __forceinline__ void wave_row(const Args& a, const FcLane& ln, const FcRow& row) {
+        if (row.ok) {
+#pragma unroll
+            for (int it = 0; it < FC_TW * CPP / 64; ++it) {
+                const int q = it * 64 + ln.lane;
+                const int px = q / CPP, cc = q % CPP;
+                if (row.ow0 + px < a.g.Wo) *reinterpret_cast<u32x4*>(a.out + row.pix * a.ldout + (int64_t)px * a.ldout + cc * 8) = *reinterpret_cast<const u32x4*>(ln.my + q * 16);
+            }
+        }
+    }
+};
+
+// K3: sums of dz and dz * xhat
+template <int CO> struct FcBwdReduce : FcPass {
+    typedef FcBwdReduceArgs Args;
+    enum { INV, OFF, GAMMA, BETA, CROWS };             // xhat = raw * INV + OFF ; z = xhat * GAMMA + BETA
+    static constexpr int RED_FLOATS = 4 * 2 * CO;
+    static constexpr bool READS_DOUT = true;
+    FcSums<CO> sums;
+    static __device__ __forceinline__ void constants(const Args& a, int ch, float (&c)[FC_CROWS]) {
+        const float g = a.gamma ? a.gamma[ch] : 1.f, bb = a.beta ? a.beta[ch] : 0.f, mu = a.mean[ch], iv = a.invstd[ch];
+        c[INV] = iv;
+        c[OFF] = -mu * iv;
+        c[GAMMA] = g;
+        c[BETA] = bb;
+    }
+    __device__ __forceinline__ void group(const Args& a, const FcLane&, int ct, int, int, bool, const float (&raw)[4], const f32x4 (&k)[CROWS], const bf16x4& dy) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float xh = raw[r] * k[INV][r] + k[OFF][r];
+            const float dz = (float)dy[r] * fc_act_grad(xh * k[GAMMA][r] + k[BETA][r], a.act);  // (dout = 0 outside the image)
+            sums.s1[ct][r] += dz;
+            sums.s2[ct][r] += dz * xh;
+        }
+    }
+    __device__ __forceinline__ void tile(const Args& a, const FcLane& ln, float (&red)[RED_FLOATS], int unit) { sums.store(a.partials, ln, red, unit); }
+};
+
+// K4: d(raw) of a wave row into the wave's [pixel][channel] image, the row's weight gradient by MFMA, one slab per workgroup
+template <int CO> struct FcBwdWgrad : FcPass {
+    typedef FcBwdWgradArgs Args;
+    enum { A0, A1, C0, C1, C2, CROWS };                    // z = raw A0 + A1 ; d(raw) = dz C0 - raw C1 - C2   (the rows of Args::coef)
+    static constexpr int NCT = CO / 16;
+    static constexpr int DROWB = CO <= 32 ? 64 : 128, DSW = tr_swz_mode(DROWB);  // row bytes / swizzle mode of the [pixel][channel] image
+    static constexpr int TILES = FC_WG_TILES;
+    static constexpr int STAGE_WAVE_BYTES = FC_TW * DROWB;
+    static constexpr int RED_FLOATS = 48 * CO;         // the [k][co] image the four waves' sums meet in
+    static constexpr bool READS_DOUT = true;
+    f32x4 dwa[3][NCT];                                 // dW[k = kt*16 + 4*l4 + r][co = ct*16 + l15]
+    __device__ __forceinline__ FcBwdWgrad() {
+#pragma unroll
+        for (int kt = 0; kt < 3; ++kt)
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) dwa[kt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    static __device__ __forceinline__ void constants(const Args& a, int ch, float (&c)[FC_CROWS]) {
+        c[A0] = a.coef[ch];
+        c[A1] = a.coef[CO + ch];
+        c[C0] = a.coef[2 * CO + ch];
+        c[C1] = a.coef[3 * CO + ch];
+        c[C2] = a.coef[4 * CO + ch];
+    }
+    // d(raw), rounded to bfloat16 as the generic path stores it, into this wave's [pixel][channel] image (one 8-byte store;
+    // the weight-gradient MFMAs read it transposed: fc_tr_load)
+    __device__ __forceinline__ void group(const Args& a, const FcLane& ln, int, int ch0, int owl, bool ok, const float (&raw)[4], const f32x4 (&k)[CROWS], const bf16x4& dy) {
+        bf16x4 o;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const float dz = (float)dy[r] * fc_act_grad(raw[r] * k[A0][r] + k[A1][r], a.act);
+            o[r] = (bf16_t)(ok ? dz * k[C0][r] - (raw[r] * k[C1][r] + k[C2][r]) : 0.f);
+        }
+        *reinterpret_cast<bf16x4*>(ln.my + owl * DROWB + ((ch0 >> 2) ^ (tr_swz<DSW>(owl) << 2)) * 8) = o;
+    }
+    // dW[k][co] += sum over the row's 64 pixels of x[pixel, k] * d(raw)[pixel, co]: pixels are the MFMA's K axis (two halves of 32).
+    // A fragment (rows = k): lane (k = kt*16 + l15, pixels 32 h + 8 l4 + j): patch[(2 ohl + kh)][2 pixel + kw + 1][c'], k = (kh*3 + kw)*4 + c'
+    // B fragment (cols = co): lane (co = ct*16 + l15, the same 8 pixels): transposed read of the [pixel][channel] image
+    __device__ __forceinline__ void wave_row(const Args&, const FcLane& ln, const FcRow& row) {
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            bf16x8 df[NCT];
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) df[ct] = fc_tr_load<DSW>(ln.my + 32 * h * DROWB, DROWB, ct * 16, ln.lane);
+#pragma unroll
+            for (int kt = 0; kt < 3; ++kt) {
+                const int k = kt * 16 + ln.l15, q = k >> 2, c = k & 3;
+                bf16x8 xf;
+                if (q < 9) {
+                    const char* base = ln.patch + (2 * row.ohl + q / 3) * FC_ROWB + (q % 3 + 1) * 8 + c * 2 + (32 * h + 8 * ln.l4) * 16;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) xf[j] = *reinterpret_cast<const bf16_t*>(base + j * 16);
+                } else {
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) xf[j] = (bf16_t)0.f;
+                }
+#pragma unroll
+                for (int ct = 0; ct < NCT; ++ct) dwa[kt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf, df[ct], dwa[kt][ct], 0, 0, 0);
+            }
+        }
+    }
+    // the four waves' sums -> one float32 slab [co][tap * 8 + c] per workgroup (the layout of wgrad_kernel's slabs for 8 padded input
+    // channels: the batched slab sum of csrc/wgrad.hip adds the workgroups' slabs in a fixed order and scatters into OIHW)
+    __device__ __forceinline__ void workgroup(const Args& a, const FcLane& ln, float (&red)[RED_FLOATS], int wg_unit) {
+        for (int wv = 0; wv < 4; ++wv) {  // wave after wave into one [k][co] image (fixed order: deterministic)
+            if (ln.wave == wv) {
+#pragma unroll
+                for (int kt = 0; kt < 3; ++kt)
+#pragma unroll
+                    for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            float* dst = &red[(kt * 16 + 4 * ln.l4 + r) * CO + ct * 16 + ln.l15];
+                            *dst = wv == 0 ? dwa[kt][ct][r] : *dst + dwa[kt][ct][r];
+                        }
+            }
+            __syncthreads();
+        }
+        float* slab = a.slab + (int64_t)wg_unit * CO * 72;
+        for (int e = ln.tid; e < CO * 72; e += 256) {
+            const int co = e / 72, col = e % 72, tap = col >> 3, c = col & 7;
+            slab[e] = c < 4 ? red[(tap * 4 + c) * CO + co] : 0.f;
+        }
+    }
+};
+
+// ---- the walk: no pass arithmetic in it ----------------------------------------------------------------------------------------------------
+template <int CO, template <int> class PassOf>
+__global__ __launch_bounds__(256, 4) void first_conv_kernel(typename PassOf<CO>::Args a) {  // (4 waves per SIMD where LDS allows: these kernels live on latency hiding)
+    typedef PassOf<CO> Pass;
     constexpr int NCT = CO / 16;                       // channel tiles of 16
-    constexpr int OUTB = FC_TW * CO * 2;               // bytes of one wave's output row segment
-    constexpr int CPP = CO / 8;                        // 16-byte chunks per output pixel
-    constexpr int DROWB = CO <= 32 ? 64 : 128, DSW = tr_swz_mode(DROWB);  // FC_BWD_WGRAD: row bytes / swizzle mode of the wave's [pixel][channel] image of d(raw)
-    constexpr int STAGEB = MODE == FC_BWD_WGRAD ? FC_TW * DROWB : OUTB;
     __shared__ __attribute__((aligned(16))) char patch[FC_PR * FC_ROWB];
-    __shared__ __attribute__((aligned(16))) char stage[(MODE == FC_APPLY || MODE == FC_BWD_WGRAD) ? 4 * STAGEB : 16];
+    __shared__ __attribute__((aligned(16))) char stage[fc_lds_len(4 * Pass::STAGE_WAVE_BYTES)];  // (wave-private: no barrier guards it)
     __shared__ __attribute__((aligned(16))) bf16_t wtab[CO * 64];  // [co][k], k = (kh * 3 + kw) * 4 + c'
-    __shared__ __attribute__((aligned(16))) float ctab[5 * CO];    // per-channel constants (below)
-    __shared__ float red[(MODE == FC_BWD_WGRAD) ? 48 * CO : 4 * 2 * CO];
+    __shared__ __attribute__((aligned(16))) float ctab[FC_CROWS * CO];
+    __shared__ float red[fc_lds_len(Pass::RED_FLOATS)];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int l15 = lane & 15, l4 = lane >> 4;
 
-    // ---- the weight table (float32 OIHW parameter -> bfloat16 [co][k]) and the per-channel constants [5][CO] (fetched from LDS per
+    // ---- the weight table (float32 OIHW parameter -> bfloat16 [co][k]) and the per-channel constants (fetched from LDS per
     // 16-pixel group: as five register arrays per lane they cost two waves per SIMD)
 #pragma unroll
     for (int i = 0; i < CO * 64 / 256; ++i) {
         const int e = tid + 256 * i, co = e >> 6, k = e & 63, q = k >> 2, c = k & 3;
-        wtab[e] = (bf16_t)((q < 9 && c < a.C) ? a.w[(co * a.C + c) * 9 + q] : 0.f);
+        wtab[e] = (bf16_t)((q < 9 && c < a.g.C) ? a.w[(co * a.g.C + c) * 9 + q] : 0.f);
     }
     if (tid < CO) {
-        float c0 = 0.f, c1 = 0.f, c2 = 0.f, c3 = 0.f, c4 = 0.f;
-        if constexpr (MODE == FC_APPLY) {
-            c0 = a.v0[tid];                            // scale
-            c1 = a.v1[tid];                            // shift
-        } else if constexpr (MODE == FC_BWD_REDUCE) {
-            const float g = a.v0 ? a.v0[tid] : 1.f, bb = a.v1 ? a.v1[tid] : 0.f, mu = a.v2[tid], iv = a.v3[tid];
-            c0 = iv;                                   // xhat = raw * iv + c1
-            c1 = -mu * iv;
-            c2 = g;                                    // z = xhat * g + b
-            c3 = bb;
-        } else if constexpr (MODE == FC_BWD_WGRAD) {
-            c0 = a.v0[tid];                            // z = raw a0 + a1 ; d(raw) = dz c0 - raw c1 - c2   (coef = [a0 | a1 | c0 | c1 | c2][CO])
-            c1 = a.v0[CO + tid];
-            c2 = a.v0[2 * CO + tid];
-            c3 = a.v0[3 * CO + tid];
-            c4 = a.v0[4 * CO + tid];
-        }
-        ctab[tid] = c0; ctab[CO + tid] = c1; ctab[2 * CO + tid] = c2; ctab[3 * CO + tid] = c3; ctab[4 * CO + tid] = c4;
+        float c[FC_CROWS] = {0.f, 0.f, 0.f, 0.f, 0.f};
+        Pass::constants(a, tid, c);
+#pragma unroll
+        for (int r = 0; r < FC_CROWS; ++r) ctab[r * CO + tid] = c[r];
     }
     __syncthreads();
     bf16x8 wf[NCT][2];                                 // this lane's weight fragments (A operand: rows = output channels)
@@ -234,214 +474,102 @@ __global__ __launch_bounds__(256, 4) void first_conv_kernel(FirstConvArgs a) {  
 #pragma unroll
         for (int h = 0; h < 2; ++h) wf[ct][h] = *reinterpret_cast<const bf16x8*>(wtab + (ct * 16 + l15) * 64 + 32 * h + 8 * l4);
 
-    float s1[NCT][4], s2[NCT][4];                      // FC_STATS / FC_BWD_REDUCE: this lane's partial sums
-#pragma unroll
-    for (int ct = 0; ct < NCT; ++ct)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) s1[ct][r] = s2[ct][r] = 0.f;
-    f32x4 dwa[3][NCT];                                 // FC_BWD_WGRAD: dW[k = kt*16 + 4*l4 + r][co = ct*16 + l15]
-#pragma unroll
-    for (int kt = 0; kt < 3; ++kt)
-#pragma unroll
-        for (int ct = 0; ct < NCT; ++ct) dwa[kt][ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    char* my = stage + ((MODE == FC_APPLY || MODE == FC_BWD_WGRAD) ? wave * STAGEB : 0);
-    constexpr int TILES = MODE == FC_BWD_WGRAD ? FC_WG_TILES : 1;
+    Pass pass;
+    const FcLane ln{tid, lane, wave, l15, l4, patch, stage + wave * Pass::STAGE_WAVE_BYTES};
     // XCD ownership of the pixel order (common.h): consecutive units - tiles of one image, image after image - run on one XCD
     const int wg_unit = xcd_unit(blockIdx.x, gridDim.x);
 #pragma unroll 1
-    for (int ti = 0; ti < TILES; ++ti) {
-        const int unit = wg_unit * TILES + ti;
-        if (unit >= a.total) break;                    // (workgroup-uniform)
-        const int tw = unit % a.tiles_w;
-        const int t2 = unit / a.tiles_w;
-        const int th = t2 % a.tiles_h, n = t2 / a.tiles_h;
+    for (int ti = 0; ti < Pass::TILES; ++ti) {
+        const int unit = wg_unit * Pass::TILES + ti;
+        if (unit >= a.g.total) break;                  // (workgroup-uniform)
+        const int tw = unit % a.g.tiles_w;
+        const int t2 = unit / a.g.tiles_w;
+        const int th = t2 % a.g.tiles_h, n = t2 / a.g.tiles_h;
         const int oh0 = th * FC_TH, ow0 = tw * FC_TW;
         if (ti > 0) __syncthreads();                   // everybody has finished reading the previous tile's patch
-        if constexpr (MODE == FC_STATS) fc_patch_from_image(a, patch, n, oh0, ow0, tid);
-        else fc_patch_from_x4(a, patch, n, oh0, ow0, tid);
+        fc_load_patch(a, patch, n, oh0, ow0, tid);
 
 #pragma unroll 1
         for (int rr = 0; rr < FC_TH / 4; ++rr) {       // this wave's output rows: wave, wave + 4
-            const int ohl = wave + 4 * rr;
+            const int ohl = ln.wave + 4 * rr;
             const int oh = oh0 + ohl;
-            const bool row_ok = oh < a.Ho;
-            const int64_t rowbase = (((int64_t)n * a.Ho + oh) * a.Wo + ow0) * a.ldout;
-            // dout of a 16-pixel group (8-byte pieces: this lane's 4 channels of its pixel, per channel tile) is requested one group ahead
-            // of its use.  The group loop is NOT unrolled: unrolled, the compiler interleaves the four groups and needs 211 registers
+            const FcRow row{ohl, ow0, oh < a.g.Ho, ((int64_t)n * a.g.Ho + oh) * a.g.Wo + ow0};
+            FcDoutAhead<NCT> dy;
+            if constexpr (Pass::READS_DOUT) dy.request(a, ln, row, 0, dy.cur);
+            // The group loop is NOT unrolled: unrolled, the compiler interleaves the four groups and needs 211 registers
             // (two waves per SIMD; a scheduling barrier per group did not stop it) - rolled, 90.
-            [[maybe_unused]] bf16x4 dy_cur[NCT], dy_nxt[NCT];
-            [[maybe_unused]] auto load_dy = [&](int mt, bf16x4 (&dst)[NCT]) {
-                const bf16_t* dyp = reinterpret_cast<const bf16_t*>(a.out);
-                const int owl = mt * 16 + l15;
-                const bool ok = row_ok && ow0 + owl < a.Wo;
-#pragma unroll
-                for (int ct = 0; ct < NCT; ++ct)
-                    dst[ct] = ok ? *reinterpret_cast<const bf16x4*>(dyp + rowbase + (int64_t)owl * a.ldout + ct * 16 + 4 * l4) : bf16x4{(bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f, (bf16_t)0.f};
-            };
-            if constexpr (MODE == FC_BWD_REDUCE || MODE == FC_BWD_WGRAD) load_dy(0, dy_cur);
 #pragma unroll 1
             for (int mt = 0; mt < 4; ++mt) {
-                const int owl = mt * 16 + l15;
-                const bool ok = row_ok && ow0 + owl < a.Wo;
-                if constexpr (MODE == FC_BWD_REDUCE || MODE == FC_BWD_WGRAD) {
-                    if (mt + 1 < 4) load_dy(mt + 1, dy_nxt);
+                const int owl = mt * 16 + ln.l15;
+                const bool ok = row.ok && ow0 + owl < a.g.Wo;
+                if constexpr (Pass::READS_DOUT) {
+                    if (mt + 1 < 4) dy.request(a, ln, row, mt + 1, dy.nxt);
                 }
                 f32x4 acc[NCT];
-                fc_conv_group<NCT>(patch, ohl, mt, l15, l4, wf, acc);
+                fc_conv_group<NCT>(patch, ohl, mt, ln.l15, ln.l4, wf, acc);
 #pragma unroll
                 for (int ct = 0; ct < NCT; ++ct) {
-                    int ch0 = ct * 16 + 4 * l4;
+                    int ch0 = ct * 16 + 4 * ln.l4;
                     asm volatile("" : "+v"(ch0));  // the constants are re-read from LDS per group: hoisted out of the loop they are 40 registers per lane
                     float raw[4];
 #pragma unroll
                     for (int r = 0; r < 4; ++r) raw[r] = (float)(bf16_t)acc[ct][r];  // the value the generic path stores
-                    if constexpr (MODE == FC_STATS) {
+                    f32x4 k[fc_lds_len(Pass::CROWS)];
 #pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const float v = ok ? raw[r] : 0.f;
-                            s1[ct][r] += v;
-                            s2[ct][r] += v * v;
-                        }
-                    } else if constexpr (MODE == FC_APPLY) {
-                        const f32x4 sc = *reinterpret_cast<const f32x4*>(ctab + ch0), sh = *reinterpret_cast<const f32x4*>(ctab + CO + ch0);
-                        bf16x4 o;
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) o[r] = (bf16_t)fc_act(raw[r] * sc[r] + sh[r], a.act);
-                        *reinterpret_cast<bf16x4*>(my + (owl * CO + ch0) * 2) = o;
-                    } else if constexpr (MODE == FC_BWD_REDUCE) {
-                        const f32x4 iv = *reinterpret_cast<const f32x4*>(ctab + ch0), of = *reinterpret_cast<const f32x4*>(ctab + CO + ch0);
-                        const f32x4 g = *reinterpret_cast<const f32x4*>(ctab + 2 * CO + ch0), bb = *reinterpret_cast<const f32x4*>(ctab + 3 * CO + ch0);
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const float xh = raw[r] * iv[r] + of[r];
-                            const float dz = (float)dy_cur[ct][r] * fc_act_grad(xh * g[r] + bb[r], a.act);  // (dout = 0 outside the image)
-                            s1[ct][r] += dz;
-                            s2[ct][r] += dz * xh;
-                        }
-                    } else {
-                        // d(raw), rounded to bfloat16 as the generic path stores it, into this wave's [pixel][channel] image (one 8-byte store;
-                        // the weight-gradient MFMAs read it transposed: fc_tr_load)
-                        const f32x4 a0 = *reinterpret_cast<const f32x4*>(ctab + ch0), a1 = *reinterpret_cast<const f32x4*>(ctab + CO + ch0);
-                        const f32x4 c0 = *reinterpret_cast<const f32x4*>(ctab + 2 * CO + ch0), c1 = *reinterpret_cast<const f32x4*>(ctab + 3 * CO + ch0);
-                        const f32x4 c2 = *reinterpret_cast<const f32x4*>(ctab + 4 * CO + ch0);
-                        bf16x4 o;
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            const float dz = (float)dy_cur[ct][r] * fc_act_grad(raw[r] * a0[r] + a1[r], a.act);
-                            o[r] = (bf16_t)(ok ? dz * c0[r] - (raw[r] * c1[r] + c2[r]) : 0.f);
-                        }
-                        *reinterpret_cast<bf16x4*>(my + owl * DROWB + ((ch0 >> 2) ^ (tr_swz<DSW>(owl) << 2)) * 8) = o;
-                    }
+                    for (int r = 0; r < Pass::CROWS; ++r) k[r] = *reinterpret_cast<const f32x4*>(ctab + r * CO + ch0);
+                    pass.group(a, ln, ct, ch0, owl, ok, raw, k, dy.cur[ct]);
                 }
-                if constexpr (MODE == FC_BWD_REDUCE || MODE == FC_BWD_WGRAD) {
-#pragma unroll
-                    for (int ct = 0; ct < NCT; ++ct) dy_cur[ct] = dy_nxt[ct];
-                }
+                if constexpr (Pass::READS_DOUT) dy.advance();
             }
-            if constexpr (MODE == FC_APPLY) {
-                // the wave's 64 pixels x CO channels leave as 16-byte chunks: consecutive lanes, consecutive bytes of the NHWC row
-                // (the staging area is this wave's own: its LDS writes and reads are ordered by the wave's program order)
-                if (row_ok) {
-                    bf16_t* outp = reinterpret_cast<bf16_t*>(a.out);
-#pragma unroll
-                    for (int it = 0; it < FC_TW * CPP / 64; ++it) {
-                        const int q = it * 64 + lane;
-                        const int px = q / CPP, cc = q % CPP;
-                        if (ow0 + px < a.Wo) *reinterpret_cast<u32x4*>(outp + rowbase + (int64_t)px * a.ldout + cc * 8) = *reinterpret_cast<const u32x4*>(my + q * 16);
-                    }
-                }
-            } else if constexpr (MODE == FC_BWD_WGRAD) {
-                // dW[k][co] += sum over the row's 64 pixels of x[pixel, k] * d(raw)[pixel, co]: pixels are the MFMA's K axis (two halves of 32).
-                // A fragment (rows = k): lane (k = kt*16 + l15, pixels 32 h + 8 l4 + j): patch[(2 ohl + kh)][2 pixel + kw + 1][c'], k = (kh*3 + kw)*4 + c'
-                // B fragment (cols = co): lane (co = ct*16 + l15, the same 8 pixels): transposed read of the [pixel][channel] image
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    bf16x8 df[NCT];
-#pragma unroll
-                    for (int ct = 0; ct < NCT; ++ct) df[ct] = fc_tr_load<DSW>(my + 32 * h * DROWB, DROWB, ct * 16, lane);
-#pragma unroll
-                    for (int kt = 0; kt < 3; ++kt) {
-                        const int k = kt * 16 + l15, q = k >> 2, c = k & 3;
-                        bf16x8 xf;
-                        if (q < 9) {
-                            const char* base = patch + (2 * ohl + q / 3) * FC_ROWB + (q % 3 + 1) * 8 + c * 2 + (32 * h + 8 * l4) * 16;
-#pragma unroll
-                            for (int j = 0; j < 8; ++j) xf[j] = *reinterpret_cast<const bf16_t*>(base + j * 16);
-                        } else {
-#pragma unroll
-                            for (int j = 0; j < 8; ++j) xf[j] = (bf16_t)0.f;
-                        }
-#pragma unroll
-                        for (int ct = 0; ct < NCT; ++ct) dwa[kt][ct] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(xf, df[ct], dwa[kt][ct], 0, 0, 0);
-                    }
-                }
-            }
+            pass.wave_row(a, ln, row);
         }
-        if constexpr (MODE == FC_STATS || MODE == FC_BWD_REDUCE) {
-#pragma unroll
-            for (int ct = 0; ct < NCT; ++ct)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    const float t1 = fc_row16_sum(s1[ct][r]), t2s = fc_row16_sum(s2[ct][r]);
-                    if (l15 == 0) {
-                        red[(wave * 2 + 0) * CO + ct * 16 + 4 * l4 + r] = t1;
-                        red[(wave * 2 + 1) * CO + ct * 16 + 4 * l4 + r] = t2s;
-                    }
-                }
-            __syncthreads();
-            if (tid < 2 * CO) {
-                const int which = tid / CO, ch = tid % CO;
-                a.partials[((int64_t)unit * 2 + which) * CO + ch] = (red[(0 * 2 + which) * CO + ch] + red[(1 * 2 + which) * CO + ch]) + (red[(2 * 2 + which) * CO + ch] + red[(3 * 2 + which) * CO + ch]);
-            }
-        }
+        pass.tile(a, ln, red, unit);
     }
-    if constexpr (MODE == FC_BWD_WGRAD) {
-        // the four waves' sums -> one float32 slab [co][tap * 8 + c] per workgroup (the layout of wgrad_kernel's slabs for 8 padded input
-        // channels: the batched slab sum of csrc/wgrad.hip adds the workgroups' slabs in a fixed order and scatters into OIHW)
-        for (int wv = 0; wv < 4; ++wv) {  // wave after wave into one [k][co] image (fixed order: deterministic)
-            if (wave == wv) {
-#pragma unroll
-                for (int kt = 0; kt < 3; ++kt)
-#pragma unroll
-                    for (int ct = 0; ct < NCT; ++ct)
-#pragma unroll
-                        for (int r = 0; r < 4; ++r) {
-                            float* dst = &red[(kt * 16 + 4 * l4 + r) * CO + ct * 16 + l15];
-                            *dst = wv == 0 ? dwa[kt][ct][r] : *dst + dwa[kt][ct][r];
-                        }
-            }
-            __syncthreads();
-        }
-        float* slab = a.slab + (int64_t)wg_unit * CO * 72;
-        for (int e = tid; e < CO * 72; e += 256) {
-            const int co = e / 72, col = e % 72, tap = col >> 3, c = col & 7;
-            slab[e] = c < 4 ? red[(tap * 4 + c) * CO + co] : 0.f;
-        }
-    }
+    pass.workgroup(a, ln, red, wg_unit);
 }
 
-template <int MODE>
-int fc_launch(const FirstConvArgs& a, int64_t cout, unsigned blocks, hipStream_t s) {
-    dim3 grid(blocks), blk(256);
-    if (cout == 16) hipLaunchKernelGGL((first_conv_kernel<16, MODE>), grid, blk, 0, s, a);
-    else if (cout == 32) hipLaunchKernelGGL((first_conv_kernel<32, MODE>), grid, blk, 0, s, a);
-    else if (cout == 48) hipLaunchKernelGGL((first_conv_kernel<48, MODE>), grid, blk, 0, s, a);
-    else hipLaunchKernelGGL((first_conv_kernel<64, MODE>), grid, blk, 0, s, a);
+template <template <int> class PassOf>
+int fc_launch(const typename PassOf<16>::Args& a, int64_t cout, unsigned blocks, hipStream_t s) {
+    void (*const kernels[4])(typename PassOf<16>::Args) = {first_conv_kernel<16, PassOf>, first_conv_kernel<32, PassOf>, first_conv_kernel<48, PassOf>, first_conv_kernel<64, PassOf>};
+    hipLaunchKernelGGL(kernels[cout / 16 - 1], dim3(blocks), dim3(256), 0, s, a);
     YMI_CHECK_LAUNCH("first_conv");
     return YMI_OK;
 }
 
-int fc_geometry(FirstConvArgs& a, int64_t n, int64_t c, int64_t h, int64_t w, int64_t cout) {
+int fc_geometry(FcGeom& g, int64_t n, int64_t c, int64_t h, int64_t w, int64_t cout, int act) {
     YMI_CHECK_ARG(c >= 1 && c <= 4 && (cout == 16 || cout == 32 || cout == 48 || cout == 64), "first_conv: c <= 4 input channels, 16 / 32 / 48 / 64 output channels");
-    YMI_CHECK_ARG(a.act == YMI_ACT_SILU || a.act == YMI_ACT_NONE, "first_conv: SiLU or no activation");
+    YMI_CHECK_ARG(act == YMI_ACT_SILU || act == YMI_ACT_NONE, "first_conv: SiLU or no activation");
     YMI_CHECK_ARG(w % 4 == 0 && h % 2 == 0 && n > 0, "first_conv: even height, width a multiple of 4");
     const int64_t ho = h / 2, wo = w / 2;
     YMI_CHECK_ARG(n * ho * wo * cout < (1ll << 31) && n * h * w * 4 < (1ll << 31), "first_conv: too large for 32-bit indexing");
-    a.N = (int)n; a.C = (int)c; a.H = (int)h; a.W = (int)w; a.Ho = (int)ho; a.Wo = (int)wo;
-    a.tiles_h = (int)((ho + FC_TH - 1) / FC_TH); a.tiles_w = (int)((wo + FC_TW - 1) / FC_TW);
-    a.total = (int)(n * a.tiles_h * a.tiles_w);
+    g.N = (int)n; g.C = (int)c; g.H = (int)h; g.W = (int)w; g.Ho = (int)ho; g.Wo = (int)wo;
+    g.tiles_h = (int)((ho + FC_TH - 1) / FC_TH); g.tiles_w = (int)((wo + FC_TW - 1) / FC_TW);
+    g.total = (int)(n * g.tiles_h * g.tiles_w);
     return YMI_OK;
+}
+
+// the backward workspace, carved for a null base (its size) and for the caller's: the reduce pass's partial rows, the apply coefficients, the
+// weight-gradient slabs and, on the next 64-byte address, the one-record table of the slab sum (1024 bytes cover the step and the record)
+struct FcBwdSpace {
+    float *part, *coef, *slab;
+    ymi_wgrad_pending* table;
+    int64_t wgs, bytes;
+};
+FcBwdSpace fc_bwd_carve(void* workspace, int64_t blocks, int64_t cout) {
+    uintptr_t at = (uintptr_t)workspace;
+    auto floats = [&](int64_t n) {
+        float* r = reinterpret_cast<float*>(at);
+        at += (uintptr_t)n * sizeof(float);
+        return r;
+    };
+    FcBwdSpace v;
+    v.wgs = (blocks + FC_WG_TILES - 1) / FC_WG_TILES;
+    v.part = floats(blocks * 2 * cout);
+    v.coef = floats(FC_CROWS * cout);
+    v.slab = floats(v.wgs * cout * 72);
+    v.table = reinterpret_cast<ymi_wgrad_pending*>((at + 63) & ~(uintptr_t)63);
+    v.bytes = (int64_t)(at - (uintptr_t)workspace) + 1024;
+    return v;
 }
 
 }  // namespace
@@ -452,42 +580,40 @@ extern "C" int64_t ymi_first_conv_stat_blocks(int64_t n, int64_t h, int64_t w) {
 }
 
 // forward: statistics pass, finalize, apply pass.  x4: receives the image as NHWC bfloat16 [n, 4, h, w] (saved for the backward pass, which
-// reads nothing else of the input).  out: bfloat16 [n, cout, h/2, w/2] NHWC.  workspace: (2 cout + (blocks + 64) 2 cout) floats.
+// reads nothing else of the input).  out: bfloat16 [n, cout, h/2, w/2] NHWC.  workspace: (2 cout + (blocks + BN_STAGE_ROWS) 2 cout) floats.
 extern "C" int ymi_first_conv_bn_act_fwd(const float* img_nchw, int64_t n, int64_t c, int64_t h, int64_t w, const float* weight_oihw, int64_t cout,
                                          const float* gamma, const float* beta, float* running_mean, float* running_var, float momentum, float eps,
                                          int32_t act, const ymi_tensor* x4, const ymi_tensor* out, float* save_mean, float* save_invstd,
                                          void* workspace, size_t workspace_bytes, void* stream) {
     YMI_CHECK_ARG(img_nchw && weight_oihw && ymi_tensor_ok(out) && ymi_tensor_ok(x4) && workspace, "first_conv: bad argument");
     YMI_CHECK_ARG(((uintptr_t)img_nchw & 15) == 0, "first_conv: 16-byte aligned image");
-    FirstConvArgs a{};
-    a.act = act;
-    int rc = fc_geometry(a, n, c, h, w, cout);
+    FcGeom g{};
+    int rc = fc_geometry(g, n, c, h, w, cout, act);
     if (rc) return rc;
-    YMI_CHECK_ARG(out->dtype == YMI_BF16 && out->n == n && out->h == a.Ho && out->w == a.Wo && out->c == cout && out->ld % 8 == 0 && ((uintptr_t)out->data & 15) == 0,
+    YMI_CHECK_ARG(out->dtype == YMI_BF16 && out->n == n && out->h == g.Ho && out->w == g.Wo && out->c == cout && out->ld % 8 == 0 && ((uintptr_t)out->data & 15) == 0,
                   "first_conv: output must be bfloat16 [n, cout, h/2, w/2] NHWC with 16-byte aligned rows");
     YMI_CHECK_ARG(x4->dtype == YMI_BF16 && x4->n == n && x4->h == h && x4->w == w && x4->c == 4 && x4->ld == 4 && ((uintptr_t)x4->data & 15) == 0,
                   "first_conv: the image copy must be dense bfloat16 [n, 4, h, w] NHWC");
-    const int64_t blocks = a.total;
-    const size_t need = (size_t)(2 * cout + (blocks + 64) * 2 * cout) * sizeof(float);
+    const int64_t blocks = g.total;
+    const size_t need = (size_t)(2 * cout + (blocks + BN_STAGE_ROWS) * 2 * cout) * sizeof(float);
     if (workspace_bytes < need) {
         ymi_set_error("first_conv: workspace %zu < %zu bytes", workspace_bytes, need);
         return YMI_EWORKSPACE;
     }
     float* scale = reinterpret_cast<float*>(workspace);
     float* shift = scale + cout;
-    a.img = img_nchw; a.w = weight_oihw; a.x4 = x4->data; a.partials = shift + cout;
+    float* partials = shift + cout;
+    bf16_t* x4p = reinterpret_cast<bf16_t*>(x4->data);
     hipStream_t s = (hipStream_t)stream;
-    rc = fc_launch<FC_STATS>(a, cout, (unsigned)blocks, s);
+    rc = fc_launch<FcStats>(FcStatsArgs{g, img_nchw, weight_oihw, x4p, partials}, cout, (unsigned)blocks, s);
     if (rc) return rc;
-    rc = ymi_bn_finalize(a.partials, blocks, n * a.Ho * a.Wo, cout, gamma, beta, running_mean, running_var, momentum, eps, scale, shift, save_mean, save_invstd, stream);
+    rc = ymi_bn_finalize(partials, blocks, n * g.Ho * g.Wo, cout, gamma, beta, running_mean, running_var, momentum, eps, scale, shift, save_mean, save_invstd, stream);
     if (rc) return rc;
-    a.out = out->data; a.ldout = out->ld; a.v0 = scale; a.v1 = shift;
-    return fc_launch<FC_APPLY>(a, cout, (unsigned)blocks, s);
+    return fc_launch<FcApply>(FcApplyArgs{g, weight_oihw, x4p, reinterpret_cast<bf16_t*>(out->data), out->ld, scale, shift, act}, cout, (unsigned)blocks, s);
 }
 
 extern "C" int64_t ymi_first_conv_bwd_workspace(int64_t n, int64_t h, int64_t w, int64_t cout) {
-    const int64_t blocks = ymi_first_conv_stat_blocks(n, h, w), wgs = (blocks + FC_WG_TILES - 1) / FC_WG_TILES;
-    return (int64_t)sizeof(float) * (blocks * 2 * cout + 5 * cout + wgs * cout * 72) + 1024;
+    return fc_bwd_carve(nullptr, ymi_first_conv_stat_blocks(n, h, w), cout).bytes;
 }
 
 // backward of the block w.r.t. its parameters (the image receives no gradient): dgamma, dbeta [cout] and the weight gradient.
@@ -497,37 +623,31 @@ extern "C" int ymi_first_conv_bn_act_bwd(const ymi_tensor* x4, const float* weig
                                          const float* save_mean, const float* save_invstd, int32_t act, const ymi_tensor* dout, float* dgamma,
                                          float* dbeta, float* dw_oihw, void* workspace, size_t workspace_bytes, ymi_wgrad_pending* pending, void* stream) {
     YMI_CHECK_ARG(ymi_tensor_ok(x4) && ymi_tensor_ok(dout) && weight_oihw && save_mean && save_invstd && dgamma && dbeta && dw_oihw && workspace, "first_conv_bwd: bad argument");
-    FirstConvArgs a{};
-    a.act = act;
-    int rc = fc_geometry(a, x4->n, c, x4->h, x4->w, cout);
+    FcGeom g{};
+    int rc = fc_geometry(g, x4->n, c, x4->h, x4->w, cout, act);
     if (rc) return rc;
     YMI_CHECK_ARG(x4->dtype == YMI_BF16 && x4->c == 4 && x4->ld == 4 && ((uintptr_t)x4->data & 15) == 0, "first_conv_bwd: the image copy must be dense bfloat16 [n, 4, h, w] NHWC");
-    YMI_CHECK_ARG(dout->dtype == YMI_BF16 && dout->n == x4->n && dout->h == a.Ho && dout->w == a.Wo && dout->c == cout && dout->ld % 4 == 0 && ((uintptr_t)dout->data & 7) == 0,
+    YMI_CHECK_ARG(dout->dtype == YMI_BF16 && dout->n == x4->n && dout->h == g.Ho && dout->w == g.Wo && dout->c == cout && dout->ld % 4 == 0 && ((uintptr_t)dout->data & 7) == 0,
                   "first_conv_bwd: dout must be bfloat16 [n, cout, h/2, w/2] NHWC");
-    const int64_t blocks = a.total, wgs = (blocks + FC_WG_TILES - 1) / FC_WG_TILES;
-    if ((int64_t)workspace_bytes < ymi_first_conv_bwd_workspace(x4->n, x4->h, x4->w, cout)) {
+    const int64_t blocks = g.total;
+    const FcBwdSpace ws = fc_bwd_carve(workspace, blocks, cout);
+    if ((int64_t)workspace_bytes < ws.bytes) {
         ymi_set_error("first_conv_bwd: workspace too small");
         return YMI_EWORKSPACE;
     }
-    float* part = reinterpret_cast<float*>(workspace);
-    float* coef = part + blocks * 2 * cout;
-    float* slab = coef + 5 * cout;
-    ymi_wgrad_pending* table = reinterpret_cast<ymi_wgrad_pending*>(slab + wgs * cout * 72);
-    table = reinterpret_cast<ymi_wgrad_pending*>(((uintptr_t)table + 63) & ~(uintptr_t)63);
+    const bf16_t* x4p = reinterpret_cast<const bf16_t*>(x4->data);
+    const bf16_t* doutp = reinterpret_cast<const bf16_t*>(dout->data);
     hipStream_t s = (hipStream_t)stream;
-    a.w = weight_oihw; a.x4 = x4->data; a.out = dout->data; a.ldout = dout->ld;
-    a.partials = part; a.v0 = gamma; a.v1 = beta; a.v2 = save_mean; a.v3 = save_invstd;
-    rc = fc_launch<FC_BWD_REDUCE>(a, cout, (unsigned)blocks, s);
+    rc = fc_launch<FcBwdReduce>(FcBwdReduceArgs{g, weight_oihw, x4p, doutp, dout->ld, ws.part, gamma, beta, save_mean, save_invstd, act}, cout, (unsigned)blocks, s);
     if (rc) return rc;
-    rc = ymi_bn_bwd_final(part, (int)blocks, (int)cout, gamma, beta, save_mean, save_invstd, 1.0f / (float)((int64_t)x4->n * a.Ho * a.Wo), dgamma, dbeta, coef, s);
+    rc = ymi_bn_bwd_final(ws.part, (int)blocks, (int)cout, gamma, beta, save_mean, save_invstd, 1.0f / (float)((int64_t)x4->n * g.Ho * g.Wo), dgamma, dbeta, ws.coef, s);
     if (rc) return rc;
-    a.v0 = coef; a.slab = slab;
-    rc = fc_launch<FC_BWD_WGRAD>(a, cout, (unsigned)wgs, s);
+    rc = fc_launch<FcBwdWgrad>(FcBwdWgradArgs{g, weight_oihw, x4p, doutp, dout->ld, ws.coef, ws.slab, act}, cout, (unsigned)ws.wgs, s);
     if (rc) return rc;
-    const ymi_wgrad_pending rec = ymi_wgrad_record(slab, dw_oihw, cout * 72, (int)wgs, 72, 8, (int)cout, (int)c, 9, false, nullptr, nullptr);
+    const ymi_wgrad_pending rec = ymi_wgrad_record(ws.slab, dw_oihw, cout * 72, (int)ws.wgs, 72, 8, (int)cout, (int)c, 9, false, nullptr, nullptr);
     if (pending) {
         *pending = rec;
         return YMI_OK;
     }
-    return ymi_wgrad_reduce_batch(&rec, 1, table, stream);
+    return ymi_wgrad_reduce_batch(&rec, 1, ws.table, stream);
 }

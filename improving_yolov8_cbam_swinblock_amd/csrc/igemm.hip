@@ -169,19 +169,6 @@ template <> struct Mma<float> {
     }
 };
 
-// sum of a value over the 16 lanes of its DPP row, result in every lane: xor-1 and xor-2 quad permutes, then the half-row and
-// row mirrors (each lane already holds its quad's / half-row's total, so the mirrored partner supplies the other one)
-template <int CTRL> __device__ __forceinline__ float dpp_add(float v) {
-    return v + __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xF, 0xF, true));
-}
-__device__ __forceinline__ float row16_sum(float v) {
-    v = dpp_add<0xB1>(v);   // quad_perm [1,0,3,2]
-    v = dpp_add<0x4E>(v);   // quad_perm [2,3,0,1]
-    v = dpp_add<0x141>(v);  // row_half_mirror
-    v = dpp_add<0x140>(v);  // row_mirror
-    return v;
-}
-
 // ---- LDS image of a kernel form: ONE description, read by the kernel, the epilogue and the launcher ------------------------------------------
 // K loop: a ring of NS stages; a stage holds the BM pixel rows, then the BN weight rows, CPR 16-byte chunks each.  The epilogue reuses the
 // bytes for the [BM][BN] output image (rows padded by 16 bytes) and, in statistics mode, the per-wave-row sums [IGEMM_MAX_WM][2][BN] behind it.

@@ -137,11 +137,6 @@ struct MlpFwdArgs {
     int T, hidden;
 };
 
-__device__ __forceinline__ uint32_t pack_bf16x2(float a, float b) {
-    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-    const bf16x2 v = {(bf16_t)a, (bf16_t)b};
-    return __builtin_bit_cast(uint32_t, v);
-}
 __device__ __forceinline__ float bf16_lo(uint32_t v) { return __builtin_bit_cast(float, v << 16); }
 __device__ __forceinline__ float bf16_hi(uint32_t v) { return __builtin_bit_cast(float, v & 0xffff0000u); }
 
