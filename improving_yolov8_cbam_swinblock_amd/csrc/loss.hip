@@ -8,6 +8,10 @@
 //
 // Everything is f32 and deterministic (fixed-order block reductions, no atomics).  top-k ties go to the lower anchor
 // index (the reference leaves tie order to torch.topk).
+//
+// Each fact has one statement: side_of (the four-lanes-per-anchor prologue of the decode and loss kernels), pred_box, map_row, ciou,
+// the gt_* / centre_inside / clamped_label rules of the dense target rows, topk_offer (the selection rule), block_combine (the
+// workgroup reductions), carve_state / carve_work (the buffer layouts), quad_grid / anchor_grid.
 #include "common.h"
 
 namespace {
@@ -23,7 +27,7 @@ struct LossGeom {
     int64_t ldb[LOSS_MAXL], ldc[LOSS_MAXL], lddb[LOSS_MAXL], lddc[LOSS_MAXL];
     int H[LOSS_MAXL], W[LOSS_MAXL], off[LOSS_MAXL + 1];
     float stride[LOSS_MAXL];
-    int nl, B, A, G, nc;
+    int nl, B, A, G, nc;  // G: target rows per image (max_boxes), the forward's only
     int dcw;  // backward: channels of the class-gradient maps (>= nc; the ones beyond nc are written as zeros: padded gradient buffers)
 };
 
@@ -64,29 +68,22 @@ __device__ __forceinline__ Anchor anchor_of(const LossGeom& g, int b, int a) {
     return r;
 }
 
-__device__ __forceinline__ float sq(float v) { return v * v; }
-
-// CIoU of xyxy boxes, b1 and b2 in the order the reference passes them (metrics.py:74-134, xywh=False, CIoU=True)
-__device__ __forceinline__ float ciou_f(const float (&b1)[4], const float (&b2)[4]) {
-    const float eps = 1e-7f;
-    const float w1 = b1[2] - b1[0], h1 = b1[3] - b1[1] + eps, w2 = b2[2] - b2[0], h2 = b2[3] - b2[1] + eps;
-    const float iw = fmaxf(fminf(b1[2], b2[2]) - fmaxf(b1[0], b2[0]), 0.f);
-    const float ih = fmaxf(fminf(b1[3], b2[3]) - fmaxf(b1[1], b2[1]), 0.f);
-    const float inter = iw * ih;
-    const float uni = w1 * h1 + w2 * h2 - inter + eps;
-    const float iou = inter / uni;
-    const float cw = fmaxf(b1[2], b2[2]) - fminf(b1[0], b2[0]);
-    const float ch = fmaxf(b1[3], b2[3]) - fminf(b1[1], b2[1]);
-    const float c2 = cw * cw + ch * ch + eps;
-    const float rho2 = (sq(b2[0] + b2[2] - b1[0] - b1[2]) + sq(b2[1] + b2[3] - b1[1] - b1[3])) * 0.25f;
-    const float dv = atanf(w2 / h2) - atanf(w1 / h1);
-    const float v = 0.40528473456935108578f * dv * dv;  // 4 / pi^2
-    const float alpha = v / (v - iou + (1.0f + eps));
-    return iou - (rho2 / c2 + v * alpha);
+// the anchor's pixel row in its level's map: map_row<const T>(g.box, g.ldb, an), map_row<T>(g.dcls, g.lddc, an), ...
+template <typename T, typename V> __device__ __forceinline__ T* map_row(V* const (&maps)[LOSS_MAXL], const int64_t (&lds)[LOSS_MAXL], const Anchor& an) {
+    return reinterpret_cast<T*>(pick(maps, an.l)) + an.pix * pick(lds, an.l);
 }
 
-// CIoU(b1, b2) and its gradient with respect to b1 (alpha is a constant, as under the reference's no_grad)
-__device__ __forceinline__ float ciou_grad(const float (&b1)[4], const float (&b2)[4], float (&g)[4]) {
+// predicted xyxy box (grid units) from the four side distances (reference dist2bbox, xywh=False)
+__device__ __forceinline__ void pred_box(const Anchor& an, const float (&d)[4], float (&b)[4]) {
+    b[0] = an.ax - d[0];
+    b[1] = an.ay - d[1];
+    b[2] = an.ax + d[2];
+    b[3] = an.ay + d[3];
+}
+
+// CIoU of xyxy boxes, b1 and b2 in the order the reference passes them (metrics.py:74-134, xywh=False, CIoU=True); GRAD: also its
+// gradient g[4] with respect to b1 (alpha is a constant, as under the reference's no_grad)
+template <bool GRAD = false> __device__ __forceinline__ float ciou(const float (&b1)[4], const float (&b2)[4], float* g = nullptr) {
     const float eps = 1e-7f;
     const float w1 = b1[2] - b1[0], h1 = b1[3] - b1[1] + eps, w2 = b2[2] - b2[0], h2 = b2[3] - b2[1] + eps;
     const float iwr = fminf(b1[2], b2[2]) - fmaxf(b1[0], b2[0]);
@@ -95,70 +92,62 @@ __device__ __forceinline__ float ciou_grad(const float (&b1)[4], const float (&b
     const float inter = iw * ih;
     const float uni = w1 * h1 + w2 * h2 - inter + eps;
     const float iou = inter / uni;
-    // d inter
-    const float on_w = iwr > 0.f ? 1.f : 0.f, on_h = ihr > 0.f ? 1.f : 0.f;
-    float dint[4];
-    dint[0] = -(b1[0] > b2[0] ? 1.f : 0.f) * on_w * ih;
-    dint[1] = -(b1[1] > b2[1] ? 1.f : 0.f) * on_h * iw;
-    dint[2] = (b1[2] < b2[2] ? 1.f : 0.f) * on_w * ih;
-    dint[3] = (b1[3] < b2[3] ? 1.f : 0.f) * on_h * iw;
-    const float duni[4] = {-h1 - dint[0], -w1 - dint[1], h1 - dint[2], w1 - dint[3]};
     const float cw = fmaxf(b1[2], b2[2]) - fminf(b1[0], b2[0]);
     const float ch = fmaxf(b1[3], b2[3]) - fminf(b1[1], b2[1]);
     const float c2 = cw * cw + ch * ch + eps;
-    const float dc2[4] = {-(b1[0] < b2[0] ? 1.f : 0.f) * 2.f * cw, -(b1[1] < b2[1] ? 1.f : 0.f) * 2.f * ch,
-                          (b1[2] > b2[2] ? 1.f : 0.f) * 2.f * cw, (b1[3] > b2[3] ? 1.f : 0.f) * 2.f * ch};
     const float sx = b2[0] + b2[2] - b1[0] - b1[2], sy = b2[1] + b2[3] - b1[1] - b1[3];
     const float rho2 = (sx * sx + sy * sy) * 0.25f;
-    const float drho[4] = {-0.5f * sx, -0.5f * sy, -0.5f * sx, -0.5f * sy};
     const float u = w1 / h1;
     const float dv = atanf(w2 / h2) - atanf(u);
-    const float kk = 0.40528473456935108578f;
+    const float kk = 0.40528473456935108578f;  // 4 / pi^2
     const float v = kk * dv * dv;
     const float alpha = v / (v - iou + (1.0f + eps));
-    const float dat = 1.0f / (1.0f + u * u);
-    const float du[4] = {-1.0f / h1, w1 / (h1 * h1), 1.0f / h1, -w1 / (h1 * h1)};
+    if constexpr (GRAD) {
+        const float on_w = iwr > 0.f ? 1.f : 0.f, on_h = ihr > 0.f ? 1.f : 0.f;
+        float dint[4];
+        dint[0] = -(b1[0] > b2[0] ? 1.f : 0.f) * on_w * ih;
+        dint[1] = -(b1[1] > b2[1] ? 1.f : 0.f) * on_h * iw;
+        dint[2] = (b1[2] < b2[2] ? 1.f : 0.f) * on_w * ih;
+        dint[3] = (b1[3] < b2[3] ? 1.f : 0.f) * on_h * iw;
+        const float duni[4] = {-h1 - dint[0], -w1 - dint[1], h1 - dint[2], w1 - dint[3]};
+        const float dc2[4] = {-(b1[0] < b2[0] ? 1.f : 0.f) * 2.f * cw, -(b1[1] < b2[1] ? 1.f : 0.f) * 2.f * ch,
+                              (b1[2] > b2[2] ? 1.f : 0.f) * 2.f * cw, (b1[3] > b2[3] ? 1.f : 0.f) * 2.f * ch};
+        const float drho[4] = {-0.5f * sx, -0.5f * sy, -0.5f * sx, -0.5f * sy};
+        const float dat = 1.0f / (1.0f + u * u);
+        const float du[4] = {-1.0f / h1, w1 / (h1 * h1), 1.0f / h1, -w1 / (h1 * h1)};
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const float diou = (dint[i] * uni - inter * duni[i]) / (uni * uni);
-        const float dpen = (drho[i] * c2 - rho2 * dc2[i]) / (c2 * c2);
-        const float dvv = 2.f * kk * dv * (-dat * du[i]);
-        g[i] = diou - dpen - alpha * dvv;
+        for (int i = 0; i < 4; ++i) {
+            const float diou = (dint[i] * uni - inter * duni[i]) / (uni * uni);
+            const float dpen = (drho[i] * c2 - rho2 * dc2[i]) / (c2 * c2);
+            const float dvv = 2.f * kk * dv * (-dat * du[i]);
+            g[i] = diou - dpen - alpha * dvv;
+        }
     }
     return iou - (rho2 / c2 + v * alpha);
 }
 
-template <typename T> __device__ __forceinline__ void load16(const T* p, float (&v)[REG]);
-template <> __device__ __forceinline__ void load16<float>(const float* p, float (&v)[REG]) {
+// one side's 16 bins as floats, by 16-byte chunks of ElemTraits<T>::CH elements: Pack<T, CH> in a loop.  (store16 says the same on the vector
+// type itself: through Pack<bf16_t, 8>::store and the float[8] in between, the bfloat16 gradient kernel's sums pair up differently in the SLP
+// vectoriser, other products are fused, and last bits of the box gradients move - profiles/loss_refactor_ab.txt.)
+template <typename T> __device__ __forceinline__ void load16(const T* p, float (&v)[REG]) {
+    constexpr int CH = ElemTraits<T>::CH;
 #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const f32x4 t = *reinterpret_cast<const f32x4*>(p + 4 * i);
-        v[4 * i] = t[0]; v[4 * i + 1] = t[1]; v[4 * i + 2] = t[2]; v[4 * i + 3] = t[3];
+    for (int i = 0; i < REG; i += CH) {
+        float t[CH];
+        Pack<T, CH>::load(p + i, t);
+#pragma unroll
+        for (int j = 0; j < CH; ++j) v[i + j] = t[j];
     }
 }
-template <> __device__ __forceinline__ void load16<bf16_t>(const bf16_t* p, float (&v)[REG]) {
+template <typename T> __device__ __forceinline__ void store16(T* p, const float (&v)[REG]) {
+    constexpr int CH = ElemTraits<T>::CH;
+    typedef T Chunk __attribute__((ext_vector_type(CH)));
 #pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const bf16x8 t = *reinterpret_cast<const bf16x8*>(p + 8 * i);
+    for (int i = 0; i < REG / CH; ++i) {
+        Chunk t;
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v[8 * i + j] = (float)t[j];
-    }
-}
-template <typename T> __device__ __forceinline__ void store16(T* p, const float (&v)[REG]);
-template <> __device__ __forceinline__ void store16<float>(float* p, const float (&v)[REG]) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const f32x4 t = {v[4 * i], v[4 * i + 1], v[4 * i + 2], v[4 * i + 3]};
-        *reinterpret_cast<f32x4*>(p + 4 * i) = t;
-    }
-}
-template <> __device__ __forceinline__ void store16<bf16_t>(bf16_t* p, const float (&v)[REG]) {
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        bf16x8 t;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) t[j] = (bf16_t)v[8 * i + j];
-        *reinterpret_cast<bf16x8*>(p + 8 * i) = t;
+        for (int j = 0; j < CH; ++j) t[j] = from_f32<T>(v[CH * i + j]);
+        *reinterpret_cast<Chunk*>(p + CH * i) = t;
     }
 }
 
@@ -191,8 +180,70 @@ __device__ __forceinline__ void quad_gather(float mine, float (&d)[4]) {
     for (int k = 0; k < 4; ++k) d[k] = __shfl(mine, base + k, 64);
 }
 
-// ---- targets: ragged (image, class, xywh normalised) rows -> dense [B, G, 5] (class, xyxy pixels) -------------
+// ---- the prologue of the kernels that give an anchor four lanes, one per box side (decode_kernel, infer_decode_kernel, loss_kernel) ----
+// thread -> (anchor, side); the side's 16 logits x, their softmax p, log-sum-exp lse and expectation e; d: the anchor's four expectations.
+// Threads past the last anchor are not live: they compute on anchor 0 (the quad shuffles want every lane) and must store nothing.
+// x and p stay arrays of the kernel, filled through references: as members of Side the float32 gradient kernel's multiply-adds came out
+// fused otherwise than before (same record).
+struct Side {
+    bool live;
+    int b, a, side;
+    int64_t ia;  // b * A + a
+    Anchor an;
+    float lse, e, d[4];
+};
+template <typename T> __device__ __forceinline__ void side_of(const LossGeom& g, Side& s, float (&x)[REG], float (&p)[REG]) {
+    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const int64_t quad = t >> 2;
+    s.side = (int)(t & 3);
+    s.live = quad < (int64_t)g.B * g.A;
+    s.b = s.live ? (int)(quad / g.A) : 0;
+    s.a = s.live ? (int)(quad - (int64_t)s.b * g.A) : 0;
+    s.ia = (int64_t)s.b * g.A + s.a;
+    s.an = anchor_of(g, s.b, s.a);
+    load16<T>(map_row<const T>(g.box, g.ldb, s.an) + s.side * REG, x);
+    s.e = softmax_expect(x, p, &s.lse);
+    quad_gather(s.e, s.d);
+}
+
+// ---- workgroup combine (256 threads = 4 waves) of N values per thread: the wave's reduction, lane 0 of each wave to sh[n][wave], barrier,
+// then every thread combines the four.  An Op states both steps, i.e. the association: (w0 + w1) + (w2 + w3) for sums and maxima, the
+// `better` chain in wave order for Best.  A caller that combines again with the same sh puts a barrier between the rounds.
+struct SumOp {
+    static __device__ __forceinline__ float wave(float v) { return wave_sum(v); }
+    static __device__ __forceinline__ float four(const float (&s)[4]) { return (s[0] + s[1]) + (s[2] + s[3]); }
+};
+struct MaxOp {
+    static __device__ __forceinline__ float wave(float v) { return wave_max(v); }
+    static __device__ __forceinline__ float four(const float (&s)[4]) { return fmaxf(fmaxf(s[0], s[1]), fmaxf(s[2], s[3])); }
+};
+struct Best {
+    float v;
+    int i;
+};
+__device__ __forceinline__ Best better(Best x, Best y) { return (y.v > x.v || (y.v == x.v && y.i < x.i)) ? y : x; }
+struct BestOp {
+    static __device__ __forceinline__ Best wave(Best mine) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) mine = better(mine, Best{__shfl_xor(mine.v, o, 64), __shfl_xor(mine.i, o, 64)});
+        return mine;
+    }
+    static __device__ __forceinline__ Best four(const Best (&s)[4]) { return better(better(better(s[0], s[1]), s[2]), s[3]); }
+};
+template <typename Op, typename V, int N> __device__ __forceinline__ void block_combine(V (&v)[N], V (&sh)[N][4]) {
+#pragma unroll
+    for (int n = 0; n < N; ++n) {
+        v[n] = Op::wave(v[n]);
+        if ((threadIdx.x & 63) == 0) sh[n][threadIdx.x >> 6] = v[n];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int n = 0; n < N; ++n) v[n] = Op::four(sh[n]);
+}
+
+// ---- targets: ragged (image, class, xywh normalised) rows -> dense [B, G, GT_ROW] (class, xyxy pixels) -------------
 // reference loss.py:176-191 preprocess; order inside an image is the row order (stable), empty slots are zero
+constexpr int GT_ROW = 5;
 __global__ void targets_kernel(const float* __restrict__ batch_idx, const float* __restrict__ cls, const float* __restrict__ xywh, int n, int B,
                                int G, float img_w, float img_h, float* __restrict__ out) {
     const int t = blockIdx.x * blockDim.x + threadIdx.x;
@@ -208,7 +259,7 @@ __global__ void targets_kernel(const float* __restrict__ batch_idx, const float*
             ++seen;
         }
     }
-    float o[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    float o[GT_ROW] = {0.f, 0.f, 0.f, 0.f, 0.f};
     if (row >= 0) {
         const float cx = xywh[row * 4 + 0] * img_w, cy = xywh[row * 4 + 1] * img_h, bw = xywh[row * 4 + 2] * img_w, bh = xywh[row * 4 + 3] * img_h;
         o[0] = cls[row];
@@ -218,26 +269,36 @@ __global__ void targets_kernel(const float* __restrict__ batch_idx, const float*
         o[4] = cy + bh / 2;
     }
 #pragma unroll
-    for (int k = 0; k < 5; ++k) out[(int64_t)t * 5 + k] = o[k];
+    for (int k = 0; k < GT_ROW; ++k) out[(int64_t)t * GT_ROW + k] = o[k];
+}
+// ... and their readers: row bg = b * G + k of the dense targets, its box, "is it a label or a padding row", "is the anchor's centre inside
+// it" (tal.py:262-283 select_candidates_in_gts), its class as an index of the class map
+__device__ __forceinline__ const float* gt_row(const float* targets, int64_t bg) { return targets + bg * GT_ROW; }
+__device__ __forceinline__ void gt_box(const float* tg, float (&gt)[4]) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) gt[k] = tg[1 + k];
+}
+__device__ __forceinline__ bool gt_valid(const float (&gt)[4]) { return (gt[0] + gt[1] + gt[2] + gt[3]) > 0.f; }
+__device__ __forceinline__ bool centre_inside(const Anchor& an, const float (&gt)[4]) {
+    const float px = an.ax * an.s, py = an.ay * an.s;
+    const float dmin = fminf(fminf(px - gt[0], py - gt[1]), fminf(gt[2] - px, gt[3] - py));
+    return dmin > TAL_EPS;
+}
+__device__ __forceinline__ int clamped_label(const float* tg, int nc) {
+    const int lab = (int)tg[0];
+    return lab < 0 ? 0 : (lab >= nc ? nc - 1 : lab);
 }
 
 // ---- K1: DFL decode -> predicted boxes in grid units [B, A, 4] ------------------------------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void decode_kernel(LossGeom g, float* __restrict__ pb) {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t quad = t >> 2;
-    const int side = (int)(t & 3);
-    const bool live = quad < (int64_t)g.B * g.A;
-    const int b = live ? (int)(quad / g.A) : 0, a = live ? (int)(quad - (int64_t)b * g.A) : 0;
-    const Anchor an = anchor_of(g, b, a);
-    float x[REG], p[REG], lse;
-    load16<T>(reinterpret_cast<const T*>(pick(g.box, an.l)) + an.pix * pick(g.ldb, an.l) + side * REG, x);
-    const float e = softmax_expect(x, p, &lse);
-    float d[4];
-    quad_gather(e, d);
-    if (live && side == 0) {
-        const f32x4 o = {an.ax - d[0], an.ay - d[1], an.ax + d[2], an.ay + d[3]};
-        *reinterpret_cast<f32x4*>(pb + quad * 4) = o;
+    Side s;
+    float x[REG], p[REG];
+    side_of<T>(g, s, x, p);
+    if (s.live && s.side == 0) {
+        float o[4];
+        pred_box(s.an, s.d, o);
+        Pack<float, 4>::store(pb + s.ia * 4, o);
     }
 }
 
@@ -245,26 +306,25 @@ __global__ __launch_bounds__(256) void decode_kernel(LossGeom g, float* __restri
 // y[b][0:4][a] = dist2bbox(DFL(box), anchor, xywh=True) * stride ; y[b][4+c][a] = sigmoid(cls[c]).  Output is the
 // reference's [B, 4+nc, A] float32 tensor (anchor index fastest).  Four lanes per anchor as in decode_kernel; the quad
 // then walks the classes.  A-major stores: the 64 lanes of a wave cover 16 consecutive anchors of 4 rows each.
+__device__ __forceinline__ void xywh_scaled(const float (&b)[4], float s, float (&o)[4]) {
+    o[0] = (b[0] + b[2]) * 0.5f * s;
+    o[1] = (b[1] + b[3]) * 0.5f * s;
+    o[2] = (b[2] - b[0]) * s;
+    o[3] = (b[3] - b[1]) * s;
+}
 template <typename T>
 __global__ __launch_bounds__(256) void infer_decode_kernel(LossGeom g, float* __restrict__ y) {
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t quad = t >> 2;
-    const int side = (int)(t & 3);
-    const bool live = quad < (int64_t)g.B * g.A;
-    const int b = live ? (int)(quad / g.A) : 0, a = live ? (int)(quad - (int64_t)b * g.A) : 0;
-    const Anchor an = anchor_of(g, b, a);
-    float x[REG], p[REG], lse;
-    load16<T>(reinterpret_cast<const T*>(pick(g.box, an.l)) + an.pix * pick(g.ldb, an.l) + side * REG, x);
-    const float e = softmax_expect(x, p, &lse);
-    float d[4];
-    quad_gather(e, d);
-    if (!live) return;
-    float* yo = y + (int64_t)b * (4 + g.nc) * g.A + a;
-    const float x1 = an.ax - d[0], y1 = an.ay - d[1], x2 = an.ax + d[2], y2 = an.ay + d[3];
-    const float box[4] = {(x1 + x2) * 0.5f * an.s, (y1 + y2) * 0.5f * an.s, (x2 - x1) * an.s, (y2 - y1) * an.s};
-    yo[(int64_t)side * g.A] = side == 0 ? box[0] : side == 1 ? box[1] : side == 2 ? box[2] : box[3];
-    const T* cp = reinterpret_cast<const T*>(pick(g.cls, an.l)) + an.pix * pick(g.ldc, an.l);
-    for (int c = side; c < g.nc; c += 4) yo[(int64_t)(4 + c) * g.A] = 1.0f / (1.0f + expf(-to_f32(cp[c])));
+    Side s;
+    float x[REG], p[REG];
+    side_of<T>(g, s, x, p);
+    if (!s.live) return;
+    float* yo = y + (int64_t)s.b * (4 + g.nc) * g.A + s.a;
+    float xyxy[4], box[4];
+    pred_box(s.an, s.d, xyxy);
+    xywh_scaled(xyxy, s.an.s, box);
+    yo[(int64_t)s.side * g.A] = s.side == 0 ? box[0] : s.side == 1 ? box[1] : s.side == 2 ? box[2] : box[3];
+    const T* cp = map_row<const T>(g.cls, g.ldc, s.an);
+    for (int c = s.side; c < g.nc; c += 4) yo[(int64_t)(4 + c) * g.A] = 1.0f / (1.0f + expf(-to_f32(cp[c])));
 }
 
 // ---- K2: alignment metric and overlaps for every (image, gt, anchor) (tal.py:118-160) -------------------------
@@ -278,20 +338,15 @@ __global__ __launch_bounds__(256) void metric_kernel(LossGeom g, const float* __
     const Anchor an = anchor_of(g, b, a);
     const f32x4 pq = *reinterpret_cast<const f32x4*>(pb + ((int64_t)b * g.A + a) * 4);
     const float pd[4] = {pq[0] * an.s, pq[1] * an.s, pq[2] * an.s, pq[3] * an.s};
-    const float px = an.ax * an.s, py = an.ay * an.s;
-    const T* cp = reinterpret_cast<const T*>(pick(g.cls, an.l)) + an.pix * pick(g.ldc, an.l);
+    const T* cp = map_row<const T>(g.cls, g.ldc, an);
     for (int k = 0; k < g.G; ++k) {
-        const float* tg = targets + ((int64_t)b * g.G + k) * 5;
-        const float gt[4] = {tg[1], tg[2], tg[3], tg[4]};
-        const bool valid = (gt[0] + gt[1] + gt[2] + gt[3]) > 0.f;
-        const float dmin = fminf(fminf(px - gt[0], py - gt[1]), fminf(gt[2] - px, gt[3] - py));
-        const bool inside = dmin > TAL_EPS;
+        const float* tg = gt_row(targets, (int64_t)b * g.G + k);
+        float gt[4];
+        gt_box(tg, gt);
         float o = 0.f, m = 0.f;
-        if (valid && inside) {
-            int lab = (int)tg[0];
-            lab = lab < 0 ? 0 : (lab >= g.nc ? g.nc - 1 : lab);
-            const float score = sigmoidf_(to_f32(cp[lab]));
-            o = fmaxf(ciou_f(gt, pd), 0.f);
+        if (gt_valid(gt) && centre_inside(an, gt)) {
+            const float score = sigmoidf_(to_f32(cp[clamped_label(tg, g.nc)]));
+            o = fmaxf(ciou(gt, pd), 0.f);
             // score^alpha * overlap^beta (reference alpha 0.5, beta 6.0): powf keeps other exponents exact too
             m = powf(score, alpha) * powf(o, beta);
         }
@@ -302,39 +357,26 @@ __global__ __launch_bounds__(256) void metric_kernel(LossGeom g, const float* __
     }
 }
 
-struct Best {
-    float v;
-    int i;
-};
-__device__ __forceinline__ Best better(Best x, Best y) { return (y.v > x.v || (y.v == x.v && y.i < x.i)) ? y : x; }
-__device__ __forceinline__ Best block_best(Best mine, Best* sh) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        Best other{__shfl_xor(mine.v, o, 64), __shfl_xor(mine.i, o, 64)};
-        mine = better(mine, other);
-    }
-    const int wave = threadIdx.x >> 6;
-    __syncthreads();
-    if ((threadIdx.x & 63) == 0) sh[wave] = mine;
-    __syncthreads();
-    Best r = sh[0];
-    for (int w = 1; w < (int)(blockDim.x >> 6); ++w) r = better(r, sh[w]);
-    return r;
-}
-
 // ---- K3: top-k anchors per gt by alignment metric (tal.py:198-229); one workgroup per (image, gt) --------------
+// the selection rule of one round: anchor a of value v is a candidate when it comes strictly after the previous pick in (value desc,
+// index asc) order; the thread keeps its best candidate
+__device__ __forceinline__ void topk_offer(Best& mine, const Best& prev, float v, int a) {
+    const bool cand = v < prev.v || (v == prev.v && a > prev.i);
+    if (cand) mine = better(mine, Best{v, a});
+}
 __global__ __launch_bounds__(256) void topk_kernel(LossGeom g, const float* __restrict__ targets, const float* __restrict__ al,
                                                    uint8_t* __restrict__ mpos, int topk) {
-    __shared__ Best sh[4];
+    __shared__ Best sh[1][4];
     const int bg = blockIdx.x;
     const int b = bg / g.G;
-    const float* tg = targets + (int64_t)bg * 5;
-    const float gt[4] = {tg[1], tg[2], tg[3], tg[4]};
-    if (!((gt[0] + gt[1] + gt[2] + gt[3]) > 0.f)) return;  // padding row: selects nothing (uniform across the block)
+    float gt[4];
+    gt_box(gt_row(targets, bg), gt);
+    if (!gt_valid(gt)) return;  // padding row: selects nothing (uniform across the block)
     const float* row = al + (int64_t)bg * g.A;
     Best prev{__builtin_inff(), -1};
     // the gt's metric row is read ONCE into registers when it fits (A <= 256 * TOPK_NV: 8400 anchors at 640x640 are 33 values per
     // thread); the k selection rounds then only scan registers.  (Ten passes over the row in L2 took 71 us of the 0.18 ms loss.)
+    // A longer row (33600 anchors at 1280x1280) is scanned in memory every round.
     constexpr int TOPK_NV = 40;
     const bool inreg = g.A <= 256 * TOPK_NV;
     float vals[TOPK_NV];
@@ -346,31 +388,18 @@ __global__ __launch_bounds__(256) void topk_kernel(LossGeom g, const float* __re
         }
     }
     for (int r = 0; r < topk && r < g.A; ++r) {
-        Best mine{-1.0f, 0x7fffffff};
+        Best mine[1] = {Best{-1.0f, 0x7fffffff}};
         if (inreg) {
 #pragma unroll
-            for (int i = 0; i < TOPK_NV; ++i) {
-                const int a = threadIdx.x + 256 * i;
-                const float v = vals[i];
-                const bool cand = v < prev.v || (v == prev.v && a > prev.i);
-                if (cand) mine = better(mine, Best{v, a});
-            }
+            for (int i = 0; i < TOPK_NV; ++i) topk_offer(mine[0], prev, vals[i], threadIdx.x + 256 * i);
         } else {
-            for (int a = threadIdx.x; a < g.A; a += 256) {
-                const float v = row[a];
-                // candidates: strictly after the previous pick in (value desc, index asc) order
-                const bool cand = v < prev.v || (v == prev.v && a > prev.i);
-                if (cand) mine = better(mine, Best{v, a});
-            }
+            for (int a = threadIdx.x; a < g.A; a += 256) topk_offer(mine[0], prev, row[a], a);
         }
-        const Best win = block_best(mine, sh);
+        __syncthreads();  // (the previous round's readers of sh)
+        block_combine<BestOp>(mine, sh);
+        const Best win = mine[0];
         if (win.i == 0x7fffffff) break;
-        if (threadIdx.x == 0) {
-            const Anchor an = anchor_of(g, b, win.i);
-            const float px = an.ax * an.s, py = an.ay * an.s;
-            const float dmin = fminf(fminf(px - gt[0], py - gt[1]), fminf(gt[2] - px, gt[3] - py));
-            if (dmin > TAL_EPS) mpos[(int64_t)bg * g.A + win.i] = 1;
-        }
+        if (threadIdx.x == 0 && centre_inside(anchor_of(g, b, win.i), gt)) mpos[(int64_t)bg * g.A + win.i] = 1;
         prev = win;
     }
 }
@@ -404,23 +433,17 @@ __global__ __launch_bounds__(256) void posmax_kernel(LossGeom g, const float* __
     __shared__ float sh[2][4];
     const int bg = blockIdx.x;
     const int b = bg / g.G, k = bg - b * g.G;
-    float ma = 0.f, mo = 0.f;
+    float m[2] = {0.f, 0.f};  // metric, overlap
     for (int a = threadIdx.x; a < g.A; a += 256) {
         if (gidx[(int64_t)b * g.A + a] == k) {
-            ma = fmaxf(ma, al[(int64_t)bg * g.A + a]);
-            mo = fmaxf(mo, ov[(int64_t)bg * g.A + a]);
+            m[0] = fmaxf(m[0], al[(int64_t)bg * g.A + a]);
+            m[1] = fmaxf(m[1], ov[(int64_t)bg * g.A + a]);
         }
     }
-    ma = wave_max(ma);
-    mo = wave_max(mo);
-    if ((threadIdx.x & 63) == 0) {
-        sh[0][threadIdx.x >> 6] = ma;
-        sh[1][threadIdx.x >> 6] = mo;
-    }
-    __syncthreads();
+    block_combine<MaxOp>(m, sh);
     if (threadIdx.x == 0) {
-        pa[bg] = fmaxf(fmaxf(sh[0][0], sh[0][1]), fmaxf(sh[0][2], sh[0][3]));
-        po[bg] = fmaxf(fmaxf(sh[1][0], sh[1][1]), fmaxf(sh[1][2], sh[1][3]));
+        pa[bg] = m[0];
+        po[bg] = m[1];
     }
 }
 
@@ -429,32 +452,31 @@ __global__ __launch_bounds__(256) void finalize_kernel(LossGeom g, const float* 
                                                        const int* __restrict__ gidx, const float* __restrict__ pa, const float* __restrict__ po,
                                                        float* __restrict__ tgt, float* __restrict__ wgt, int* __restrict__ lab,
                                                        float* __restrict__ tss_part) {
-    __shared__ float sh[4];
+    __shared__ float sh[1][4];
     const int b = blockIdx.y;
     const int a = blockIdx.x * 256 + threadIdx.x;
-    float w = 0.f;
+    float w[1] = {0.f};
     if (a < g.A) {
         const int64_t ia = (int64_t)b * g.A + a;
         const int k = gidx[ia];
-        f32x4 tb = {0.f, 0.f, 0.f, 0.f};
+        float tb[4] = {0.f, 0.f, 0.f, 0.f};
         int lb = -1;
         if (k >= 0) {
             const int64_t bg = (int64_t)b * g.G + k;
-            const float* tg = targets + bg * 5;
+            const float* tg = gt_row(targets, bg);
             const Anchor an = anchor_of(g, b, a);
-            w = al[bg * g.A + a] * po[bg] / (pa[bg] + TAL_EPS);
-            lb = (int)tg[0];
-            lb = lb < 0 ? 0 : (lb >= g.nc ? g.nc - 1 : lb);
-            tb = f32x4{tg[1] / an.s, tg[2] / an.s, tg[3] / an.s, tg[4] / an.s};
+            w[0] = al[bg * g.A + a] * po[bg] / (pa[bg] + TAL_EPS);
+            lb = clamped_label(tg, g.nc);
+            gt_box(tg, tb);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) tb[i] = tb[i] / an.s;
         }
-        *reinterpret_cast<f32x4*>(tgt + ia * 4) = tb;
-        wgt[ia] = w;
+        Pack<float, 4>::store(tgt + ia * 4, tb);
+        wgt[ia] = w[0];
         lab[ia] = lb;
     }
-    w = wave_sum(w);
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = w;
-    __syncthreads();
-    if (threadIdx.x == 0) tss_part[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
+    block_combine<SumOp>(w, sh);
+    if (threadIdx.x == 0) tss_part[(int64_t)blockIdx.y * gridDim.x + blockIdx.x] = w[0];
 }
 
 // ---- K7: loss sums (GRAD = false) or gradients with respect to the maps (GRAD = true) --------------------------
@@ -464,23 +486,16 @@ __global__ __launch_bounds__(256) void loss_kernel(LossGeom g, const float* __re
                                                    const int* __restrict__ lab, const float* __restrict__ scal, const float* __restrict__ gout,
                                                    const float* __restrict__ gscale, float* __restrict__ part) {
     __shared__ float sh[3][4];
-    const int64_t t = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    const int64_t quad = t >> 2;
-    const int side = (int)(t & 3);
-    const bool live = quad < (int64_t)g.B * g.A;
-    const int b = live ? (int)(quad / g.A) : 0, a = live ? (int)(quad - (int64_t)b * g.A) : 0;
-    const Anchor an = anchor_of(g, b, a);
-    const int64_t ia = (int64_t)b * g.A + a;
-    float x[REG], p[REG], lse;
-    load16<T>(reinterpret_cast<const T*>(pick(g.box, an.l)) + an.pix * pick(g.ldb, an.l) + side * REG, x);
-    const float e = softmax_expect(x, p, &lse);
-    float d[4];
-    quad_gather(e, d);
-    const float w = wgt[ia];
-    const int lb = lab[ia];
-    const f32x4 tq = *reinterpret_cast<const f32x4*>(tgt + ia * 4);
-    const float tb[4] = {tq[0], tq[1], tq[2], tq[3]};
-    const float pbx[4] = {an.ax - d[0], an.ay - d[1], an.ax + d[2], an.ay + d[3]};
+    Side s;
+    float x[REG], p[REG];
+    side_of<T>(g, s, x, p);
+    const Anchor& an = s.an;
+    const int side = s.side;
+    const float w = wgt[s.ia];
+    const int lb = lab[s.ia];
+    float tb[4], pbx[4];
+    Pack<float, 4>::load(tgt + s.ia * 4, tb);
+    pred_box(an, s.d, pbx);
     float s_box = 0.f, s_cls = 0.f, s_dfl = 0.f;
     // DFL target of this side (loss.py:101-104, 75-83)
     const float raw_t = side == 0 ? an.ax - tb[0] : side == 1 ? an.ay - tb[1] : side == 2 ? tb[2] - an.ax : tb[3] - an.ay;
@@ -496,17 +511,17 @@ __global__ __launch_bounds__(256) void loss_kernel(LossGeom g, const float* __re
     }
     if (lb >= 0) {  // foreground anchor
         if (!GRAD) {
-            if (side == 0) s_box = (1.0f - ciou_f(pbx, tb)) * w;
+            if (side == 0) s_box = (1.0f - ciou(pbx, tb)) * w;
             float xl = 0.f, xr = 0.f;
 #pragma unroll
             for (int j = 0; j < REG; ++j) {
                 xl = j == tl ? x[j] : xl;
                 xr = j == tl + 1 ? x[j] : xr;
             }
-            s_dfl = ((lse - xl) * wl + (lse - xr) * wr) * 0.25f * w;
+            s_dfl = ((s.lse - xl) * wl + (s.lse - xr) * wr) * 0.25f * w;
         } else {
             float gc[4];
-            (void)ciou_grad(pbx, tb, gc);
+            (void)ciou<true>(pbx, tb, gc);
             // d loss_box / d dist_k: x1 = ax - d0, y1 = ay - d1, x2 = ax + d2, y2 = ay + d3 ; loss = (1 - ciou) * w
             const float gd = (side < 2 ? gc[side] : -gc[side]) * w * g_box;
             const float kd = 0.25f * w * g_dfl;
@@ -514,52 +529,44 @@ __global__ __launch_bounds__(256) void loss_kernel(LossGeom g, const float* __re
 #pragma unroll
             for (int j = 0; j < REG; ++j) {
                 const float hot = (j == tl ? wl : 0.f) + (j == tl + 1 ? wr : 0.f);
-                o[j] = gd * p[j] * ((float)j - e) + kd * (p[j] - hot);
+                o[j] = gd * p[j] * ((float)j - s.e) + kd * (p[j] - hot);
             }
-            if (live) store16<T>(reinterpret_cast<T*>(pick(g.dbox, an.l)) + an.pix * pick(g.lddb, an.l) + side * REG, o);
+            if (s.live) store16<T>(map_row<T>(g.dbox, g.lddb, an) + side * REG, o);
         }
-    } else if (GRAD && live) {
+    } else if (GRAD && s.live) {
         float o[REG];
 #pragma unroll
         for (int j = 0; j < REG; ++j) o[j] = 0.f;
-        store16<T>(reinterpret_cast<T*>(pick(g.dbox, an.l)) + an.pix * pick(g.lddb, an.l) + side * REG, o);
+        store16<T>(map_row<T>(g.dbox, g.lddb, an) + side * REG, o);
     }
     // classification: BCE with logits against target score (label == c) * weight  (loss.py:233)
-    if (live) {
-        const T* cp = reinterpret_cast<const T*>(pick(g.cls, an.l)) + an.pix * pick(g.ldc, an.l);
+    if (s.live) {
+        const T* cp = map_row<const T>(g.cls, g.ldc, an);
         for (int c = side; c < g.nc; c += 4) {
             const float xv = to_f32(cp[c]);
             const float tv = c == lb ? w : 0.f;
-            if (!GRAD) {
-                s_cls += fmaxf(xv, 0.f) - xv * tv + log1pf(__expf(-fabsf(xv)));
-            } else {
-                T* dp = reinterpret_cast<T*>(pick(g.dcls, an.l)) + an.pix * pick(g.lddc, an.l);
-                dp[c] = from_f32<T>((sigmoidf_(xv) - tv) * g_cls);
-            }
+            if (!GRAD) s_cls += fmaxf(xv, 0.f) - xv * tv + log1pf(__expf(-fabsf(xv)));
+            else map_row<T>(g.dcls, g.lddc, an)[c] = from_f32<T>((sigmoidf_(xv) - tv) * g_cls);
         }
         if (GRAD) {  // zero padding channels of a padded gradient buffer (the consumer's weight-gradient GEMM reads them)
-            T* dp = reinterpret_cast<T*>(pick(g.dcls, an.l)) + an.pix * pick(g.lddc, an.l);
-            for (int c = g.nc + side; c < g.dcw; c += 4) dp[c] = from_f32<T>(0.f);
+            for (int c = g.nc + side; c < g.dcw; c += 4) map_row<T>(g.dcls, g.lddc, an)[c] = from_f32<T>(0.f);
         }
     }
     if (!GRAD) {
-        if (!live) s_box = s_cls = s_dfl = 0.f;
-        s_box = wave_sum(s_box);
-        s_cls = wave_sum(s_cls);
-        s_dfl = wave_sum(s_dfl);
-        if ((threadIdx.x & 63) == 0) {
-            sh[0][threadIdx.x >> 6] = s_box;
-            sh[1][threadIdx.x >> 6] = s_cls;
-            sh[2][threadIdx.x >> 6] = s_dfl;
+        if (!s.live) s_box = s_cls = s_dfl = 0.f;
+        float sum[3] = {s_box, s_cls, s_dfl};  // (gathered here: summed in an array from the start, the other product of the DFL term is fused)
+        block_combine<SumOp>(sum, sh);
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) part[(int64_t)blockIdx.x * 3 + k] = sum[k];
         }
-        __syncthreads();
-        if (threadIdx.x < 3) part[(int64_t)blockIdx.x * 3 + threadIdx.x] = (sh[threadIdx.x][0] + sh[threadIdx.x][1]) + (sh[threadIdx.x][2] + sh[threadIdx.x][3]);
     }
 }
 
 // ---- K8: fixed-order final sums: scal[0] = sum of target scores, loss[k] = sum_k / max(scal[0], 1) ------------
 // out_scale (optional, [6]): loss[k] = raw_k * out_scale[k] and loss[3 + k] = raw_k * out_scale[3 + k] - the criterion's two results
 // (loss * gains * batch for backward, loss * gains for logging: reference loss.py:250-255) without elementwise launches behind this one
+// (a 256-wide tree in double precision over any number of partial rows: not a block_combine)
 __global__ __launch_bounds__(256) void loss_final_kernel(const float* __restrict__ tss_part, int n_tss, const float* __restrict__ part, int n_part,
                                                          float* __restrict__ scal, float* __restrict__ loss, const float* __restrict__ out_scale) {
     __shared__ double sh[4][256];
@@ -597,6 +604,14 @@ __global__ __launch_bounds__(256) void loss_final_kernel(const float* __restrict
     }
 }
 
+// ---- host: grids, buffer layouts, geometry -----------------------------------------------------------------------------------------------
+// four lanes per anchor (decode_kernel, infer_decode_kernel, loss_kernel) / one thread per anchor, images along y (metric, assign, finalize)
+dim3 quad_grid(int64_t B, int64_t A) { return dim3((unsigned)((B * A * 4 + 255) / 256)); }
+dim3 anchor_grid(int64_t B, int64_t A) { return dim3((unsigned)((A + 255) / 256), (unsigned)B); }
+template <typename... P, typename... Q> void launch(void (*kernel)(P...), dim3 grid, hipStream_t s, Q... args) {
+    hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, args...);
+}
+
 struct Carve {
     char* p;
     size_t used;
@@ -607,22 +622,49 @@ struct Carve {
     }
 };
 
+// what the forward leaves for the backward; the size is the carve of a null base
 struct StateView {
     float *tgt, *wgt, *scal;
     int* lab;
+    size_t bytes;
 };
-static StateView carve_state(void* state, int64_t BA, size_t* bytes) {
+StateView carve_state(void* state, int64_t BA) {
     Carve c{reinterpret_cast<char*>(state), 0};
     StateView v;
     v.tgt = c.take<float>((size_t)BA * 4);
     v.wgt = c.take<float>((size_t)BA);
     v.lab = c.take<int>((size_t)BA);
     v.scal = c.take<float>(4);
-    *bytes = c.used;
+    v.bytes = c.used;
+    return v;
+}
+// the forward's scratch buffers, likewise
+struct WorkView {
+    float *pb, *ov, *al;  // predicted boxes [B, A, 4]; overlaps and alignment metric [B, G, A]
+    uint8_t* mpos;        // positive mask [B, G, A]
+    int* gidx;            // gt index per anchor [B, A]
+    float *pa, *po;       // per-gt max metric and max overlap [B, G]
+    float *tss_part, *part;  // partial sums: weights per finalize workgroup, (box, cls, dfl) per loss workgroup
+    size_t bytes;
+};
+WorkView carve_work(void* workspace, int64_t B, int64_t A, int64_t G) {
+    const int64_t BA = B * A, BGA = BA * G, BG = B * G;
+    Carve c{reinterpret_cast<char*>(workspace), 0};
+    WorkView v;
+    v.pb = c.take<float>((size_t)BA * 4);
+    v.ov = c.take<float>((size_t)BGA);
+    v.al = c.take<float>((size_t)BGA);
+    v.mpos = c.take<uint8_t>((size_t)BGA);
+    v.gidx = c.take<int>((size_t)BA);
+    v.pa = c.take<float>((size_t)BG);
+    v.po = c.take<float>((size_t)BG);
+    v.tss_part = c.take<float>((size_t)(BA / 256 + B + 1));
+    v.part = c.take<float>((size_t)(BA * 4 / 256 + 2) * 3);
+    v.bytes = c.used;
     return v;
 }
 
-static int fill_geom(LossGeom& g, int32_t nl, const ymi_tensor* box, const ymi_tensor* cls, const float* strides, int64_t G, const char* what) {
+int fill_geom(LossGeom& g, int32_t nl, const ymi_tensor* box, const ymi_tensor* cls, const float* strides, const char* what) {
     YMI_CHECK_ARG(nl >= 1 && nl <= LOSS_MAXL && box && cls && strides, "%s: 1..%d levels", what, LOSS_MAXL);
     g = LossGeom{};
     g.nl = nl;
@@ -648,9 +690,26 @@ static int fill_geom(LossGeom& g, int32_t nl, const ymi_tensor* box, const ymi_t
     for (int l = nl; l <= LOSS_MAXL; ++l) g.off[l] = off;
     g.B = (int)box[0].n;
     g.A = off;
-    g.G = (int)G;
     g.nc = (int)cls[0].c;
-    YMI_CHECK_ARG(G >= 1 && (int64_t)g.B * g.G * g.A < (1ll << 31), "%s: max_boxes >= 1 and B*G*A < 2^31", what);
+    YMI_CHECK_ARG((int64_t)g.B * g.A < (1ll << 31), "%s: B*A < 2^31", what);
+    return YMI_OK;
+}
+// the gradient maps of the backward: shaped as the maps; the class gradients may be wider (one width, dcw, for every level)
+int fill_grad_geom(LossGeom& g, const ymi_tensor* box, const ymi_tensor* cls, const ymi_tensor* dbox, const ymi_tensor* dcls, const char* what) {
+    YMI_CHECK_ARG(dbox && dcls && ymi_tensor_ok(&dcls[0]), "%s: gradient maps", what);
+    g.dcw = (int)dcls[0].c;
+    for (int l = 0; l < g.nl; ++l) {
+        const ymi_tensor &db = dbox[l], &dc = dcls[l], &cm = cls[l];
+        YMI_CHECK_ARG(ymi_tensor_ok(&db) && ymi_tensor_ok(&dc) && ymi_same_shape(&db, &box[l]) && dc.n == cm.n && dc.h == cm.h && dc.w == cm.w &&
+                          dc.c >= cm.c && dc.c == g.dcw && db.dtype == box[l].dtype && dc.dtype == cm.dtype,
+                      "%s: gradient map %d", what, l);
+        const int es = (int)ymi_esize(db.dtype);
+        YMI_CHECK_ARG(((uintptr_t)db.data % 16) == 0 && (db.ld * es) % 16 == 0, "%s: gradient map alignment", what);
+        g.dbox[l] = db.data;
+        g.dcls[l] = dc.data;
+        g.lddb[l] = db.ld;
+        g.lddc[l] = dc.ld;
+    }
     return YMI_OK;
 }
 }  // namespace
@@ -667,19 +726,8 @@ extern "C" int ymi_detect_targets(const float* batch_idx, const float* cls, cons
 
 extern "C" int ymi_detect_loss_sizes(int64_t batch, int64_t anchors, int64_t max_boxes, size_t* state_bytes, size_t* workspace_bytes) {
     YMI_CHECK_ARG(batch > 0 && anchors > 0 && max_boxes > 0 && state_bytes && workspace_bytes, "detect_loss_sizes: args");
-    const int64_t BA = batch * anchors, BGA = BA * max_boxes, BG = batch * max_boxes;
-    (void)carve_state(nullptr, BA, state_bytes);
-    Carve c{nullptr, 0};
-    c.take<float>((size_t)BA * 4);      // predicted boxes
-    c.take<float>((size_t)BGA);         // overlaps
-    c.take<float>((size_t)BGA);         // alignment metric
-    c.take<uint8_t>((size_t)BGA);       // positive mask
-    c.take<int>((size_t)BA);            // gt index per anchor
-    c.take<float>((size_t)BG);          // per-gt max metric
-    c.take<float>((size_t)BG);          // per-gt max overlap
-    c.take<float>((size_t)(BA / 256 + batch + 1));      // weight partial sums
-    c.take<float>((size_t)(BA * 4 / 256 + 2) * 3);      // loss partial sums
-    *workspace_bytes = c.used;
+    *state_bytes = carve_state(nullptr, batch * anchors).bytes;
+    *workspace_bytes = carve_work(nullptr, batch, anchors, max_boxes).bytes;
     return YMI_OK;
 }
 
@@ -687,43 +735,30 @@ extern "C" int ymi_detect_loss_fwd(int32_t nl, const ymi_tensor* box_maps, const
                                    int64_t max_boxes, int32_t topk, float alpha, float beta, const float* out_scale, float* loss_out, void* state,
                                    size_t state_bytes, void* workspace, size_t workspace_bytes, void* stream) {
     LossGeom g;
-    int rc = fill_geom(g, nl, box_maps, cls_maps, strides, max_boxes, "detect_loss_fwd");
+    int rc = fill_geom(g, nl, box_maps, cls_maps, strides, "detect_loss_fwd");
     if (rc) return rc;
+    g.G = (int)max_boxes;
+    YMI_CHECK_ARG(max_boxes >= 1 && (int64_t)g.B * g.G * g.A < (1ll << 31), "detect_loss_fwd: max_boxes >= 1 and B*G*A < 2^31");
     YMI_CHECK_ARG(targets && loss_out && state && workspace && topk >= 1, "detect_loss_fwd: null argument");
-    size_t need_s = 0, need_w = 0;
-    ymi_detect_loss_sizes(g.B, g.A, g.G, &need_s, &need_w);
-    if (state_bytes < need_s || workspace_bytes < need_w) {
-        ymi_set_error("detect_loss_fwd: state %zu < %zu or workspace %zu < %zu bytes", state_bytes, need_s, workspace_bytes, need_w);
+    const StateView st = carve_state(state, (int64_t)g.B * g.A);
+    const WorkView w = carve_work(workspace, g.B, g.A, g.G);
+    if (state_bytes < st.bytes || workspace_bytes < w.bytes) {
+        ymi_set_error("detect_loss_fwd: state %zu < %zu or workspace %zu < %zu bytes", state_bytes, st.bytes, workspace_bytes, w.bytes);
         return YMI_EWORKSPACE;
     }
-    const int64_t BA = (int64_t)g.B * g.A, BGA = BA * g.G, BG = (int64_t)g.B * g.G;
-    size_t sb;
-    StateView st = carve_state(state, BA, &sb);
-    Carve c{reinterpret_cast<char*>(workspace), 0};
-    float* pb = c.take<float>((size_t)BA * 4);
-    float* ov = c.take<float>((size_t)BGA);
-    float* al = c.take<float>((size_t)BGA);
-    uint8_t* mpos = c.take<uint8_t>((size_t)BGA);
-    int* gidx = c.take<int>((size_t)BA);
-    float* pa = c.take<float>((size_t)BG);
-    float* po = c.take<float>((size_t)BG);
-    float* tss_part = c.take<float>((size_t)(BA / 256 + g.B + 1));
-    float* part = c.take<float>((size_t)(BA * 4 / 256 + 2) * 3);
     hipStream_t s = (hipStream_t)stream;
-    const bool bf = box_maps[0].dtype == YMI_BF16;
-    const unsigned qblocks = (unsigned)((BA * 4 + 255) / 256);
-    const dim3 agrid((unsigned)((g.A + 255) / 256), (unsigned)g.B);
-    if (bf) hipLaunchKernelGGL(decode_kernel<bf16_t>, dim3(qblocks), dim3(256), 0, s, g, pb);
-    else hipLaunchKernelGGL(decode_kernel<float>, dim3(qblocks), dim3(256), 0, s, g, pb);
-    if (bf) hipLaunchKernelGGL(metric_kernel<bf16_t>, agrid, dim3(256), 0, s, g, targets, pb, ov, al, mpos, alpha, beta);
-    else hipLaunchKernelGGL(metric_kernel<float>, agrid, dim3(256), 0, s, g, targets, pb, ov, al, mpos, alpha, beta);
-    hipLaunchKernelGGL(topk_kernel, dim3((unsigned)BG), dim3(256), 0, s, g, targets, al, mpos, (int)topk);
-    hipLaunchKernelGGL(assign_kernel, agrid, dim3(256), 0, s, g, ov, mpos, gidx);
-    hipLaunchKernelGGL(posmax_kernel, dim3((unsigned)BG), dim3(256), 0, s, g, ov, al, gidx, pa, po);
-    hipLaunchKernelGGL(finalize_kernel, agrid, dim3(256), 0, s, g, targets, al, gidx, pa, po, st.tgt, st.wgt, st.lab, tss_part);
-    if (bf) hipLaunchKernelGGL((loss_kernel<bf16_t, false>), dim3(qblocks), dim3(256), 0, s, g, st.tgt, st.wgt, st.lab, st.scal, nullptr, nullptr, part);
-    else hipLaunchKernelGGL((loss_kernel<float, false>), dim3(qblocks), dim3(256), 0, s, g, st.tgt, st.wgt, st.lab, st.scal, nullptr, nullptr, part);
-    hipLaunchKernelGGL(loss_final_kernel, dim3(1), dim3(256), 0, s, tss_part, (int)(agrid.x * agrid.y), part, (int)qblocks, st.scal, loss_out, out_scale);
+    const dim3 qgrid = quad_grid(g.B, g.A), agrid = anchor_grid(g.B, g.A), ggrid((unsigned)(g.B * g.G));
+    dispatch_dtype(box_maps[0].dtype, [&](auto t) {
+        typedef typename decltype(t)::type T;
+        launch(decode_kernel<T>, qgrid, s, g, w.pb);
+        launch(metric_kernel<T>, agrid, s, g, targets, w.pb, w.ov, w.al, w.mpos, alpha, beta);
+        launch(topk_kernel, ggrid, s, g, targets, w.al, w.mpos, (int)topk);
+        launch(assign_kernel, agrid, s, g, w.ov, w.mpos, w.gidx);
+        launch(posmax_kernel, ggrid, s, g, w.ov, w.al, w.gidx, w.pa, w.po);
+        launch(finalize_kernel, agrid, s, g, targets, w.al, w.gidx, w.pa, w.po, st.tgt, st.wgt, st.lab, w.tss_part);
+        launch(loss_kernel<T, false>, qgrid, s, g, st.tgt, st.wgt, st.lab, st.scal, nullptr, nullptr, w.part);
+        launch(loss_final_kernel, dim3(1), s, w.tss_part, (int)(agrid.x * agrid.y), w.part, (int)qgrid.x, st.scal, loss_out, out_scale);
+    });
     YMI_CHECK_LAUNCH("detect_loss_fwd");
     return YMI_OK;
 }
@@ -732,45 +767,27 @@ extern "C" int ymi_detect_loss_bwd(int32_t nl, const ymi_tensor* box_maps, const
                                    size_t state_bytes, const float* grad_loss, const float* grad_scale, const ymi_tensor* dbox_maps, const ymi_tensor* dcls_maps,
                                    void* stream) {
     LossGeom g;
-    int rc = fill_geom(g, nl, box_maps, cls_maps, strides, 1, "detect_loss_bwd");
+    int rc = fill_geom(g, nl, box_maps, cls_maps, strides, "detect_loss_bwd");
     if (rc) return rc;
     YMI_CHECK_ARG(state && grad_loss && dbox_maps && dcls_maps, "detect_loss_bwd: null argument");
-    const int64_t BA = (int64_t)g.B * g.A;
-    size_t sb;
-    StateView st = carve_state(const_cast<void*>(state), BA, &sb);
-    YMI_CHECK_ARG(state_bytes >= sb, "detect_loss_bwd: state too small");
-    for (int l = 0; l < nl; ++l) {
-        const ymi_tensor &dc = dcls_maps[l], &cm = cls_maps[l];
-        YMI_CHECK_ARG(ymi_tensor_ok(&dbox_maps[l]) && ymi_tensor_ok(&dc) && ymi_same_shape(&dbox_maps[l], &box_maps[l]) && dc.n == cm.n && dc.h == cm.h &&
-                          dc.w == cm.w && dc.c >= cm.c && dc.c == dcls_maps[0].c && dbox_maps[l].dtype == box_maps[l].dtype && dc.dtype == cm.dtype,
-                      "detect_loss_bwd: gradient map %d", l);
-        const int es = (int)ymi_esize(dbox_maps[l].dtype);
-        YMI_CHECK_ARG(((uintptr_t)dbox_maps[l].data % 16) == 0 && (dbox_maps[l].ld * es) % 16 == 0, "detect_loss_bwd: gradient map alignment");
-        g.dbox[l] = dbox_maps[l].data;
-        g.dcls[l] = dcls_maps[l].data;
-        g.dcw = (int)dcls_maps[l].c;
-        g.lddb[l] = dbox_maps[l].ld;
-        g.lddc[l] = dcls_maps[l].ld;
-    }
-    const unsigned qblocks = (unsigned)((BA * 4 + 255) / 256);
-    hipStream_t s = (hipStream_t)stream;
-    if (box_maps[0].dtype == YMI_BF16)
-        hipLaunchKernelGGL((loss_kernel<bf16_t, true>), dim3(qblocks), dim3(256), 0, s, g, st.tgt, st.wgt, st.lab, st.scal, grad_loss, grad_scale, nullptr);
-    else
-        hipLaunchKernelGGL((loss_kernel<float, true>), dim3(qblocks), dim3(256), 0, s, g, st.tgt, st.wgt, st.lab, st.scal, grad_loss, grad_scale, nullptr);
+    const StateView st = carve_state(const_cast<void*>(state), (int64_t)g.B * g.A);
+    YMI_CHECK_ARG(state_bytes >= st.bytes, "detect_loss_bwd: state too small");
+    rc = fill_grad_geom(g, box_maps, cls_maps, dbox_maps, dcls_maps, "detect_loss_bwd");
+    if (rc) return rc;
+    dispatch_dtype(box_maps[0].dtype, [&](auto t) {
+        launch(loss_kernel<typename decltype(t)::type, true>, quad_grid(g.B, g.A), (hipStream_t)stream, g, st.tgt, st.wgt, st.lab, st.scal, grad_loss,
+               grad_scale, nullptr);
+    });
     YMI_CHECK_LAUNCH("detect_loss_bwd");
     return YMI_OK;
 }
 
 extern "C" int ymi_detect_decode(int32_t nl, const ymi_tensor* box_maps, const ymi_tensor* cls_maps, const float* strides, float* y, void* stream) {
     LossGeom g;
-    int rc = fill_geom(g, nl, box_maps, cls_maps, strides, 1, "detect_decode");
+    int rc = fill_geom(g, nl, box_maps, cls_maps, strides, "detect_decode");
     if (rc) return rc;
     YMI_CHECK_ARG(y, "detect_decode: null output");
-    const int64_t BA = (int64_t)g.B * g.A;
-    const unsigned qblocks = (unsigned)((BA * 4 + 255) / 256);
-    if (box_maps[0].dtype == YMI_BF16) hipLaunchKernelGGL(infer_decode_kernel<bf16_t>, dim3(qblocks), dim3(256), 0, (hipStream_t)stream, g, y);
-    else hipLaunchKernelGGL(infer_decode_kernel<float>, dim3(qblocks), dim3(256), 0, (hipStream_t)stream, g, y);
+    dispatch_dtype(box_maps[0].dtype, [&](auto t) { launch(infer_decode_kernel<typename decltype(t)::type>, quad_grid(g.B, g.A), (hipStream_t)stream, g, y); });
     YMI_CHECK_LAUNCH("detect_decode");
     return YMI_OK;
 }

@@ -371,6 +371,32 @@ def test_hip_loss_vs_oracle_random_batches(nb, nc):
         torch.testing.assert_close(x.grad.cpu(), y.grad, rtol=2e-3, atol=2e-5)
 
 
+def test_hip_loss_vs_oracle_topk_row_in_memory():
+    """12,096 anchors (96 / 48 / 24 maps): more than the 10,240 metric values a top-k workgroup keeps in registers, so every selection
+    round scans the gt's row in memory (the path of 1280 x 1280 images).  Every gt has at least 156 anchors of positive metric and the
+    eleven largest metrics of a gt are at least 5.6e-4 apart relatively, so the selected set depends neither on tie order nor on
+    rounding; comparison and tolerances as in test_hip_loss_vs_oracle_random_batches."""
+    crit, ocrit = _product_crit(3), _oracle_crit(3)
+    g = torch.Generator().manual_seed(22)
+    preds = [torch.randn(2, 67, s, s, generator=g) for s in (96, 48, 24)]
+    counts = [7, 3]  # labels per image
+    n = sum(counts)
+    bi = torch.cat([torch.full((c,), float(i)) for i, c in enumerate(counts)])
+    boxes = torch.cat((torch.rand(n, 2, generator=g) * 0.6 + 0.2, torch.rand(n, 2, generator=g) * 0.3 + 0.05), 1)
+    cls = torch.randint(0, 3, (n, 1), generator=g).float()
+    batch = {"batch_idx": bi, "cls": cls, "bboxes": boxes}
+    pg = [p.clone().to(dev()).requires_grad_(True) for p in preds]
+    po = [p.clone().requires_grad_(True) for p in preds]
+    a, ia = crit(pg, {k: v.to(dev()) for k, v in batch.items()})
+    b, ib = ocrit(po, batch)
+    torch.testing.assert_close(a.cpu(), b, rtol=2e-4, atol=2e-5)
+    torch.testing.assert_close(ia.cpu(), ib, rtol=2e-4, atol=2e-5)
+    a.sum().backward()
+    b.sum().backward()
+    for x, y in zip(pg, po):
+        torch.testing.assert_close(x.grad.cpu(), y.grad, rtol=2e-3, atol=2e-5)
+
+
 def test_hip_loss_bf16_maps_and_max_boxes_hint():
     """bf16 maps (the training dtype): same loss as on the f32 copy of the same bf16 values; a max_boxes hint larger
     than needed changes nothing (the extra slots are padding rows)."""
