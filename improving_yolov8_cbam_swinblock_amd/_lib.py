@@ -133,6 +133,14 @@ _SIGNATURES = {
                                      _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
     "ymi_detect_loss_bwd": (_c_i32, [_c_i32, _TP, _TP, ctypes.POINTER(ctypes.c_float), _vp, _sz, _vp, _vp, _TP, _TP, _vp]),
     "ymi_detect_decode": (_c_i32, [_c_i32, _TP, _TP, ctypes.POINTER(ctypes.c_float), _vp, _vp]),
+    "ymi_depth_to_space2": (_c_i32, [_TP, _TP, _vp]),
+    "ymi_space_to_depth2": (_c_i32, [_TP, _TP, _vp]),
+    "ymi_detect_loss_fwd_assign": (_c_i32, [_c_i32, _TP, _TP, ctypes.POINTER(ctypes.c_float), _vp, _c_i64, _c_i32, ctypes.c_float, ctypes.c_float,
+                                            _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
+    "ymi_detect_decode_seg": (_c_i32, [_c_i32, _TP, _TP, _TP, ctypes.POINTER(ctypes.c_float), _vp, _vp]),
+    "ymi_mask_loss_sizes": (_c_i32, [_c_i64, _c_i64, _c_i64, _c_i32, ctypes.POINTER(ctypes.c_size_t)]),
+    "ymi_mask_loss_fwd": (_c_i32, [_c_i32, _TP, _TP, _vp, _c_i32, _c_i64, _c_i64, _vp, _vp, _c_i64, _c_i32, _c_f32, _c_f32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ymi_mask_loss_bwd": (_c_i32, [_c_i32, _TP, _TP, _vp, _c_i32, _c_i64, _c_i64, _c_i64, _c_i32, _vp, _sz, _vp, _vp, _TP, _TP, _vp]),
     "ymi_detect_nms_sizes": (_c_i32, [_c_i64, _c_i64, _c_i64, _c_i64, _c_i64, ctypes.POINTER(ctypes.c_size_t)]),
     "ymi_detect_nms": (_c_i32, [_vp, _c_i64, _c_i64, _c_i64, _c_f32, _c_f32, _c_i32, _c_i32, ctypes.POINTER(_c_i32), _c_i32, _c_i64, _c_i64, _c_f32,
                                 _vp, _vp, _vp, _sz, _vp]),

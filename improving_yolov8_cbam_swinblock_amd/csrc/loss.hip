@@ -327,6 +327,31 @@ __global__ __launch_bounds__(256) void infer_decode_kernel(LossGeom g, float* __
     for (int c = s.side; c < g.nc; c += 4) yo[(int64_t)(4 + c) * g.A] = 1.0f / (1.0f + expf(-to_f32(cp[c])));
 }
 
+// ... and Segment's (head.py:186-208): rows 4 + nc .. of y are the anchor's nm mask coefficients, copied as they are.  MaskMaps: the per-level
+// coefficient maps [B, H, W, nm]
+struct MaskMaps {
+    const void* mc[LOSS_MAXL];
+    int64_t ld[LOSS_MAXL];
+    int nm;
+};
+template <typename T>
+__global__ __launch_bounds__(256) void infer_decode_seg_kernel(LossGeom g, MaskMaps mm, float* __restrict__ y) {
+    Side s;
+    float x[REG], p[REG];
+    side_of<T>(g, s, x, p);
+    if (!s.live) return;
+    float* yo = y + (int64_t)s.b * (4 + g.nc + mm.nm) * g.A + s.a;
+    float xyxy[4], box[4];
+    pred_box(s.an, s.d, xyxy);
+    xywh_scaled(xyxy, s.an.s, box);
+    yo[(int64_t)s.side * g.A] = s.side == 0 ? box[0] : s.side == 1 ? box[1] : s.side == 2 ? box[2] : box[3];
+    const T* cp = map_row<const T>(g.cls, g.ldc, s.an);
+    for (int c = s.side; c < g.nc; c += 4) yo[(int64_t)(4 + c) * g.A] = 1.0f / (1.0f + expf(-to_f32(cp[c])));
+    const MaskMaps& cm = mm;
+    const T* mp = map_row<const T>(cm.mc, cm.ld, s.an);
+    for (int c = s.side; c < mm.nm; c += 4) yo[(int64_t)(4 + g.nc + c) * g.A] = to_f32(mp[c]);
+}
+
 // ---- K2: alignment metric and overlaps for every (image, gt, anchor) (tal.py:118-160) -------------------------
 template <typename T>
 __global__ __launch_bounds__(256) void metric_kernel(LossGeom g, const float* __restrict__ targets, const float* __restrict__ pb,
@@ -731,9 +756,11 @@ extern "C" int ymi_detect_loss_sizes(int64_t batch, int64_t anchors, int64_t max
     return YMI_OK;
 }
 
-extern "C" int ymi_detect_loss_fwd(int32_t nl, const ymi_tensor* box_maps, const ymi_tensor* cls_maps, const float* strides, const float* targets,
-                                   int64_t max_boxes, int32_t topk, float alpha, float beta, const float* out_scale, float* loss_out, void* state,
-                                   size_t state_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+// gidx_out (optional, [B, A] int32): the assignment's gt index per anchor (-1: background) is written there instead of into the workspace,
+// for a stage that follows the detection loss (the mask loss of seg.hip); everything computed is the same
+extern "C" int ymi_detect_loss_fwd_assign(int32_t nl, const ymi_tensor* box_maps, const ymi_tensor* cls_maps, const float* strides, const float* targets,
+                                          int64_t max_boxes, int32_t topk, float alpha, float beta, const float* out_scale, float* loss_out, void* state,
+                                          size_t state_bytes, void* workspace, size_t workspace_bytes, int32_t* gidx_out, void* stream) {
     LossGeom g;
     int rc = fill_geom(g, nl, box_maps, cls_maps, strides, "detect_loss_fwd");
     if (rc) return rc;
@@ -741,7 +768,8 @@ extern "C" int ymi_detect_loss_fwd(int32_t nl, const ymi_tensor* box_maps, const
     YMI_CHECK_ARG(max_boxes >= 1 && (int64_t)g.B * g.G * g.A < (1ll << 31), "detect_loss_fwd: max_boxes >= 1 and B*G*A < 2^31");
     YMI_CHECK_ARG(targets && loss_out && state && workspace && topk >= 1, "detect_loss_fwd: null argument");
     const StateView st = carve_state(state, (int64_t)g.B * g.A);
-    const WorkView w = carve_work(workspace, g.B, g.A, g.G);
+    WorkView w = carve_work(workspace, g.B, g.A, g.G);
+    if (gidx_out) w.gidx = gidx_out;
     if (state_bytes < st.bytes || workspace_bytes < w.bytes) {
         ymi_set_error("detect_loss_fwd: state %zu < %zu or workspace %zu < %zu bytes", state_bytes, st.bytes, workspace_bytes, w.bytes);
         return YMI_EWORKSPACE;
@@ -761,6 +789,13 @@ extern "C" int ymi_detect_loss_fwd(int32_t nl, const ymi_tensor* box_maps, const
     });
     YMI_CHECK_LAUNCH("detect_loss_fwd");
     return YMI_OK;
+}
+
+extern "C" int ymi_detect_loss_fwd(int32_t nl, const ymi_tensor* box_maps, const ymi_tensor* cls_maps, const float* strides, const float* targets,
+                                   int64_t max_boxes, int32_t topk, float alpha, float beta, const float* out_scale, float* loss_out, void* state,
+                                   size_t state_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+    return ymi_detect_loss_fwd_assign(nl, box_maps, cls_maps, strides, targets, max_boxes, topk, alpha, beta, out_scale, loss_out, state, state_bytes,
+                                      workspace, workspace_bytes, nullptr, stream);
 }
 
 extern "C" int ymi_detect_loss_bwd(int32_t nl, const ymi_tensor* box_maps, const ymi_tensor* cls_maps, const float* strides, const void* state,
@@ -789,5 +824,26 @@ extern "C" int ymi_detect_decode(int32_t nl, const ymi_tensor* box_maps, const y
     YMI_CHECK_ARG(y, "detect_decode: null output");
     dispatch_dtype(box_maps[0].dtype, [&](auto t) { launch(infer_decode_kernel<typename decltype(t)::type>, quad_grid(g.B, g.A), (hipStream_t)stream, g, y); });
     YMI_CHECK_LAUNCH("detect_decode");
+    return YMI_OK;
+}
+
+extern "C" int ymi_detect_decode_seg(int32_t nl, const ymi_tensor* box_maps, const ymi_tensor* cls_maps, const ymi_tensor* mc_maps, const float* strides,
+                                     float* y, void* stream) {
+    LossGeom g;
+    int rc = fill_geom(g, nl, box_maps, cls_maps, strides, "detect_decode_seg");
+    if (rc) return rc;
+    YMI_CHECK_ARG(y && mc_maps, "detect_decode_seg: null argument");
+    MaskMaps mm{};
+    mm.nm = (int)mc_maps[0].c;
+    for (int l = 0; l < nl; ++l) {
+        const ymi_tensor& m = mc_maps[l];
+        YMI_CHECK_ARG(ymi_tensor_ok(&m) && m.n == box_maps[l].n && m.h == box_maps[l].h && m.w == box_maps[l].w && m.c == mm.nm && m.dtype == box_maps[0].dtype,
+                      "detect_decode_seg: coefficient map %d", l);
+        mm.mc[l] = m.data;
+        mm.ld[l] = m.ld;
+    }
+    dispatch_dtype(box_maps[0].dtype,
+                   [&](auto t) { launch(infer_decode_seg_kernel<typename decltype(t)::type>, quad_grid(g.B, g.A), (hipStream_t)stream, g, mm, y); });
+    YMI_CHECK_LAUNCH("detect_decode_seg");
     return YMI_OK;
 }

@@ -18,6 +18,10 @@ class DetectionPredictor:
 
     def __init__(self, model, imgsz=640, conf=0.25, iou=0.7, classes=None, agnostic_nms=False, max_det=300, batch=32, dtype=torch.bfloat16,
                  augment=False, rect=False):
+        layers = getattr(model, "model", None)
+        if layers is not None and getattr(layers[-1], "nm", 0):
+            raise NotImplementedError("DetectionPredictor on a SegmentationModel: NMS rows with mask coefficients and process_mask are not built "
+                                      "(README, Segmentation); the model's eval forward gives the decoded [B, 4 + nc + nm, A] rows and the prototypes")
         self.model = model
         self.imgsz = (int(imgsz), int(imgsz)) if isinstance(imgsz, int) else (int(imgsz[0]), int(imgsz[1]))
         self.conf, self.iou, self.classes, self.agnostic_nms, self.max_det = conf, iou, classes, agnostic_nms, max_det

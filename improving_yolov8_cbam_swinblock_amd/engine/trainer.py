@@ -12,6 +12,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib, ops
+from ..nn.modules.head import Segment
 from .ddp import GradientBuckets
 from .optim import FlatFold, FusedAdamax, FusedAdamW, FusedNAdam, FusedRAdam, FusedRMSprop, FusedSGD, ModelEMA
 
@@ -65,6 +66,22 @@ def synthetic_batch(batch, imgsz, device, seed, boxes_per_image=4):
         "bboxes": torch.cat((ctr, wh), 1).to(device),
         "max_boxes": boxes_per_image,
     }
+
+
+def synthetic_seg_batch(batch, imgsz, device, seed, boxes_per_image=4):
+    """synthetic_batch with "masks": the overlap encoding [B, imgsz / 4, imgsz / 4] uint8 of an ellipse inscribed in every box (pixel value =
+    1 + index of the box among its image's labels, later boxes on top) - the batch a SegmentationModel trains on."""
+    out = synthetic_batch(batch, imgsz, device, seed, boxes_per_image)
+    m = imgsz // 4
+    c = (torch.arange(m, dtype=torch.float32, device=device) + 0.5) / m
+    boxes = out["bboxes"].view(batch, boxes_per_image, 4)
+    masks = torch.zeros(batch, m, m, dtype=torch.uint8, device=device)
+    for k in range(boxes_per_image):
+        cx, cy, bw, bh = (boxes[:, k, i].view(batch, 1, 1) for i in range(4))
+        inside = ((c.view(1, 1, m) - cx) / (bw / 2)) ** 2 + ((c.view(1, m, 1) - cy) / (bh / 2)) ** 2 <= 1.0
+        masks[inside] = k + 1
+    out["masks"] = masks
+    return out
 
 
 def preprocess_batch(batch, imgsz, stride, multi_scale=False, rng=random, device=None):
@@ -186,6 +203,11 @@ class TrainStep:
         self.ema = ModelEMA(model) if ema is True else (ema or None)
         self.opt = build_optimizer(model, name=optimizer, lr=lr, momentum=momentum, decay=decay, ema=self.ema)
         self.use_graph = bool(graph)
+        self.segment = isinstance(model.model[-1], Segment)
+        if self.segment and (world_size != 1 or graph == "tail"):
+            # (built and tested: eager, graph=True and graph="split" on one rank)
+            raise NotImplementedError('TrainStep on a SegmentationModel is built for one rank, eager, graph=True or graph="split": '
+                                      f"world_size={world_size}, graph={graph!r} is not")
         self.full_graph = self.use_graph and world_size == 1 and graph not in ("split", "tail")
         self.overlap_graphs = self.use_graph and not self.full_graph and graph != "tail"
         self.params = [p for p in model.parameters() if p.requires_grad]
@@ -259,6 +281,8 @@ class TrainStep:
         reading tensors nobody fills any more.  Only the image may change shape: labels and max_boxes are static across all shapes."""
         if batch.get("max_boxes") is None:
             raise ValueError("graph=True needs batch['max_boxes'] (static target shape)")
+        if self.segment and not (torch.is_tensor(batch.get("masks")) and batch["masks"].is_cuda):
+            raise ValueError("graph=True on a SegmentationModel needs batch['masks'] on the device: it is a static input of the captured graph")
         key = tuple(batch["img"].shape)
         first = next(iter(self._shapes.values()), None)
         # image_shapes == 1: the one record takes every batch - another image shape fails the static-shape check like any other tensor
@@ -356,6 +380,8 @@ class TrainStep:
 
     # ---- gradient accumulation (reference trainer.py:305,397) ------------------------------------------------------------------------
     def _accumulating_call(self, batch, update):
+        if self.segment:
+            raise NotImplementedError("gradient accumulation (update=False) is not built for a SegmentationModel")
         if not update:
             if self.use_graph and not (self.full_graph or self.overlap_graphs):
                 raise ValueError('update=False is not supported with graph="tail": gradient accumulation needs eager mode, graph=True or graph="split"')
@@ -537,8 +563,8 @@ class TrainStep:
         self.model.train()
         with torch.autocast("cuda", dtype=self.dtype, enabled=self.dtype != torch.float32):
             loss, items = self.model(batch)
-        if self._seed is None or self._seed.device != loss.device:
-            self._seed = torch.full((3,), float(self.world), dtype=torch.float32, device=loss.device)
+        if self._seed is None or self._seed.device != loss.device or self._seed.numel() != loss.numel():  # ([3] detection, [4] segmentation)
+            self._seed = torch.full((loss.numel(),), float(self.world), dtype=torch.float32, device=loss.device)
         return loss, items
 
     @contextlib.contextmanager

@@ -36,6 +36,8 @@ class DetectionValidator:
                  loss=False):
         if match not in ("device", "host"):
             raise ValueError(f"match is 'device' or 'host', got {match!r}")
+        if getattr(model.model[-1], "nm", 0):
+            raise NotImplementedError("DetectionValidator on a SegmentationModel: NMS rows with mask coefficients and mask mAP are not built (README, Segmentation)")
         self.model = model
         self.augment = bool(augment)  # test-time augmentation: the forward is model.predict(img, augment=True) (reference engine/validator.py:214)
         self.conf, self.iou, self.max_det = conf, iou, max_det

@@ -295,3 +295,29 @@ class C2PSA(nn.Module):
             b = m(b)
         y = ops.concat([a, b])
         return self.cv2(y, out=out)
+
+
+class _Up2x2(nn.ConvTranspose2d):
+    """Proto's transposed convolution: an nn.ConvTranspose2d (same state-dict keys, weight [c1, c2, 2, 2]) whose forward is the MFMA 1x1 GEMM
+    with the weight viewed as [4 * c2, c1], followed by the depth-to-space kernel (ops.conv_transpose2x2)."""
+
+    def forward(self, x):
+        x = ops.to_internal(x)
+        if not ops.conv_transpose2x2_ok(self, x.dtype):
+            raise NotImplementedError(f"ConvTranspose2d({self.in_channels}, {self.out_channels}, {self.kernel_size}, {self.stride}) in {x.dtype}: built for "
+                                      f"kernel 2, stride 2, no padding and channel counts in whole 16-byte chunks (multiples of {ops.chunk_elems(x.dtype)})")
+        return ops.conv_transpose2x2(x, self.weight, self.bias)
+
+
+class Proto(nn.Module):
+    """mask prototypes: Conv 3x3 -> ConvTranspose2d 2x2 stride 2 -> Conv 3x3 -> Conv 1x1 (reference block.py:80-100)."""
+
+    def __init__(self, c1, c_=256, c2=32):
+        super().__init__()
+        self.cv1 = Conv(c1, c_, k=3)
+        self.upsample = _Up2x2(c_, c_, 2, 2, 0, bias=True)
+        self.cv2 = Conv(c_, c_, k=3)
+        self.cv3 = Conv(c_, c2)
+
+    def forward(self, x):
+        return self.cv3(self.cv2(self.upsample(self.cv1(x))))

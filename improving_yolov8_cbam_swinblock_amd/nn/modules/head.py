@@ -6,7 +6,7 @@ import torch
 import torch.nn as nn
 
 from ... import ops
-from .block import DFL
+from .block import DFL, Proto
 from .conv import Conv, DWConv
 
 
@@ -146,14 +146,66 @@ class Detect(nn.Module):
             maps = [ops.to_internal(t) for t in box]
             box = [t[:, : self.reg_max * 4].contiguous(memory_format=torch.channels_last) for t in maps]
             cls = [t[:, self.reg_max * 4 :].contiguous(memory_format=torch.channels_last) for t in maps]
-        key = (self.stride.data_ptr(), self.stride._version, self.stride.device)  # re-read after `stride` is assigned, edited or moved
+        return ops.detect_decode(box, cls, self._strides())
+
+    def _strides(self):
+        """host copy of `stride`, re-read after it is assigned, edited or moved (one device->host read, not one per call)."""
+        key = (self.stride.data_ptr(), self.stride._version, self.stride.device)
         if getattr(self, "_stride_key", None) != key:
-            self._stride_host = [float(s) for s in self.stride]  # one device->host read, not one per call
+            self._stride_host = [float(s) for s in self.stride]
             self._stride_key = key
-        return ops.detect_decode(box, cls, self._stride_host)
+        return self._stride_host
 
     def bias_init(self):
         """reference head.py:144-155."""
         for a, b, s in zip(self.cv2, self.cv3, self.stride):
             a[-1].bias.data[:] = 1.0
             b[-1].bias.data[: self.nc] = math.log(5 / self.nc / (640 / s) ** 2)
+
+
+class SegPreds:
+    """train-mode Segment output for the loss, nothing concatenated: box[i] [B, 64, H, W], cls[i] [B, nc, H, W], mc[i] [B, nm, H, W] (the NHWC
+    maps the convolutions wrote) and the prototype map proto [B, nm, 4H0, 4W0 / 2]."""
+
+    def __init__(self, box, cls, mc, proto):
+        self.box, self.cls, self.mc, self.proto = box, cls, mc, proto
+
+
+class Segment(Detect):
+    """Detect plus mask prototypes (proto) and per-anchor mask coefficients (cv4): reference head.py:186-208.
+    train -> (feats, mc [B, nm, A], p); eval -> (cat([y, mc], 1) [B, 4 + nc + nm, A], (feats, mc, p))."""
+
+    def __init__(self, nc=80, nm=32, npr=256, ch=()):
+        super().__init__(nc, ch)
+        self.nm = nm
+        self.npr = npr
+        self.proto = Proto(ch[0], self.npr, self.nm)
+        c4 = max(ch[0] // 4, self.nm)
+        self.cv4 = nn.ModuleList(nn.Sequential(Conv(x, c4, 3), Conv(c4, c4, 3), _Out1x1(c4, self.nm, 1)) for x in ch)
+
+    def _mask_maps(self, x):
+        """-> (prototype map, [coefficient map of each level]); cv4 runs level by level."""
+        return self.proto(x[0]), [self._branch(self.cv4[i], ops.to_internal(x[i])) for i in range(self.nl)]
+
+    def forward(self, x):
+        x = list(x)
+        p, mcs = self._mask_maps(x)
+        bs = p.shape[0]
+        mc = torch.cat([m.reshape(bs, self.nm, -1) for m in mcs], 2)
+        box, cls = self._maps(x)
+        for i in range(self.nl):
+            x[i] = ops.concat([box[i], cls[i]])
+        if self.training:
+            return x, mc, p
+        if self.reg_max != 16:
+            raise NotImplementedError("the decode kernel is built for reg_max = 16")
+        y = ops.detect_decode_seg(box, cls, mcs, self._strides())  # box decode, class sigmoid and the coefficient rows in one launch
+        self.shape = x[0].shape
+        return y if self.export else (y, (x, mc, p))
+
+    def forward_split(self, x):
+        """train-mode maps without any concat, for v8SegmentationLoss: -> SegPreds."""
+        x = list(x)
+        p, mcs = self._mask_maps(x)
+        box, cls = self._maps(x)
+        return SegPreds(box, cls, mcs, p)

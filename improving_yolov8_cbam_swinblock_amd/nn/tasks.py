@@ -16,10 +16,10 @@ import torch.nn as nn
 import yaml
 
 from .. import ops
-from ..utils.loss import DEFAULT_HYP, SplitPreds, v8DetectionLoss
+from ..utils.loss import DEFAULT_HYP, SplitPreds, v8DetectionLoss, v8SegmentationLoss
 from ..utils.ops import make_divisible
 from ..utils.torch_utils import fuse_conv_and_bn, initialize_weights, intersect_dicts
-from .modules import C2f, C2PSA, C3, C3k2, CBAM, PSA, SPPF, Bottleneck, C3Ghost, Concat, Conv, Detect, DWConv, GhostBottleneck, GhostConv, SwinBlock, Upsample
+from .modules import C2f, C2PSA, C3, C3k2, CBAM, PSA, SPPF, Bottleneck, C3Ghost, Concat, Conv, Detect, DWConv, GhostBottleneck, GhostConv, Segment, SwinBlock, Upsample
 
 CFG_DIR = Path(__file__).resolve().parents[1] / "cfg" / "models" / "v8"
 CFG_DIRS = (CFG_DIR, CFG_DIR.parent / "11")  # bare YAML names are looked up here, in this order
@@ -42,10 +42,25 @@ MODULES = {
     "SwinBlock": SwinBlock,
     "Concat": Concat,
     "Detect": Detect,
+    "Segment": Segment,
     "nn.Upsample": Upsample,  # the YAML's torch.nn.Upsample row runs as the HIP nearest-2x kernel
 }
 BASE_MODULES = frozenset({Conv, C2f, SPPF, Bottleneck, DWConv, GhostConv, GhostBottleneck, C3, C3Ghost, C3k2, C2PSA, PSA})  # width-scaled (c1, c2, ...) constructors: tasks.py:1376-1413
 REPEAT_MODULES = frozenset({C2f, C3, C3Ghost, C3k2, C2PSA})  # repeats passed as an argument: tasks.py:1414-1432
+
+
+def srcs_of(m):
+    """absolute indices of the layers module m reads."""
+    return [m.i - 1 if j == -1 else j for j in ([m.f] if isinstance(m.f, int) else m.f)]
+
+
+def _head_reads(m, first):
+    """convolutions of a Detect / Segment head that read one of its inputs: the box and class branches (ONE convolution when the sibling
+    first convolutions run as a pair), Segment's coefficient branch cv4 and, on the first input, its Proto."""
+    n = 1 if m.pair_ok else 2
+    if isinstance(m, Segment):
+        n += 2 if first else 1
+    return n
 
 
 def guess_model_scale(model_path):
@@ -117,14 +132,16 @@ def parse_model(d, ch, verbose=False):
                     args[3] = True
         elif m is Concat:
             c2 = sum(ch[x] for x in f)
-        elif m is Detect:
+        elif m in (Detect, Segment):
             args.append([ch[x] for x in f])
+            if m is Segment:  # the prototype width is width-scaled (tasks.py:1482-1488)
+                args[2] = make_divisible(min(args[2], max_channels) * width, 8)
             m.legacy = legacy  # read by the constructor below; v8 YAMLs have no C3k2 row and keep True (tasks.py:1355,1457-1465,1488)
         else:  # CBAM, SwinBlock, Upsample: arguments untouched, channels pass through (tasks.py:1503-1504)
             c2 = ch[f]
         m_ = nn.Sequential(*(m(*args) for _ in range(n))) if n > 1 else m(*args)
-        if m is Detect:  # (the instance keeps its branch) the class default goes back to the v8 one for Detects built outside parse_model
-            Detect.legacy = True
+        if m in (Detect, Segment):  # (the instance keeps its branch) the class default goes back to the v8 one for heads built outside parse_model
+            m.legacy = True
         t = str(m)[8:-2].replace("__main__.", "")
         m_.np = sum(x.numel() for x in m_.parameters())
         m_.i, m_.f, m_.type = i, f, t
@@ -177,7 +194,7 @@ class BaseModel(nn.Module):
                 if leaf_of and m.i >= nb_layers:  # a head layer: boundary tensors are read through their detached leaves
                     x = [leaf_of.get(id(t), t) for t in x] if isinstance(x, list) else leaf_of.get(id(x), x)
                 if split_head and isinstance(m, Detect):
-                    return SplitPreds(*m.forward_split(x))
+                    return m.forward_split(x) if isinstance(m, Segment) else SplitPreds(*m.forward_split(x))
                 if plan is None:
                     x = m(x)
                 elif isinstance(m, Concat):
@@ -218,7 +235,7 @@ class BaseModel(nn.Module):
                 for j in ([m.f] if isinstance(m.f, int) else m.f):
                     j = m.i - 1 if j == -1 else j
                     if j < nb:
-                        out[j] = out.get(j, 0) + (2 if (isinstance(m, Detect) and not m.pair_ok) else 1)
+                        out[j] = out.get(j, 0) + (_head_reads(m, j == srcs_of(m)[0]) if isinstance(m, Detect) else 1)
         return dict(sorted(out.items()))  # {boundary layer: number of head consumers of its output}
 
     def _graph_plan(self):
@@ -241,7 +258,7 @@ class BaseModel(nn.Module):
                 if j < 0:
                     continue
                 # Detect reads each input with two branches - as ONE convolution when its sibling first convolutions run as a pair
-                consumers[j] = consumers.get(j, 0) + ((1 if m.pair_ok else 2) if isinstance(m, Detect) else 1)
+                consumers[j] = consumers.get(j, 0) + (_head_reads(m, j == srcs[m.i][0]) if isinstance(m, Detect) else 1)
                 ok[j] = ok.get(j, True) and isinstance(m, join_ok)
             if isinstance(m, Concat):
                 off, total = 0, sum(outs[j][0] for j in srcs[m.i])
@@ -455,3 +472,17 @@ class DetectionModel(BaseModel):
         for k in sorted({0, len(y) - 1}):
             y[k] = y[k][..., ranges[k][0] : ranges[k][1]]
         return y
+
+
+class SegmentationModel(DetectionModel):
+    """YOLO segmentation model (reference tasks.py:466-483): a DetectionModel whose head is a Segment and whose criterion is
+    v8SegmentationLoss."""
+
+    def __init__(self, cfg="yolov8n-seg.yaml", ch=3, nc=None, verbose=False):
+        super().__init__(cfg=cfg, ch=ch, nc=nc, verbose=verbose)
+
+    def init_criterion(self):
+        return v8SegmentationLoss(self)
+
+    def _predict_augment(self, x):
+        raise NotImplementedError("test-time augmentation merges box rows only: it is not built for the mask coefficients of a SegmentationModel")

@@ -35,6 +35,10 @@ from .blocks import (  # noqa: F401
     _WindowReverse, _map_array, add_residual, c2f_split, cbam, concat, detect_decode, detect_loss, detect_nms, detect_targets, gelu, layernorm, psa_attention, sppf_pool_cat,
     swin_ln_mlp, swin_ln_mlp_ok, swin_mlp, upsample2x, window_attention, window_pad, window_partition, window_partition_index, window_reverse,
 )
+from .seg import (  # noqa: F401
+    _ConvTranspose2x2, _DetectLossAssign, _MaskLoss, conv_transpose2x2, conv_transpose2x2_ok, depth_to_space2, detect_decode_seg, detect_loss_assign, mask_loss,
+    space_to_depth2,
+)
 from .resize import letterbox, letterbox_geometry, scale_boxes, scale_boxes_params, scale_image, scale_rows, tta_clip_ranges, tta_merge  # noqa: F401
 from .augment import affine_matrix, augment_batch, hsv_luts, invert_affine, mosaic_placement  # noqa: F401
 from .validate import VAL_MATCH_LABEL_CHUNK, val_match  # noqa: F401

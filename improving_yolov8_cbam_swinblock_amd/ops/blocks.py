@@ -636,6 +636,12 @@ class _DetectLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, targets, strides, topk, alpha, beta, scale6, *maps):
+        return _DetectLoss.run(ctx, targets, strides, topk, alpha, beta, scale6, maps)[:2]
+
+    @staticmethod
+    def run(ctx, targets, strides, topk, alpha, beta, scale6, maps, assign=False):
+        """the forward's one body -> (loss, items, gidx): with `assign` the assignment's gt index per anchor [B, A] int32 (-1: background) is
+        handed over too (ops.seg._DetectLossAssign); without it gidx is None and the library keeps the index in its workspace."""
         nl = len(maps) // 2
         box, cls = maps[:nl], maps[nl:]
         dev = box[0].device
@@ -647,18 +653,19 @@ class _DetectLoss(torch.autograd.Function):
         state = torch.empty(sb.value, dtype=torch.uint8, device=dev)
         ws = workspace(wb.value, dev, "detloss")
         out = torch.empty(6, dtype=torch.float32, device=dev)
+        gidx = torch.empty((b, anchors), dtype=torch.int32, device=dev) if assign else None
         st = (ctypes.c_float * nl)(*[float(s) for s in strides])
         check(
-            L().ymi_detect_loss_fwd(nl, _map_array(box), _map_array(cls), st, ptr(targets), g, int(topk), float(alpha), float(beta), ptr(scale6), ptr(out),
-                                    ptr(state), state.numel(), ptr(ws), ws.numel(), stream_ptr()),
+            L().ymi_detect_loss_fwd_assign(nl, _map_array(box), _map_array(cls), st, ptr(targets), g, int(topk), float(alpha), float(beta), ptr(scale6),
+                                           ptr(out), ptr(state), state.numel(), ptr(ws), ws.numel(), ptr(gidx), stream_ptr()),
             "detect_loss_fwd",
         )
         ctx.save_for_backward(state, scale6, *maps)
         ctx.strides = st
         loss, items = out[:3], out[3:]
-        ctx.mark_non_differentiable(items)
+        ctx.mark_non_differentiable(*((items,) if gidx is None else (items, gidx)))
         ctx.set_materialize_grads(False)  # (no zero tensor for `items`: it was a fill launch per step)
-        return loss, items
+        return loss, items, gidx
 
     @staticmethod
     def backward(ctx, gl, _gitems):

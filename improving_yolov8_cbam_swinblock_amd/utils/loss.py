@@ -53,10 +53,10 @@ class v8DetectionLoss:
         return int(torch.bincount(batch_idx.reshape(-1).long(), minlength=batch_size).max())
 
     def __call__(self, preds, batch):
-        if isinstance(preds, SplitPreds):
+        if hasattr(preds, "box") and hasattr(preds, "cls"):  # SplitPreds, or Segment's SegPreds
             box, cls = list(preds.box), list(preds.cls)
         else:  # list of [B, no, H, W] maps (reference layout): split the channels again (loss.py:205-207)
-            feats = preds[1] if isinstance(preds, tuple) else preds
+            feats = self._feats(preds)
             box = [f[:, : self.reg_max * 4] for f in feats]
             cls = [f[:, self.reg_max * 4 :] for f in feats]
         if not box[0].is_cuda:
@@ -76,4 +76,56 @@ class v8DetectionLoss:
         if scale is None:
             gh = [float(self.hyp.box), float(self.hyp.cls), float(self.hyp.dfl)]
             scale = self._scales[B] = torch.tensor([g * B for g in gh] + gh, dtype=torch.float32, device=box[0].device)
+        return self._finish(box, cls, targets, scale, preds, batch)
+
+    def _feats(self, preds):
+        """the per-level [B, no, H, W] maps of a Detect output: the train-mode list, or the second entry of the eval-mode tuple."""
+        return preds[1] if isinstance(preds, tuple) else preds
+
+    def _finish(self, box, cls, targets, scale, preds, batch):
         return ops.detect_loss(box, cls, self.stride_list, targets, scale, self.topk, self.alpha, self.beta)
+
+
+class v8SegmentationLoss(v8DetectionLoss):
+    """criterion(preds, batch) -> (loss * batch_size [4], loss.detach() [4]) in the order box, seg, cls, dfl (reference loss.py:258-438).
+
+    preds: the Segment head's SegPreds (training fast path), its train-mode output (feats, mc [B, nm, A], p) or its eval output (y, (feats,
+    mc, p)).  batch["masks"]: the overlap encoding [B, Hm, Wm], uint8 or float32 (pixel value = 1 + index of the object among the image's
+    labels, 0 = background), read at the prototype map's size with F.interpolate(mode="nearest")'s index rule inside the kernel.
+    The detection stages run once (ops.detect_loss_assign: box, cls and dfl are v8DetectionLoss's numbers bit for bit) and hand the
+    assignment to the mask stage (ops.mask_loss, csrc/seg.hip); every shape is static given max_boxes and nothing is read back."""
+
+    def __init__(self, model, tal_topk=10):
+        super().__init__(model, tal_topk)
+        self.overlap = bool(getattr(self.hyp, "overlap_mask", True))
+        if not self.overlap:
+            raise NotImplementedError("overlap_mask=False (one mask per label, reference loss.py:427-428) is not built: the mask-loss kernel reads "
+                                      "the overlap encoding [B, H, W]")
+        self.nm = model.model[-1].nm
+
+    def _feats(self, preds):
+        return (preds if len(preds) == 3 else preds[1])[0]
+
+    def _finish(self, box, cls, targets, scale, preds, batch):
+        from ..nn.modules.head import SegPreds
+
+        if isinstance(preds, SegPreds):
+            mc, proto = list(preds.mc), preds.proto
+        else:
+            feats, mcat, proto = preds if len(preds) == 3 else preds[1]
+            B = mcat.shape[0]
+            sizes = [int(f.shape[2] * f.shape[3]) for f in feats]
+            mc = [m.reshape(B, self.nm, f.shape[2], f.shape[3]) for m, f in zip(mcat.split(sizes, 2), feats)]
+        dt = box[0].dtype
+        mc = [_nhwc_map(t if t.dtype == dt else t.to(dt), True) for t in mc]
+        proto = _nhwc_map(ops.to_internal(proto, dt), True)
+        masks = batch["masks"]
+        if masks.dim() != 3 or masks.shape[0] != proto.shape[0]:
+            raise ValueError(f"batch['masks'] must be the overlap encoding [B, H, W], got {tuple(masks.shape)}")
+        if masks.dtype not in (torch.uint8, torch.float32):
+            masks = masks.float()
+        masks = masks.to(proto.device).contiguous()
+        h, w = box[0].shape[2:]
+        s0 = self.stride_list[0]
+        loss3, items3, gidx = ops.detect_loss_assign(box, cls, self.stride_list, targets, scale, self.topk, self.alpha, self.beta)
+        return ops.mask_loss(loss3, items3, gidx, targets, masks, scale, self.topk, w * s0, h * s0, proto, mc)

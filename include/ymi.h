@@ -421,6 +421,42 @@ int ymi_detect_loss_bwd(int32_t nl, const ymi_tensor* box_maps, const ymi_tensor
  * sigmoid(class logits); anchors in the reference's order (level, y, x), centre offset 0.5. */
 int ymi_detect_decode(int32_t nl, const ymi_tensor* box_maps, const ymi_tensor* cls_maps, const float* strides, float* y, void* stream);
 
+/* ------------------------------------------------------------------ instance segmentation ---- */
+
+/* nn.ConvTranspose2d(c, c, 2, 2, 0) of Proto (nn/modules/block.py:80-100) is four 1x1 GEMMs, one per output sub-pixel: ymi_conv2d_fwd with the
+ * weight viewed as [4c, c] gives src [N,H,W,4c], channel (2a + b) * c + k; this copy puts it at dst [N,2H,2W,c] (2y + a, 2x + b, k).
+ * Channels and pixel strides in whole 16-byte chunks, both tensors of one dtype. */
+int ymi_depth_to_space2(const ymi_tensor* src, const ymi_tensor* dst, void* stream);
+/* the inverse: src [N,2H,2W,c] -> dst [N,H,W,4c] (the output gradient, for the data- and weight-gradient GEMMs) */
+int ymi_space_to_depth2(const ymi_tensor* src, const ymi_tensor* dst, void* stream);
+/* ymi_detect_loss_fwd that also hands the assignment over: gidx_out (device [batch, anchors] int32, or NULL) receives the gt index of every
+ * anchor (-1: background), reference utils/tal.py target_gt_idx under fg_mask.  Everything else is computed as without it. */
+int ymi_detect_loss_fwd_assign(int32_t nl, const ymi_tensor* box_maps, const ymi_tensor* cls_maps, const float* strides, const float* targets,
+                               int64_t max_boxes, int32_t topk, float alpha, float beta, const float* out_scale, float* loss_out, void* state,
+                               size_t state_bytes, void* workspace, size_t workspace_bytes, int32_t* gidx_out, void* stream);
+/* Segment's eval output (nn/modules/head.py:186-208): ymi_detect_decode with the anchors' mask coefficients behind the classes,
+ * y [B][4+nc+nm][A] float32; mc_maps[l]: [B,H_l,W_l,nm] of Segment.cv4[l]. */
+int ymi_detect_decode_seg(int32_t nl, const ymi_tensor* box_maps, const ymi_tensor* cls_maps, const ymi_tensor* mc_maps, const float* strides,
+                          float* y, void* stream);
+/* The mask term of v8SegmentationLoss (utils/loss.py:349-438; crop_mask utils/ops.py:661-677) with overlap-encoded masks, nm = 32.
+ * mc_maps[l]: [B,H_l,W_l,32] coefficient maps, proto: [B,mh,mw,32] (both f32 or bf16, read as they are; sums in f32); masks: device
+ * [B,masks_h,masks_w] uint8 (masks_f32 = 0) or float32, read with F.interpolate(mode="nearest")'s index rule when its size is not (mh, mw);
+ * gidx: as ymi_detect_loss_fwd_assign writes it; targets: as ymi_detect_targets writes them; det_out6: the six results of the detection
+ * loss; scale6: its out_scale.  out8[0..3] = (box, seg, cls, dfl) scaled for backward, out8[4..7] = scaled for logging; seg takes the box
+ * gain.  Foreground anchors per image are bounded by min(anchors, topk * max_boxes): every grid is static, nothing is read back, no atomics
+ * (fixed summation order).  state: ymi_mask_loss_sizes bytes, kept for the backward.
+ * Precondition the library cannot check: gidx holds batch * A entries and targets batch * max_boxes * 5, with A = the sum of H_l * W_l over
+ * mc_maps and the levels in the order of the box maps the assignment was made on (ops.mask_loss checks the shapes). */
+int ymi_mask_loss_sizes(int64_t batch, int64_t anchors, int64_t max_boxes, int32_t topk, size_t* state_bytes);
+int ymi_mask_loss_fwd(int32_t nl, const ymi_tensor* mc_maps, const ymi_tensor* proto, const void* masks, int32_t masks_f32, int64_t masks_h,
+                      int64_t masks_w, const int32_t* gidx, const float* targets, int64_t max_boxes, int32_t topk, float img_w, float img_h,
+                      const float* det_out6, const float* scale6, float* out8, void* state, size_t state_bytes, void* stream);
+/* gradients of grad_out8[1] * out8[1] with respect to the coefficient maps (rows of foreground anchors only: the caller zero-fills dmc_maps)
+ * and to the prototype map (every pixel written). */
+int ymi_mask_loss_bwd(int32_t nl, const ymi_tensor* mc_maps, const ymi_tensor* proto, const void* masks, int32_t masks_f32, int64_t masks_h,
+                      int64_t masks_w, int64_t max_boxes, int32_t topk, const void* state, size_t state_bytes, const float* grad_out8,
+                      const float* scale6, const ymi_tensor* dmc_maps, const ymi_tensor* dproto, void* stream);
+
 /* non_max_suppression (utils/ops.py:181-332, as models/yolo/detect/val.py:113-133 and the predictor call it) on y [B][4+nc][A] float32 as
  * ymi_detect_decode writes it -> det [B][max_det][6] float32, rows (x1, y1, x2, y2, conf, cls) in kept order and zero past the count, and
  * count [B] int32 (csrc/nms.hip: three launches of B workgroups, no host round trip, no data-dependent grid: graph-capturable).
