@@ -144,6 +144,10 @@ _SIGNATURES = {
     "ymi_detect_nms_sizes": (_c_i32, [_c_i64, _c_i64, _c_i64, _c_i64, _c_i64, ctypes.POINTER(ctypes.c_size_t)]),
     "ymi_detect_nms": (_c_i32, [_vp, _c_i64, _c_i64, _c_i64, _c_f32, _c_f32, _c_i32, _c_i32, ctypes.POINTER(_c_i32), _c_i32, _c_i64, _c_i64, _c_f32,
                                 _vp, _vp, _vp, _sz, _vp]),
+    "ymi_detect_nms_seg": (_c_i32, [_vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_f32, _c_f32, _c_i32, _c_i32, ctypes.POINTER(_c_i32), _c_i32, _c_i64, _c_i64,
+                                    _c_f32, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "ymi_process_mask": (_c_i32, [_TP, _vp, _vp, _vp, _c_i64, _c_i64, _c_i64, _c_i32, _vp, _vp, _vp]),
+    "ymi_mask_overlap": (_c_i32, [_vp, _vp, _vp, _c_i64, _c_i64, _TP, _c_i64, _c_i64, _vp, _c_i32, _c_i64, _c_i64, _c_i64, _vp, _vp, _vp, _vp]),
     "ymi_scale_image": (_c_i32, [_vp, _c_i32, _c_i64, _c_i64, _c_i64, _vp, _c_i64, _c_i64, _c_i64, _c_i64, _c_f32, _c_i32, _c_i32, _c_i32, _vp]),
     "ymi_tta_merge": (_c_i32, [_c_i32, ctypes.POINTER(_vp), ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64), ctypes.POINTER(_c_f32),
                                ctypes.POINTER(_c_i32), ctypes.POINTER(_c_i64), ctypes.POINTER(_c_i64), _c_i64, _c_i64, _vp, _vp]),
@@ -153,6 +157,7 @@ _SIGNATURES = {
     "ymi_augment_boxes": (_c_i32, [_vp, _c_i64, _vp, _c_i64, _c_f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "ymi_val_match": (_c_i32, [_vp, _vp, _c_i64, _c_i64, _vp, _vp, _vp, _c_i64, _c_f32, _c_f32, _vp, ctypes.POINTER(_c_f32), _c_i32, _c_i32, _vp, _vp, _c_i64,
                               _c_f32, _c_f32, _vp]),
+    "ymi_val_match_masks": (_c_i32, [_vp, _vp, _c_i64, _c_i64, _vp, _vp, _c_i64, _vp, _vp, _vp, _c_i64, ctypes.POINTER(_c_f32), _c_i32, _c_i32, _vp, _vp]),
     "ymi_opt_chunk_elems": (_c_i64, []),
     "ymi_opt_grad_norm": (_c_i32, [_vp, _vp, _c_i32, _c_i32, _c_i64, ctypes.POINTER(_vp), _vp, _vp, _c_i64, _c_i64, _vp, _c_i32, _vp]),
     "ymi_opt_update": (_c_i32, [_vp, _vp, _c_i32, _c_i32, _c_i64, ctypes.POINTER(_vp), _vp, _vp, _c_i32, _vp]),

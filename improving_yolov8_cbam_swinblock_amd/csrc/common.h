@@ -323,7 +323,25 @@ __device__ __forceinline__ float unit_of_byte(uint32_t u) {
     return __builtin_fmaf(r, rc, q);
 }
 
-// ---- in-launch hand-offs between workgroups (round 5) ----------------------------------------------------------------------------
+// ATen's area_pixel_compute_source_index (align_corners = false, bilinear) and the neighbour / weight rule of upsample_bilinear2d.  Its users
+// (resize.hip, maskdec.hip) are compiled with -ffp-contract=off: the coordinate must round as a product and a difference (resize.hip's head).
+struct Tap {
+    int i0, i1;
+    float l0, l1;
+};
+__device__ __forceinline__ Tap tap_of(int dst, float scale, int in) {
+    float s = ((float)dst + 0.5f) * scale - 0.5f;
+    s = s < 0.0f ? 0.0f : s;
+    Tap t;
+    t.i0 = (int)s;  // (s >= 0: truncation is floor)
+    t.i0 = t.i0 > in - 1 ? in - 1 : t.i0;  // (never taken for hs <= Hp sizes that ATen accepts; keeps every read in bounds whatever scale is passed)
+    t.i1 = t.i0 + (t.i0 < in - 1 ? 1 : 0);
+    t.l1 = s - (float)t.i0;
+    t.l0 = 1.0f - t.l1;
+    return t;
+}
+
+// ---- in-launch hand-offs between workgroups (round 5)----------------------------------------------------------------------------
 // The per-XCD L2s are not coherent and a CU's L1 is never refreshed by another CU's stores, so a workgroup that consumes another
 // workgroup's bytes INSIDE a launch needs them written through and read past its L1.  The form used here (MI355X_MICROARCH.md,
 // "Valid forms", first table row; cdna_hip_programming.md Guideline 16 R1): every handed-off byte is stored with an agent-scope relaxed

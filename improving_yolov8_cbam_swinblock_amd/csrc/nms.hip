@@ -5,6 +5,8 @@
 //                          only candidates at or above it are written (equal scores: lowest indices first), so the key buffer is max_nms long
 //   2. nms_sort_kernel   : bitonic sort of the keys, descending: descending score, then ascending anchor, then ascending class
 //   3. nms_scan_kernel   : greedy suppression in sorted order against the kept list in LDS; leaves when max_det are kept
+// The kernels take the rows of y per image as an argument: 4 + nc, or 4 + nc + nm for Segment's output (ymi_detect_nms_seg), where only rows
+// 4 .. 4 + nc are scores and the scan also writes the kept anchors' nm coefficient rows; no decision depends on nm.
 // Integer LDS atomics (histogram counts) are the only atomics: every result is a function of the input alone, bit for bit.
 // This file is compiled with -ffp-contract=off (Makefile): area_i + area_j - inter must round as three operations, as in
 // torchvision's nms carried out in float32, and the class offset b + cls * max_wh as a product and a sum.  Division is the compiler's IEEE
@@ -98,14 +100,14 @@ __device__ __forceinline__ void select_digit(const int* hist, int need, int* wsu
     __syncthreads();
 }
 
-__global__ __launch_bounds__(NMS_THREADS) void nms_select_kernel(const float* __restrict__ y, int A, int nc, float conf, int multi, int filter,
+__global__ __launch_bounds__(NMS_THREADS) void nms_select_kernel(const float* __restrict__ y, int A, int nc, int rows, float conf, int multi, int filter,
                                                                  ClassMask mask, int max_nms, int npad, uint64_t* __restrict__ keys,
                                                                  int* __restrict__ ncand) {
     __shared__ int hist[SELECT_BINS];
     __shared__ int wsum[NMS_WAVES + 1];
     __shared__ int sel[2];
     const int b = blockIdx.x, tid = threadIdx.x;
-    const float* yb = y + (size_t)b * (4 + nc) * A;
+    const float* yb = y + (size_t)b * rows * A;
     uint64_t* kb = keys + (size_t)b * npad;
 
     // the score of rank max_nms: cut (score bits) and, among candidates with exactly that score, how many to take (lowest indices first)
@@ -257,9 +259,11 @@ __device__ __forceinline__ bool suppresses(const Box& k, const Box& c, float thr
 // One workgroup per image: SCAN_CHUNK candidates at a time in sorted order.  Phase A (all SCAN_SEGS * SCAN_CHUNK threads): thread (candidate,
 // segment) tests its candidate against every SCAN_SEGS-th kept box, so the kept list is walked by four waves per SIMD at once.  Phase B (the first
 // wave): resolves the chunk in order, 64 candidates at a time, with wave operations only.  The rows are written at the end, from the kept indices.
-__global__ __launch_bounds__(SCAN_THREADS) void nms_scan_kernel(const float* __restrict__ y, int A, int nc, const uint64_t* __restrict__ keys, int npad,
+// rows: the rows of y per image (4 + nc, or 4 + nc + nm with mask coefficients behind the scores); coef (or null): [B][max_det][nm], the kept anchors'
+// coefficient rows, zero past the count.
+__global__ __launch_bounds__(SCAN_THREADS) void nms_scan_kernel(const float* __restrict__ y, int A, int nc, int rows, const uint64_t* __restrict__ keys, int npad,
                                                                 const int* __restrict__ ncand, float iou_thres, float max_wh, int max_det,
-                                                                float* __restrict__ det, int* __restrict__ count) {
+                                                                float* __restrict__ det, int* __restrict__ count, float* __restrict__ coef, int nm) {
     extern __shared__ float kept[];  // [5][max_det]: offset boxes and areas of the kept candidates; then [max_det] their positions in the sorted list
     __shared__ float cbox[5][SCAN_CHUNK];
     __shared__ int calive[SCAN_CHUNK];
@@ -268,7 +272,7 @@ __global__ __launch_bounds__(SCAN_THREADS) void nms_scan_kernel(const float* __r
     int* kq = reinterpret_cast<int*>(kept + 5 * max_det);
     const int b = blockIdx.x, tid = threadIdx.x, lane = tid & (YMI_WAVE - 1);
     const int cand = tid & (SCAN_CHUNK - 1), seg = tid / SCAN_CHUNK;
-    const float* yb = y + (size_t)b * (4 + nc) * A;
+    const float* yb = y + (size_t)b * rows * A;
     const uint64_t* kb = keys + (size_t)b * npad;
     float* db = det + (size_t)b * max_det * 6;
     const int n = ncand[b];
@@ -364,6 +368,15 @@ __global__ __launch_bounds__(SCAN_THREADS) void nms_scan_kernel(const float* __r
         r[5] = (float)cls;
     }
     for (int i = nk * 6 + tid; i < max_det * 6; i += SCAN_THREADS) db[i] = 0.0f;
+    if (coef) {  // (workgroup-uniform)
+        float* cb = coef + (size_t)b * max_det * nm;
+        for (int e = tid; e < nk * nm; e += SCAN_THREADS) {
+            const int i = e / nm, m = e - i * nm;
+            const uint32_t idx = ~(uint32_t)kb[kq[i]];
+            cb[e] = yb[(size_t)(4 + nc + m) * A + idx / nc];
+        }
+        for (int e = nk * nm + tid; e < max_det * nm; e += SCAN_THREADS) cb[e] = 0.0f;
+    }
     if (tid == 0) count[b] = nk;
 }
 
@@ -386,44 +399,64 @@ extern "C" int ymi_detect_nms_sizes(int64_t batch, int64_t anchors, int64_t nc, 
     return YMI_OK;
 }
 
-extern "C" int ymi_detect_nms(const float* y, int64_t batch, int64_t nc, int64_t anchors, float conf_thres, float iou_thres, int32_t multi_label,
-                              int32_t agnostic, const int32_t* host_classes, int32_t n_classes, int64_t max_det, int64_t max_nms, float max_wh, float* det,
-                              int32_t* count, void* workspace, size_t workspace_bytes, void* stream) {
+namespace {
+// the one host body of ymi_detect_nms (nm == 0, coef == NULL) and ymi_detect_nms_seg
+int detect_nms_run(const char* who, const float* y, int64_t batch, int64_t nc, int64_t nm, int64_t anchors, float conf_thres, float iou_thres,
+                   int32_t multi_label, int32_t agnostic, const int32_t* host_classes, int32_t n_classes, int64_t max_det, int64_t max_nms, float max_wh,
+                   float* det, int32_t* count, float* coef, void* workspace, size_t workspace_bytes, void* stream) {
     size_t need = 0;
     const int rc = ymi_detect_nms_sizes(batch, anchors, nc, max_nms, max_det, &need);
     if (rc != YMI_OK) return rc;
-    YMI_CHECK_ARG(y && det && count && workspace, "detect_nms: null pointer");
-    YMI_CHECK_ARG(conf_thres >= 0.0f && conf_thres <= 1.0f, "detect_nms: conf_thres %g outside [0, 1]", (double)conf_thres);
-    YMI_CHECK_ARG(iou_thres >= 0.0f && iou_thres <= 1.0f, "detect_nms: iou_thres %g outside [0, 1]", (double)iou_thres);
-    YMI_CHECK_ARG(max_wh >= 0.0f, "detect_nms: max_wh must not be negative");
-    YMI_CHECK_ARG(n_classes >= 0 && (n_classes == 0 || host_classes), "detect_nms: classes");
-    YMI_CHECK_ARG(!host_classes || nc <= NMS_MAX_NC, "detect_nms: the class filter covers %d classes", NMS_MAX_NC);
-    if (((uintptr_t)y & 3) || ((uintptr_t)det & 3) || ((uintptr_t)count & 3) || ((uintptr_t)workspace & 7)) {
-        ymi_set_error("detect_nms: y / det / count need 4-byte, the workspace 8-byte alignment");
+    YMI_CHECK_ARG(y && det && count && workspace, "%s: null pointer", who);
+    YMI_CHECK_ARG(conf_thres >= 0.0f && conf_thres <= 1.0f, "%s: conf_thres %g outside [0, 1]", who, (double)conf_thres);
+    YMI_CHECK_ARG(iou_thres >= 0.0f && iou_thres <= 1.0f, "%s: iou_thres %g outside [0, 1]", who, (double)iou_thres);
+    YMI_CHECK_ARG(max_wh >= 0.0f, "%s: max_wh must not be negative", who);
+    YMI_CHECK_ARG(n_classes >= 0 && (n_classes == 0 || host_classes), "%s: classes", who);
+    YMI_CHECK_ARG(!host_classes || nc <= NMS_MAX_NC, "%s: the class filter covers %d classes", who, NMS_MAX_NC);
+    YMI_CHECK_ARG(nm >= 0 && nm <= (1 << 16) && (4 + nc + nm) * anchors < ((int64_t)1 << 31), "%s: nm in [0, 65536] and (4 + nc + nm) * anchors below 2^31", who);
+    if (((uintptr_t)y & 3) || ((uintptr_t)det & 3) || ((uintptr_t)count & 3) || ((uintptr_t)coef & 3) || ((uintptr_t)workspace & 7)) {
+        ymi_set_error("%s: y / det / count / coef need 4-byte, the workspace 8-byte alignment", who);
         return YMI_EALIGN;
     }
     if (workspace_bytes < need) {
-        ymi_set_error("detect_nms: workspace of %zu bytes, %zu needed", workspace_bytes, need);
+        ymi_set_error("%s: workspace of %zu bytes, %zu needed", who, workspace_bytes, need);
         return YMI_EWORKSPACE;
     }
     ClassMask mask = {};
     for (int i = 0; i < n_classes; ++i) {
-        YMI_CHECK_ARG(host_classes[i] >= 0 && host_classes[i] < nc, "detect_nms: class %d outside [0, %lld)", host_classes[i], (long long)nc);
+        YMI_CHECK_ARG(host_classes[i] >= 0 && host_classes[i] < nc, "%s: class %d outside [0, %lld)", who, host_classes[i], (long long)nc);
         mask.w[host_classes[i] >> 5] |= 1u << (host_classes[i] & 31);
     }
     const int64_t cap = max_nms < anchors * nc ? max_nms : anchors * nc;
     const int npad = next_pow2(cap);
+    const int rows = (int)(4 + nc + nm);
     uint64_t* keys = (uint64_t*)workspace;
     int* ncand = (int*)((char*)workspace + (size_t)batch * npad * 8);
     hipStream_t s = (hipStream_t)stream;
     const int multi = multi_label && nc > 1;  // reference ops.py:255
-    hipLaunchKernelGGL(nms_select_kernel, dim3((unsigned)batch), dim3(NMS_THREADS), 0, s, y, (int)anchors, (int)nc, conf_thres, multi, host_classes ? 1 : 0,
+    hipLaunchKernelGGL(nms_select_kernel, dim3((unsigned)batch), dim3(NMS_THREADS), 0, s, y, (int)anchors, (int)nc, rows, conf_thres, multi, host_classes ? 1 : 0,
                        mask, (int)cap, npad, keys, ncand);
     YMI_CHECK_LAUNCH("detect_nms (select)");
     hipLaunchKernelGGL(nms_sort_kernel, dim3((unsigned)batch), dim3(NMS_THREADS), 0, s, keys, npad, ncand);
     YMI_CHECK_LAUNCH("detect_nms (sort)");
-    hipLaunchKernelGGL(nms_scan_kernel, dim3((unsigned)batch), dim3(SCAN_THREADS), (size_t)max_det * 6 * sizeof(float), s, y, (int)anchors, (int)nc, keys, npad,
-                       ncand, iou_thres, agnostic ? 0.0f : max_wh, (int)max_det, det, count);
+    hipLaunchKernelGGL(nms_scan_kernel, dim3((unsigned)batch), dim3(SCAN_THREADS), (size_t)max_det * 6 * sizeof(float), s, y, (int)anchors, (int)nc, rows, keys, npad,
+                       ncand, iou_thres, agnostic ? 0.0f : max_wh, (int)max_det, det, count, coef, (int)nm);
     YMI_CHECK_LAUNCH("detect_nms (scan)");
     return YMI_OK;
+}
+}  // namespace
+
+extern "C" int ymi_detect_nms(const float* y, int64_t batch, int64_t nc, int64_t anchors, float conf_thres, float iou_thres, int32_t multi_label,
+                              int32_t agnostic, const int32_t* host_classes, int32_t n_classes, int64_t max_det, int64_t max_nms, float max_wh, float* det,
+                              int32_t* count, void* workspace, size_t workspace_bytes, void* stream) {
+    return detect_nms_run("detect_nms", y, batch, nc, 0, anchors, conf_thres, iou_thres, multi_label, agnostic, host_classes, n_classes, max_det, max_nms, max_wh,
+                          det, count, nullptr, workspace, workspace_bytes, stream);
+}
+
+extern "C" int ymi_detect_nms_seg(const float* y, int64_t batch, int64_t nc, int64_t nm, int64_t anchors, float conf_thres, float iou_thres,
+                                  int32_t multi_label, int32_t agnostic, const int32_t* host_classes, int32_t n_classes, int64_t max_det, int64_t max_nms,
+                                  float max_wh, float* det, int32_t* count, float* coef, void* workspace, size_t workspace_bytes, void* stream) {
+    YMI_CHECK_ARG(nm >= 1 && coef, "detect_nms_seg: nm >= 1 and a coefficient output");
+    return detect_nms_run("detect_nms_seg", y, batch, nc, nm, anchors, conf_thres, iou_thres, multi_label, agnostic, host_classes, n_classes, max_det, max_nms,
+                          max_wh, det, count, coef, workspace, workspace_bytes, stream);
 }

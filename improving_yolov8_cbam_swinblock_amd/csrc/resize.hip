@@ -39,23 +39,6 @@ template <typename T, bool NORM> __device__ __forceinline__ void load_group(cons
     }
 }
 
-// ATen's area_pixel_compute_source_index (align_corners = false, bilinear) and the neighbour / weight rule of upsample_bilinear2d
-struct Tap {
-    int i0, i1;
-    float l0, l1;
-};
-__device__ __forceinline__ Tap tap_of(int dst, float scale, int in) {
-    float s = ((float)dst + 0.5f) * scale - 0.5f;
-    s = s < 0.0f ? 0.0f : s;
-    Tap t;
-    t.i0 = (int)s;  // (s >= 0: truncation is floor)
-    t.i0 = t.i0 > in - 1 ? in - 1 : t.i0;  // (never taken for hs <= Hp sizes that ATen accepts; keeps every read in bounds whatever scale is passed)
-    t.i1 = t.i0 + (t.i0 < in - 1 ? 1 : 0);
-    t.l1 = s - (float)t.i0;
-    t.l0 = 1.0f - t.l1;
-    return t;
-}
-
 struct ScaleArgs {
     const void* src;
     float* dst;

@@ -26,11 +26,23 @@ struct Levels {
 // class id of a float class column (the reference's .int(): truncation) or -1 when it lies outside [0, nc)
 __device__ __forceinline__ int class_index(float c, int nc) { return (c > -1.0f && c < (float)nc) ? (int)c : -1; }
 
+// the overlap source of ymi_val_match_masks: the integer counts ymi_mask_overlap leaves (bin j + 1 belongs to the image's j-th label in table order)
+struct MaskCounts {
+    const int* inter;      // [B][max_det][n_bins]
+    const int* area_pred;  // [B][max_det]
+    const int* area_gt;    // [B][n_bins]
+    int n_bins;
+};
+
+// MASKS = false: the overlap of a detection with a label is box_iou of their boxes; true: mask_iou on the counts of `mc` (lab_box, img_w, img_h, native
+// and cm are not read: the confusion matrix is box-based).  Everything else - staging, claims, ties, levels - is the one body below.
+template <bool MASKS>
 __global__ __launch_bounds__(VM_THREADS) void val_match_kernel(const float* __restrict__ det, const int* __restrict__ count, int max_det,
                                                                const int* __restrict__ lab_img, const float* __restrict__ lab_cls,
                                                                const float* __restrict__ lab_box, int n_labels, float img_w, float img_h,
                                                                const float* __restrict__ native, Levels levels, int n_levels, int single_cls,
-                                                               uint8_t* __restrict__ tp, int* __restrict__ cm, int nc, float cm_conf, float cm_iou) {
+                                                               uint8_t* __restrict__ tp, int* __restrict__ cm, int nc, float cm_conf, float cm_iou,
+                                                               MaskCounts mc) {
     __shared__ float lx1[VM_CHUNK], ly1[VM_CHUNK], lx2[VM_CHUNK], ly2[VM_CHUNK], lar[VM_CHUNK], lcl[VM_CHUNK];  // the image's labels of this chunk
     __shared__ int lid[VM_CHUNK];                                  // their rows in the table (pass 3: the chunk's claimed flags)
     __shared__ int claim[VM_MAX_DET], cclaim[VM_MAX_DET];          // per detection: table row claimed for tp / for the matrix (-1: none)
@@ -66,7 +78,12 @@ __global__ __launch_bounds__(VM_THREADS) void val_match_kernel(const float* __re
             if (w < wave) pos += t;
             total += t;
         }
-        if (mine) {
+        if (MASKS) {
+            if (mine) {
+                lcl[pos] = single_cls ? 0.0f : lab_cls[l];
+                lid[pos] = l;
+            }
+        } else if (mine) {
             const float* q = lab_box + (size_t)l * 4;
             const float hw = q[2] / 2.0f, hh = q[3] / 2.0f;
             float x1 = (q[0] - hw) * img_w, y1 = (q[1] - hh) * img_h, x2 = (q[0] + hw) * img_w, y2 = (q[1] + hh) * img_h;
@@ -85,13 +102,23 @@ __global__ __launch_bounds__(VM_THREADS) void val_match_kernel(const float* __re
         for (int d = tid; d < n; d += VM_THREADS) {
             const float* p = db + (size_t)d * 6;
             const float px1 = p[0], py1 = p[1], px2 = p[2], py2 = p[3], pcl = single_cls ? 0.0f : p[5];
-            const float par = (px2 - px1) * (py2 - py1);
+            const float par = MASKS ? (float)mc.area_pred[(size_t)b * max_det + d] : (px2 - px1) * (py2 - py1);
+            const int* irow = MASKS ? mc.inter + ((size_t)b * max_det + d) * mc.n_bins : nullptr;
             int c = claim[d], cc = cclaim[d];
             float s = strength[d], ci = ciou[d];
             for (int j = 0; j < total; ++j) {
-                const float w = fmaxf(fminf(lx2[j], px2) - fmaxf(lx1[j], px1), 0.0f), h = fmaxf(fminf(ly2[j], py2) - fmaxf(ly1[j], py1), 0.0f);
-                const float inter = w * h;
-                const float iou = inter / (((lar[j] + par) - inter) + 1e-7f);
+                float iou = 0.0f;
+                if (MASKS) {  // mask_iou on integer counts; labels at or beyond n_bins - 1 overlap nothing
+                    const int bin = n_mine + j + 1;
+                    if (bin < mc.n_bins) {
+                        const float inter = (float)irow[bin];
+                        iou = inter / ((((float)mc.area_gt[(size_t)b * mc.n_bins + bin] + par) - inter) + 1e-7f);
+                    }
+                } else {
+                    const float w = fmaxf(fminf(lx2[j], px2) - fmaxf(lx1[j], px1), 0.0f), h = fmaxf(fminf(ly2[j], py2) - fmaxf(ly1[j], py1), 0.0f);
+                    const float inter = w * h;
+                    iou = inter / (((lar[j] + par) - inter) + 1e-7f);
+                }
                 const float ov = iou * (lcl[j] == pcl ? 1.0f : 0.0f);
                 if (c < 0 || ov > s) {  // strict: the first maximum in table order
                     s = ov;
@@ -185,8 +212,32 @@ extern "C" int ymi_val_match(const float* det, const int32_t* count, int64_t bat
     }
     Levels lv = {};
     for (int i = 0; i < n_levels; ++i) lv.v[i] = levels[i];
-    hipLaunchKernelGGL(val_match_kernel, dim3((unsigned)batch), dim3(VM_THREADS), 0, (hipStream_t)stream, det, count, (int)max_det, lab_img, lab_cls, lab_box,
-                       (int)n_labels, img_w, img_h, native, lv, (int)n_levels, single_cls ? 1 : 0, tp, cm, (int)nc, cm_conf, cm_iou);
+    hipLaunchKernelGGL(val_match_kernel<false>, dim3((unsigned)batch), dim3(VM_THREADS), 0, (hipStream_t)stream, det, count, (int)max_det, lab_img, lab_cls,
+                       lab_box, (int)n_labels, img_w, img_h, native, lv, (int)n_levels, single_cls ? 1 : 0, tp, cm, (int)nc, cm_conf, cm_iou, MaskCounts{});
     YMI_CHECK_LAUNCH("val_match");
+    return YMI_OK;
+}
+
+extern "C" int ymi_val_match_masks(const float* det, const int32_t* count, int64_t batch, int64_t max_det, const int32_t* lab_img, const float* lab_cls,
+                                   int64_t n_labels, const int32_t* inter, const int32_t* area_pred, const int32_t* area_gt, int64_t n_bins,
+                                   const float* levels, int32_t n_levels, int32_t single_cls, uint8_t* tp_m, void* stream) {
+    YMI_CHECK_ARG(batch > 0 && batch < ((int64_t)1 << 31), "val_match_masks: bad batch");
+    YMI_CHECK_ARG(max_det > 0 && max_det <= VM_MAX_DET, "val_match_masks: max_det in [1, %d]", VM_MAX_DET);
+    YMI_CHECK_ARG(levels && n_levels > 0 && n_levels <= YMI_VALMATCH_MAX_LEVELS, "val_match_masks: 1 to %d IoU levels", YMI_VALMATCH_MAX_LEVELS);
+    YMI_CHECK_ARG(n_labels >= 0 && n_labels < ((int64_t)1 << 31) - VM_CHUNK, "val_match_masks: the label table must have fewer than 2^31 rows");
+    YMI_CHECK_ARG(det && count && tp_m && inter && area_pred && area_gt, "val_match_masks: null pointer");
+    YMI_CHECK_ARG(n_labels == 0 || (lab_img && lab_cls), "val_match_masks: null label table");
+    YMI_CHECK_ARG(n_bins >= 1 && n_bins <= YMI_MASK_MAX_BINS, "val_match_masks: n_bins in [1, %d]", YMI_MASK_MAX_BINS);
+    if (((uintptr_t)det & 3) || ((uintptr_t)count & 3) || ((uintptr_t)lab_img & 3) || ((uintptr_t)lab_cls & 3) || ((uintptr_t)inter & 3) ||
+        ((uintptr_t)area_pred & 3) || ((uintptr_t)area_gt & 3)) {
+        ymi_set_error("val_match_masks: det / count / labels / counts need 4-byte alignment");
+        return YMI_EALIGN;
+    }
+    Levels lv = {};
+    for (int i = 0; i < n_levels; ++i) lv.v[i] = levels[i];
+    const MaskCounts mc = {inter, area_pred, area_gt, (int)n_bins};
+    hipLaunchKernelGGL(val_match_kernel<true>, dim3((unsigned)batch), dim3(VM_THREADS), 0, (hipStream_t)stream, det, count, (int)max_det, lab_img, lab_cls,
+                       nullptr, (int)n_labels, 1.0f, 1.0f, nullptr, lv, (int)n_levels, single_cls ? 1 : 0, tp_m, nullptr, 0, 0.0f, 0.0f, mc);
+    YMI_CHECK_LAUNCH("val_match_masks");
     return YMI_OK;
 }

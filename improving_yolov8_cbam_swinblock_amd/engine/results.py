@@ -1,5 +1,5 @@
-"""Minimal Boxes and Results with the reference's names and arithmetic (ultralytics/engine/results.py:187-280, :1041-1256).  Tensors stay on the
-device they arrive on; there is no plotting, saving, masks, keypoints or tracking."""
+"""Minimal Boxes, Masks and Results with the reference's names and arithmetic (ultralytics/engine/results.py:187-280, :1041-1256, :1259-1330).
+Tensors stay on the device they arrive on; there is no plotting, saving, mask contours (Masks.xy / xyn), keypoints or tracking."""
 import torch
 
 from ..utils.ops import xyxy2xywh
@@ -60,20 +60,56 @@ class Boxes:
         return f"Boxes(n={len(self)}, orig_shape={tuple(self.orig_shape)})"
 
 
-class Results:
-    """one image's detections: orig_shape (h, w), boxes (Boxes), names ({class id: name}), path."""
+class Masks:
+    """data [n, H, W] uint8 0 / 1 masks at the letterboxed network input's shape, one per box and in the boxes' order; orig_shape (h, w) of
+    the image (reference engine/results.py:1259).  The reference holds float 0 / 1; contour tracing (xy, xyn) is not built."""
 
-    def __init__(self, orig_shape, path=None, names=None, boxes=None):
+    def __init__(self, masks, orig_shape):
+        if masks.ndim == 2:
+            masks = masks[None, :]
+        assert masks.ndim == 3, f"expected [n, H, W] masks but got {tuple(masks.shape)}"
+        self.data = masks
+        self.orig_shape = orig_shape
+
+    @property
+    def shape(self):
+        return self.data.shape
+
+    @property
+    def xy(self):
+        raise NotImplementedError("Masks.xy: contour tracing (the reference's cv2.findContours step) is not built")
+
+    @property
+    def xyn(self):
+        raise NotImplementedError("Masks.xyn: contour tracing (the reference's cv2.findContours step) is not built")
+
+    def cpu(self):
+        return Masks(self.data.cpu(), self.orig_shape)
+
+    def __len__(self):
+        return len(self.data)
+
+    def __repr__(self):
+        return f"Masks(n={len(self)}, shape={tuple(self.data.shape[1:])}, orig_shape={tuple(self.orig_shape)})"
+
+
+class Results:
+    """one image's detections: orig_shape (h, w), boxes (Boxes), names ({class id: name}), path, masks (Masks or None)."""
+
+    def __init__(self, orig_shape, path=None, names=None, boxes=None, masks=None):
         self.orig_shape = tuple(int(v) for v in orig_shape[:2])
         self.boxes = Boxes(boxes, self.orig_shape) if boxes is not None and not isinstance(boxes, Boxes) else boxes
+        self.masks = Masks(masks, self.orig_shape) if masks is not None and not isinstance(masks, Masks) else masks
         self.names = names
         self.path = path
 
     def cpu(self):
-        return Results(self.orig_shape, self.path, self.names, self.boxes.cpu() if self.boxes is not None else None)
+        return Results(self.orig_shape, self.path, self.names, self.boxes.cpu() if self.boxes is not None else None,
+                       self.masks.cpu() if self.masks is not None else None)
 
     def __len__(self):
         return len(self.boxes) if self.boxes is not None else 0
 
     def __repr__(self):
-        return f"Results(path={self.path!r}, orig_shape={self.orig_shape}, boxes={len(self)})"
+        tail = f", masks={len(self.masks)}" if self.masks is not None else ""
+        return f"Results(path={self.path!r}, orig_shape={self.orig_shape}, boxes={len(self)}{tail})"

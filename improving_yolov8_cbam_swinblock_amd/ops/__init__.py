@@ -32,13 +32,13 @@ from .conv import (  # noqa: F401
 from .dwconv import _DwConvAffineAct, _DwConvBnAct, dwconv_affine_act, dwconv_bn_act  # noqa: F401
 from .blocks import (  # noqa: F401
     _Act, _AddResidual, _C2fSplit, _Cbam, _Concat, _DetectLoss, _LayerNorm, _PsaAttention, _SppfPool, _SwinLnMlp, _SwinMlp, _Upsample2x, _WindowAttention,
-    _WindowReverse, _map_array, add_residual, c2f_split, cbam, concat, detect_decode, detect_loss, detect_nms, detect_targets, gelu, layernorm, psa_attention, sppf_pool_cat,
+    _WindowReverse, _map_array, add_residual, c2f_split, cbam, concat, detect_decode, detect_loss, detect_nms, detect_nms_seg, detect_targets, gelu, layernorm, psa_attention, sppf_pool_cat,
     swin_ln_mlp, swin_ln_mlp_ok, swin_mlp, upsample2x, window_attention, window_pad, window_partition, window_partition_index, window_reverse,
 )
 from .seg import (  # noqa: F401
     _ConvTranspose2x2, _DetectLossAssign, _MaskLoss, conv_transpose2x2, conv_transpose2x2_ok, depth_to_space2, detect_decode_seg, detect_loss_assign, mask_loss,
-    space_to_depth2,
+    mask_overlap, process_mask, space_to_depth2,
 )
 from .resize import letterbox, letterbox_geometry, scale_boxes, scale_boxes_params, scale_image, scale_rows, tta_clip_ranges, tta_merge  # noqa: F401
 from .augment import affine_matrix, augment_batch, hsv_luts, invert_affine, mosaic_placement  # noqa: F401
-from .validate import VAL_MATCH_LABEL_CHUNK, val_match  # noqa: F401
+from .validate import VAL_MATCH_LABEL_CHUNK, val_match, val_match_masks  # noqa: F401

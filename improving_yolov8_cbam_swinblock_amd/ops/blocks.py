@@ -706,20 +706,24 @@ def detect_decode(box_maps, cls_maps, strides):
     return y
 
 
-def detect_nms(y, conf_thres=0.25, iou_thres=0.45, *, multi_label=False, agnostic=False, classes=None, max_det=300, max_nms=30000, max_wh=7680):
-    """non_max_suppression of reference utils/ops.py:181-332 on the decoded Detect output y [B, 4+nc, A] float32, on the device
-    (csrc/nms.hip): -> (det [B, max_det, 6] float32 rows (x1, y1, x2, y2, conf, cls) in kept order, zero past the count; count [B] int32).
-    Both stay on the device and nothing synchronises: the call can be captured in a graph.  Order: descending score, equal scores by
-    ascending anchor then class (the library's own tie rule).  The reference's wall-clock time limit is not reproduced."""
+def _detect_nms(y, nc, conf_thres, iou_thres, multi_label, agnostic, classes, max_det, max_nms, max_wh):
+    """the one body of detect_nms (nc = rows - 4) and detect_nms_seg (mask coefficient rows behind the nc scores)."""
+    who = "detect_nms" if nc is None else "detect_nms_seg"
     if not y.is_cuda:
         raise RuntimeError("libyolo_mi355 kernels need tensors on the MI355X (cuda) device; there is no CPU path")
     if y.dim() != 3 or y.shape[1] < 5 or y.dtype != torch.float32:
-        raise ValueError(f"detect_nms takes the decoded Detect output [B, 4 + nc, A] in float32, got {tuple(y.shape)} {y.dtype}")
+        raise ValueError(f"{who} takes the decoded Detect output [B, 4 + nc, A] in float32, got {tuple(y.shape)} {y.dtype}")
     y = y.detach()
     if not y.is_contiguous():
         y = y.contiguous()
     b, no, a = (int(v) for v in y.shape)
-    nc = no - 4
+    nm = 0
+    if nc is None:
+        nc = no - 4
+    else:
+        nc, nm = int(nc), no - 4 - int(nc)
+        if nc < 1 or nm < 1:
+            raise ValueError(f"detect_nms_seg: {no} rows do not hold 4 box rows, nc = {nc} scores and at least one mask coefficient")
     cl = sorted({int(c) for c in classes}) if classes is not None else []
     wb = ctypes.c_size_t(0)
     check(L().ymi_detect_nms_sizes(b, a, nc, int(max_nms), int(max_det), _byref(wb)), "detect_nms_sizes")
@@ -727,6 +731,27 @@ def detect_nms(y, conf_thres=0.25, iou_thres=0.45, *, multi_label=False, agnosti
     det = torch.empty((b, int(max_det), 6), dtype=torch.float32, device=y.device)
     count = torch.empty((b,), dtype=torch.int32, device=y.device)
     arr = (ctypes.c_int32 * max(len(cl), 1))(*cl) if classes is not None else None  # (an empty list is a filter that keeps nothing, as in the reference)
-    check(L().ymi_detect_nms(ptr(y), b, nc, a, float(conf_thres), float(iou_thres), int(bool(multi_label)), int(bool(agnostic)), arr, len(cl), int(max_det),
-                             int(max_nms), float(max_wh), ptr(det), ptr(count), ptr(ws), ws.numel(), stream_ptr()), "detect_nms")
+    if not nm:
+        check(L().ymi_detect_nms(ptr(y), b, nc, a, float(conf_thres), float(iou_thres), int(bool(multi_label)), int(bool(agnostic)), arr, len(cl), int(max_det),
+                                 int(max_nms), float(max_wh), ptr(det), ptr(count), ptr(ws), ws.numel(), stream_ptr()), "detect_nms")
+        return det, None, count
+    coef = torch.empty((b, int(max_det), nm), dtype=torch.float32, device=y.device)
+    check(L().ymi_detect_nms_seg(ptr(y), b, nc, nm, a, float(conf_thres), float(iou_thres), int(bool(multi_label)), int(bool(agnostic)), arr, len(cl),
+                                 int(max_det), int(max_nms), float(max_wh), ptr(det), ptr(count), ptr(coef), ptr(ws), ws.numel(), stream_ptr()), "detect_nms_seg")
+    return det, coef, count
+
+
+def detect_nms(y, conf_thres=0.25, iou_thres=0.45, *, multi_label=False, agnostic=False, classes=None, max_det=300, max_nms=30000, max_wh=7680):
+    """non_max_suppression of reference utils/ops.py:181-332 on the decoded Detect output y [B, 4+nc, A] float32, on the device
+    (csrc/nms.hip): -> (det [B, max_det, 6] float32 rows (x1, y1, x2, y2, conf, cls) in kept order, zero past the count; count [B] int32).
+    Both stay on the device and nothing synchronises: the call can be captured in a graph.  Order: descending score, equal scores by
+    ascending anchor then class (the library's own tie rule).  The reference's wall-clock time limit is not reproduced."""
+    det, _, count = _detect_nms(y, None, conf_thres, iou_thres, multi_label, agnostic, classes, max_det, max_nms, max_wh)
     return det, count
+
+
+def detect_nms_seg(y, nc, conf_thres=0.25, iou_thres=0.45, *, multi_label=False, agnostic=False, classes=None, max_det=300, max_nms=30000, max_wh=7680):
+    """detect_nms on Segment's eval output y [B, 4 + nc + nm, A]: only rows 4 .. 4 + nc are scores -> (det [B, max_det, 6], coef [B, max_det, nm]
+    float32: the kept anchors' mask coefficient rows, zero past the count; count [B] int32).  det and count are detect_nms's on y[:, :4 + nc],
+    bit for bit; det stays six wide, so ops.scale_boxes, ops.val_match and Results take it unchanged.  Any nm >= 1."""
+    return _detect_nms(y, nc, conf_thres, iou_thres, multi_label, agnostic, classes, max_det, max_nms, max_wh)

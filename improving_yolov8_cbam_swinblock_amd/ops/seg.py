@@ -183,3 +183,82 @@ def detect_decode_seg(box_maps, cls_maps, mc_maps, strides):
     check(L().ymi_detect_decode_seg(nl, _map_array([t.detach() for t in box_maps]), _map_array([t.detach() for t in cls_maps]),
                                     _map_array([t.detach() for t in mc_maps]), st, ptr(y), stream_ptr()), "detect_decode_seg")
     return y
+
+
+# ---- mask decode and mask overlap (csrc/maskdec.hip) ---------------------------------------------------------------------------------
+MASK_MAX_BINS = 256  # YMI_MASK_MAX_BINS
+
+
+def _proto_map(proto, who):
+    """the prototype map as the kernels take it: [B, nm, mh, mw] bfloat16 / float32 in NHWC memory (what Proto's eval output is; anything
+    else is brought there)."""
+    if proto.dim() != 4:
+        raise ValueError(f"{who}: the prototype map is [B, nm, mh, mw], got {tuple(proto.shape)}")
+    if proto.shape[1] != NM:
+        raise NotImplementedError(f"{who}: the mask kernels are built for nm = {NM} prototypes, got {proto.shape[1]}")
+    if not proto.is_cuda:
+        raise RuntimeError("libyolo_mi355 kernels need tensors on the MI355X (cuda) device; there is no CPU path")
+    proto = proto.detach()
+    if proto.dtype not in (torch.float32, torch.bfloat16):
+        proto = proto.float()
+    if not is_nhwc(proto):
+        proto = proto.contiguous(memory_format=torch.channels_last)
+    return proto
+
+
+def process_mask(proto, box, coef, img, shape, upsample=False):
+    """process_mask of reference utils/ops.py:680-710 for rows of a whole batch, one launch (ymi_process_mask).  proto [B, 32, mh, mw]
+    (Proto's eval output); box [N, 4] float32 in the pixels of the network input `shape` = (ih, iw); coef [N, 32]; img [N] int: the row's
+    image (outside [0, B): a zero mask) -> (mask [N, mh, mw] (upsample=False) or [N, ih, iw] (upsample=True) uint8 0 / 1, area [N] int32: the
+    mask's sum).  Nothing synchronises."""
+    proto = _proto_map(proto, "process_mask")
+    n = int(box.shape[0])
+    ih, iw = int(shape[0]), int(shape[1])
+    if box.dim() != 2 or box.shape[1] != 4 or tuple(coef.shape) != (n, NM) or int(img.numel()) != n:
+        raise ValueError(f"process_mask: box {tuple(box.shape)}, coef {tuple(coef.shape)}, img {tuple(img.shape)} are not N rows of 4, {NM} and 1")
+    dev = proto.device
+    box = box.detach().to(dev, torch.float32).contiguous()
+    coef = coef.detach().to(dev, torch.float32).contiguous()
+    img = img.detach().to(dev).reshape(-1).to(torch.int32).contiguous()
+    oh, ow = (ih, iw) if upsample else (int(proto.shape[2]), int(proto.shape[3]))
+    mask = torch.empty((n, oh, ow), dtype=torch.uint8, device=dev)
+    area = torch.empty((n,), dtype=torch.int32, device=dev)
+    if n:
+        check(L().ymi_process_mask(_byref(as_ymi(proto)), ptr(box), ptr(coef), ptr(img), n, ih, iw, int(bool(upsample)), ptr(mask), ptr(area), stream_ptr()),
+              "process_mask")
+    return mask, area
+
+
+def mask_overlap(det, coef, count, proto, masks, shape, n_bins=MASK_MAX_BINS):
+    """the integer counts mask_iou needs, for a batch, one launch and no mask stack (ymi_mask_overlap).  det [B, max_det, 6], coef
+    [B, max_det, 32], count [B] as ops.detect_nms_seg leaves them (boxes in the pixels of the network input `shape` = (ih, iw)); proto
+    [B, 32, mh, mw]; masks [B, mh, mw] uint8 or float32: the batch's overlap encoding (0 background, v: the image's v-th object)
+    -> (inter [B, max_det, n_bins], area_pred [B, max_det], area_gt [B, n_bins]) int32 on the device.  An encoding of another size than the
+    prototype map is refused (the reference would resample it)."""
+    proto = _proto_map(proto, "mask_overlap")
+    b, max_det = int(det.shape[0]), int(det.shape[1])
+    if det.dim() != 3 or det.shape[2] != 6 or det.dtype != torch.float32 or not det.is_contiguous() or not det.is_cuda:
+        raise ValueError(f"mask_overlap takes a contiguous float32 [B, max_det, 6] device tensor, got {tuple(det.shape)} {det.dtype}")
+    if tuple(coef.shape) != (b, max_det, NM) or coef.dtype != torch.float32 or not coef.is_contiguous() or not coef.is_cuda:
+        raise ValueError(f"mask_overlap: coef is a contiguous float32 [B, max_det, {NM}] device tensor, got {tuple(coef.shape)} {coef.dtype}")
+    if count.dtype != torch.int32 or tuple(count.shape) != (b,) or not count.is_cuda or not count.is_contiguous():
+        raise ValueError("mask_overlap: count is an int32 [B] tensor on the device")
+    if masks.dim() != 3 or masks.shape[0] != b:
+        raise ValueError(f"mask_overlap: the overlap encoding is [B, mh, mw], got {tuple(masks.shape)} for {b} images")
+    if tuple(masks.shape[1:]) != tuple(proto.shape[2:]):
+        raise NotImplementedError(f"mask_overlap: the overlap encoding is {tuple(masks.shape[1:])}, the prototype map {tuple(proto.shape[2:])}; "
+                                  "resampling the encoding (reference segment/val.py:266-268) is not built")
+    if not 1 <= int(n_bins) <= MASK_MAX_BINS:
+        raise ValueError(f"mask_overlap: n_bins in [1, {MASK_MAX_BINS}], got {n_bins}")
+    dev = det.device
+    masks = masks.detach().to(dev)
+    if masks.dtype not in (torch.uint8, torch.float32):
+        masks = masks.float()
+    masks = masks.contiguous()
+    inter = torch.empty((b, max_det, int(n_bins)), dtype=torch.int32, device=dev)
+    area_pred = torch.empty((b, max_det), dtype=torch.int32, device=dev)
+    area_gt = torch.empty((b, int(n_bins)), dtype=torch.int32, device=dev)
+    check(L().ymi_mask_overlap(ptr(det.detach()), ptr(coef.detach()), ptr(count), b, max_det, _byref(as_ymi(proto)), int(shape[0]), int(shape[1]), ptr(masks),
+                               int(masks.dtype == torch.float32), masks.shape[1], masks.shape[2], int(n_bins), ptr(inter), ptr(area_pred), ptr(area_gt),
+                               stream_ptr()), "mask_overlap")
+    return inter, area_pred, area_gt

@@ -58,3 +58,37 @@ def val_match(det, count, batch_idx, cls, bboxes, img_shape, levels, ori_shapes=
     check(L().ymi_val_match(ptr(det.detach()), ptr(count), b, max_det, ptr(lab_img), ptr(lab_cls), ptr(lab_box), n_lab, float(img_shape[1]), float(img_shape[0]),
                             ptr(native), arr, len(lv), int(bool(single_cls)), ptr(tp), ptr(cm), nc, float(cm_conf), float(cm_iou), stream_ptr()), "val_match")
     return tp
+
+
+def val_match_masks(det, count, batch_idx, cls, inter, area_pred, area_gt, levels, single_cls=False):
+    """val_match's tp rule with mask_iou in place of box_iou (reference models/yolo/segment/val.py:231-273, overlap=True), one launch
+    (ymi_val_match_masks): the overlap of detection d with the image's j-th label (table order) is
+    inter[d, j + 1] / ((area_gt[j + 1] + area_pred[d]) - inter[d, j + 1] + 1e-7) in float32 on ops.mask_overlap's integer counts; labels at or
+    beyond n_bins - 1 overlap nothing.  -> tp_m [B, max_det, len(levels)] uint8 on the device, zero past the count."""
+    if not det.is_cuda:
+        raise RuntimeError("libyolo_mi355 kernels need tensors on the MI355X (cuda) device; there is no CPU path")
+    if det.dim() != 3 or det.shape[2] != 6 or det.dtype != torch.float32 or not det.is_contiguous():
+        raise ValueError(f"val_match_masks takes a contiguous float32 [B, max_det, 6] tensor, got {tuple(det.shape)} {det.dtype}")
+    b, max_det = int(det.shape[0]), int(det.shape[1])
+    if not 1 <= max_det <= VALMATCH_MAX_DET or b < 1:
+        raise ValueError(f"val_match_masks: max_det in [1, {VALMATCH_MAX_DET}] and at least one image, got {tuple(det.shape)}")
+    if count.dtype != torch.int32 or tuple(count.shape) != (b,) or not count.is_cuda or not count.is_contiguous():
+        raise ValueError("val_match_masks: count is an int32 [B] tensor on the device")
+    n_bins = int(inter.shape[-1])
+    for name, t, shape in (("inter", inter, (b, max_det, n_bins)), ("area_pred", area_pred, (b, max_det)), ("area_gt", area_gt, (b, n_bins))):
+        if tuple(t.shape) != shape or t.dtype != torch.int32 or not t.is_cuda or not t.is_contiguous():
+            raise ValueError(f"val_match_masks: {name} is a contiguous int32 {shape} device tensor, got {tuple(t.shape)} {t.dtype}")
+    lv = [float(v) for v in (levels.tolist() if torch.is_tensor(levels) else levels)]
+    if not 1 <= len(lv) <= VALMATCH_MAX_LEVELS:
+        raise ValueError(f"val_match_masks: 1 to {VALMATCH_MAX_LEVELS} IoU levels, got {len(lv)}")
+    dev = det.device
+    n_lab = int(batch_idx.numel())
+    if int(cls.numel()) != n_lab:
+        raise ValueError(f"val_match_masks: {n_lab} batch_idx rows, {cls.numel()} classes")
+    lab_img = batch_idx.detach().to(dev).reshape(-1).to(torch.int32).contiguous()
+    lab_cls = cls.detach().to(dev).reshape(-1).float().contiguous()
+    tp = torch.empty((b, max_det, len(lv)), dtype=torch.uint8, device=dev)
+    arr = (ctypes.c_float * len(lv))(*lv)
+    check(L().ymi_val_match_masks(ptr(det.detach()), ptr(count), b, max_det, ptr(lab_img), ptr(lab_cls), n_lab, ptr(inter), ptr(area_pred), ptr(area_gt), n_bins,
+                                  arr, len(lv), int(bool(single_cls)), ptr(tp), stream_ptr()), "val_match_masks")
+    return tp

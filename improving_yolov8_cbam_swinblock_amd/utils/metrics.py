@@ -1,4 +1,5 @@
-"""Detection metrics under the reference's public names: box_iou, match_predictions, ConfusionMatrix, compute_ap, ap_per_class, Metric, DetMetrics.
+"""Detection metrics under the reference's public names: box_iou, mask_iou, match_predictions, ConfusionMatrix, compute_ap, ap_per_class, Metric, DetMetrics,
+SegmentMetrics.
 
 The text of this module is the project's own, written from the definitions of the quantities.  What is shared with the reference
 (ultralytics/utils/metrics.py, engine/validator.py) is the interface - names, signatures, result keys - and the numbers: the tp matrices and
@@ -257,3 +258,43 @@ class DetMetrics:
         out = dict(zip(self.keys, self.mean_results()))
         out["fitness"] = self.fitness
         return out
+
+
+def mask_iou(mask1, mask2, eps=1e-7):
+    """[N, n] x [M, n] flattened 0 / 1 masks -> [N, M] IoU in float32: inter / ((area1 + area2) - inter + eps) (reference utils/metrics.py:137).
+    Every sum is an integer count, exact in float32 below 2^24 pixels, so the result does not depend on the order of summation; the device
+    path forms the same quotient from ops.mask_overlap's integer counts (ops.val_match_masks)."""
+    a, b = torch.as_tensor(mask1).float(), torch.as_tensor(mask2).float()
+    inter = torch.matmul(a, b.T).clamp_(0)
+    union = (a.sum(1)[:, None] + b.sum(1)[None]) - inter
+    return inter / (union + eps)
+
+
+class SegmentMetrics:
+    """box and mask precision, recall, mAP50 and mAP50-95 of a segmentation model from the validator's statistics (reference
+    utils/metrics.py:932-1066); fitness is the sum of the two Metrics' fitness."""
+
+    keys = [f"metrics/{k}({t})" for t in "BM" for k in ("precision", "recall", "mAP50", "mAP50-95")]
+
+    def __init__(self, names=None):
+        self.names = dict(names or {})
+        self.box, self.seg = Metric(), Metric()
+
+    def process(self, tp, tp_m, conf, pred_cls, target_cls):
+        self.seg.nc = self.box.nc = len(self.names)
+        self.seg.update(ap_per_class(tp_m, conf, pred_cls, target_cls)[2:])
+        self.box.update(ap_per_class(tp, conf, pred_cls, target_cls)[2:])
+
+    def mean_results(self):
+        return self.box.mean_results() + self.seg.mean_results()
+
+    def class_result(self, i):
+        return self.box.class_result(i) + self.seg.class_result(i)
+
+    maps = property(lambda self: self.box.maps + self.seg.maps)
+    fitness = property(lambda self: self.seg.fitness() + self.box.fitness())
+    ap_class_index = property(lambda self: self.box.ap_class_index)
+
+    @property
+    def results_dict(self):
+        return dict(zip(self.keys + ["fitness"], self.mean_results() + [self.fitness]))

@@ -476,6 +476,39 @@ int ymi_detect_nms_sizes(int64_t batch, int64_t anchors, int64_t nc, int64_t max
 int ymi_detect_nms(const float* y, int64_t batch, int64_t nc, int64_t anchors, float conf_thres, float iou_thres, int32_t multi_label,
                    int32_t agnostic, const int32_t* host_classes, int32_t n_classes, int64_t max_det, int64_t max_nms, float max_wh, float* det,
                    int32_t* count, void* workspace, size_t workspace_bytes, void* stream);
+/* The same on Segment's eval output y [B][4 + nc + nm][A] (ymi_detect_decode_seg): only rows 4 .. 4 + nc are scores; every decision, and so det
+ * and count, are ymi_detect_nms's on y[:, :4 + nc], bit for bit.  coef [B][max_det][nm] float32 receives y[b][4 + nc + m][a] of the kept
+ * anchors, zero past the count.  Any nm >= 1; the workspace is ymi_detect_nms_sizes's. */
+int ymi_detect_nms_seg(const float* y, int64_t batch, int64_t nc, int64_t nm, int64_t anchors, float conf_thres, float iou_thres, int32_t multi_label,
+                       int32_t agnostic, const int32_t* host_classes, int32_t n_classes, int64_t max_det, int64_t max_nms, float max_wh, float* det,
+                       int32_t* count, float* coef, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------- mask decode ---- */
+/* process_mask / crop_mask (utils/ops.py:661-710) and the counts of mask_iou (utils/metrics.py:137), csrc/maskdec.hip.  One launch each, grids
+ * from shapes only, no workspace, nothing read back; the only atomics are integer adds.  proto: the prototype map [B][nm][mh][mw] as Proto's
+ * eval output has it (logical NCHW, NHWC memory: n = B, h = mh, w = mw, c = nm = YMI_MASK_NM, 16-byte aligned pixels), bfloat16 or float32.
+ * (ih, iw): the network input's size, the space the boxes are in.
+ *   logit      : the float32 sum over m of coef[m] * proto[b][m][r][c], channel order, one fused multiply-add per term
+ *   crop       : x1' = x1 * float32(mw / iw), x2' likewise, y1' = y1 * float32(mh / ih), y2' likewise (one rounded product each); pixel (r, c)
+ *                is inside when c >= x1' && c < x2' && r >= y1' && r < y2'; the cropped logit is 0 outside
+ * ymi_process_mask: box [n][4] float32, coef [n][nm] float32, img [n] int32 (the row's image; outside [0, B): a zero mask) ->
+ *   mask [n][oh][ow] uint8 (0 / 1), area [n] int32 (the mask's sum).  upsample == 0: (oh, ow) = (mh, mw), mask = cropped logit > 0.
+ *   upsample != 0: (oh, ow) = (ih, iw) >= (mh, mw): the cropped logits resampled as F.interpolate(mode="bilinear", align_corners=False) does
+ *   (the index and weight rule of ymi_scale_image), then > 0.
+ * ymi_mask_overlap: det [batch][max_det][6], count [batch] and coef [batch][max_det][nm] as ymi_detect_nms_seg leaves them, boxes in network-
+ *   input pixels; masks [batch][masks_h][masks_w]: the overlap encoding (0 background, v the image's v-th object), uint8 or float32
+ *   (masks_f32 != 0), of the prototype map's size (other sizes are refused: the reference would resample) ->
+ *   inter [batch][max_det][n_bins], area_pred [batch][max_det], area_gt [batch][n_bins] int32, n_bins <= YMI_MASK_MAX_BINS: over the pixels inside
+ *   detection d's crop with logit > 0, area_pred counts one and inter[.][v] counts one where the encoding is v < n_bins; area_gt[v] counts
+ *   the image's pixels whose encoding is v.  Rows at or beyond count[b] are zero.  mask_iou(label j, detection d) is then
+ *   inter[d][j + 1] / ((area_gt[j + 1] + area_pred[d]) - inter[d][j + 1] + 1e-7f), every operand an exact integer (ymi_val_match_masks). */
+#define YMI_MASK_NM 32
+#define YMI_MASK_MAX_BINS 256
+int ymi_process_mask(const ymi_tensor* proto, const float* box, const float* coef, const int32_t* img, int64_t n, int64_t ih, int64_t iw,
+                     int32_t upsample, uint8_t* mask, int32_t* area, void* stream);
+int ymi_mask_overlap(const float* det, const float* coef, const int32_t* count, int64_t batch, int64_t max_det, const ymi_tensor* proto, int64_t ih,
+                     int64_t iw, const void* masks, int32_t masks_f32, int64_t masks_h, int64_t masks_w, int64_t n_bins, int32_t* inter,
+                     int32_t* area_pred, int32_t* area_gt, void* stream);
 
 /* ------------------------------------------------------------------------ image rescaling ---- */
 /* F.interpolate(mode="bilinear", align_corners=False) of an image batch with what the reference does around it, as one launch
@@ -659,6 +692,14 @@ int ymi_augment_boxes(const float* rows, int64_t n, const ymi_augment_label_imag
 int ymi_val_match(const float* det, const int32_t* count, int64_t batch, int64_t max_det, const int32_t* lab_img, const float* lab_cls,
                   const float* lab_box, int64_t n_labels, float img_w, float img_h, const float* native, const float* levels, int32_t n_levels,
                   int32_t single_cls, uint8_t* tp, int32_t* cm, int64_t nc, float cm_conf, float cm_iou, void* stream);
+/* The tp rule above with mask_iou in place of box_iou (models/yolo/segment/val.py:231-273 with overlap=True), the same kernel body: the overlap
+ * of detection d with the image's j-th label in table order is, in float32, one rounding per operation,
+ *   inter[b][d][j + 1] / (((area_gt[b][j + 1] + area_pred[b][d]) - inter[b][d][j + 1]) + 1e-7f)
+ * on the counts ymi_mask_overlap leaves; labels with j + 1 >= n_bins overlap nothing.  Claims, ties, levels and single_cls as in ymi_val_match.
+ * -> tp_m [batch][max_det][n_levels] uint8.  No confusion matrix: that stays box-based. */
+int ymi_val_match_masks(const float* det, const int32_t* count, int64_t batch, int64_t max_det, const int32_t* lab_img, const float* lab_cls,
+                        int64_t n_labels, const int32_t* inter, const int32_t* area_pred, const int32_t* area_gt, int64_t n_bins, const float* levels,
+                        int32_t n_levels, int32_t single_cls, uint8_t* tp_m, void* stream);
 
 /* ------------------------------------------------------------------------- optimizer step ---- */
 /* The update either side of backward, reference engine/trainer.py:614-622 (optimizer_step: clip_grad_norm_(10.0),
