@@ -17,6 +17,8 @@ struct CV {
     const void* p;
     int64_t ld;
 };
+// every kernel here reads and writes 4-element Packs (8 B bf16 / 16 B f32): c, ld and the base must all be 4-element aligned
+static inline bool cbam_base_ok(const ymi_tensor* t) { return ((uintptr_t)t->data % (4 * ymi_esize(t->dtype))) == 0; }
 
 // ---------------------------------------------------------------------------------- forward
 // grid (ceil(C/CB), N); block 256 = (CB/4 channel groups) x pixel lanes
@@ -194,6 +196,7 @@ extern "C" int ymi_cbam_fwd(const ymi_tensor* x, const float* w1, const float* w
     YMI_CHECK_ARG(ymi_tensor_ok(x) && ymi_tensor_ok(out) && ymi_same_shape(x, out) && x->dtype == out->dtype, "cbam_fwd: tensors");
     YMI_CHECK_ARG(w1 && w2 && wsa && ca && pooled && pool_argmax && smap && smap_argmax && sa, "cbam_fwd: null buffer");
     YMI_CHECK_ARG(x->c % 4 == 0 && x->ld % 4 == 0 && out->ld % 4 == 0, "cbam_fwd: channels must be a multiple of 4");
+    YMI_CHECK_ARG(cbam_base_ok(x) && cbam_base_ok(out), "cbam_fwd: tensors must start on a 4-element boundary");
     YMI_CHECK_ARG(hidden >= 1 && hidden <= 1024 && (ksa == 3 || ksa == 7), "cbam_fwd: hidden/kernel");
     hipStream_t s = (hipStream_t)stream;
     const int N = (int)x->n, H = (int)x->h, W = (int)x->w, C = (int)x->c, HW = H * W;
@@ -472,7 +475,9 @@ extern "C" int ymi_cbam_bwd(const ymi_tensor* x, const ymi_tensor* dout, const f
     YMI_CHECK_ARG(ymi_tensor_ok(x) && ymi_tensor_ok(dout) && ymi_tensor_ok(dx) && ymi_same_shape(x, dout) && ymi_same_shape(x, dx), "cbam_bwd: tensors");
     YMI_CHECK_ARG(x->dtype == dout->dtype && x->dtype == dx->dtype, "cbam_bwd: dtypes");
     YMI_CHECK_ARG(x->c % 4 == 0 && x->c <= 1024 && x->ld % 4 == 0 && dout->ld % 4 == 0 && dx->ld % 4 == 0, "cbam_bwd: channels multiple of 4, <= 1024");
+    YMI_CHECK_ARG(cbam_base_ok(x) && cbam_base_ok(dout) && cbam_base_ok(dx), "cbam_bwd: tensors must start on a 4-element boundary");
     YMI_CHECK_ARG(w1 && w2 && wsa && ca && pooled && pool_argmax && smap && smap_argmax && sa && dw1 && dw2 && dwsa && workspace, "cbam_bwd: null buffer");
+    YMI_CHECK_ARG(hidden >= 1 && hidden <= 1024 && (ksa == 3 || ksa == 7), "cbam_bwd: hidden/kernel");
     const int N = (int)x->n, H = (int)x->h, W = (int)x->w, C = (int)x->c, HW = H * W, Hd = (int)hidden, K = (int)ksa;
     const size_t need = ymi_cbam_bwd_workspace(N, H, W, C, Hd);
     if (workspace_bytes < need) {

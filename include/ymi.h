@@ -330,7 +330,9 @@ int ymi_sppf_pool3_bwd(const ymi_tensor* y0, const ymi_tensor* y1, const ymi_ten
 /* out = x * ca * sa with ca = sigmoid(MLP(avg) + MLP(max)) (nn/modules/cbam.py:29-38),
  * sa = sigmoid(conv7x7([mean_c(x*ca), max_c(x*ca)])) (cbam.py:48-53), composed as cbam.py:62-71.
  * w1: [hidden][C] f32, w2: [C][hidden] f32, wsa: [2][k][k] f32.  Saved for backward: ca [N][C] f32,
- * smap [N][H][W][2] f32 (mean,max of x*ca), sa [N][H][W] f32, and the arg-max indices. */
+ * smap [N][H][W][2] f32 (mean,max of x*ca), sa [N][H][W] f32, and the arg-max indices.
+ * x, out, dout, dx: c and ld multiples of 4 and the base on a 4-element boundary (YMI_EINVAL otherwise);
+ * k = 3 or 7, 1 <= hidden <= 1024, and C <= 1024 in the backward. */
 int ymi_cbam_fwd(const ymi_tensor* x, const float* w1, const float* w2, int64_t hidden, const float* wsa, int64_t ksa,
                  const ymi_tensor* out, float* ca, float* pooled /*[N][2][C]*/, int32_t* pool_argmax /*[N][C]*/, float* smap,
                  int32_t* smap_argmax /*[N][H][W]*/, float* sa, void* stream);
