@@ -11,16 +11,75 @@
 // load, wave-reduce), apply (k*k*2-tap stencil from the tiny f32 map + final scale).  x is streamed
 // 3 times (pool, stats, apply) and out written once; the second and third reads hit L2 / Infinity
 // Cache for the shapes of this model (26 MB at bs 32).
+#include <initializer_list>
+
 #include "common.h"
 
 struct CV {
     const void* p;
     int64_t ld;
 };
-// every kernel here reads and writes 4-element Packs (8 B bf16 / 16 B f32): c, ld and the base must all be 4-element aligned
-static inline bool cbam_base_ok(const ymi_tensor* t) { return ((uintptr_t)t->data % (4 * ymi_esize(t->dtype))) == 0; }
+// every kernel here reads and writes 4-element Packs (common.h: vec4_ok); row p of a view
+template <typename T> __device__ __forceinline__ T* row(CV v, int64_t p) { return reinterpret_cast<T*>(const_cast<void*>(v.p)) + p * v.ld; }
+
+// ---- the rules the kernels share ---------------------------------------------------------------------------------------------------
+// a wave and its pixel: p = n * HW + q of the batch, the ca row of its image
+struct PixWave {
+    int lane, n, q;
+    int64_t p;
+    bool live;
+    const float* cap;
+};
+__device__ __forceinline__ PixWave pix_wave(int64_t p, int n, int HW, int C, const float* ca, bool live = true) {
+    return PixWave{(int)(threadIdx.x & 63), n, (int)(p - (int64_t)n * HW), p, live, ca + (int64_t)n * C};
+}
+// the launches of ceil(NP / 4) workgroups of four waves: wave w of workgroup b has pixel 4 b + w
+__device__ __forceinline__ PixWave grid_pix_wave(int64_t NP, int HW, int C, const float* ca) {
+    const int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    return pix_wave(p, (int)(p / HW), HW, C, ca, p < NP);
+}
+// a lane's channel groups c .. c + 3: 256 channels a trip
+template <typename F> __device__ __forceinline__ void for_chan4(int C, int lane, F&& f) { for (int c = lane * 4; c < C; c += 256) f(c); }
+__device__ __forceinline__ bool in_map(int h, int w, int H, int W) { return h >= 0 && h < H && w >= 0 && w < W; }
+// f(t, q) for this lane's taps t of the K x K stencil around (h, w) whose neighbour q = hh * W + ww lies in the map; SIGN -1: the adjoint's p - off_t
+template <int SIGN, typename F> __device__ __forceinline__ void stencil_taps(int h, int w, int H, int W, int K, int lane, F&& f) {
+    for (int t = lane, R = K / 2; t < K * K; t += 64) {
+        const int hh = h + SIGN * (t / K - R), ww = w + SIGN * (t % K - R);
+        if (in_map(hh, ww, H, W)) f(t, hh * W + ww);
+    }
+}
+// the first maximum: in scan order strictly greater wins; two scans combine by "greater, or equal with the lower index"
+__device__ __forceinline__ void first_max_scan(float v, int i, float& m, int& bi) { if (v > m) { m = v; bi = i; } }
+__device__ __forceinline__ void first_max_merge(float v, int i, float& m, int& bi) { if (v > m || (v == m && i < bi)) { m = v; bi = i; } }
+// the channel MLP's first layer (both MLP kernels): pooled[n] into LDS; hidden unit h of this wave, a = W1[h] avg and m = W1[h] max by lanes,
+// then wave_sum.  extra(c) rides in the same trip (the kernels are chains of load latencies: every round of loads is issued together)
+__device__ __forceinline__ void stage_pooled(const float* pooled, int n, int C, float* sp) {
+    for (int i = threadIdx.x, nt = blockDim.x; i < 2 * C; i += nt) sp[i] = pooled[(int64_t)n * 2 * C + i];
+}
+template <typename F> __device__ __forceinline__ void hidden_unit(const float* w1, const float* sp, int C, int h, int lane, float& a, float& m, F&& extra) {
+    float acc_m = 0.f, acc_a = 0.f;  // (in this order: declared a first, the compiler pairs the two chains as (m, a) and cbam_mlp_kernel takes 66 VGPRs for 60)
+    const float* wr = w1 + (int64_t)h * C;
+#pragma unroll 8
+    for (int c = lane; c < C; c += 64) {
+        const float w = wr[c];
+        acc_a += w * sp[c];
+        acc_m += w * sp[C + c];
+        extra(c);
+    }
+    a = wave_sum(acc_a);
+    m = wave_sum(acc_m);
+}
+__device__ __forceinline__ float relu_sum(float a, float m) { return fmaxf(a, 0.f) + fmaxf(m, 0.f); }
 
 // ---------------------------------------------------------------------------------- forward
+// one pixel of a pixel lane's four channels (a function: as a lambda that captures the three arrays the loops' adds and compares come out in another order)
+__device__ __forceinline__ void pool_pixel(const float (&v)[4], int p, float (&sum)[4], float (&mx)[4], int (&ix)[4]) {
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+        sum[r] += v[r];
+        first_max_scan(v[r], p, mx[r], ix[r]);
+    }
+}
 // grid (ceil(C/CB), N); block 256 = (CB/4 channel groups) x pixel lanes
 template <typename T>
 __global__ __launch_bounds__(256) void cbam_pool_kernel(CV x, int HW, int C, float* __restrict__ pooled, int* __restrict__ amax) {
@@ -32,7 +91,7 @@ __global__ __launch_bounds__(256) void cbam_pool_kernel(CV x, int HW, int C, flo
     __shared__ int s_idx[PY][CB];
     const int gx = threadIdx.x % GX, py = threadIdx.x / GX;
     const int n = blockIdx.y, c = blockIdx.x * CB + gx * 4;
-    const T* xp = reinterpret_cast<const T*>(x.p) + (int64_t)n * HW * x.ld;
+    const T* xp = row<T>(x, (int64_t)n * HW);
     float sum[4] = {0.f, 0.f, 0.f, 0.f}, mx[4];
     int ix[4] = {0, 0, 0, 0};
 #pragma unroll
@@ -44,21 +103,12 @@ __global__ __launch_bounds__(256) void cbam_pool_kernel(CV x, int HW, int C, flo
 #pragma unroll
             for (int u = 0; u < 4; ++u) Pack<T, 4>::load(xp + (int64_t)(p + u * PY) * x.ld + c, v[u]);
 #pragma unroll
-            for (int u = 0; u < 4; ++u)
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    sum[r] += v[u][r];
-                    if (v[u][r] > mx[r]) { mx[r] = v[u][r]; ix[r] = p + u * PY; }  // strictly greater: first maximum in scan order
-                }
+            for (int u = 0; u < 4; ++u) pool_pixel(v[u], p + u * PY, sum, mx, ix);
         }
         for (; p < HW; p += PY) {
             float v[4];
             Pack<T, 4>::load(xp + (int64_t)p * x.ld + c, v);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                sum[r] += v[r];
-                if (v[r] > mx[r]) { mx[r] = v[r]; ix[r] = p; }
-            }
+            pool_pixel(v, p, sum, mx, ix);
         }
     }
 #pragma unroll
@@ -75,9 +125,7 @@ __global__ __launch_bounds__(256) void cbam_pool_kernel(CV x, int HW, int C, flo
             int bi = 0;
             for (int q = 0; q < PY; ++q) {
                 s += s_sum[q][threadIdx.x];
-                const float v = s_max[q][threadIdx.x];
-                const int i2 = s_idx[q][threadIdx.x];
-                if (v > m || (v == m && i2 < bi)) { m = v; bi = i2; }
+                first_max_merge(s_max[q][threadIdx.x], s_idx[q][threadIdx.x], m, bi);
             }
             pooled[((int64_t)n * 2 + 0) * C + cc] = s / (float)HW;
             pooled[((int64_t)n * 2 + 1) * C + cc] = m;
@@ -94,21 +142,13 @@ __global__ __launch_bounds__(1024) void cbam_mlp_kernel(const float* __restrict_
     float* sp = sh;
     float* hs = sh + 2 * C;
     const int n = blockIdx.x, nt = blockDim.x, nw = nt >> 6;
-    for (int i = threadIdx.x; i < 2 * C; i += nt) sp[i] = pooled[(int64_t)n * 2 * C + i];
+    stage_pooled(pooled, n, C, sp);
     __syncthreads();
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     for (int h = wave; h < Hd; h += nw) {
-        float a = 0.f, m = 0.f;
-        const float* wr = w1 + (int64_t)h * C;
-#pragma unroll 8
-        for (int c = lane; c < C; c += 64) {
-            const float w = wr[c];
-            a += w * sp[c];
-            m += w * sp[C + c];
-        }
-        a = wave_sum(a);
-        m = wave_sum(m);
-        if (lane == 0) hs[h] = fmaxf(a, 0.f) + fmaxf(m, 0.f);
+        float a, m;
+        hidden_unit(w1, sp, C, h, lane, a, m, [](int) {});
+        if (lane == 0) hs[h] = relu_sum(a, m);
     }
     __syncthreads();
     for (int c = threadIdx.x; c < C; c += nt) {
@@ -124,35 +164,28 @@ __global__ __launch_bounds__(1024) void cbam_mlp_kernel(const float* __restrict_
 template <typename T>
 __global__ __launch_bounds__(256) void cbam_stats_kernel(CV x, int64_t NP, int HW, int C, const float* __restrict__ ca, float* __restrict__ smap,
                                                          int* __restrict__ sarg) {
-    const int lane = threadIdx.x & 63;
-    const int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (p >= NP) return;
-    const int n = (int)(p / HW);
-    const T* xp = reinterpret_cast<const T*>(x.p) + p * x.ld;
-    const float* cap = ca + (int64_t)n * C;
+    const PixWave pw = grid_pix_wave(NP, HW, C, ca);
+    if (!pw.live) return;
+    const T* xp = row<T>(x, pw.p);
     float s = 0.f, m = -__builtin_inff();
     int mi = 0x7fffffff;
-    for (int c = lane * 4; c < C; c += 256) {
+    for_chan4(C, pw.lane, [&](int c) {
         float v[4];
         Pack<T, 4>::load(xp + c, v);
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            const float t = v[r] * cap[c + r];
+            const float t = v[r] * pw.cap[c + r];
             s += t;
-            if (t > m) { m = t; mi = c + r; }
+            first_max_scan(t, c + r, m, mi);
         }
-    }
+    });
     s = wave_sum(s);
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float om = __shfl_xor(m, o, 64);
-        const int oi = __shfl_xor(mi, o, 64);
-        if (om > m || (om == m && oi < mi)) { m = om; mi = oi; }
-    }
-    if (lane == 0) {
-        smap[p * 2 + 0] = s / (float)C;
-        smap[p * 2 + 1] = m;
-        sarg[p] = mi;
+    for (int o = 32; o > 0; o >>= 1) first_max_merge(__shfl_xor(m, o, 64), __shfl_xor(mi, o, 64), m, mi);
+    if (pw.lane == 0) {
+        smap[pw.p * 2 + 0] = s / (float)C;
+        smap[pw.p * 2 + 1] = m;
+        sarg[pw.p] = mi;
     }
 }
 
@@ -161,60 +194,56 @@ template <typename T>
 __global__ __launch_bounds__(256) void cbam_apply_kernel(CV x, CV out, int N, int H, int W, int C, const float* __restrict__ ca,
                                                          const float* __restrict__ smap, const float* __restrict__ wsa, int K,
                                                          float* __restrict__ sa_out) {
-    const int lane = threadIdx.x & 63;
-    const int64_t NP = (int64_t)N * H * W;
-    const int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (p >= NP) return;
-    const int w = (int)(p % W), h = (int)((p / W) % H), n = (int)(p / ((int64_t)W * H));
-    const int R = K / 2;
+    const PixWave pw = grid_pix_wave((int64_t)N * H * W, H * W, C, ca);
+    if (!pw.live) return;
+    const float* sm = smap + (int64_t)pw.n * H * W * 2;
     float u = 0.f;
-    for (int t = lane; t < K * K; t += 64) {
-        const int hh = h + t / K - R, ww = w + t % K - R;
-        if (hh >= 0 && hh < H && ww >= 0 && ww < W) {
-            const int64_t q = ((int64_t)n * H + hh) * W + ww;
-            u += wsa[t] * smap[q * 2 + 0] + wsa[K * K + t] * smap[q * 2 + 1];
-        }
-    }
+    stencil_taps<1>(pw.q / W, pw.q % W, H, W, K, pw.lane, [&](int t, int q) { u += wsa[t] * sm[q * 2 + 0] + wsa[K * K + t] * sm[q * 2 + 1]; });
     u = wave_sum(u);
     const float sa = sigmoidf_(u);
-    if (lane == 0) sa_out[p] = sa;
-    const T* xp = reinterpret_cast<const T*>(x.p) + p * x.ld;
-    T* op = reinterpret_cast<T*>(const_cast<void*>(out.p)) + p * out.ld;
-    const float* cap = ca + (int64_t)n * C;
-    for (int c = lane * 4; c < C; c += 256) {
+    if (pw.lane == 0) sa_out[pw.p] = sa;
+    const T* xp = row<T>(x, pw.p);
+    T* op = row<T>(out, pw.p);
+    for_chan4(C, pw.lane, [&](int c) {
         float v[4];
         Pack<T, 4>::load(xp + c, v);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = v[r] * cap[c + r] * sa;
+        for (int r = 0; r < 4; ++r) v[r] = v[r] * pw.cap[c + r] * sa;
         Pack<T, 4>::store(op + c, v);
-    }
+    });
+}
+
+// ---------------------------------------------------------------------------------- host side
+template <typename... P, typename... Q> static void launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds, hipStream_t s, Q... args) {
+    hipLaunchKernelGGL(kernel, grid, block, lds, s, args...);
+}
+// what the forward and the backward ask of their maps (the first gives shape and dtype) and of hidden / ksa
+static int cbam_check(const char* entry, std::initializer_list<const ymi_tensor*> maps, int64_t hidden, int64_t ksa) {
+    const ymi_tensor* x = *maps.begin();
+    for (const ymi_tensor* t : maps) YMI_CHECK_ARG(ymi_tensor_ok(t) && ymi_same_shape(x, t) && x->dtype == t->dtype, "%s: tensors", entry);
+    for (const ymi_tensor* t : maps) YMI_CHECK_ARG(vec4_ok(t), "%s: channels, ld and the base of every tensor must be multiples of 4 elements", entry);
+    YMI_CHECK_ARG(hidden >= 1 && hidden <= 1024 && (ksa == 3 || ksa == 7), "%s: hidden/kernel", entry);
+    return YMI_OK;
 }
 
 extern "C" int ymi_cbam_fwd(const ymi_tensor* x, const float* w1, const float* w2, int64_t hidden, const float* wsa, int64_t ksa,
                             const ymi_tensor* out, float* ca, float* pooled, int32_t* pool_argmax, float* smap, int32_t* smap_argmax,
                             float* sa, void* stream) {
-    YMI_CHECK_ARG(ymi_tensor_ok(x) && ymi_tensor_ok(out) && ymi_same_shape(x, out) && x->dtype == out->dtype, "cbam_fwd: tensors");
+    if (int rc = cbam_check("cbam_fwd", {x, out}, hidden, ksa)) return rc;
     YMI_CHECK_ARG(w1 && w2 && wsa && ca && pooled && pool_argmax && smap && smap_argmax && sa, "cbam_fwd: null buffer");
-    YMI_CHECK_ARG(x->c % 4 == 0 && x->ld % 4 == 0 && out->ld % 4 == 0, "cbam_fwd: channels must be a multiple of 4");
-    YMI_CHECK_ARG(cbam_base_ok(x) && cbam_base_ok(out), "cbam_fwd: tensors must start on a 4-element boundary");
-    YMI_CHECK_ARG(hidden >= 1 && hidden <= 1024 && (ksa == 3 || ksa == 7), "cbam_fwd: hidden/kernel");
     hipStream_t s = (hipStream_t)stream;
     const int N = (int)x->n, H = (int)x->h, W = (int)x->w, C = (int)x->c, HW = H * W;
     const int64_t NP = (int64_t)N * HW;
     CV xv{x->data, x->ld}, ov{out->data, out->ld};
     dim3 gp((C + 63) / 64, N), gw((unsigned)((NP + 3) / 4));
     const size_t mlp_lds = (size_t)(2 * C + hidden) * sizeof(float);
-    if (x->dtype == YMI_BF16) {
-        hipLaunchKernelGGL(cbam_pool_kernel<bf16_t>, gp, dim3(256), 0, s, xv, HW, C, pooled, pool_argmax);
-        hipLaunchKernelGGL(cbam_mlp_kernel, dim3(N), dim3(1024), mlp_lds, s, pooled, w1, w2, C, (int)hidden, ca);
-        hipLaunchKernelGGL(cbam_stats_kernel<bf16_t>, gw, dim3(256), 0, s, xv, NP, HW, C, ca, smap, smap_argmax);
-        hipLaunchKernelGGL(cbam_apply_kernel<bf16_t>, gw, dim3(256), 0, s, xv, ov, N, H, W, C, ca, smap, wsa, (int)ksa, sa);
-    } else {
-        hipLaunchKernelGGL(cbam_pool_kernel<float>, gp, dim3(256), 0, s, xv, HW, C, pooled, pool_argmax);
-        hipLaunchKernelGGL(cbam_mlp_kernel, dim3(N), dim3(1024), mlp_lds, s, pooled, w1, w2, C, (int)hidden, ca);
-        hipLaunchKernelGGL(cbam_stats_kernel<float>, gw, dim3(256), 0, s, xv, NP, HW, C, ca, smap, smap_argmax);
-        hipLaunchKernelGGL(cbam_apply_kernel<float>, gw, dim3(256), 0, s, xv, ov, N, H, W, C, ca, smap, wsa, (int)ksa, sa);
-    }
+    dispatch_dtype(x->dtype, [&](auto t) {
+        typedef typename decltype(t)::type T;
+        launch(cbam_pool_kernel<T>, gp, dim3(256), 0, s, xv, HW, C, pooled, pool_argmax);
+        launch(cbam_mlp_kernel, dim3(N), dim3(1024), mlp_lds, s, pooled, w1, w2, C, (int)hidden, ca);
+        launch(cbam_stats_kernel<T>, gw, dim3(256), 0, s, xv, NP, HW, C, ca, smap, smap_argmax);
+        launch(cbam_apply_kernel<T>, gw, dim3(256), 0, s, xv, ov, N, H, W, C, ca, smap, wsa, (int)ksa, sa);
+    });
     YMI_CHECK_LAUNCH("cbam_fwd");
     return YMI_OK;
 }
@@ -224,25 +253,22 @@ extern "C" int ymi_cbam_fwd(const ymi_tensor* x, const float* w1, const float* w
 template <typename T>
 __global__ __launch_bounds__(256) void cbam_bwd_du_kernel(CV x, CV dout, int64_t NP, int HW, int C, const float* __restrict__ ca,
                                                           const float* __restrict__ sa, float* __restrict__ du) {
-    const int lane = threadIdx.x & 63;
-    const int64_t p = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-    if (p >= NP) return;
-    const int n = (int)(p / HW);
-    const T* xp = reinterpret_cast<const T*>(x.p) + p * x.ld;
-    const T* dp = reinterpret_cast<const T*>(dout.p) + p * dout.ld;
-    const float* cap = ca + (int64_t)n * C;
+    const PixWave pw = grid_pix_wave(NP, HW, C, ca);
+    if (!pw.live) return;
+    const T* xp = row<T>(x, pw.p);
+    const T* dp = row<T>(dout, pw.p);
     float s = 0.f;
-    for (int c = lane * 4; c < C; c += 256) {
+    for_chan4(C, pw.lane, [&](int c) {
         float v[4], d[4];
         Pack<T, 4>::load(xp + c, v);
         Pack<T, 4>::load(dp + c, d);
 #pragma unroll
-        for (int r = 0; r < 4; ++r) s += d[r] * v[r] * cap[c + r];
-    }
+        for (int r = 0; r < 4; ++r) s += d[r] * v[r] * pw.cap[c + r];
+    });
     s = wave_sum(s);
-    if (lane == 0) {
-        const float a = sa[p];
-        du[p] = s * a * (1.f - a);
+    if (pw.lane == 0) {
+        const float a = sa[pw.p];
+        du[pw.p] = s * a * (1.f - a);
     }
 }
 
@@ -255,41 +281,31 @@ __global__ __launch_bounds__(256) void cbam_bwd_dx_kernel(CV x, CV dout, CV dx, 
                                                           const int* __restrict__ sarg, const float* __restrict__ wsa, int K,
                                                           float* __restrict__ dcap /*[N][PB][C]*/, int PB) {
     __shared__ float part[4][1024 + 4];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int HW = H * W;
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6, HW = H * W;
     // blockIdx.x = n * PB + pb ; each block walks pixels pb*4+wv, +4*PB, ... of image n (wave per pixel)
     const int n = blockIdx.x / PB, pb = blockIdx.x % PB;
-    const int R = K / 2;
-    const float* cap = ca + (int64_t)n * C;
+    const float* dun = du + (int64_t)n * HW;
     // per-wave accumulation of dx1*x over its pixels, channel c = lane*4 + 256*i + r  (C <= 1024 -> i < 4)
-    float acc[4][4];
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) acc[i][r] = 0.f;
+    float acc[4][4] = {};
     for (int q = pb * 4 + wv; q < HW; q += 4 * PB) {
-        const int h = q / W, w = q % W;
-        const int64_t p = (int64_t)n * HW + q;
+        const PixWave pw = pix_wave((int64_t)n * HW + q, n, HW, C, ca);
         float d0 = 0.f, d1 = 0.f;
-        for (int t = lane; t < K * K; t += 64) {
-            // forward: u[p'] += wsa[j][t] * sm[p' + (ty-R, tx-R)]  =>  dsm[p] gets du[p - off] * wsa[j][t]
-            const int hh = h - (t / K - R), ww = w - (t % K - R);
-            if (hh >= 0 && hh < H && ww >= 0 && ww < W) {
-                const float g = du[((int64_t)n * H + hh) * W + ww];
-                d0 += g * wsa[t];
-                d1 += g * wsa[K * K + t];
-            }
-        }
+        // forward: u[p'] += wsa[j][t] * sm[p' + (ty-R, tx-R)]  =>  dsm[p] gets du[p - off] * wsa[j][t]
+        stencil_taps<-1>(q / W, q % W, H, W, K, lane, [&](int t, int nb) {
+            const float g = dun[nb];
+            d0 += g * wsa[t];
+            d1 += g * wsa[K * K + t];
+        });
         d0 = wave_sum(d0);
         d1 = wave_sum(d1);
-        const float a = sa[p];
-        const int am = sarg[p];
-        const T* xp = reinterpret_cast<const T*>(x.p) + p * x.ld;
-        const T* dp = reinterpret_cast<const T*>(dout.p) + p * dout.ld;
-        T* op = reinterpret_cast<T*>(const_cast<void*>(dx.p)) + p * dx.ld;
+        const float a = sa[pw.p];
+        const int am = sarg[pw.p];
+        const T* xp = row<T>(x, pw.p);
+        const T* dp = row<T>(dout, pw.p);
+        T* op = row<T>(dx, pw.p);
         const float dmean = d0 / (float)C;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) {
+        for (int i = 0; i < 4; ++i) {  // for_chan4's trips with compile-time slots: acc stays in registers
             const int c = lane * 4 + 256 * i;
             if (c < C) {
                 float v[4], d[4], o[4];
@@ -298,7 +314,7 @@ __global__ __launch_bounds__(256) void cbam_bwd_dx_kernel(CV x, CV dout, CV dx, 
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const float dx1 = d[r] * a + dmean + ((c + r == am) ? d1 : 0.f);
-                    o[r] = dx1 * cap[c + r];
+                    o[r] = dx1 * pw.cap[c + r];
                     acc[i][r] += dx1 * v[r];
                 }
                 Pack<T, 4>::store(op + c, o);
@@ -330,7 +346,7 @@ __global__ __launch_bounds__(1024) void cbam_bwd_mlp_kernel(const float* __restr
     float* dh = pre + 2 * Hd;
     const int n = blockIdx.x, nt = blockDim.x, nw = nt >> 6;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int i = threadIdx.x; i < 2 * C; i += nt) sp[i] = pooled[(int64_t)n * 2 * C + i];
+    stage_pooled(pooled, n, C, sp);
     for (int c = threadIdx.x; c < C; c += nt) {
         float s = 0.f;
 #pragma unroll 8
@@ -342,18 +358,12 @@ __global__ __launch_bounds__(1024) void cbam_bwd_mlp_kernel(const float* __restr
     }
     __syncthreads();
     for (int h = wave; h < Hd; h += nw) {
-        float a = 0.f, m = 0.f, g = 0.f;
-#pragma unroll 8
-        for (int c = lane; c < C; c += 64) {
-            const float w = w1[(int64_t)h * C + c];
-            a += w * sp[c];
-            m += w * sp[C + c];
-            g += w2[(int64_t)c * Hd + h] * sdz[c];
-        }
-        a = wave_sum(a); m = wave_sum(m); g = wave_sum(g);
+        float a, m, g = 0.f;
+        hidden_unit(w1, sp, C, h, lane, a, m, [&](int c) { g += w2[(int64_t)c * Hd + h] * sdz[c]; });
+        g = wave_sum(g);
         if (lane == 0) {
             pre[h] = a; pre[Hd + h] = m; dh[h] = g;
-            hsum[(int64_t)n * Hd + h] = fmaxf(a, 0.f) + fmaxf(m, 0.f);
+            hsum[(int64_t)n * Hd + h] = relu_sum(a, m);
             dpre[((int64_t)n * 2 + 0) * Hd + h] = a > 0.f ? g : 0.f;
             dpre[((int64_t)n * 2 + 1) * Hd + h] = m > 0.f ? g : 0.f;
         }
@@ -411,17 +421,15 @@ __global__ __launch_bounds__(1024) void cbam_bwd_wsa_kernel(const float* __restr
         const uint32_t q = p + blockDim.x;
         const uint32_t r0 = p / uw, r1 = q / uw;
         const int w0 = (int)(p - r0 * uw), h0 = (int)(r0 % uh), w1 = (int)(q - r1 * uw), h1 = (int)(r1 % uh);
-        const bool ok0 = h0 + dy >= 0 && h0 + dy < H && w0 + dx >= 0 && w0 + dx < W;
-        const bool ok1 = h1 + dy >= 0 && h1 + dy < H && w1 + dx >= 0 && w1 + dx < W;
-        const float a0 = ok0 ? du[p] * smap[((int64_t)p + shift) * 2 + j] : 0.f;
-        const float a1 = ok1 ? du[q] * smap[((int64_t)q + shift) * 2 + j] : 0.f;
+        const float a0 = in_map(h0 + dy, w0 + dx, H, W) ? du[p] * smap[((int64_t)p + shift) * 2 + j] : 0.f;
+        const float a1 = in_map(h1 + dy, w1 + dx, H, W) ? du[q] * smap[((int64_t)q + shift) * 2 + j] : 0.f;
         s0 += a0;
         s1 += a1;
     }
     if (p < NP) {
         const uint32_t r0 = p / uw;
         const int w0 = (int)(p - r0 * uw), h0 = (int)(r0 % uh);
-        if (h0 + dy >= 0 && h0 + dy < H && w0 + dx >= 0 && w0 + dx < W) s0 += du[p] * smap[((int64_t)p + shift) * 2 + j];
+        if (in_map(h0 + dy, w0 + dx, H, W)) s0 += du[p] * smap[((int64_t)p + shift) * 2 + j];
     }
     float s = wave_sum(s0 + s1);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
@@ -437,13 +445,13 @@ __global__ __launch_bounds__(1024) void cbam_bwd_wsa_kernel(const float* __restr
 template <typename T>
 __global__ void cbam_bwd_pool_kernel(CV dx, int64_t NP, int HW, int C, const float* __restrict__ dpool, const int* __restrict__ amax) {
     const uint32_t groups = (uint32_t)(C / 4), total = (uint32_t)NP * groups, uhw = (uint32_t)HW;  // host: NP * C / 4 < 2^31
-    T* dp = reinterpret_cast<T*>(const_cast<void*>(dx.p));
     const float inv = 1.f / (float)HW;
     for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
         const uint32_t p = i / groups, g = i - p * groups;
         const uint32_t n = p / uhw, q = p - n * uhw;
+        T* dp = row<T>(dx, p) + g * 4;
         float v[4];
-        Pack<T, 4>::load(dp + (int64_t)p * dx.ld + g * 4, v);
+        Pack<T, 4>::load(dp, v);
         const float4 da = *reinterpret_cast<const float4*>(dpool + ((int64_t)n * 2 + 0) * C + g * 4);
         const float4 dm = *reinterpret_cast<const float4*>(dpool + ((int64_t)n * 2 + 1) * C + g * 4);
         const int4 am = *reinterpret_cast<const int4*>(amax + (int64_t)n * C + g * 4);
@@ -451,7 +459,7 @@ __global__ void cbam_bwd_pool_kernel(CV dx, int64_t NP, int HW, int C, const flo
         v[1] += da.y * inv + (am.y == (int)q ? dm.y : 0.f);
         v[2] += da.z * inv + (am.z == (int)q ? dm.z : 0.f);
         v[3] += da.w * inv + (am.w == (int)q ? dm.w : 0.f);
-        Pack<T, 4>::store(dp + (int64_t)p * dx.ld + g * 4, v);
+        Pack<T, 4>::store(dp, v);
     }
 }
 
@@ -462,22 +470,35 @@ static int cbam_pb(int HW) {
     return pb;
 }
 
+// ONE statement of the backward's workspace: du [N*H*W] | dcap [N][PB][C] | dz [N][C] | hsum [N][Hd] | dpre [N][2][Hd] | dpool [N][2][C], each
+// sub-buffer on a 16-byte boundary of a 16-byte aligned base (float4 reads of dpool); `floats` counts what the six hold, without the rounding
+struct CbamWork {
+    float *du, *dcap, *dz, *hsum, *dpre, *dpool;
+    int64_t floats;
+};
+static CbamWork cbam_carve(float* base, int64_t N, int64_t H, int64_t W, int64_t C, int64_t Hd) {
+    const int64_t PB = cbam_pb((int)(H * W));
+    int64_t off = 0, floats = 0;
+    auto take = [&](int64_t cnt) {
+        float* p = base ? base + off : nullptr;
+        off += (cnt + 3) / 4 * 4;
+        floats += cnt;
+        return p;
+    };
+    return CbamWork{take(N * H * W), take(N * PB * C), take(N * C), take(N * Hd), take(2 * N * Hd), take(2 * N * C), floats};  // (braces: left to right)
+}
+// the carve of a null base, 4 floats of slack for each of the six roundings, 256 bytes for the caller's base alignment
 extern "C" size_t ymi_cbam_bwd_workspace(int64_t n, int64_t h, int64_t w, int64_t c, int64_t hidden) {
-    const int pb = cbam_pb((int)(h * w));
-    // du [N*H*W] | dcap [N][PB][C] | dz [N][C] | hsum [N][Hd] | dpre [N][2][Hd] | dpool [N][2][C]
-    return (size_t)(n * h * w + n * pb * c + n * c + n * hidden + 2 * n * hidden + 2 * n * c + 6 * 4) * sizeof(float) + 256;
+    return (size_t)(cbam_carve(nullptr, n, h, w, c, hidden).floats + 6 * 4) * sizeof(float) + 256;
 }
 
 extern "C" int ymi_cbam_bwd(const ymi_tensor* x, const ymi_tensor* dout, const float* w1, const float* w2, int64_t hidden, const float* wsa,
                             int64_t ksa, const float* ca, const float* pooled, const int32_t* pool_argmax, const float* smap,
                             const int32_t* smap_argmax, const float* sa, const ymi_tensor* dx, float* dw1, float* dw2, float* dwsa,
                             void* workspace, size_t workspace_bytes, void* stream) {
-    YMI_CHECK_ARG(ymi_tensor_ok(x) && ymi_tensor_ok(dout) && ymi_tensor_ok(dx) && ymi_same_shape(x, dout) && ymi_same_shape(x, dx), "cbam_bwd: tensors");
-    YMI_CHECK_ARG(x->dtype == dout->dtype && x->dtype == dx->dtype, "cbam_bwd: dtypes");
-    YMI_CHECK_ARG(x->c % 4 == 0 && x->c <= 1024 && x->ld % 4 == 0 && dout->ld % 4 == 0 && dx->ld % 4 == 0, "cbam_bwd: channels multiple of 4, <= 1024");
-    YMI_CHECK_ARG(cbam_base_ok(x) && cbam_base_ok(dout) && cbam_base_ok(dx), "cbam_bwd: tensors must start on a 4-element boundary");
+    if (int rc = cbam_check("cbam_bwd", {x, dout, dx}, hidden, ksa)) return rc;
+    YMI_CHECK_ARG(x->c <= 1024, "cbam_bwd: at most 1024 channels");
     YMI_CHECK_ARG(w1 && w2 && wsa && ca && pooled && pool_argmax && smap && smap_argmax && sa && dw1 && dw2 && dwsa && workspace, "cbam_bwd: null buffer");
-    YMI_CHECK_ARG(hidden >= 1 && hidden <= 1024 && (ksa == 3 || ksa == 7), "cbam_bwd: hidden/kernel");
     const int N = (int)x->n, H = (int)x->h, W = (int)x->w, C = (int)x->c, HW = H * W, Hd = (int)hidden, K = (int)ksa;
     const size_t need = ymi_cbam_bwd_workspace(N, H, W, C, Hd);
     if (workspace_bytes < need) {
@@ -487,32 +508,23 @@ extern "C" int ymi_cbam_bwd(const ymi_tensor* x, const ymi_tensor* dout, const f
     const int PB = cbam_pb(HW);
     const int64_t NP = (int64_t)N * HW;
     YMI_CHECK_ARG(NP * (C / 4) < ((int64_t)1 << 31), "cbam_bwd: N*H*W*C/4 must stay below 2^31");
-    auto up4 = [](int64_t v) { return (v + 3) / 4 * 4; };  // sub-buffers start on 16-byte boundaries (float4 reads of dpool)
     YMI_CHECK_ARG(((uintptr_t)workspace & 15) == 0, "cbam_bwd: workspace must be 16-byte aligned");
-    float* du = reinterpret_cast<float*>(workspace);
-    float* dcap = du + up4(NP);
-    float* dz = dcap + up4((int64_t)N * PB * C);
-    float* hsum = dz + up4((int64_t)N * C);
-    float* dpre = hsum + up4((int64_t)N * Hd);
-    float* dpool = dpre + up4((int64_t)2 * N * Hd);
+    const CbamWork k = cbam_carve(reinterpret_cast<float*>(workspace), N, H, W, C, Hd);
     hipStream_t s = (hipStream_t)stream;
     CV xv{x->data, x->ld}, dv{dout->data, dout->ld}, ov{dx->data, dx->ld};
     dim3 gw((unsigned)((NP + 3) / 4));
     const size_t lds3 = (size_t)(3 * C + 3 * Hd) * sizeof(float);
     int64_t ge = (NP * (C / 4) + 255) / 256;
     if (ge > 4096) ge = 4096;
-    if (x->dtype == YMI_BF16) {
-        hipLaunchKernelGGL(cbam_bwd_du_kernel<bf16_t>, gw, dim3(256), 0, s, xv, dv, NP, HW, C, ca, sa, du);
-        hipLaunchKernelGGL(cbam_bwd_dx_kernel<bf16_t>, dim3(N * PB), dim3(256), 0, s, xv, dv, ov, N, H, W, C, ca, sa, du, smap_argmax, wsa, K, dcap, PB);
-    } else {
-        hipLaunchKernelGGL(cbam_bwd_du_kernel<float>, gw, dim3(256), 0, s, xv, dv, NP, HW, C, ca, sa, du);
-        hipLaunchKernelGGL(cbam_bwd_dx_kernel<float>, dim3(N * PB), dim3(256), 0, s, xv, dv, ov, N, H, W, C, ca, sa, du, smap_argmax, wsa, K, dcap, PB);
-    }
-    hipLaunchKernelGGL(cbam_bwd_mlp_kernel, dim3(N), dim3(1024), lds3, s, dcap, PB, pooled, ca, w1, w2, C, Hd, dz, hsum, dpre, dpool);
-    hipLaunchKernelGGL(cbam_bwd_w_kernel, dim3((2 * C * Hd + 255) / 256), dim3(256), 0, s, dz, hsum, dpre, pooled, N, C, Hd, dw1, dw2);
-    hipLaunchKernelGGL(cbam_bwd_wsa_kernel, dim3(2 * K * K), dim3(1024), 0, s, du, smap, N, H, W, K, dwsa);
-    if (x->dtype == YMI_BF16) hipLaunchKernelGGL(cbam_bwd_pool_kernel<bf16_t>, dim3((unsigned)ge), dim3(256), 0, s, ov, NP, HW, C, dpool, pool_argmax);
-    else hipLaunchKernelGGL(cbam_bwd_pool_kernel<float>, dim3((unsigned)ge), dim3(256), 0, s, ov, NP, HW, C, dpool, pool_argmax);
+    dispatch_dtype(x->dtype, [&](auto t) {
+        typedef typename decltype(t)::type T;
+        launch(cbam_bwd_du_kernel<T>, gw, dim3(256), 0, s, xv, dv, NP, HW, C, ca, sa, k.du);
+        launch(cbam_bwd_dx_kernel<T>, dim3(N * PB), dim3(256), 0, s, xv, dv, ov, N, H, W, C, ca, sa, k.du, smap_argmax, wsa, K, k.dcap, PB);
+        launch(cbam_bwd_mlp_kernel, dim3(N), dim3(1024), lds3, s, k.dcap, PB, pooled, ca, w1, w2, C, Hd, k.dz, k.hsum, k.dpre, k.dpool);
+        launch(cbam_bwd_w_kernel, dim3((2 * C * Hd + 255) / 256), dim3(256), 0, s, k.dz, k.hsum, k.dpre, pooled, N, C, Hd, dw1, dw2);
+        launch(cbam_bwd_wsa_kernel, dim3(2 * K * K), dim3(1024), 0, s, k.du, smap, N, H, W, K, dwsa);
+        launch(cbam_bwd_pool_kernel<T>, dim3((unsigned)ge), dim3(256), 0, s, ov, NP, HW, C, k.dpool, pool_argmax);
+    });
     YMI_CHECK_LAUNCH("cbam_bwd");
     return YMI_OK;
 }

@@ -55,6 +55,10 @@ static inline int ymi_stat_fixed_point_shift(int64_t count) {
 // its partials with this many rows more than it writes (the conv block's statistics, first_conv.hip's forward workspace)
 constexpr int BN_STAGE_ROWS = 64;
 static inline size_t ymi_esize(int dtype) { return dtype == YMI_BF16 ? 2 : 4; }
+// 4-element Pack accesses (8 B bf16 / 16 B f32, below) need c, ld and the base on 4-element boundaries (elementwise.hip, cbam.hip)
+static inline bool vec4_ok(const ymi_tensor* t) {
+    return t->c % 4 == 0 && t->ld % 4 == 0 && ((uintptr_t)t->data % (4 * ymi_esize(t->dtype))) == 0;
+}
 static inline bool ymi_same_shape(const ymi_tensor* a, const ymi_tensor* b) {
     return a->n == b->n && a->h == b->h && a->w == b->w && a->c == b->c;
 }

@@ -11,9 +11,6 @@ static inline dim3 ew_grid(int64_t work) {
     if (b < 1) b = 1;
     return dim3((unsigned)b);
 }
-static inline bool vec4_ok(const ymi_tensor* t) {
-    return t->c % 4 == 0 && t->ld % 4 == 0 && ((uintptr_t)t->data % (4 * ymi_esize(t->dtype))) == 0;
-}
 
 struct TV {  // device view of a ymi_tensor
     void* p;
@@ -66,10 +63,9 @@ extern "C" int ymi_nchw_to_nhwc(const float* src, int64_t n, int64_t c, int64_t 
         YMI_CHECK_LAUNCH("nchw_to_nhwc");
         return YMI_OK;
     }
-    if (dst->dtype == YMI_BF16)
-        hipLaunchKernelGGL(nchw_to_nhwc_kernel<bf16_t>, ew_grid(total), dim3(256), 0, (hipStream_t)stream, src, (int)c, h * w, np, tv(dst));
-    else
-        hipLaunchKernelGGL(nchw_to_nhwc_kernel<float>, ew_grid(total), dim3(256), 0, (hipStream_t)stream, src, (int)c, h * w, np, tv(dst));
+    dispatch_dtype(dst->dtype, [&](auto t) {
+        hipLaunchKernelGGL(nchw_to_nhwc_kernel<typename decltype(t)::type>, ew_grid(total), dim3(256), 0, (hipStream_t)stream, src, (int)c, h * w, np, tv(dst));
+    });
     YMI_CHECK_LAUNCH("nchw_to_nhwc");
     return YMI_OK;
 }
@@ -89,10 +85,9 @@ __global__ void nhwc_to_nchw_kernel(TV s, float* __restrict__ dst, int64_t HW, i
 extern "C" int ymi_nhwc_to_nchw(const ymi_tensor* src, float* dst, void* stream) {
     YMI_CHECK_ARG(ymi_tensor_ok(src) && dst, "nhwc_to_nchw: bad tensor");
     const int64_t hw = src->h * src->w, total = src->n * src->c * hw;
-    if (src->dtype == YMI_BF16)
-        hipLaunchKernelGGL(nhwc_to_nchw_kernel<bf16_t>, ew_grid(total), dim3(256), 0, (hipStream_t)stream, tv(src), dst, hw, total);
-    else
-        hipLaunchKernelGGL(nhwc_to_nchw_kernel<float>, ew_grid(total), dim3(256), 0, (hipStream_t)stream, tv(src), dst, hw, total);
+    dispatch_dtype(src->dtype, [&](auto t) {
+        hipLaunchKernelGGL(nhwc_to_nchw_kernel<typename decltype(t)::type>, ew_grid(total), dim3(256), 0, (hipStream_t)stream, tv(src), dst, hw, total);
+    });
     YMI_CHECK_LAUNCH("nhwc_to_nchw");
     return YMI_OK;
 }
@@ -153,16 +148,14 @@ static int launch_move(const ymi_tensor* src, const ymi_tensor* dst, const char*
     const int64_t total = ymi_pixels(dst) * (vec ? dst->c / 4 : dst->c);
     YMI_CHECK_ARG(total < (1ll << 31), "%s: tensor too large for 32-bit indexing", what);
     dim3 g = ew_grid(total), b(256);
-#define YMI_MV(TS, TD)                                                                              \
-    do {                                                                                            \
-        if (vec) hipLaunchKernelGGL((move_kernel<TS, TD, MODE, true>), g, b, 0, stream, tv(src), tv(dst));  \
-        else hipLaunchKernelGGL((move_kernel<TS, TD, MODE, false>), g, b, 0, stream, tv(src), tv(dst));     \
-    } while (0)
-    if (src->dtype == YMI_BF16 && dst->dtype == YMI_BF16) YMI_MV(bf16_t, bf16_t);
-    else if (src->dtype == YMI_F32 && dst->dtype == YMI_F32) YMI_MV(float, float);
-    else if (src->dtype == YMI_F32 && dst->dtype == YMI_BF16) YMI_MV(float, bf16_t);
-    else YMI_MV(bf16_t, float);
-#undef YMI_MV
+    dispatch_dtype(src->dtype, [&](auto ts) {
+        dispatch_dtype(dst->dtype, [&](auto td) {
+            typedef typename decltype(ts)::type TS;
+            typedef typename decltype(td)::type TD;
+            if (vec) hipLaunchKernelGGL((move_kernel<TS, TD, MODE, true>), g, b, 0, stream, tv(src), tv(dst));
+            else hipLaunchKernelGGL((move_kernel<TS, TD, MODE, false>), g, b, 0, stream, tv(src), tv(dst));
+        });
+    });
     YMI_CHECK_LAUNCH(what);
     return YMI_OK;
 }
@@ -211,10 +204,10 @@ extern "C" int ymi_pack_conv_weight_fwd(const float* w, int64_t o, int64_t i, in
                                         void* dst, void* stream) {
     YMI_CHECK_ARG(w && dst && ipad >= i && o > 0 && i > 0, "pack_conv_weight_fwd: args");
     const int64_t total = o * kh * kw * ipad;
-    if (dtype == YMI_BF16)
-        hipLaunchKernelGGL(pack_fwd_kernel<bf16_t>, ew_grid(total), dim3(256), 0, (hipStream_t)stream, w, (int)o, (int)i, (int)kh, (int)kw, (int)ipad, (bf16_t*)dst);
-    else
-        hipLaunchKernelGGL(pack_fwd_kernel<float>, ew_grid(total), dim3(256), 0, (hipStream_t)stream, w, (int)o, (int)i, (int)kh, (int)kw, (int)ipad, (float*)dst);
+    dispatch_dtype(dtype, [&](auto t) {
+        typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(pack_fwd_kernel<T>, ew_grid(total), dim3(256), 0, (hipStream_t)stream, w, (int)o, (int)i, (int)kh, (int)kw, (int)ipad, (T*)dst);
+    });
     YMI_CHECK_LAUNCH("pack_conv_weight_fwd");
     return YMI_OK;
 }
@@ -256,12 +249,11 @@ extern "C" int ymi_pack_conv_weight_dgrad_ex(const float* w, int64_t o_real, int
             }
         d.off = off;
         const int64_t total = i * d.ntaps * o;
-        if (total > 0) {
-            if (dtype == YMI_BF16)
-                hipLaunchKernelGGL(pack_dgrad_kernel<bf16_t>, ew_grid(total), dim3(256), 0, (hipStream_t)stream, w, (int)o_real, (int)o, (int)i, (int)kh, (int)kw, d, (bf16_t*)dst);
-            else
-                hipLaunchKernelGGL(pack_dgrad_kernel<float>, ew_grid(total), dim3(256), 0, (hipStream_t)stream, w, (int)o_real, (int)o, (int)i, (int)kh, (int)kw, d, (float*)dst);
-        }
+        if (total > 0)
+            dispatch_dtype(dtype, [&](auto t) {
+                typedef typename decltype(t)::type T;
+                hipLaunchKernelGGL(pack_dgrad_kernel<T>, ew_grid(total), dim3(256), 0, (hipStream_t)stream, w, (int)o_real, (int)o, (int)i, (int)kh, (int)kw, d, (T*)dst);
+            });
         off += total;
     }
     YMI_CHECK_LAUNCH("pack_conv_weight_dgrad");
@@ -288,10 +280,10 @@ __global__ void pack_matrix_kernel(const float* __restrict__ src, int R, int C, 
 extern "C" int ymi_pack_matrix(const float* src, int64_t rows, int64_t cols, int32_t transpose, int32_t dtype, void* dst, void* stream) {
     YMI_CHECK_ARG(src && dst && rows > 0 && cols > 0, "pack_matrix: args");
     const int64_t total = rows * cols;
-    if (dtype == YMI_BF16)
-        hipLaunchKernelGGL(pack_matrix_kernel<bf16_t>, ew_grid(total), dim3(256), 0, (hipStream_t)stream, src, (int)rows, (int)cols, transpose, (bf16_t*)dst);
-    else
-        hipLaunchKernelGGL(pack_matrix_kernel<float>, ew_grid(total), dim3(256), 0, (hipStream_t)stream, src, (int)rows, (int)cols, transpose, (float*)dst);
+    dispatch_dtype(dtype, [&](auto t) {
+        typedef typename decltype(t)::type T;
+        hipLaunchKernelGGL(pack_matrix_kernel<T>, ew_grid(total), dim3(256), 0, (hipStream_t)stream, src, (int)rows, (int)cols, transpose, (T*)dst);
+    });
     YMI_CHECK_LAUNCH("pack_matrix");
     return YMI_OK;
 }
@@ -411,20 +403,6 @@ __global__ __launch_bounds__(256) void stat_rows_reduce_kernel(const float* __re
 // `part` may be overwritten beyond row `blocks` (callers size it with ymi_conv2d_stat_blocks + BN_STAGE_ROWS rows).
 static int bn_finalize_impl(const float* part, int64_t blocks, int64_t count, int64_t c, const float* gamma, const float* beta,
                             float* rmean, float* rvar, float momentum, float eps, float* scale, float* shift, float* smean,
-                            float* sinv, BnParams2 p2, void* stream);
-extern "C" int ymi_bn_finalize(const float* part, int64_t blocks, int64_t count, int64_t c, const float* gamma, const float* beta,
-                               float* rmean, float* rvar, float momentum, float eps, float* scale, float* shift, float* smean,
-                               float* sinv, void* stream) {
-    return bn_finalize_impl(part, blocks, count, c, gamma, beta, rmean, rvar, momentum, eps, scale, shift, smean, sinv, BnParams2{nullptr, nullptr, nullptr, nullptr, 0}, stream);
-}
-extern "C" int ymi_bn_finalize_pair(const float* part, int64_t blocks, int64_t count, int64_t c, int64_t split, const float* gamma, const float* beta,
-                                    float* rmean, float* rvar, const float* gamma2, const float* beta2, float* rmean2, float* rvar2, float momentum,
-                                    float eps, float* scale, float* shift, float* smean, float* sinv, void* stream) {
-    YMI_CHECK_ARG(split > 0 && split < c && gamma2 && beta2, "bn_finalize_pair: split");
-    return bn_finalize_impl(part, blocks, count, c, gamma, beta, rmean, rvar, momentum, eps, scale, shift, smean, sinv, BnParams2{gamma2, beta2, rmean2, rvar2, (int)split}, stream);
-}
-static int bn_finalize_impl(const float* part, int64_t blocks, int64_t count, int64_t c, const float* gamma, const float* beta,
-                            float* rmean, float* rvar, float momentum, float eps, float* scale, float* shift, float* smean,
                             float* sinv, BnParams2 p2, void* stream) {
     YMI_CHECK_ARG(part && scale && shift && blocks > 0 && count > 0 && c > 0, "bn_finalize: args");
     const float* src = part;
@@ -440,6 +418,17 @@ static int bn_finalize_impl(const float* part, int64_t blocks, int64_t count, in
                        (double)count, (int)c, gamma, beta, rmean, rvar, momentum, eps, scale, shift, smean, sinv, p2);
     YMI_CHECK_LAUNCH("bn_finalize");
     return YMI_OK;
+}
+extern "C" int ymi_bn_finalize(const float* part, int64_t blocks, int64_t count, int64_t c, const float* gamma, const float* beta,
+                               float* rmean, float* rvar, float momentum, float eps, float* scale, float* shift, float* smean,
+                               float* sinv, void* stream) {
+    return bn_finalize_impl(part, blocks, count, c, gamma, beta, rmean, rvar, momentum, eps, scale, shift, smean, sinv, BnParams2{nullptr, nullptr, nullptr, nullptr, 0}, stream);
+}
+extern "C" int ymi_bn_finalize_pair(const float* part, int64_t blocks, int64_t count, int64_t c, int64_t split, const float* gamma, const float* beta,
+                                    float* rmean, float* rvar, const float* gamma2, const float* beta2, float* rmean2, float* rvar2, float momentum,
+                                    float eps, float* scale, float* shift, float* smean, float* sinv, void* stream) {
+    YMI_CHECK_ARG(split > 0 && split < c && gamma2 && beta2, "bn_finalize_pair: split");
+    return bn_finalize_impl(part, blocks, count, c, gamma, beta, rmean, rvar, momentum, eps, scale, shift, smean, sinv, BnParams2{gamma2, beta2, rmean2, rvar2, (int)split}, stream);
 }
 
 template <typename T, bool VEC>
@@ -605,7 +594,25 @@ extern "C" int ymi_scale_shift_act(const ymi_tensor* raw, const float* scale, co
 static int conv_bn_act_fwd_impl(const ymi_tensor* x, const void* w_packed, int64_t cout, int64_t kh, int64_t kw, int64_t stride,
                                 const float* gamma, const float* beta, float* running_mean, float* running_var, BnParams2 p2, float momentum,
                                 float eps, int32_t act, const ymi_tensor* residual, const ymi_tensor* raw, const ymi_tensor* out,
-                                float* save_mean, float* save_invstd, void* workspace, size_t workspace_bytes, void* stream);
+                                float* save_mean, float* save_invstd, void* workspace, size_t workspace_bytes, void* stream) {
+    YMI_CHECK_ARG(ymi_tensor_ok(raw) && ymi_tensor_ok(out) && workspace, "conv2d_bn_silu_fwd: bad tensor");
+    const int64_t m = ymi_pixels(raw);
+    const int64_t maxblk = ymi_conv2d_stat_blocks(m, cout);
+    const size_t need = (size_t)(maxblk * 2 * cout + 2 * cout) * sizeof(float);
+    if (workspace_bytes < need) {
+        ymi_set_error("conv2d_bn_silu_fwd: workspace %zu < %zu bytes", workspace_bytes, need);
+        return YMI_EWORKSPACE;
+    }
+    float* scale = reinterpret_cast<float*>(workspace);
+    float* shift = scale + cout;
+    float* part = shift + cout;
+    int64_t blocks = 0;
+    int rc = ymi_conv2d_fwd(x, w_packed, cout, kh, kw, stride, nullptr, nullptr, YMI_ACT_NONE, nullptr, raw, part, &blocks, stream);
+    if (rc) return rc;
+    rc = bn_finalize_impl(part, blocks, m, cout, gamma, beta, running_mean, running_var, momentum, eps, scale, shift, save_mean, save_invstd, p2, stream);
+    if (rc) return rc;
+    return ymi_scale_shift_act(raw, scale, shift, act, residual, out, stream);
+}
 extern "C" int ymi_conv2d_bn_silu_fwd(const ymi_tensor* x, const void* w_packed, int64_t cout, int64_t kh, int64_t kw, int64_t stride,
                                       const float* gamma, const float* beta, float* running_mean, float* running_var, float momentum,
                                       float eps, int32_t act, const ymi_tensor* residual, const ymi_tensor* raw, const ymi_tensor* out,
@@ -626,28 +633,6 @@ extern "C" int ymi_conv2d_bn_silu_fwd_pair(const ymi_tensor* x, const void* w_pa
     return conv_bn_act_fwd_impl(x, w_packed, cout, kh, kw, stride, gamma, beta, running_mean, running_var,
                                 BnParams2{gamma2, beta2, running_mean2, running_var2, (int)split}, momentum, eps, act, nullptr, raw, out, save_mean, save_invstd,
                                 workspace, workspace_bytes, stream);
-}
-static int conv_bn_act_fwd_impl(const ymi_tensor* x, const void* w_packed, int64_t cout, int64_t kh, int64_t kw, int64_t stride,
-                                const float* gamma, const float* beta, float* running_mean, float* running_var, BnParams2 p2, float momentum,
-                                float eps, int32_t act, const ymi_tensor* residual, const ymi_tensor* raw, const ymi_tensor* out,
-                                float* save_mean, float* save_invstd, void* workspace, size_t workspace_bytes, void* stream) {
-    YMI_CHECK_ARG(ymi_tensor_ok(raw) && ymi_tensor_ok(out) && workspace, "conv2d_bn_silu_fwd: bad tensor");
-    const int64_t m = ymi_pixels(raw);
-    const int64_t maxblk = ymi_conv2d_stat_blocks(m, cout);
-    const size_t need = (size_t)(maxblk * 2 * cout + 2 * cout) * sizeof(float);
-    if (workspace_bytes < need) {
-        ymi_set_error("conv2d_bn_silu_fwd: workspace %zu < %zu bytes", workspace_bytes, need);
-        return YMI_EWORKSPACE;
-    }
-    float* scale = reinterpret_cast<float*>(workspace);
-    float* shift = scale + cout;
-    float* part = shift + cout;
-    int64_t blocks = 0;
-    int rc = ymi_conv2d_fwd(x, w_packed, cout, kh, kw, stride, nullptr, nullptr, YMI_ACT_NONE, nullptr, raw, part, &blocks, stream);
-    if (rc) return rc;
-    rc = bn_finalize_impl(part, blocks, m, cout, gamma, beta, running_mean, running_var, momentum, eps, scale, shift, save_mean, save_invstd, p2, stream);
-    if (rc) return rc;
-    return ymi_scale_shift_act(raw, scale, shift, act, residual, out, stream);
 }
 
 // The same Conv block with the BatchNorm statistics as fixed-point atomic sums and the finalize inside the affine pass: TWO launches

@@ -29,8 +29,8 @@ Bounds (every other output):  |got - ref| <= r |ref| + gamma_k A
   error passes through sigma' <= 1/4.  So for a sigmoid output A = Az / 4 with z's k, plus (6 + 2|z|) u |ref|.
 
 k per output, T = ceil(C / 256), PB = cbam_pb(HW), Pw = ceil(HW / (4 PB)), with the loop or line each term comes from:
-  pooled[:, 0]  ceil(HW / 16) + 17     cbam_pool_kernel: `sum[r] += v` per pixel lane (both pixel loops), 16 x `s += s_sum[q]`, `s / HW`
-  ca            z: ceil(C / 64) + Hd + 9   cbam_mlp_kernel: `w * sp[c]` 1, `a +=` ceil(C / 64), wave_sum 6, fmaxf + fmaxf 1,
+  pooled[:, 0]  ceil(HW / 16) + 17     cbam_pool_kernel: `sum[r] += v` per pixel lane (pool_pixel, both pixel loops), 16 x `s += s_sum[q]`, `s / HW`
+  ca            z: ceil(C / 64) + Hd + 9   cbam_mlp_kernel: (hidden_unit) `w * sp[c]` 1, `acc_a +=` ceil(C / 64), wave_sum 6, (relu_sum) fmaxf + fmaxf 1,
                                            `wr[h] * hs[h]` 1, `z +=` Hd; then sigmoidf_
   smap[..., 0]  4T + 8                 cbam_stats_kernel: `v * cap` 1, `s += t` 4T, wave_sum 6, `s / C` 1
   sa            u: 9                   cbam_apply_kernel: `wsa * smap` 1, the inner `+` 1, `u +=` 1 (K * K <= 64: one tap a lane),
@@ -41,7 +41,7 @@ k per output, T = ceil(C / 256), PB = cbam_pb(HW), Pw = ceil(HW / (4 PB)), with 
   dx, 1st part  k_du + 12              `dx1 * cap`; a bfloat16 dx is ROUNDED HERE (first store) ...
   dcap          k_du + 12 + Pw + 3     `dx1 * v` 1, `acc +=` Pw, `part[0] + .. + part[3]` 3
   dz            k_dz = k_du + 18 + Pw + PB   cbam_bwd_mlp_kernel: `s += dcap` PB, `s * a` 1, `* (1 - a)` 2
-  hsum          k_hs = ceil(C / 64) + 8  `w * sp` 1, `a +=` ceil(C / 64), wave_sum 6, fmaxf + fmaxf 1
+  hsum          k_hs = ceil(C / 64) + 8  (hidden_unit) `w * sp` 1, `acc_a +=` ceil(C / 64), wave_sum 6, (relu_sum) fmaxf + fmaxf 1
   dh            k_dh = k_dz + ceil(C / 64) + 7   `w2 * sdz` 1, `g +=` ceil(C / 64), wave_sum 6
   dpool         k_dp = k_dh + 1 + Hd   `dh * w` 1, `da +=` Hd
   dw2           k_dz + k_hs + 1 + N    cbam_bwd_w_kernel: `dz * hsum` (two computed factors), `s +=` N
