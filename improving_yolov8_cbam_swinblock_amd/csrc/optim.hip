@@ -203,53 +203,59 @@ __global__ __launch_bounds__(256) void opt_update_kernel(const ymi_opt_entry* __
     }
     constexpr bool adam = RULE != 0;
     const float decay_mul = 1.f - lr * wd;
+    // One body for the vector path, its scalar tail and the scalar path.  Every multiply-add that is fused is written as fmaf and nothing else
+    // may be (contract(off); the Makefile builds this file with -ffp-contract=fast-honor-pragmas): left to the compiler, the packed-math
+    // pass fused the EMA's multiply-add in some lanes of a float4 and not in others, so the same element rounded differently by its position
+    // and by the alignment of its tensor.  tests/test_gpu_optim_exact.py holds the paths to bit equality.  Which sums are fused and which are
+    // not is what the vector path of parameters and moments had been compiled to all along: aligned tensors step as they always did.
     auto one = [&](float pv, float gv, float bv, float sv, float ev, float& po, float& bo, float& so, float& eo) {
+#pragma clang fp contract(off)
         so = sv;
         if (MODE == 0 && RULE >= 3 && g) {
             float gr = gv * gscale;
             if (wd != 0.f) gr = gr + wd * pv;                // grad.add(param, alpha=weight_decay)
             if (RULE == 3) {                                 // torch.optim.Adamax
-                bo = bv + (gr - bv) * omb1;                  // exp_avg.lerp_(grad, 1 - beta1)
+                bo = fmaf(gr - bv, omb1, bv);                // exp_avg.lerp_(grad, 1 - beta1)
                 so = fmaxf(sv * b2, fabsf(gr) + eps);        // exp_inf = max(exp_inf * beta2, |grad| + eps)
-                po = pv - step_size * (bo / so);             // param.addcdiv_(exp_avg, exp_inf, value=-lr / bias_correction1)
+                po = fmaf(-step_size, bo / so, pv);          // param.addcdiv_(exp_avg, exp_inf, value=-lr / bias_correction1)
             } else if (RULE == 4) {                          // torch.optim.NAdam
-                bo = bv + (gr - bv) * omb1;
-                so = sv * b2 + omb2 * gr * gr;
+                bo = fmaf(gr - bv, omb1, bv);
+                so = fmaf(omb2 * gr, gr, sv * b2);
                 const float denom = sqrtf(so / c2) + eps;    // exp_avg_sq.div(bias_correction2).sqrt().add_(eps)
                 const float p1 = pv - (lr * c0) * (gr / denom);   // param.addcdiv_(grad, denom, value=-lr (1 - mu) / (1 - mu_product))
                 po = p1 - (lr * c1) * (bo / denom);               // param.addcdiv_(exp_avg, denom, value=-lr mu_next / (1 - mu_product mu_next))
             } else if (RULE == 5) {                          // torch.optim.RAdam
-                bo = bv + (gr - bv) * omb1;
-                so = sv * b2 + omb2 * gr * gr;
+                bo = fmaf(gr - bv, omb1, bv);
+                so = fmaf(omb2 * gr, gr, sv * b2);
                 const float bce = bo * ibc1;                 // exp_avg / bias_correction1
                 if (c1 != 0.f) po = pv - ((bce * lr) * (bc2s / (sqrtf(so) + eps))) * c0;  // bias_corrected_exp_avg * lr * adaptive * rect
                 else po = pv - bce * lr;
             } else {                                         // torch.optim.RMSprop(momentum > 0), alpha = b2
-                so = sv * b2 + omb2 * gr * gr;               // square_avg.mul_(alpha).addcmul_(grad, grad, value=1 - alpha)
+                so = fmaf(omb2 * gr, gr, sv * b2);           // square_avg.mul_(alpha).addcmul_(grad, grad, value=1 - alpha)
                 const float avg = sqrtf(so) + eps;
-                bo = bv * mom + gr / avg;                    // buf.mul_(momentum).addcdiv_(grad, avg)
-                po = pv - lr * bo;
+                bo = fmaf(bv, mom, gr / avg);                // buf.mul_(momentum).addcdiv_(grad, avg)
+                po = fmaf(-lr, bo, pv);
             }
         } else if (MODE == 0 && adam && g) {
             float gr = gv * gscale;
-            float pw = pv;
-            if (RULE == 1) pw = pv * decay_mul;             // AdamW: param.mul_(1 - lr * weight_decay)
-            else if (wd != 0.f) gr = gr + wd * pv;          // Adam: grad.add(param, alpha=weight_decay)
-            bo = bv + (gr - bv) * omb1;                     // exp_avg.lerp_(grad, 1 - beta1)
-            so = sv * b2 + omb2 * gr * gr;                  // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
+            if (RULE == 2 && wd != 0.f) gr = gr + wd * pv;  // Adam: grad.add(param, alpha=weight_decay)
+            // exp_avg.lerp_(grad, 1 - beta1); AdamW has nothing between the scaling and the difference, and takes both in one fma
+            bo = fmaf(RULE == 1 ? fmaf(gv, gscale, -bv) : gr - bv, omb1, bv);
+            so = fmaf(omb2 * gr, gr, sv * b2);              // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
             const float denom = sqrtf(so) / bc2s + eps;     // (exp_avg_sq.sqrt() / bias_correction2_sqrt).add_(eps)
-            po = pw - step_size * (bo / denom);             // param.addcdiv_(exp_avg, denom, value=-lr / bias_correction1)
+            // param.addcdiv_(exp_avg, denom, value=-lr / bias_correction1); AdamW: param.mul_(1 - lr * weight_decay) first, two products and a difference
+            po = RULE == 1 ? pv * decay_mul - step_size * (bo / denom) : fmaf(-step_size, bo / denom, pv);
         } else if (MODE == 0 && g) {
             float gr = gv * gscale;
             if (wd != 0.f) gr = gr + wd * pv;           // grad.add(param, alpha=weight_decay)
-            bo = bv * mom + gr;                         // buf.mul_(momentum).add_(grad)   (first step: buf = 0 -> grad)
-            gr = nest ? gr + mom * bo : bo;             // grad.add(buf, alpha=momentum)
-            po = pv - lr * gr;                          // param.add_(grad, alpha=-lr)
+            bo = fmaf(bv, mom, gr);                     // buf.mul_(momentum).add_(grad)   (first step: buf = 0 -> grad)
+            gr = nest ? fmaf(mom, bo, gr) : bo;         // grad.add(buf, alpha=momentum)
+            po = fmaf(-lr, gr, pv);                     // param.add_(grad, alpha=-lr)
         } else {
             po = pv;
             bo = bv;
         }
-        eo = ev * d + omd * po;                         // v *= d; v += (1 - d) * model value
+        eo = fmaf(ev, d, omd * po);                     // v *= d; v += (1 - d) * model value
     };
     const bool vec = ((((uintptr_t)p) | ((uintptr_t)g) | ((uintptr_t)buf) | ((uintptr_t)sec) | ((uintptr_t)ema)) & 15) == 0;
     const bool upd = MODE == 0 && g;

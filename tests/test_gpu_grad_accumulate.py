@@ -1,27 +1,18 @@
 """GPU: ymi_opt_grad_accumulate (csrc/optim.hip) through FusedSGD.accumulate / step / discard_pending, on its own: a toy module whose
-parameter lengths sit on every edge of the kernel's chunking (ymi_opt_chunk_elems, YMI_OPT_MAX_GRADS tensors per launch)."""
+parameter lengths sit on every edge of the kernel's chunking (ymi_opt_chunk_elems, YMI_OPT_MAX_GRADS tensors per launch).  The two fused
+optimizers are compared with each other bit for bit, and the second with the float64 restatement tests/optim_exact.py after each step: a fault
+in the tail handling, the scalar path or the second range would be the same on both fused sides."""
 import pytest
 import torch
-import torch.nn as nn
+
+import optim_exact as X
+from optim_exact import Toy
 
 pytestmark = pytest.mark.gpu
 
 
 def dev():
     return torch.device("cuda:0")
-
-
-class Toy(nn.Module):
-    def __init__(self, c):
-        super().__init__()
-        g = torch.Generator().manual_seed(3)
-        mk = lambda n: nn.Parameter(torch.randn(n, generator=g).to(dev()))  # noqa: E731
-        for k, n in enumerate((1, 7, c - 1, c, c + 1, 3 * c + 5)):
-            setattr(self, f"w{k}", mk(n))
-        base = torch.randn(1001, generator=g).to(dev())
-        self.odd = nn.Parameter(base[1:])          # a view: 4 bytes past a 16-byte boundary
-        self.nograd = mk(9)                        # never receives a gradient
-        self.small_bias = nn.ParameterList([mk(3) for _ in range(450)])  # group 0; with the others 458 tensors: a second launch range
 
 
 def seeded_grads(model, seed, scale):
@@ -64,7 +55,10 @@ def test_accumulate_kernel_folds_steps_and_clears():
     torch.cuda.synchronize()
     assert opt.pending == 0 and float(opt._arena.abs().max()) == 0.0
     pb = dict(zip(a.parameters(), b.parameters()))
-    ref.step({pb[p]: g1[p] + g2[p] for p in g1})
+    sums = {pb[p]: g1[p] + g2[p] for p in g1}
+    before = X.class_before(ref, sums)
+    ref.step(sums)
+    X.class_after(ref, before)               # the third party: the float64 restatement, every element of parameters and momentum
     torch.cuda.synchronize()
     assert opt.grad_norm() == ref.grad_norm() and opt.grad_norm() > 10.0  # the clip is active, on the total
     for (n, p), q in zip(a.named_parameters(), b.parameters()):
@@ -72,7 +66,10 @@ def test_accumulate_kernel_folds_steps_and_clears():
     # second round: one fold, then the updating step folds its own gradients in; then a discarded fold leaves no trace
     opt.accumulate(g2)
     opt.step(g1)
-    ref.step({pb[p]: g2[p] + g1[p] for p in g1})
+    sums = {pb[p]: g2[p] + g1[p] for p in g1}
+    before = X.class_before(ref, sums)
+    ref.step(sums)
+    X.class_after(ref, before)
     opt.accumulate(g1)
     opt.discard_pending()
     torch.cuda.synchronize()
