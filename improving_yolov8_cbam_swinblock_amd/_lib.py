@@ -211,6 +211,14 @@ class WgradPending(ctypes.Structure):
 class OptEntry(ctypes.Structure):
     _fields_ = [("param", _vp), ("momentum", _vp), ("ema", _vp), ("numel", _c_i64), ("group", _c_i32), ("_pad", _c_i32), ("second", _vp), ("acc", _vp)]
 
+
+class OptState(ctypes.Structure):  # csrc/optim.hip OptState: the state record of the optimizer step (include/ymi.h, `state`)
+    _fields_ = [("clip", _c_f32), ("norm", _c_f32), ("ema_d", _c_f32), ("ema_1md", _c_f32), ("updates", _c_i64), ("steps", _c_i64), ("inv_bc1", _c_f32),
+                ("bc2_sqrt", _c_f32), ("c0", _c_f32), ("c1", _c_f32), ("c2", _c_f32), ("c3", _c_f32), ("mu_product", ctypes.c_double)]
+
+
+assert ctypes.sizeof(OptState) == 64
+
 _lib = None
 _lock = threading.Lock()
 

@@ -12,13 +12,36 @@ Hyper-parameters live in a device array that is rewritten only when `param_group
 """
 import ctypes
 import math
+from collections import namedtuple
 from copy import deepcopy
 
 import torch
 import torch.nn as nn
 
 from .. import _lib
-from .._lib import OPT_MAX_GRADS, OptEntry, check, stream_ptr
+from .._lib import OPT_MAX_GRADS, OptEntry, OptState, check, stream_ptr
+
+# the 20 floats of csrc/optim.hip's `hyper`, in the order of its enum Hyper (lr and wd: one value per parameter group)
+HYPER_FIELDS = ("lr", "wd", "momentum", "max_norm", "ema_decay", "ema_tau", "nesterov", "grad_scale", "beta2", "eps", "rule", "one_minus_beta2", "one_minus_beta1",
+                "momentum_decay", "beta1_tail", "momentum_decay_tail")
+_HYPER_ZERO = dict.fromkeys(HYPER_FIELDS[2:], 0.0)
+_STATE_DTYPE = {ctypes.c_float: torch.float32, ctypes.c_int64: torch.int64, ctypes.c_double: torch.float64}
+# field of the state record -> (the type to view the record in, the field's index in that view)
+_STATE_SLOT = {name: (_STATE_DTYPE[t], getattr(OptState, name).offset // ctypes.sizeof(t)) for name, t in OptState._fields_}
+Range = namedtuple("Range", "first n chunk0 n_chunks has_grads")  # one launch: tensors [first, first + n), chunks [chunk0, chunk0 + n_chunks)
+
+
+def build_table(entries, dev):
+    """[OptEntry] -> (host table, device table, device chunk map [(tensor, chunk)], first chunk of each entry (+ the total))"""
+    chunk = int(_lib.lib().ymi_opt_chunk_elems())
+    tab = (OptEntry * len(entries))(*entries)
+    cmap, first = [], []
+    for i, e in enumerate(entries):
+        first.append(len(cmap))
+        cmap.extend((i, c) for c in range((e.numel + chunk - 1) // chunk))
+    first.append(len(cmap))
+    table = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev)
+    return tab, table, torch.tensor(cmap, dtype=torch.int32).reshape(-1, 2).contiguous().to(dev), first
 
 
 def param_groups_of(model):
@@ -77,7 +100,15 @@ class ModelEMA:
 class FusedSGD:
     """SGD(momentum, nesterov) over the reference's three parameter groups + gradient clipping (+ EMA), fused."""
 
-    RULE = 0  # csrc/optim.hip hyper[14]: 0 SGD-momentum, 1 AdamW, 2 Adam, 3 Adamax, 4 NAdam, 5 RAdam, 6 RMSprop
+    RULE = 0  # csrc/optim.hip enum Rule: 0 SGD-momentum, 1 AdamW, 2 Adam, 3 Adamax, 4 NAdam, 5 RAdam, 6 RMSprop
+    # state_dict() / load_state_dict(), in torch.optim's format of the class: (state key, the list that holds its tensors) in torch's order;
+    # whether `step` is stored (then a parameter has state only once it stepped with a gradient); further per-parameter entries, each a field of
+    # the state record with a method of its name; the group keys restored on load; the group keys torch appends after `params`
+    STATE_BUFFERS = (("momentum_buffer", "momentum"),)
+    STORES_STEP = False
+    EXTRA_STATE = ()
+    LOAD_KEYS = ("lr", "initial_lr", "momentum", "nesterov", "weight_decay")
+    GROUP_DEFAULTS = {"maximize": False, "foreach": None, "differentiable": False, "fused": None}
 
     def __init__(self, model, lr=0.01, momentum=0.937, decay=5e-4, nesterov=True, max_norm=10.0, ema=None, sgd=True):
         self.model = model
@@ -89,13 +120,12 @@ class FusedSGD:
             {"params": g_norm, "lr": lr, "initial_lr": lr, "momentum": momentum, "nesterov": nesterov, "weight_decay": 0.0, "dampening": 0},
         ]
         self.max_norm = float(max_norm) if max_norm else 0.0
-        self.world = 1  # gradients are scaled by 1 / world inside the kernels (hyper[11]): TrainStep hands over the SUM over ranks and sets this
+        self.world = 1  # gradients are scaled by 1 / world inside the kernels (grad_scale): TrainStep hands over the SUM over ranks and sets this
         self.ema = ema
         self.sgd = sgd
         self._state = None
         self._table = None
         self._hyper_host = None
-        self._keep = []
         # gradient accumulation (accumulate()): a float32 arena the parameters' gradients are folded into, allocated on first use
         self._arena = None
         self._acc = []       # per parameter: its slice of the arena
@@ -139,39 +169,30 @@ class FusedSGD:
                         raise RuntimeError("ModelEMA entries must be float32")
                     entries.append((mt, None, et, 0))
                     self.ema_only.append(mt)
-        chunk = int(_lib.lib().ymi_opt_chunk_elems())
-        tab = (OptEntry * len(entries))()
-        cmap, self.ranges = [], []  # ranges: (first tensor, n tensors, first chunk, n chunks, has grads)
-        first_chunk_of = []
-        for i, (p, buf, e, gi) in enumerate(entries):
-            sec = self.second[i].data_ptr() if self.RULE and i < self.n_sgd else None
-            tab[i] = OptEntry(p.data_ptr(), buf.data_ptr() if buf is not None else None, e.data_ptr() if e is not None else None, p.numel(), gi, 0, sec, None)
-            first_chunk_of.append(len(cmap))
-            for c in range((p.numel() + chunk - 1) // chunk):
-                cmap.append((i, c))
-        first_chunk_of.append(len(cmap))
+        ptr = lambda t: t.data_ptr() if t is not None else None  # noqa: E731
+        self._tab_host, self._table, self._cmap, first_chunk_of = build_table(
+            [OptEntry(ptr(p), ptr(buf), ptr(e), p.numel(), gi, 0, ptr(self.second[i]) if self.RULE and i < self.n_sgd else None, None)
+             for i, (p, buf, e, gi) in enumerate(entries)], dev)
         # sgd=False (stand-alone ModelEMA.update): every entry goes through the gradient path with no gradients, so the
         # counter / decay kernel runs and the update kernel leaves parameters alone
+        self.ranges = []
         for lo, hi, has in ((0, self.n_sgd, True), (self.n_sgd, len(entries), not self.sgd)):
             for a in range(lo, hi, OPT_MAX_GRADS):
                 b = min(a + OPT_MAX_GRADS, hi)
-                self.ranges.append((a, b - a, first_chunk_of[a], first_chunk_of[b] - first_chunk_of[a], has))
+                self.ranges.append(Range(a, b - a, first_chunk_of[a], first_chunk_of[b] - first_chunk_of[a], has))
         self._entries = entries
-        self._tab_host = tab
         self._arena, self._acc, self.pending = None, [], 0  # (a rebuild drops pending sums: the tensors they belonged to are gone)
         self._acc_seen = set()
-        self._table = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dev)
-        self._cmap = torch.tensor(cmap, dtype=torch.int32).reshape(-1, 2).contiguous().to(dev)
-        self.n_grad_chunks = first_chunk_of[self.n_sgd] if self.sgd else len(cmap)
+        self.n_grad_chunks = first_chunk_of[self.n_sgd] if self.sgd else first_chunk_of[-1]
         self._partials = torch.zeros(max(self.n_grad_chunks, 1), dtype=torch.float32, device=dev)
         had = getattr(self, "_state", None) is not None
-        steps = int(self._state.view(torch.int64)[3]) if had else 0  # rebuild: keep Adam's t ...
-        mu_product = float(self._state.view(torch.float64)[7]) if had else 0.0  # ... and NAdam's running product
-        self._state = torch.zeros(64, dtype=torch.uint8, device=dev)
+        steps = self._state_get("steps") if had else 0  # rebuild: keep Adam's t ...
+        mu_product = self._state_get("mu_product") if had else 0.0  # ... and NAdam's running product
+        self._state = torch.zeros(ctypes.sizeof(OptState), dtype=torch.uint8, device=dev)
         if steps:
-            self._state.view(torch.int64)[3] = steps
-            self._state.view(torch.float64)[7] = mu_product
-        self._dev_updates = 0  # host mirror of the device-side EMA update counter (_state[2]); see _sync_updates
+            self._state_set("steps", steps)
+            self._state_set("mu_product", mu_product)
+        self._dev_updates = 0  # host mirror of the device-side EMA update counter (the record's `updates`); see _sync_updates
         self._hyper = torch.zeros(20, dtype=torch.float32, device=dev)
         self._hyper_host = None  # a fresh device array: the next sync_hyper() must fill it
         self._ptrs = [p.data_ptr() for p, *_ in entries]
@@ -179,33 +200,41 @@ class FusedSGD:
     def _stale(self):
         return self._table is None or any(p.data_ptr() != q for (p, *_), q in zip(self._entries, self._ptrs))
 
+    # ---- the state record (OptState) by field name ---------------------------------------------------------------------------
+    def _state_get(self, name):
+        """one device->host read"""
+        dtype, k = _STATE_SLOT[name]
+        return self._state.view(dtype)[k].item()
+
+    def _state_set(self, name, value):
+        """one fill on the device"""
+        dtype, k = _STATE_SLOT[name]
+        self._state.view(dtype)[k] = value
+
+    # ---- the hyper array by field name ---------------------------------------------------------------------------------------
+    def hyper_values(self):
+        """the 20 floats of csrc/optim.hip's `hyper` as Python floats (host only): what every class sets, then what _rule_fields() adds"""
+        g, ema = self.param_groups, self.ema
+        v = {**_HYPER_ZERO, "max_norm": self.max_norm, "ema_decay": ema.decay_max if ema is not None else 0.0, "ema_tau": ema.tau if ema is not None else 1.0,
+             "grad_scale": 1.0 / self.world, "rule": self.RULE, **self._rule_fields()}
+        assert len(v) == len(_HYPER_ZERO), set(v) - set(_HYPER_ZERO)  # (a hook named a field the layout does not have)
+        return [float(grp["lr"]) for grp in g] + [float(grp["weight_decay"]) for grp in g] + [float(v[k]) for k in _HYPER_ZERO]
+
     def sync_hyper(self):
         """push lr / momentum / weight decay to the device if a scheduler changed them (call before replaying a graph
         that captured step(); step() calls it itself)."""
-        g = self.param_groups
-        ema = self.ema
-        host = [g[0]["lr"], g[1]["lr"], g[2]["lr"], g[0]["weight_decay"], g[1]["weight_decay"], g[2]["weight_decay"], self._beta1(),
-                self.max_norm, ema.decay_max if ema is not None else 0.0, ema.tau if ema is not None else 1.0, 1.0 if g[0].get("nesterov") else 0.0,
-                1.0 / self.world, *self._rule_hyper(), *self._rule_extra()]
-        host = [float(v) for v in host]
+        host = self.hyper_values()
         if host != self._hyper_host:
             self._hyper.copy_(torch.tensor(host, dtype=torch.float32))
             self._hyper_host = host
         self._sync_updates()
 
-    def _beta1(self):
+    def _rule_fields(self):
+        """the hyper fields this class sets, after checking that the three groups agree on them"""
         g = self.param_groups
         if any(grp["momentum"] != g[0]["momentum"] or grp["nesterov"] != g[0]["nesterov"] for grp in g):
             raise RuntimeError("FusedSGD: momentum / nesterov are shared by the three groups (as the reference sets them)")
-        return g[0]["momentum"]
-
-    def _rule_hyper(self):
-        """hyper[12..16]: beta2, eps, rule, 1 - beta2, 1 - beta1."""
-        return 0.0, 0.0, float(self.RULE), 0.0, 0.0
-
-    def _rule_extra(self):
-        """hyper[17..19]."""
-        return 0.0, 0.0, 0.0
+        return {"momentum": g[0]["momentum"], "nesterov": 1.0 if g[0]["nesterov"] else 0.0}
 
     def _sync_updates(self):
         """the kernel derives the EMA decay from a DEVICE counter; `ema.updates` is the host's view of it.  A caller may set
@@ -213,7 +242,7 @@ class FusedSGD:
         (trainer.py:771) - possibly after the tables were built: push it whenever it differs from what the device holds
         (runs before every step and before every graph replay, outside captured regions)."""
         if self.ema is not None and self._table is not None and int(self.ema.updates) != self._dev_updates:
-            self._state.view(torch.int64)[2] = int(self.ema.updates)
+            self._state_set("updates", int(self.ema.updates))
             self._dev_updates = int(self.ema.updates)
 
     def count_updates(self, delta):
@@ -224,6 +253,20 @@ class FusedSGD:
             self._dev_updates += delta
 
     # ---- the step --------------------------------------------------------------------------------------------------
+    def _gather(self, r, grads_of):
+        """the gradients of range r -> (ctypes array of their addresses, null where there is none; whether there is any; the float32 contiguous
+        copies made of gradients that were not, to keep alive until the launches are issued)"""
+        arr, found, keep = (ctypes.c_void_p * r.n)(), False, []
+        for i, p in enumerate(self.params[r.first:r.first + r.n]):  # (empty for the ranges of EMA-only entries)
+            g = grads_of.get(p) if grads_of is not None else p.grad
+            if g is not None:
+                if g.dtype != torch.float32 or not g.is_contiguous() or g.shape != p.shape:
+                    g = g.to(torch.float32).contiguous()
+                    keep.append(g)
+                arr[i] = g.data_ptr()
+                found = True
+        return arr, found, keep
+
     def step(self, grads_of=None):
         """grads_of: optional {param: gradient tensor} (default: p.grad).  Parameters without a gradient keep their
         value and momentum (torch.optim.SGD skips them) but still enter the EMA."""
@@ -234,36 +277,20 @@ class FusedSGD:
             self._build()
         self.sync_hyper()
         L = _lib.lib()
-        tab, cmap = ctypes.c_void_p(self._table.data_ptr()), self._cmap
-        st = stream_ptr()
-        grad_arrays = []
-        for first, n, c0, nc, has in self.ranges:
-            if not has:
-                grad_arrays.append(None)
-                continue
-            arr = (ctypes.c_void_p * n)()
-            for i in range(n if first < self.n_sgd else 0):
-                p = self.params[first + i]
-                g = grads_of.get(p) if grads_of is not None else p.grad
-                if g is not None:
-                    if g.dtype != torch.float32 or not g.is_contiguous() or g.shape != p.shape:
-                        g = g.to(torch.float32).contiguous()
-                        self._keep.append(g)
-                    arr[i] = g.data_ptr()
-            grad_arrays.append(arr)
-        last_grad = max((i for i, r in enumerate(self.ranges) if r[4]), default=-1)
-        for i, (first, n, c0, nc, has) in enumerate(self.ranges):
-            if has and nc:
-                check(L.ymi_opt_grad_norm(tab, ctypes.c_void_p(cmap.data_ptr() + c0 * 8), first, n, nc, grad_arrays[i], ctypes.c_void_p(self._hyper.data_ptr()),
-                                          ctypes.c_void_p(self._partials.data_ptr()), c0, self.n_grad_chunks, ctypes.c_void_p(self._state.data_ptr()),
-                                          1 if i == last_grad else 0, st), "opt_grad_norm")
+        vp = ctypes.c_void_p
+        tab, hyper, state, st = vp(self._table.data_ptr()), vp(self._hyper.data_ptr()), vp(self._state.data_ptr()), stream_ptr()
+        gathered = [self._gather(r, grads_of) if r.has_grads else None for r in self.ranges]  # (holds the converted copies until the launches are issued)
+        last_grad = max((i for i, r in enumerate(self.ranges) if r.has_grads), default=-1)
+        for i, r in enumerate(self.ranges):
+            if r.has_grads and r.n_chunks:
+                check(L.ymi_opt_grad_norm(tab, vp(self._cmap.data_ptr() + r.chunk0 * 8), r.first, r.n, r.n_chunks, gathered[i][0], hyper, vp(self._partials.data_ptr()),
+                                          r.chunk0, self.n_grad_chunks, state, 1 if i == last_grad else 0, st), "opt_grad_norm")
         if last_grad < 0:
             raise RuntimeError("FusedSGD.step(): nothing to update")
-        for i, (first, n, c0, nc, has) in enumerate(self.ranges):
-            if nc:
-                check(L.ymi_opt_update(tab, ctypes.c_void_p(cmap.data_ptr() + c0 * 8), first, n, nc, grad_arrays[i] if has else None,
-                                       ctypes.c_void_p(self._hyper.data_ptr()), ctypes.c_void_p(self._state.data_ptr()), int(self.RULE), st), "opt_update")
-        self._keep.clear()
+        for i, r in enumerate(self.ranges):
+            if r.n_chunks:
+                check(L.ymi_opt_update(tab, vp(self._cmap.data_ptr() + r.chunk0 * 8), r.first, r.n, r.n_chunks, gathered[i][0] if r.has_grads else None, hyper, state,
+                                       int(self.RULE), st), "opt_update")
         if self.ema is not None:
             self.ema.updates += 1
             self._dev_updates += 1
@@ -296,23 +323,14 @@ class FusedSGD:
         tab = ctypes.c_void_p(self._table.data_ptr())
         st = stream_ptr()
         keep = []
-        for first, n, c0, nc, has in self.ranges:
-            if not (has and nc) or first >= self.n_sgd:
+        for r in self.ranges:
+            if not (r.has_grads and r.n_chunks) or r.first >= self.n_sgd:
                 continue
-            arr = (ctypes.c_void_p * n)()
-            any_grad = False
-            for i in range(n):
-                p = self.params[first + i]
-                g = grads_of.get(p) if grads_of is not None else p.grad
-                if g is not None:
-                    if g.dtype != torch.float32 or not g.is_contiguous() or g.shape != p.shape:
-                        g = g.to(torch.float32).contiguous()
-                        keep.append(g)
-                    arr[i] = g.data_ptr()
-                    self._acc_seen.add(first + i)
-                    any_grad = True
-            if any_grad:
-                check(L.ymi_opt_grad_accumulate(tab, ctypes.c_void_p(self._cmap.data_ptr() + c0 * 8), first, n, nc, arr, st), "opt_grad_accumulate")
+            arr, found, copies = self._gather(r, grads_of)
+            keep += copies
+            self._acc_seen.update(r.first + i for i in range(r.n) if arr[i])
+            if found:
+                check(L.ymi_opt_grad_accumulate(tab, ctypes.c_void_p(self._cmap.data_ptr() + r.chunk0 * 8), r.first, r.n, r.n_chunks, arr, st), "opt_grad_accumulate")
         self.pending += 1
 
     def step_pending(self):
@@ -334,11 +352,11 @@ class FusedSGD:
 
     def grad_norm(self):
         """total gradient norm of the last step (before clipping), as clip_grad_norm_ returns it: one device->host read."""
-        return float(self._state.view(torch.float32)[1])
+        return self._state_get("norm")
 
     def steps_taken(self):
-        """optimizer steps taken so far, counted on the device (one device->host read)."""
-        return int(self._state.view(torch.int64)[3]) if self._table is not None else 0
+        """optimizer steps taken so far (Adam's t), counted on the device (one device->host read)."""
+        return self._state_get("steps") if self._table is not None else 0
 
     def zero_grad(self, set_to_none=True):
         for grp in self.param_groups:
@@ -348,31 +366,45 @@ class FusedSGD:
                 elif p.grad is not None:
                     p.grad.zero_()
 
-    # ---- torch.optim.SGD-compatible state (checkpoint contract: trainer.py:546 stores optimizer.state_dict()) ---------
+    # ---- torch.optim-compatible state (checkpoint contract: trainer.py:546 stores optimizer.state_dict()) ---------------
     def state_dict(self):
         if self._table is None:
             self._build()
+        t = float(self.steps_taken()) if self.STORES_STEP else 0.0
+        defaults = self.GROUP_DEFAULTS | ({"fused": None, "decoupled_weight_decay": self.RULE == 1} if self.RULE in (1, 2) else {})
         state, groups, idx = {}, [], 0
         for grp in self.param_groups:
             ids = []
-            for _ in grp["params"]:
-                state[idx] = {"momentum_buffer": self.momentum[idx]}
+            for p in grp["params"]:
+                if not self.STORES_STEP or (t > 0 and p.requires_grad):  # torch creates a parameter's state at its first step with a gradient
+                    state[idx] = ({"step": torch.tensor(t)} if self.STORES_STEP else {}) | {k: getattr(self, a)[idx] for k, a in self.STATE_BUFFERS}
+                    for k in self.EXTRA_STATE:
+                        state[idx][k] = torch.tensor(getattr(self, k)())
                 ids.append(idx)
                 idx += 1
-            groups.append({k: v for k, v in grp.items() if k != "params"} | {"params": ids, "maximize": False, "foreach": None, "differentiable": False, "fused": None})
+            groups.append({k: v for k, v in grp.items() if k != "params"} | {"params": ids} | defaults)
         return {"state": state, "param_groups": groups}
 
     def load_state_dict(self, sd):
         if self._table is None:
             self._build()
         for grp, saved in zip(self.param_groups, sd["param_groups"]):
-            for k in ("lr", "initial_lr", "momentum", "nesterov", "weight_decay"):
+            for k in self.LOAD_KEYS:
                 if k in saved:
-                    grp[k] = saved[k]
+                    grp[k] = tuple(saved[k]) if k == "betas" else saved[k]
+        steps = 0
         for idx, st in sd["state"].items():
-            buf = st.get("momentum_buffer")
-            if buf is not None:
-                self.momentum[int(idx)].copy_(buf.to(self.momentum[int(idx)].dtype))
+            for k, a in self.STATE_BUFFERS:
+                buf = st[k] if self.STORES_STEP else st.get(k)  # (torch.optim.SGD holds None before a parameter's first step)
+                if buf is not None:
+                    getattr(self, a)[int(idx)].copy_(buf.to(torch.float32))
+            if self.STORES_STEP:
+                steps = max(steps, int(float(st["step"])))
+            for k in self.EXTRA_STATE:
+                if k in st:
+                    self._state_set(k, float(st[k]))
+        if self.STORES_STEP:
+            self._state_set("steps", steps)  # one t for every parameter (they step together)
 
 
 class FlatFold:
@@ -384,17 +416,9 @@ class FlatFold:
         for d in dsts:
             if d.dtype != torch.float32 or not d.is_contiguous() or d.dim() != 1:
                 raise RuntimeError("FlatFold adds flat contiguous float32 buffers")
-        chunk = int(_lib.lib().ymi_opt_chunk_elems())
-        tab = (OptEntry * len(dsts))()
-        cmap, self._range = [], []
-        for i, d in enumerate(dsts):
-            tab[i] = OptEntry(None, None, None, d.numel(), 0, 0, None, d.data_ptr())
-            n = (d.numel() + chunk - 1) // chunk
-            self._range.append((len(cmap), n))
-            cmap.extend((i, c) for c in range(n))
+        _, self._table, self._cmap, first = build_table([OptEntry(None, None, None, d.numel(), 0, 0, None, d.data_ptr()) for d in dsts], dsts[0].device)
+        self._range = [(a, b - a) for a, b in zip(first, first[1:])]  # (first chunk, chunks) of each destination
         self.dsts = list(dsts)
-        self._table = torch.frombuffer(bytearray(bytes(tab)), dtype=torch.uint8).to(dsts[0].device)
-        self._cmap = torch.tensor(cmap, dtype=torch.int32).reshape(-1, 2).contiguous().to(dsts[0].device)
 
     def add(self, i, src):
         if src.dtype != torch.float32 or not src.is_contiguous() or src.numel() != self.dsts[i].numel():
@@ -415,6 +439,10 @@ class FusedAdamW(FusedSGD):
 
     RULE = 1
     SECOND_KEY = "exp_avg_sq"  # (Adamax: exp_inf)
+    STATE_BUFFERS = (("exp_avg", "momentum"), (SECOND_KEY, "second"))
+    STORES_STEP = True
+    LOAD_KEYS = ("lr", "initial_lr", "betas", "eps", "weight_decay")
+    GROUP_DEFAULTS = {"maximize": False, "foreach": None, "capturable": False, "differentiable": False}
 
     def __init__(self, model, lr=0.001, betas=(0.9, 0.999), eps=1e-8, decay=5e-4, max_norm=10.0, ema=None, decoupled=True):
         super().__init__(model, lr=lr, momentum=betas[0], decay=decay, nesterov=False, max_norm=max_norm, ema=ema)
@@ -424,58 +452,16 @@ class FusedAdamW(FusedSGD):
                 grp.pop(k)
             grp.update(betas=(float(betas[0]), float(betas[1])), eps=float(eps), amsgrad=False)
 
-    def _beta1(self):
+    def _rule_fields(self):
         g = self.param_groups
         if any(tuple(grp["betas"]) != tuple(g[0]["betas"]) or grp["eps"] != g[0]["eps"] for grp in g):
             raise RuntimeError("FusedAdamW: betas / eps are shared by the three groups (as the reference sets them)")
-        return g[0]["betas"][0]
-
-    def _rule_hyper(self):
-        g = self.param_groups[0]
-        return g["betas"][1], g["eps"], float(self.RULE), 1 - g["betas"][1], 1 - g["betas"][0]
+        b1, b2 = g[0]["betas"]
+        return {"momentum": b1, "beta2": b2, "eps": g[0]["eps"], "one_minus_beta2": 1 - b2, "one_minus_beta1": 1 - b1}
 
     @property
     def exp_avg(self):
         return self.momentum
-
-    def steps_taken(self):
-        """Adam's t (one device->host read)."""
-        return int(self._state.view(torch.int64)[3]) if self._table is not None else 0
-
-    def state_dict(self):
-        if self._table is None:
-            self._build()
-        t = float(self.steps_taken())
-        state, groups, idx = {}, [], 0
-        for grp in self.param_groups:
-            ids = []
-            for p in grp["params"]:
-                if t > 0 and p.requires_grad:  # torch creates a parameter's state at its first step with a gradient
-                    state[idx] = {"step": torch.tensor(t), "exp_avg": self.momentum[idx], self.SECOND_KEY: self.second[idx]}
-                    if self.RULE == 4:
-                        state[idx]["mu_product"] = torch.tensor(self.mu_product())
-                ids.append(idx)
-                idx += 1
-            extra = {"fused": None, "decoupled_weight_decay": self.RULE == 1} if self.RULE in (1, 2) else {}
-            groups.append({k: v for k, v in grp.items() if k != "params"} | {"params": ids, "maximize": False, "foreach": None, "capturable": False,
-                                                                             "differentiable": False} | extra)
-        return {"state": state, "param_groups": groups}
-
-    def load_state_dict(self, sd):
-        if self._table is None:
-            self._build()
-        for grp, saved in zip(self.param_groups, sd["param_groups"]):
-            for k in ("lr", "initial_lr", "betas", "eps", "weight_decay"):
-                if k in saved:
-                    grp[k] = tuple(saved[k]) if k == "betas" else saved[k]
-        steps = 0
-        for idx, st in sd["state"].items():
-            self.momentum[int(idx)].copy_(st["exp_avg"].to(torch.float32))
-            self.second[int(idx)].copy_(st[self.SECOND_KEY].to(torch.float32))
-            steps = max(steps, int(float(st["step"])))
-            if self.RULE == 4 and "mu_product" in st:
-                self._state.view(torch.float64)[7] = float(st["mu_product"])
-        self._state.view(torch.int64)[3] = steps  # one t for every parameter (they step together)
 
 
 class FusedAdamax(FusedAdamW):
@@ -483,6 +469,7 @@ class FusedAdamax(FusedAdamW):
     p -= lr / (1 - beta1^t) * exp_avg / exp_inf; weight decay added to the gradient.  State layout: step, exp_avg, exp_inf."""
 
     SECOND_KEY = "exp_inf"
+    STATE_BUFFERS = (("exp_avg", "momentum"), (SECOND_KEY, "second"))
 
     def __init__(self, model, lr=0.002, betas=(0.9, 0.999), eps=1e-8, decay=5e-4, max_norm=10.0, ema=None):
         super().__init__(model, lr=lr, betas=betas, eps=eps, decay=decay, max_norm=max_norm, ema=ema, decoupled=False)
@@ -495,6 +482,8 @@ class FusedNAdam(FusedAdamW):
     """torch.optim.NAdam (momentum_decay 4e-3, weight decay added to the gradient): the Nesterov momentum schedule
     mu_t = beta1 (1 - 0.5 * 0.96^(t * momentum_decay)) and its running product are kept on the device.  State: step, mu_product, exp_avg, exp_avg_sq."""
 
+    EXTRA_STATE = ("mu_product",)
+
     def __init__(self, model, lr=0.002, betas=(0.9, 0.999), eps=1e-8, decay=5e-4, max_norm=10.0, ema=None, momentum_decay=4e-3):
         super().__init__(model, lr=lr, betas=betas, eps=eps, decay=decay, max_norm=max_norm, ema=ema, decoupled=False)
         self.RULE = 4
@@ -502,14 +491,14 @@ class FusedNAdam(FusedAdamW):
             grp.pop("amsgrad", None)
             grp.update(momentum_decay=float(momentum_decay), decoupled_weight_decay=False)
 
-    def _rule_extra(self):
-        """momentum_decay, and the float32 tails of beta1 and momentum_decay (the device rebuilds both to double precision)."""
-        f32 = lambda v: float(torch.tensor(v, dtype=torch.float32))
+    def _rule_fields(self):
+        """... and momentum_decay, with the float32 tails of beta1 and momentum_decay (the device rebuilds both to double precision)."""
+        f32 = lambda v: float(torch.tensor(v, dtype=torch.float32))  # noqa: E731
         b1, md = float(self.param_groups[0]["betas"][0]), float(self.param_groups[0]["momentum_decay"])
-        return md, b1 - f32(b1), md - f32(md)
+        return super()._rule_fields() | {"momentum_decay": md, "beta1_tail": b1 - f32(b1), "momentum_decay_tail": md - f32(md)}
 
     def mu_product(self):
-        return float(self._state.view(torch.float64)[7]) if self.steps_taken() else 1.0
+        return self._state_get("mu_product") if self.steps_taken() else 1.0
 
 
 class FusedRAdam(FusedAdamW):
@@ -529,6 +518,10 @@ class FusedRMSprop(FusedSGD):
     State layout: step, square_avg, momentum_buffer."""
 
     RULE = 6
+    STATE_BUFFERS = (("square_avg", "second"), ("momentum_buffer", "momentum"))
+    STORES_STEP = True
+    LOAD_KEYS = ("lr", "initial_lr", "momentum", "alpha", "eps", "weight_decay")
+    GROUP_DEFAULTS = FusedAdamW.GROUP_DEFAULTS
 
     def __init__(self, model, lr=0.01, momentum=0.937, alpha=0.99, eps=1e-8, decay=5e-4, max_norm=10.0, ema=None):
         super().__init__(model, lr=lr, momentum=momentum, decay=decay, nesterov=False, max_norm=max_norm, ema=ema)
@@ -537,45 +530,8 @@ class FusedRMSprop(FusedSGD):
                 grp.pop(k)
             grp.update(alpha=float(alpha), eps=float(eps), centered=False)
 
-    def _beta1(self):
+    def _rule_fields(self):
         g = self.param_groups
         if any(grp["momentum"] != g[0]["momentum"] or grp["alpha"] != g[0]["alpha"] or grp["eps"] != g[0]["eps"] for grp in g):
             raise RuntimeError("FusedRMSprop: momentum / alpha / eps are shared by the three groups (as the reference sets them)")
-        return g[0]["momentum"]
-
-    def _rule_hyper(self):
-        g = self.param_groups[0]
-        return g["alpha"], g["eps"], float(self.RULE), 1 - g["alpha"], 0.0
-
-    def steps_taken(self):
-        return int(self._state.view(torch.int64)[3]) if self._table is not None else 0
-
-    def state_dict(self):
-        if self._table is None:
-            self._build()
-        t = float(self.steps_taken())
-        state, groups, idx = {}, [], 0
-        for grp in self.param_groups:
-            ids = []
-            for p in grp["params"]:
-                if t > 0 and p.requires_grad:
-                    state[idx] = {"step": torch.tensor(t), "square_avg": self.second[idx], "momentum_buffer": self.momentum[idx]}
-                ids.append(idx)
-                idx += 1
-            groups.append({k: v for k, v in grp.items() if k != "params"} | {"params": ids, "maximize": False, "foreach": None, "capturable": False,
-                                                                             "differentiable": False})
-        return {"state": state, "param_groups": groups}
-
-    def load_state_dict(self, sd):
-        if self._table is None:
-            self._build()
-        for grp, saved in zip(self.param_groups, sd["param_groups"]):
-            for k in ("lr", "initial_lr", "momentum", "alpha", "eps", "weight_decay"):
-                if k in saved:
-                    grp[k] = saved[k]
-        steps = 0
-        for idx, st in sd["state"].items():
-            self.second[int(idx)].copy_(st["square_avg"].to(torch.float32))
-            self.momentum[int(idx)].copy_(st["momentum_buffer"].to(torch.float32))
-            steps = max(steps, int(float(st["step"])))
-        self._state.view(torch.int64)[3] = steps
+        return {"momentum": g[0]["momentum"], "beta2": g[0]["alpha"], "eps": g[0]["eps"], "one_minus_beta2": 1 - g[0]["alpha"]}

@@ -221,7 +221,7 @@ class TrainStep:
             self._boundary = model.boundary_layers()
             groups = [self._head_params, self._back_params]
         self.buckets = GradientBuckets(model, world_size, bucket_bytes, overlap=not self.use_graph, groups=groups)
-        # the buckets hold gradient SUMS over ranks; the fused step applies 1 / world (hyper[11]) - no divide launches
+        # the buckets hold gradient SUMS over ranks; the fused step applies 1 / world (the grad scale of its hyper array) - no divide launches
         self.opt.world = world_size
         self._seed = None
         self._held = []  # model-side buffers the captured graphs write (_hold_captured)

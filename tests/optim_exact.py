@@ -3,7 +3,7 @@
   scalars()     everything opt_finalize_kernel writes into the 64-byte state record, in Python floats, with the float32 rounding points
                 the kernel documents (or, round32=False, with none of them: what torch.optim computes on float64 parameters).
   update()      one step of one tensor in float64 from float32 inputs, after torch.optim's single-tensor formulas as the comments of
-                opt_update_kernel name them; restate_step() applies it to a list of entries.
+                opt_update (csrc/optim.hip) name them; restate_step() applies it to a list of entries.
   scaled_err()  per-element error over the magnitudes that entered the result.
   F32_DISTANCE  the distance of float32 torch.optim (+ clip_grad_norm_ + the oracle's ModelEMA) from this restatement, measured by
                 tests/test_host_optim_check.py; the bounds of tests/test_gpu_optim_exact.py are MARGIN times these.
@@ -53,7 +53,7 @@ def ulps32(a, b):
 # ------------------------------------------------------------------------------------------------------------------ hyper and state
 def hyper_vector(rule, lr, wd, beta1, *, max_norm=10.0, ema_decay=0.9999, tau=2000.0, nesterov=False, gscale=1.0, beta2=0.999, eps=1e-8,
                  momentum_decay=4e-3, round32=True):
-    """the 20 floats of optim.hip's `hyper` as engine/optim.py::sync_hyper fills them (lr, wd: one value per group; beta1 is the momentum of
+    """the 20 floats of optim.hip's `hyper` as engine/optim.py::hyper_values fills them (lr, wd: one value per group; beta1 is the momentum of
     SGD / RMSprop; beta2 is RMSprop's alpha).  round32: every entry rounded to float32, as the device array holds it."""
     h = [*lr, *wd, beta1, max_norm, ema_decay, tau, 1.0 if nesterov else 0.0, gscale, 0.0, 0.0, float(rule), 0.0, 0.0, 0.0, 0.0, 0.0]
     if rule:

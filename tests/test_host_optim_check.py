@@ -300,10 +300,45 @@ def test_planted_fault_is_beyond_the_gpu_bound(fault):
 
 
 def test_update_body_is_built_with_its_own_contraction():
-    """vector path, tail and scalar path of opt_update_kernel round alike only while the shared body states its fused multiply-adds itself and
-    the build honours its contract(off) pragma (the GPU test holds the paths to bit equality; this holds the build to what that needs)"""
+    """vector path, tail and scalar path of opt_update_kernel round alike only while the one element body states its fused multiply-adds itself
+    and the build honours its contract(off) pragma (the GPU test holds the paths to bit equality; this holds the build to what that needs)"""
     csrc = Path(__file__).resolve().parents[1] / "improving_yolov8_cbam_swinblock_amd" / "csrc"
     assert "FLAGS_optim := -ffp-contract=fast-honor-pragmas" in (csrc / "Makefile").read_text()
     src = (csrc / "optim.hip").read_text()
-    body = src[src.index("auto one = [&]"):src.index("const bool vec =")]
-    assert "#pragma clang fp contract(off)" in body and "eo = fmaf(ev, d, omd * po);" in body
+    # the body: the scalar overload of opt_update, up to the float4 overload that calls it four times
+    body = src[src.index("Updated<float> opt_update(const StepScalars& k"):src.index("Updated<f32x4> opt_update(const StepScalars& k")]
+    assert body.index("{") < body.index("#pragma clang fp contract(off)") < body.index("fmaf(")  # the pragma heads the compound statement
+    assert "#pragma clang fp contract(off)" in body and "o.ema = fmaf(ev, k.d, k.omd * o.p);" in body
+    assert src.count("fmaf(ev,") == 1 and src.count("k.omd *") == 1  # the EMA line is defined once: no path has a copy to drift
+
+
+@pytest.mark.parametrize("rule", sorted(X.RULES))
+def test_host_hyper_values_follow_the_layout_of_the_restatement(rule):
+    """engine/optim.py::hyper_values (built by field name, in the order of optim.hip's enum Hyper) against optim_exact.hyper_vector (built by
+    index): the two statements of the 20-float layout agree for every class, with a distinct lr and weight decay in every group.  No device:
+    the optimizers build no tables before their first step."""
+    from improving_yolov8_cbam_swinblock_amd.engine import optim as O
+
+    model = X.Toy(X.CHUNK, "cpu")
+    ema = O.ModelEMA(model, decay=0.9995, tau=1500)
+    common = {"decay": 5e-4, "max_norm": 7.0, "ema": ema}
+    adam = {"betas": (0.91, 0.9985), "eps": 3e-8, **common}
+    opt = {0: lambda: O.FusedSGD(model, lr=0.01, momentum=0.93, nesterov=True, **common), 1: lambda: O.FusedAdamW(model, lr=0.002, **adam),
+           2: lambda: O.FusedAdamW(model, lr=0.002, decoupled=False, **adam), 3: lambda: O.FusedAdamax(model, lr=0.002, **adam),
+           4: lambda: O.FusedNAdam(model, lr=0.002, momentum_decay=3e-3, **adam), 5: lambda: O.FusedRAdam(model, lr=0.002, **adam),
+           6: lambda: O.FusedRMSprop(model, lr=0.01, momentum=0.93, alpha=0.985, eps=3e-8, **common)}[rule]()
+    assert opt.RULE == rule and opt._table is None
+    lr, wd = (0.011, 0.0052, 0.023), (1e-5, 5e-4, 2e-4)
+    for grp, a, b in zip(opt.param_groups, lr, wd):
+        grp["lr"], grp["weight_decay"] = a, b
+    opt.world = 4
+    beta1, beta2 = (0.93, 0.985 if rule == 6 else 0.999) if rule in (0, 6) else (0.91, 0.9985)
+    want = X.hyper_vector(rule, lr, wd, beta1, max_norm=7.0, ema_decay=0.9995, tau=1500.0, nesterov=rule == 0, gscale=0.25, beta2=beta2, eps=3e-8,
+                          momentum_decay=3e-3, round32=False)
+    got = opt.hyper_values()
+    assert len(got) == 20 == len(O.HYPER_FIELDS) + 4 and all(type(v) is float for v in got)
+    if rule == 4:  # the float32 tails of beta1 and momentum_decay, which hyper_vector leaves 0 without round32
+        assert got[18:] == [0.91 - X.f32(0.91), 3e-3 - X.f32(3e-3)] and all(got[18:])
+        got = got[:18] + [0.0, 0.0]
+    assert got == want, [(i, g, w) for i, (g, w) in enumerate(zip(got, want)) if g != w]
+    assert opt._table is None  # (nothing was built, nothing touched a device)
