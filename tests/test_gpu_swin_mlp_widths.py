@@ -7,6 +7,8 @@ import functools
 import pytest
 import torch
 
+from swin_mlp_exact import decode_pre
+
 pytestmark = pytest.mark.gpu
 
 WIDTHS = [128, 384]
@@ -170,8 +172,9 @@ def test_forward_matches_the_unfused_kernels(c):
 @pytest.mark.parametrize("c", WIDTHS)
 @pytest.mark.parametrize("t,hidden,strided", [(33, 32, False), (421, None, False), (421, None, True)])
 def test_backward_data_path_against_float64(c, t, hidden, strided):
-    """post = gelu(pre), d_pre = bf16(d_out W2) * gelu'(pre), d_u = d_pre W1, all as written row-major; pre is the float64 chain's (the kernel
-    reads its own saved copy, whose private layout is not decoded here: a wrong unit or token would be O(1) in post)"""
+    """post = gelu(pre), d_pre = bf16(d_out W2) * gelu'(pre), d_u = d_pre W1, all as written row-major, against the float64 chain; the saved
+    pre-activations the kernel reads back, decoded from their private layout (tests/swin_mlp_exact.py), against that chain's pre with the
+    bounds of tests/test_gpu_swin_mlp_fused.py::test_fused_forward_against_float64"""
     L, lib = _lib()
     hidden = hidden or 4 * c
     k = _case(c, t, hidden)
@@ -188,6 +191,9 @@ def test_backward_data_path_against_float64(c, t, hidden, strided):
                                          ctypes.byref(L.as_ymi(du)), L.stream_ptr()), "bwd_data")
     torch.cuda.synchronize()
     pd = k["ref"][3].double()
+    dp = (decode_pre(k["pre"], c, t, hidden).double() - pd).abs()
+    assert dp.max().item() <= 2.0 ** -6 * pd.abs().max().item()
+    assert (dp > 2.0 ** -8 * (pd.abs() + 0.05)).double().mean().item() < 0.02
     rpost = torch.nn.functional.gelu(pd)
     w1b, w2b = k["w1"].to(torch.bfloat16).double(), k["w2"].to(torch.bfloat16).double()
     dpost = (dout.double() @ w2b).to(torch.bfloat16).double()
