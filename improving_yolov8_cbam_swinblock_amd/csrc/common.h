@@ -400,6 +400,12 @@ struct BnCoefArgs {
     float* coef;  // [5][C] or nullptr
     GammaBeta2 g2;
 };
+// the one statement of the apply pass's arithmetic (reduce_bwd.hip: bn_act_bwd_apply_kernel; wgrad.hip: conv1x1_bwd_kernel, which forms draw on its
+// operand path): draw = dout * act'(raw * a0 + a1) * c0 - (raw * c1 + c2)
+template <int ACT> __device__ __forceinline__ float bn_bwd_apply_one(float d, float x, float a0, float a1, float c0, float c1, float c2) {
+    const float dz = d * act_grad<ACT>(x * a0 + a1);
+    return dz * c0 - (x * c1 + c2);
+}
 // a final pass: sum `blocks` partial rows [block][2][C] per channel into out0 (dbeta) / out1 (dgamma), either may be null, and derive bn.coef
 struct BnFinal {
     const float* part;
@@ -544,6 +550,12 @@ int ymi_conv2d_fwd_statacc(const ymi_tensor* x, const void* w_packed, int64_t co
 int ymi_chan_reduce_final(const float* part, int blocks, int C, float* out0, float* out1, hipStream_t stream);
 int ymi_bn_bwd_final(const float* part, int blocks, int C, const float* gamma, const float* beta, const float* mean, const float* inv, float inv_count,
                      float* dgamma, float* dbeta, float* coef, hipStream_t stream);
+
+// reduce_bwd.hip: a BatchNorm + activation backward up to the apply pass's coefficients - the reduce pass and the final pass (riding in a held
+// weight-gradient launch when there is one).  dgamma / dbeta are written; *coef points at [a0 | a1 | c0 | c1 | c2][C] inside `workspace`
+// (ymi_bn_act_bwd's size), valid for later launches of `stream` until the workspace is reused.
+int ymi_bn_act_bwd_coef(const ymi_tensor* dout, const ymi_tensor* raw, const float* gamma, const float* save_mean, const float* save_invstd, const float* beta,
+                        GammaBeta2 g2, int32_t act, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, hipStream_t stream, const float** coef);
 
 // wgrad.hip: the record ymi_wgrad_reduce_batch sums the slabs of one launch from ([splits][elems] slabs, elems = padded Cout * ng, a multiple of 8;
 // first_block is filled in by the batched sum).  It sets the sum's geometry: more interleaved split chains per output element the more splits there are,

@@ -307,8 +307,7 @@ __global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(RV dout, RV raw, 
             float o[G];
 #pragma unroll
             for (int r = 0; r < G; ++r) {
-                const float dz = d[r] * act_grad<ACT>(x[r] * a0[r] + a1[r]);
-                o[r] = dz * c0[r] - (x[r] * c1[r] + c2[r]);
+                o[r] = bn_bwd_apply_one<ACT>(d[r], x[r], a0[r], a1[r], c0[r], c1[r], c2[r]);
             }
             Pack<T, G>::store(op + p * draw.ld + g * G, o);
         };
@@ -328,8 +327,7 @@ __global__ __launch_bounds__(256) void bn_act_bwd_apply_kernel(RV dout, RV raw, 
 #pragma unroll
             for (int r = 0; r < G; ++r) {
                 const int c = g * G + r;
-                const float dz = d[r] * act_grad<ACT>(x[r] * coef[c] + coef[C + c]);
-                o[r] = dz * coef[2 * C + c] - (x[r] * coef[3 * C + c] + coef[4 * C + c]);
+                o[r] = bn_bwd_apply_one<ACT>(d[r], x[r], coef[c], coef[C + c], coef[2 * C + c], coef[3 * C + c], coef[4 * C + c]);
             }
             Pack<T, G>::store(op + p * draw.ld + g * G, o);
         }
@@ -372,14 +370,11 @@ extern "C" int ymi_bn_act_bwd_pair(const ymi_tensor* dout, const ymi_tensor* raw
     YMI_CHECK_ARG(dout && split > 0 && split < dout->c && split % 4 == 0 && gamma2 && beta2, "bn_act_bwd_pair: split");
     return bn_act_bwd_impl(dout, raw, gamma, save_mean, save_invstd, beta, GammaBeta2{gamma2, beta2, (int)split}, act, draw, dgamma, dbeta, workspace, workspace_bytes, stream);
 }
-static int bn_act_bwd_impl(const ymi_tensor* dout, const ymi_tensor* raw, const float* gamma, const float* save_mean,
-                           const float* save_invstd, const float* beta, GammaBeta2 g2, int32_t act, const ymi_tensor* draw, float* dgamma,
-                           float* dbeta, void* workspace, size_t workspace_bytes, void* stream) {
-    YMI_CHECK_ARG(ymi_tensor_ok(dout) && ymi_tensor_ok(raw) && ymi_tensor_ok(draw) && ymi_same_shape(dout, raw) && ymi_same_shape(dout, draw),
-                  "bn_act_bwd: shapes");
-    YMI_CHECK_ARG(dout->dtype == raw->dtype && raw->dtype == draw->dtype, "bn_act_bwd: dtypes");
+int ymi_bn_act_bwd_coef(const ymi_tensor* dout, const ymi_tensor* raw, const float* gamma, const float* save_mean, const float* save_invstd, const float* beta,
+                        GammaBeta2 g2, int32_t act, float* dgamma, float* dbeta, void* workspace, size_t workspace_bytes, hipStream_t s, const float** coef_out) {
+    YMI_CHECK_ARG(ymi_tensor_ok(dout) && ymi_tensor_ok(raw) && ymi_same_shape(dout, raw), "bn_act_bwd: shapes");
+    YMI_CHECK_ARG(dout->dtype == raw->dtype, "bn_act_bwd: dtypes");
     YMI_CHECK_ARG(save_mean && save_invstd && dgamma && dbeta && workspace, "bn_act_bwd: null argument");
-    YMI_CHECK_ARG(draw->ld % 4 == 0, "bn_act_bwd: draw ld");
     const int64_t P = ymi_pixels(dout);
     const int C = (int)dout->c;
     const int rblocks = reduce_blocks(P, C);
@@ -388,19 +383,17 @@ static int bn_act_bwd_impl(const ymi_tensor* dout, const ymi_tensor* raw, const 
         ymi_set_error("bn_act_bwd: workspace %zu < %zu", workspace_bytes, need);
         return YMI_EWORKSPACE;
     }
-    hipStream_t s = (hipStream_t)stream;
     int blocks = 0;
     float* coef = (float*)workspace + (size_t)rblocks * 2 * C;
     double* xrows = reinterpret_cast<double*>(coef + 6 * (size_t)C);  // (8-byte aligned: the workspace is, and every term is a multiple of 8 bytes)
     const BnCoefArgs bn{gamma, beta, save_mean, save_invstd, 1.0f / (float)P, coef, g2};
+    *coef_out = coef;
     if (bn_tail_on() && C <= 1024) {
         // dbeta = sum dz, dgamma = sum dz*xhat and the apply pass's coefficients from the reduce kernel's last workgroups
         unsigned* tickets = ymi_ticket_slot();
         YMI_CHECK_ARG(tickets, "bn_act_bwd: ticket counters");
-        int rc = launch_chan_reduce<1>(dout, raw, gamma, beta, save_mean, save_invstd, act, (float*)workspace, &blocks, s, "bn_act_bwd(reduce)", g2,
-                                       ReduceTail{tickets, rblocks % 32 == 0 ? 32 : 8, xrows, dbeta, dgamma, bn});
-        if (rc) return rc;
-        return launch_bn_apply(dout, raw, draw, act, coef, s);
+        return launch_chan_reduce<1>(dout, raw, gamma, beta, save_mean, save_invstd, act, (float*)workspace, &blocks, s, "bn_act_bwd(reduce)", g2,
+                                     ReduceTail{tickets, rblocks % 32 == 0 ? 32 : 8, xrows, dbeta, dgamma, bn});
     }
     int rc = launch_chan_reduce<1>(dout, raw, gamma, beta, save_mean, save_invstd, act, (float*)workspace, &blocks, s, "bn_act_bwd(reduce)", g2);
     if (rc) return rc;
@@ -409,7 +402,20 @@ static int bn_act_bwd_impl(const ymi_tensor* dout, const ymi_tensor* raw, const 
     const BnFinal f{(const float*)workspace, blocks, C, dbeta, dgamma, bn};
     if (C <= 1024 && ymi_wgrad_issue_held(&f, s)) YMI_CHECK_LAUNCH("bn_act_bwd(final, riding)");
     else if ((rc = launch_final(f, s, "bn_act_bwd(final)")) != YMI_OK) return rc;
-    return launch_bn_apply(dout, raw, draw, act, coef, s);
+    return YMI_OK;
+}
+// the whole backward: the coefficients (above), then the apply pass
+static int bn_act_bwd_impl(const ymi_tensor* dout, const ymi_tensor* raw, const float* gamma, const float* save_mean,
+                           const float* save_invstd, const float* beta, GammaBeta2 g2, int32_t act, const ymi_tensor* draw, float* dgamma,
+                           float* dbeta, void* workspace, size_t workspace_bytes, void* stream) {
+    YMI_CHECK_ARG(ymi_tensor_ok(dout) && ymi_tensor_ok(raw) && ymi_tensor_ok(draw) && ymi_same_shape(dout, raw) && ymi_same_shape(dout, draw),
+                  "bn_act_bwd: shapes");
+    YMI_CHECK_ARG(dout->dtype == raw->dtype && raw->dtype == draw->dtype, "bn_act_bwd: dtypes");
+    YMI_CHECK_ARG(draw->ld % 4 == 0, "bn_act_bwd: draw ld");
+    const float* coef = nullptr;
+    const int rc = ymi_bn_act_bwd_coef(dout, raw, gamma, save_mean, save_invstd, beta, g2, act, dgamma, dbeta, workspace, workspace_bytes, (hipStream_t)stream, &coef);
+    if (rc) return rc;
+    return launch_bn_apply(dout, raw, draw, act, coef, (hipStream_t)stream);
 }
 
 // dx = dy * gelu'(pre)

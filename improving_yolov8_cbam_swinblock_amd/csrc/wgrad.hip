@@ -400,6 +400,23 @@ __device__ __forceinline__ void wg_store_slab_staged(char* ring, int wave, int l
     }
 }
 
+// ---- which tile a workgroup runs -------------------------------------------------------------------------------------------------------------
+// -> (bx, by, bz) = column block, row block, pixel split; false: a padding id of the XCD-mapped grid.  first: workgroups ahead of the tiles (riders).
+__device__ __forceinline__ bool wg_tile_of_block(const WgradArgs& a, int first, int& bx, int& by, int& bz) {
+    if (a.xcd_map) {
+        const int id = (int)blockIdx.x - first, xcd = id & 7, seq = id >> 3, nxy = a.nx * a.ny;
+        const int zi = seq / nxy, t = seq - zi * nxy;
+        const int spx = (a.splits + 7) >> 3;
+        bz = xcd * spx + zi;
+        if (zi >= spx || bz >= a.splits) return false;
+        by = t / a.nx;
+        bx = t - by * a.nx;
+    } else {
+        bx = blockIdx.x; by = blockIdx.y; bz = blockIdx.z;
+    }
+    return true;
+}
+
 // ---- the kernel ------------------------------------------------------------------------------------------------------------------------------
 // BIAS: the instantiation that also forms the bias gradient's partials (its own code object: the 4 * TR accumulator registers and the branch
 // cost the bias-free launches 3-4 % when they were a run-time option of one kernel)
@@ -429,17 +446,7 @@ __global__ __launch_bounds__(256, (BM == 128 ? 3 : WG_WAVES)) void wgrad_kernel(
         if ((int)blockIdx.x * 32 < rider.f.C) bn_final_block<NT, false>(rider.f, (int)blockIdx.x, reinterpret_cast<double*>(smem));  // (else: a padding workgroup of the rider block)
         return;
     }
-    if (a.xcd_map) {
-        const int id = (int)blockIdx.x - rider.nwg, xcd = id & 7, seq = id >> 3, nxy = a.nx * a.ny;
-        const int zi = seq / nxy, t = seq - zi * nxy;
-        const int spx = (a.splits + 7) >> 3;
-        bz = xcd * spx + zi;
-        if (zi >= spx || bz >= a.splits) return;  // padding ids leave before any barrier
-        by = t / a.nx;
-        bx = t - by * a.nx;
-    } else {
-        bx = blockIdx.x; by = blockIdx.y; bz = blockIdx.z;
-    }
+    if (!wg_tile_of_block(a, rider.nwg, bx, by, bz)) return;  // padding ids leave before any barrier
     const int j0 = bx * WG_BN, co0 = by * BM;
     const int m_begin = bz * a.pix_per_split;
     const int m_end = min(a.Mpix, m_begin + a.pix_per_split);
@@ -501,6 +508,230 @@ __global__ __launch_bounds__(256, (BM == 128 ? 3 : WG_WAVES)) void wgrad_kernel(
     }
 }
 
+// ---- backward of a 1x1 stride-1 Conv block in one kernel: BatchNorm apply, data gradient and weight gradient --------------------------------------
+// draw - the gradient of the block's raw convolution output - has exactly two readers, the data-gradient and the weight-gradient GEMM, and for a
+// 1x1 stride-1 convolution each uses every element once.  This kernel forms draw on the operand path instead: a workgroup owns a pixel split and a
+// 128-wide block of input channels and holds ALL output channels (BM = Cout = 64 or 128).  Per 32-pixel step its threads load dout and raw rows
+// into registers, apply bn_bwd_apply_one (the apply pass's arithmetic, coefficients of the thread's channel group in registers), round to
+// bfloat16 and store into the ring's dY image exactly where the LDS-DMA pieces of wgrad_kernel would have landed; X rows come in by LDS-DMA.  The
+// image then feeds two products: dW += draw^T X (WFrag::step, accumulators in registers for the whole split, slab store and slab sum as wgrad_kernel's)
+// and dx[32][128] = draw W, with W the data-gradient operand [Cin][Cout] held in registers as MFMA A fragments (the draw fragments are plain
+// 16-byte reads of the same image), summed with up to two addends in float32, rounded once and stored as whole 256-byte row segments through LDS.
+// draw never reaches HBM.  Column blocks beyond the first recompute draw from rows their XCD's L2 already holds (a split's tiles run back to back).
+struct Conv1x1BwdArgs {
+    WgradArgs w;  // x, slab, Mpix, CoutP (= BM), Cin (= NG), split and grid geometry; dy is unused
+    const void* dout;
+    const void* raw;
+    int64_t ld_dout, ld_raw;
+    const float* coef;  // [a0 | a1 | c0 | c1 | c2][Cout]
+    const void* wd;     // data-gradient operand [Cin][Cout] bfloat16
+    void* dx;
+    const void* add1;
+    const void* add2;
+    int64_t ld_dx, ld_a1, ld_a2;
+};
+constexpr int C1_DROW = WG_BN * 4 + 16;  // a float32 row of the dx stage, padded
+template <int BM> constexpr size_t conv1x1_bwd_lds_bytes() { return wgrad_lds_bytes<bf16_t, BM>() + (size_t)WG_BK * C1_DROW; }
+
+// LDS accesses of the K loop as inline assembly, for WFrag's reason: the compiler puts `s_waitcnt vmcnt(0)` in front of LDS accesses that follow
+// LDS-DMA pieces and would wait for the NEXT step's loads in every step.  The loop's own waits and barriers order them.
+__device__ __forceinline__ u32x4 c1_lds_read16(const char* p) {
+    u32x4 v;
+    asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"((uint32_t)(uintptr_t)(lptr_t)p));
+    return v;
+}
+// (the value comes straight out of an MFMA: the compiler does not know that this statement is an LDS instruction reading it and leaves out the
+// wait states an XDL result needs before a DS read - up to 19 for a 16-pass MFMA - so they are written here)
+__device__ __forceinline__ void c1_lds_write16_mfma(char* p, f32x4 v) {
+    asm volatile("s_nop 15\n\ts_nop 3\n\tds_write_b128 %0, %1" ::"v"((uint32_t)(uintptr_t)(lptr_t)p), "v"(v) : "memory");
+}
+
+template <int BM, int ACT>
+__global__ __launch_bounds__(256, (BM == 128 ? 2 : 3)) void conv1x1_bwd_kernel(Conv1x1BwdArgs p) {
+    using T = bf16_t;
+    using G = WgTile<T, BM>;
+    constexpr int NT = G::NT, TR = G::TR, TC = G::TC, WM = G::WM, STAGE = G::STAGE, NS = WG_NS, NY = G::NY, NX = G::NX;
+    constexpr int RING = NS * STAGE;
+    constexpr int KK = BM / 32;  // 32-deep steps of the data-gradient product's reduction over the output channels
+    static_assert(G::YT == NT && WG_BK == 32 && NS == 2, "every thread owns NY chunks of the dY image; two stages");
+    static_assert(RING >= (NT / 64) * SlabStage<bf16_t, TR>::BYTES && RING >= (NT / 64) * SlabStage<float, TR>::BYTES, "the staged slab stores use the ring");
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    char* dxs = smem + RING;  // [32][C1_DROW]: a step's dx tile in float32
+
+    const WgradArgs& a = p.w;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wr = wave / G::WCOLS, wc = wave % G::WCOLS;
+    int bx, by, bz;
+    if (!wg_tile_of_block(a, 0, bx, by, bz)) return;
+    const int j0 = bx * WG_BN;
+    const int m_begin = bz * a.pix_per_split;
+    const int m_end = min(a.Mpix, m_begin + a.pix_per_split);
+    const G ld(a, tid, j0, 0);
+
+    // this thread's channel group of the dY image and its coefficients
+    float k0[8], k1[8], k2[8], k3[8], k4[8];
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        const int c = ld.ych + r;
+        k0[r] = p.coef[c];
+        k1[r] = p.coef[BM + c];
+        k2[r] = p.coef[2 * BM + c];
+        k3[r] = p.coef[3 * BM + c];
+        k4[r] = p.coef[4 * BM + c];
+    }
+    // W as A fragments: this wave's two 16-channel tiles of the column block; lane = (input channel, 8 consecutive output channels)
+    bf16x8 wf[2][KK];
+#pragma unroll
+    for (int ct = 0; ct < 2; ++ct) {
+        const int ci = j0 + (2 * wave + ct) * 16 + (lane & 15);
+#pragma unroll
+        for (int kk = 0; kk < KK; ++kk) {
+            u32x4 v = {0u, 0u, 0u, 0u};
+            if (ci < a.Cin) v = *reinterpret_cast<const u32x4*>(reinterpret_cast<const T*>(p.wd) + (int64_t)ci * BM + kk * 32 + (lane >> 4) * 8);
+            wf[ct][kk] = __builtin_bit_cast(bf16x8, v);
+        }
+    }
+    // The pixel order of the sum is wgrad_kernel's for the same tensors (pw_shift by the same host rule), so a split's partial - and with it the
+    // rounded slab and dW - is bit for bit what the three launches give: row r of a step is pixel origin + r in raster order, and pixel
+    // (r >> pw_shift, r & (pw - 1)) of a ph x pw patch in patch order (WgPatchWalk; stride 1 and one tap here: a pixel is one row of every
+    // tensor).  Splits are whole patches in patch order, so only raster order meets rows beyond the split's end.
+    const bool patch = a.pw_shift >= 0;  // (uniform)
+    const int pw = patch ? 1 << a.pw_shift : WG_BK, ph = WG_BK / pw;
+    auto row_off = [&](int row) { return patch ? (row >> a.pw_shift) * a.W + (row & (pw - 1)) : row; };
+    struct { int m, wo, ho; } org, nxt;  // origin pixel of the current step and of the next (scalar)
+    org.m = m_begin; org.wo = org.ho = 0;
+    if (patch) {
+        const int pidx = m_begin / WG_BK, npw = a.W >> a.pw_shift, nph = a.H / ph;
+        const int t = pidx / npw, wp = pidx - t * npw;
+        const int n = t / nph, hp = t - n * nph;
+        org.wo = wp * pw; org.ho = hp * ph;
+        org.m = (n * a.H + org.ho) * a.W + org.wo;
+    }
+    auto advance = [&](auto o) {
+        if (!patch) { o.m += WG_BK; return o; }
+        o.wo += pw; o.m += pw;
+        if (o.wo == a.W) {
+            o.wo = 0; o.ho += ph; o.m += (ph - 1) * a.W;
+            if (o.ho == a.H) o.ho = 0;
+        }
+        return o;
+    };
+    // X pieces: row x_row(i) of the step, this thread's chunk; out-of-range lanes (padding columns, rows beyond the tensor) read zeros
+    uint32_t xv[NX];
+#pragma unroll
+    for (int i = 0; i < NX; ++i) xv[i] = ld.x_cok ? (uint32_t)((row_off(ld.x_row(i)) * (int)a.ldx + ld.ci) * 2) : 0x80000000u;
+    int yo[NY];  // pixel offsets of this thread's dY rows
+#pragma unroll
+    for (int i = 0; i < NY; ++i) yo[i] = row_off(ld.y_row(i));
+    // the dx tile's store map: a thread owns 8 channels (chunk) of rows drow, drow + 16
+    const int dch = tid & 15, drow = tid >> 4;
+    const bool d_cok = j0 + dch * 8 < a.Cin;
+    const int dro[2] = {row_off(drow), row_off(drow + 16)};
+
+    f32x4 acc[TR][TC];
+#pragma unroll
+    for (int r = 0; r < TR; ++r)
+#pragma unroll
+        for (int c = 0; c < TC; ++c) acc[r][c] = f32x4{0.f, 0.f, 0.f, 0.f};
+    f32x4 accb[1] = {f32x4{0.f, 0.f, 0.f, 0.f}};
+
+    const int nk = (m_end - m_begin + WG_BK - 1) / WG_BK;
+    u32x4 rd[NY], rr[NY];
+    auto load_rows = [&](int mo) {  // dout / raw chunks of the step with origin mo (masked: rows beyond the split's end are not read)
+#pragma unroll
+        for (int i = 0; i < NY; ++i) {
+            const int m = mo + yo[i];
+            rd[i] = rr[i] = u32x4{0u, 0u, 0u, 0u};
+            if (patch || m < m_end) {
+                rd[i] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const T*>(p.dout) + (int64_t)m * p.ld_dout + ld.ych);
+                rr[i] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const T*>(p.raw) + (int64_t)m * p.ld_raw + ld.ych);
+            }
+        }
+    };
+    auto issue_x = [&](int s, int mo) {
+        char* Xs = smem + s * STAGE + G::YBYTES;
+        const uint32_t soff = __builtin_amdgcn_readfirstlane((uint32_t)mo * (uint32_t)a.ldx * 2u);
+#pragma unroll
+        for (int i = 0; i < NX; ++i) wg_buffer_to_lds(a.x, a.x_bytes, G::x_slot(Xs, i, wave), xv[i], soff);
+    };
+    load_rows(org.m);
+    issue_x(0, org.m);
+    for (int kt = 0; kt < nk; ++kt, org = nxt) {
+        const int mk = org.m;
+        nxt = advance(org);
+        char* Ys = smem + (kt & 1) * STAGE;
+        // draw of this step from the rows in registers -> the dY image; rows beyond the split's end hold zeros (after the arithmetic: -c2 otherwise)
+#pragma unroll
+        for (int i = 0; i < NY; ++i) {
+            const bf16x8 d = __builtin_bit_cast(bf16x8, rd[i]), x = __builtin_bit_cast(bf16x8, rr[i]);
+            const bool ok = patch || mk + yo[i] < m_end;
+            bf16x8 o;
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+                const float v = bn_bwd_apply_one<ACT>((float)d[r], (float)x[r], k0[r], k1[r], k2[r], k3[r], k4[r]);
+                o[r] = (bf16_t)(ok ? v : 0.0f);
+            }
+            *reinterpret_cast<bf16x8*>(Ys + (i * NT + tid) * 16) = o;
+        }
+        // the image and this step's X pieces are in LDS for every wave; every wave is through the previous step
+        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        // loads of the next step fly under this step's products
+        if (kt + 1 < nk) {
+            issue_x((kt + 1) & 1, nxt.m);
+            load_rows(nxt.m);
+        }
+        // product 1: dW += draw^T X
+        WFrag<T>::template step<BM, TR, TC, false>(Ys, Ys + G::YBYTES, wr * WM, wc * 64, lane, acc, false, accb);
+        // product 2: dx^T[ci][px] = W^T draw^T - operands swapped as in product 1, so a lane's four values are consecutive input channels of one pixel
+#pragma unroll
+        for (int pt = 0; pt < 2; ++pt) {  // 16 pixels at a time: the draw fragments of one half stay in registers
+            u32x4 bq[KK];
+            const int px = pt * 16 + (lane & 15);
+            const int sw = tr_swz<tr_swz_mode(BM * 2)>(px) << 1;
+#pragma unroll
+            for (int kk = 0; kk < KK; ++kk) bq[kk] = c1_lds_read16(Ys + px * (BM * 2) + (((kk * 4 + (lane >> 4)) ^ sw) << 4));
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+#pragma unroll
+            for (int kk = 0; kk < KK; ++kk) asm volatile("" : "+v"(bq[kk]));
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) {
+                f32x4 d = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int kk = 0; kk < KK; ++kk) d = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[ct][kk], __builtin_bit_cast(bf16x8, bq[kk]), d, 0, 0, 0);
+                c1_lds_write16_mfma(dxs + px * C1_DROW + ((2 * wave + ct) * 16 + 4 * (lane >> 4)) * 4, d);
+            }
+        }
+        asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
+        // the dx tile: + addends (read before the store: an addend may be dx itself), one rounding, whole row segments.  The addends are read
+        // here, behind the next step's loads: held in registers across the products they cost the kernel a workgroup per CU.
+#pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            const int row = drow + 16 * h, m = mk + dro[h];
+            const bool ok = (patch || m < m_end) && d_cok;
+            u32x4 ra[2] = {u32x4{0u, 0u, 0u, 0u}, u32x4{0u, 0u, 0u, 0u}};  // both addends of a row in flight together
+            if (ok && p.add1) ra[0] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const T*>(p.add1) + (int64_t)m * p.ld_a1 + j0 + dch * 8);
+            if (ok && p.add2) ra[1] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const T*>(p.add2) + (int64_t)m * p.ld_a2 + j0 + dch * 8);
+            u32x4 lo = c1_lds_read16(dxs + row * C1_DROW + dch * 32), hi = c1_lds_read16(dxs + row * C1_DROW + dch * 32 + 16);
+            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+            asm volatile("" : "+v"(lo), "+v"(hi));
+            const f32x4 flo = __builtin_bit_cast(f32x4, lo), fhi = __builtin_bit_cast(f32x4, hi);
+            float v[8] = {flo[0], flo[1], flo[2], flo[3], fhi[0], fhi[1], fhi[2], fhi[3]};
+#pragma unroll
+            for (int q = 0; q < 2; ++q) {  // (a missing addend is zeros: x + 0 is x)
+                const bf16x8 t = __builtin_bit_cast(bf16x8, ra[q]);
+#pragma unroll
+                for (int r = 0; r < 8; ++r) v[r] += (float)t[r];
+            }
+            if (ok) Pack<T, 8>::store(reinterpret_cast<T*>(p.dx) + (int64_t)m * p.ld_dx + j0 + dch * 8, v);
+        }
+    }
+
+    const int64_t slab_off = (int64_t)bz * a.CoutP * a.NG;
+    const int row0 = wr * WM, col0 = j0 + wc * 64;
+    if (a.slab_bf16) wg_store_slab_staged<bf16_t>(smem, wave, lane, acc, reinterpret_cast<bf16_t*>(a.slab) + slab_off, row0, col0, a.CoutP, a.NG);
+    else wg_store_slab_staged<float>(smem, wave, lane, acc, reinterpret_cast<float*>(a.slab) + slab_off, row0, col0, a.CoutP, a.NG);
+}
 
 // ---- the slab sums -----------------------------------------------------------------------------------------------------------------------------
 // the sum of the `splits` values p[e], p[e + stride], ... in a fixed order (deterministic): four independent chains keep the split loads in flight,
@@ -669,6 +900,20 @@ extern "C" size_t ymi_conv2d_bwd_weight_workspace(int64_t m_rows, int64_t cout, 
 
 static int wgrad_impl(const ymi_tensor* x, const ymi_tensor* dy, int64_t cout_real, int64_t cin_real, int64_t kh, int64_t kw, int64_t stride,
                       float* dw_oihw, float* dbias, void* workspace, size_t workspace_bytes, ymi_wgrad_pending* pending, void* stream);
+static int wgrad_slab_sum(const WgradArgs& a, int64_t cout_real, int64_t cin_real, int64_t ntaps, float* dw_oihw, float* dbias, ymi_wgrad_pending* pending,
+                          hipStream_t s);
+// the patch order of the pixel sum for these operands (bfloat16, the operands as buffers below 2^31 bytes, whole 32-pixel steps): log2 of the widest
+// power-of-two patch width that divides Wo with a height that divides Ho; -1: raster order.  ONE rule: every kernel that sums these pixels uses it.
+static int wgrad_patch_shift(const ymi_tensor* x, const ymi_tensor* dy) {
+    const int64_t xb = ymi_pixels(x) * x->ld * ymi_esize(x->dtype), yb = ymi_pixels(dy) * dy->ld * ymi_esize(dy->dtype);
+    const int64_t margin = (x->w + 2) * x->ld * (int64_t)ymi_esize(x->dtype);
+    if (!(x->dtype == YMI_BF16 && ymi_opt(OPT_WGRAD_PATCH) && xb + margin < (1ll << 31) && yb < (1ll << 31) && ymi_pixels(dy) % WG_BK == 0)) return -1;
+    for (int sh = 5; sh >= 0; --sh) {
+        const int pw = 1 << sh, ph = WG_BK >> sh;
+        if (dy->w % pw == 0 && dy->h % ph == 0) return sh;
+    }
+    return -1;
+}
 
 // ---- a launch, possibly held back (common.h: BnRider) ------------------------------------------------------------------------------------
 struct WgradLaunch {
@@ -847,21 +1092,10 @@ static int wgrad_impl(const ymi_tensor* x, const ymi_tensor* dy, int64_t cout_re
     wg_find_divisor(a.Ho, &a.ho_mul, &a.ho_shr);
     a.nx = (int)((ng + bn - 1) / bn); a.ny = (int)((dy->c + bm - 1) / bm); a.splits = p.splits;
     // patch order of the pixel sum (see wgrad_kernel): the widest power-of-two patch width that divides Wo with a height that divides Ho
-    a.pw_shift = -1;
-    {
-        const int64_t xb = ymi_pixels(x) * x->ld * ymi_esize(x->dtype), yb = ymi_pixels(dy) * dy->ld * ymi_esize(dy->dtype);
-        const int64_t margin = (x->w + 2) * x->ld * (int64_t)ymi_esize(x->dtype);
-        if (bf16 && ymi_opt(OPT_WGRAD_PATCH) && xb + margin < (1ll << 31) && yb < (1ll << 31) && mpix % WG_BK == 0) {
-            for (int sh = 5; sh >= 0; --sh) {
-                const int pw = 1 << sh, ph = WG_BK >> sh;
-                if (dy->w % pw == 0 && dy->h % ph == 0) {
-                    a.pw_shift = sh;
-                    break;
-                }
-            }
-            a.x_bytes = (uint32_t)xb;
-            a.y_bytes = (uint32_t)yb;
-        }
+    a.pw_shift = wgrad_patch_shift(x, dy);
+    if (a.pw_shift >= 0) {
+        a.x_bytes = (uint32_t)(ymi_pixels(x) * x->ld * ymi_esize(x->dtype));
+        a.y_bytes = (uint32_t)(ymi_pixels(dy) * dy->ld * ymi_esize(dy->dtype));
     }
     a.xcd_map = p.splits >= 8 ? 1 : 0;  // (all tiles of a pixel split on one XCD: 275 -> 105 MB of HBM reads per launch)
     dim3 grid((unsigned)a.nx, (unsigned)a.ny, (unsigned)p.splits);
@@ -884,21 +1118,101 @@ static int wgrad_impl(const ymi_tensor* x, const ymi_tensor* dy, int64_t cout_re
         }
     }
     YMI_CHECK_LAUNCH("wgrad");
+    return wgrad_slab_sum(a, cout_real, cin_real, kh * kw, dw_oihw, dbias, pending, s);
+}
+
+// what follows a launch that wrote the slabs of `a`: the record of the batched sum, or the per-launch sums
+static int wgrad_slab_sum(const WgradArgs& a, int64_t cout_real, int64_t cin_real, int64_t ntaps, float* dw_oihw, float* dbias, ymi_wgrad_pending* pending,
+                          hipStream_t s) {
     if (pending) {  // the slab sum is left to ymi_wgrad_reduce_batch (one launch for every layer of the backward pass)
-        *pending = ymi_wgrad_record(a.slab, dw_oihw, (int64_t)a.CoutP * a.NG, p.splits, a.NG, a.Cin, (int)cout_real, (int)cin_real, (int)(kh * kw), slab_bf16,
+        *pending = ymi_wgrad_record(a.slab, dw_oihw, (int64_t)a.CoutP * a.NG, a.splits, a.NG, a.Cin, (int)cout_real, (int)cin_real, (int)ntaps, a.slab_bf16 != 0,
                                     a.bias_slab, dbias);
     } else {
-        const int64_t total = cout_real * kh * kw * cin_real;
+        const int64_t total = cout_real * ntaps * cin_real;
         int64_t gb = (total + 255) / 256;
         if (gb > 2048) gb = 2048;
-        hipLaunchKernelGGL(slab_bf16 ? wgrad_reduce_kernel<true> : wgrad_reduce_kernel<false>, dim3((unsigned)gb), dim3(256), 0, s, (const void*)a.slab, p.splits,
-                           a.CoutP, a.NG, a.Cin, (int)cout_real, (int)cin_real, (int)(kh * kw), dw_oihw);
+        hipLaunchKernelGGL(a.slab_bf16 ? wgrad_reduce_kernel<true> : wgrad_reduce_kernel<false>, dim3((unsigned)gb), dim3(256), 0, s, (const void*)a.slab, a.splits,
+                           a.CoutP, a.NG, a.Cin, (int)cout_real, (int)cin_real, (int)ntaps, dw_oihw);
     }
     YMI_CHECK_LAUNCH("wgrad_reduce");
     if (dbias && !pending) {
-        // bias gradient: the sum of the per-split column sums, written straight into the caller's buffer of dy->c floats (the real channels come first)
-        hipLaunchKernelGGL(wgrad_bias_reduce_kernel, dim3((unsigned)((dy->c + 255) / 256)), dim3(256), 0, s, (const float*)a.bias_slab, p.splits, (int)dy->c, dbias);
+        // bias gradient: the sum of the per-split column sums, written straight into the caller's buffer of CoutP floats (the real channels come first)
+        hipLaunchKernelGGL(wgrad_bias_reduce_kernel, dim3((unsigned)((a.CoutP + 255) / 256)), dim3(256), 0, s, (const float*)a.bias_slab, a.splits, a.CoutP, dbias);
         YMI_CHECK_LAUNCH("wgrad_bias_reduce");
     }
     return YMI_OK;
+}
+
+// ---- the fused backward of a 1x1 stride-1 Conv block (conv1x1_bwd_kernel) ------------------------------------------------------------------------
+// scope: bfloat16, Cout in {64, 128} dense in dout / raw (they may be channel slices), Cin a multiple of 8 up to 512 = x's and dx's channels
+static bool conv1x1_bwd_scope(const ymi_tensor* dout, const ymi_tensor* raw, const ymi_tensor* x, const ymi_tensor* add1, const ymi_tensor* add2,
+                              const ymi_tensor* dx) {
+    if (!(ymi_tensor_ok(dout) && ymi_tensor_ok(raw) && ymi_tensor_ok(x) && ymi_tensor_ok(dx))) return false;
+    if (add2 && !add1) return false;
+    const ymi_tensor* all[6] = {dout, raw, x, dx, add1, add2};
+    for (const ymi_tensor* t : all)
+        if (t && !(ymi_tensor_ok(t) && t->dtype == YMI_BF16 && t->c % 8 == 0 && t->ld % 8 == 0 && (uintptr_t)t->data % 16 == 0 && ymi_pixels(t) * t->ld < (1ll << 30))) return false;
+    if (!(ymi_same_shape(dout, raw) && (dout->c == 64 || dout->c == 128))) return false;
+    if (!(x->n == dout->n && x->h == dout->h && x->w == dout->w && x->c <= 512 && ymi_same_shape(x, dx))) return false;
+    return (!add1 || ymi_same_shape(add1, dx)) && (!add2 || ymi_same_shape(add2, dx));
+}
+extern "C" int ymi_conv1x1_bn_act_bwd_ok(const ymi_tensor* dout, const ymi_tensor* raw, const ymi_tensor* x, const ymi_tensor* add1, const ymi_tensor* add2,
+                                         const ymi_tensor* dx) {
+    return conv1x1_bwd_scope(dout, raw, x, add1, add2, dx) ? 1 : 0;
+}
+extern "C" size_t ymi_conv1x1_bn_act_bwd_workspace(int64_t m_rows, int64_t cout, int64_t cin) {
+    const int rblocks = 2048;  // (an upper bound of the reduce pass's rows, as ymi_bn_act_bwd's callers size it)
+    const size_t bn = (((size_t)rblocks * 2 * cout + 6 * (size_t)cout) * sizeof(float) + 64 * (size_t)cout * sizeof(double) + 255) / 256 * 256;
+    return bn + ymi_conv2d_bwd_weight_workspace(m_rows, cout, cin, 1, 1);
+}
+extern "C" int ymi_conv1x1_bn_act_bwd(const ymi_tensor* dout, const ymi_tensor* raw, const float* gamma, const float* save_mean, const float* save_invstd,
+                                      const float* beta, int32_t act, const ymi_tensor* x, const void* w_dgrad_packed, const ymi_tensor* add1,
+                                      const ymi_tensor* add2, const ymi_tensor* dx, float* dgamma, float* dbeta, float* dw_oihw, void* workspace,
+                                      size_t workspace_bytes, ymi_wgrad_pending* pending, void* stream) {
+    YMI_CHECK_ARG(conv1x1_bwd_scope(dout, raw, x, add1, add2, dx), "conv1x1_bn_act_bwd: outside the fused kernel's scope (ymi_conv1x1_bn_act_bwd_ok)");
+    YMI_CHECK_ARG(w_dgrad_packed && (uintptr_t)w_dgrad_packed % 16 == 0 && dw_oihw && workspace, "conv1x1_bn_act_bwd: bad argument");
+    const int64_t mpix = ymi_pixels(dout);
+    const int bm = (int)dout->c, cin = (int)x->c;
+    const size_t need = ymi_conv1x1_bn_act_bwd_workspace(mpix, bm, cin);
+    if (workspace_bytes < need) {
+        ymi_set_error("conv1x1_bn_act_bwd: workspace %zu < %zu bytes", workspace_bytes, need);
+        return YMI_EWORKSPACE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const size_t bn_bytes = need - ymi_conv2d_bwd_weight_workspace(mpix, bm, cin, 1, 1);
+    const float* coef = nullptr;
+    int rc = ymi_bn_act_bwd_coef(dout, raw, gamma, save_mean, save_invstd, beta, GammaBeta2{nullptr, nullptr, 0}, act, dgamma, dbeta, workspace, bn_bytes, s, &coef);
+    if (rc) return rc;
+    WgradPlan p = wgrad_plan(mpix, bm, cin, bm, 2);
+    const bool slab_bf16 = p.splits >= 16;  // (wgrad_impl's rule)
+    if (!slab_bf16) p = wgrad_plan(mpix, bm, cin, bm, 4);
+    Conv1x1BwdArgs k{};
+    WgradArgs& a = k.w;
+    a.x = x->data; a.slab = reinterpret_cast<char*>(workspace) + bn_bytes; a.slab_bf16 = slab_bf16 ? 1 : 0;
+    a.ldx = x->ld; a.Mpix = (int)mpix; a.H = a.Ho = (int)x->h; a.W = a.Wo = (int)x->w;
+    a.stride = 1; a.pad = 0; a.KW = 1;
+    a.CoutP = bm; a.Cin = cin; a.NG = cin; a.pix_per_split = p.pix_per_split;
+    a.nx = (cin + WG_BN - 1) / WG_BN; a.ny = 1; a.splits = p.splits;
+    a.x_bytes = (uint32_t)(((mpix - 1) * x->ld + x->c) * 2);  // X as a buffer: pieces beyond it (the last step's rows past the tensor) read zeros
+    a.xcd_map = p.splits >= 8 ? 1 : 0;
+    a.pw_shift = wgrad_patch_shift(x, dout);  // (the choice ymi_conv2d_bwd_weight makes for x and a draw of dout's shape: inside this kernel's scope the byte limits never decide)
+    k.dout = dout->data; k.raw = raw->data; k.ld_dout = dout->ld; k.ld_raw = raw->ld;
+    k.coef = coef; k.wd = w_dgrad_packed;
+    k.dx = dx->data; k.ld_dx = dx->ld;
+    k.add1 = add1 ? add1->data : nullptr; k.ld_a1 = add1 ? add1->ld : 0;
+    k.add2 = add2 ? add2->data : nullptr; k.ld_a2 = add2 ? add2->ld : 0;
+    dim3 grid((unsigned)a.nx, 1, (unsigned)p.splits);
+    if (a.xcd_map) grid = dim3((unsigned)(8 * ((p.splits + 7) / 8) * a.nx), 1, 1);
+    int prof = -1;
+    if (ymi_prof_enabled())  // both products' FLOP; dout + raw + x in, dx (+ addends) out, the weight gradient
+        prof = ymi_prof_start(s, 1, 4.0 * (double)mpix * bm * cin, ((double)mpix * (2.0 * bm + (2.0 + (add1 ? 1 : 0) + (add2 ? 1 : 0)) * cin)) * 2.0 + (double)bm * cin * 4.0,
+                              2500.0);
+    dispatch_dtype_act(YMI_BF16, act, [&](auto, auto ac) {
+        constexpr int ACT = decltype(ac)::value;
+        if (bm == 128) hipLaunchKernelGGL((conv1x1_bwd_kernel<128, ACT>), grid, dim3(256), conv1x1_bwd_lds_bytes<128>(), s, k);
+        else hipLaunchKernelGGL((conv1x1_bwd_kernel<64, ACT>), grid, dim3(256), conv1x1_bwd_lds_bytes<64>(), s, k);
+    });
+    ymi_prof_stop(s, prof);
+    YMI_CHECK_LAUNCH("conv1x1_bn_act_bwd");
+    return wgrad_slab_sum(a, bm, cin, 1, dw_oihw, nullptr, pending, s);
 }

@@ -24,6 +24,7 @@ HOOKS = {
     "first_conv": True,      # layer 0 through the direct kernels of csrc/first_conv.hip (False: the generic path)
     "stat_atomics": True,    # BatchNorm statistics as fixed-point atomic sums, finalized inside the affine pass (False: per-block rows + a finalize launch)
     "wgrad_rider": True,     # BatchNorm-backward final passes ride in the previous layer's weight-gradient launch (False: their own launches)
+    "fused_bwd_1x1": True,   # backward of 1x1 Conv blocks with 64 / 128 output channels as one kernel after the BatchNorm sums (False: apply pass + two GEMMs)
 }
 
 

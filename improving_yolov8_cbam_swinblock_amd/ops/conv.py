@@ -188,6 +188,36 @@ def _bn_act_bwd(dout, raw, stats, act, gamma, beta, second=None):
     return draw, dgamma, dbeta
 
 
+def _conv1x1_bwd_fused(dout, raw, stats, act, gamma, beta, x, weight, job):
+    """the backward of a 1x1 stride-1 Conv block as ymi_conv1x1_bn_act_bwd: job (of _dgrad_prepare) names the result, the packed operand and the
+    addends of the data gradient.  -> (dgamma, dbeta, dw), the weight gradient complete or registered with the pass's deferred slab sum as
+    _wgrad's; None when the tensors are outside the kernel's scope (nothing was launched).  The launch runs on the current stream and is
+    never held for a rider: the next layer waits for its dx."""
+    lib = L()
+    o, cin = weight.shape[0], weight.shape[1]
+    dev = x.device
+    a1 = _byref(as_ymi(job.fused[0])) if len(job.fused) > 0 else None
+    a2 = _byref(as_ymi(job.fused[1])) if len(job.fused) > 1 else None
+    tdo, traw, tx, tdx = as_ymi(dout), as_ymi(raw), as_ymi(x), as_ymi(job.dxv)
+    if not lib.ymi_conv1x1_bn_act_bwd_ok(_byref(tdo), _byref(traw), _byref(tx), a1, a2, _byref(tdx)):
+        return None
+    dgamma = torch.empty(o, dtype=torch.float32, device=dev)
+    dbeta = torch.empty(o, dtype=torch.float32, device=dev)
+    params = (weight,)
+    defer = RUN.defer and _in_backward() and _adoptable(params)
+    dw = _new_dw(o, cin, 1, dev, params, None)
+    need = int(lib.ymi_conv1x1_bn_act_bwd_workspace(tdo.n * tdo.h * tdo.w, o, cin))
+    # (the slabs live in the workspace: a deferred sum needs it alive until the end-of-pass flush)
+    ws = torch.empty(need, dtype=torch.uint8, device=dev) if defer else workspace(need, dev, "conv1x1bwd")
+    rec = _lib.WgradPending() if defer else None
+    if defer:
+        _defer_wgrad(rec, (ws, x, dout, raw), weight)
+    check(lib.ymi_conv1x1_bn_act_bwd(_byref(tdo), _byref(traw), ptr(gamma), ptr(stats[0]), ptr(stats[1]), ptr(beta), act, _byref(tx), ptr(job.wd), a1, a2,
+                                     _byref(tdx), ptr(dgamma), ptr(dbeta), ptr(dw), ptr(ws), ws.numel(), _byref(rec) if defer else None, stream_ptr()),
+          "conv1x1_bn_act_bwd")
+    return dgamma, dbeta, dw
+
+
 class _ConvBnAct(torch.autograd.Function):
     """act(BatchNorm_train(conv(x))) (+ residual).  Reference: Conv.forward, nn/modules/conv.py:69-79
     (+ Bottleneck add, nn/modules/block.py:488)."""
@@ -238,16 +268,34 @@ class _ConvBnAct(torch.autograd.Function):
         dtype = x.dtype
         o, _, k, _ = weight.shape
         dout = grad_nhwc(dout, dtype)
-        draw, dgamma, dbeta = _bn_act_bwd(dout, raw, stats, act, gamma, beta)
         join, res_join = ctx.joins
+        want_dx, want_dw = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
         # the residual hand-through first: when x is both the input and the residual (Bottleneck shortcut), the data
         # gradient below is then the join's last consumer and adds `dout` in its epilogue
-        dres = _join_plain(res_join, dout) if (has_res and ctx.needs_input_grad[10]) else None
+        hand_res = has_res and ctx.needs_input_grad[10]
+        if (HOOKS["fused_bwd_1x1"] and want_dx and want_dw and k == 1 and stride == 1 and dtype == torch.bfloat16 and o in (64, 128)
+                and x.shape[1] == cin and cin <= 128 and not _deferred_twice((weight,))):
+            # a 1x1 block: BatchNorm apply, data gradient and weight gradient in ONE kernel, draw is never stored (csrc/wgrad.hip: conv1x1_bwd_kernel).
+            # One 128-wide block of input channels only: with two or three column blocks, each forming draw again, the kernel measured level with
+            # or slower than the three launches (profiles/conv1x1_bwd_fused_ab.txt); the library's scope is wider than this routing rule.
+            dres = _join_plain(res_join, dout) if hand_res else None
+            job, deposit = _dgrad_joined_prepare(join, dout, weight, k, stride, x.shape, dtype)  # (dout stands in for draw: the same shape)
+            done = _conv1x1_bwd_fused(dout, raw, stats, act, gamma, beta, x, weight, job)
+            if done is None:  # outside the kernel's scope after all: the three launches, with the job as prepared
+                draw, dgamma, dbeta = _bn_act_bwd(dout, raw, stats, act, gamma, beta)
+                dx = _dgrad_joined_finish(join, _dgrad_launch(job._replace(dy=draw, ty=as_ymi(draw))), deposit)
+                dw, _ = _wgrad_maybe_async(x, draw, o, cin, k, stride, False, (weight,))
+            else:
+                dgamma, dbeta, dw = done
+                dx = _dgrad_joined_finish(join, _dgrad_finish(job), deposit)
+            return dx, dw, dgamma, dbeta, None, None, None, None, None, None, dres, None, None, None
+        draw, dgamma, dbeta = _bn_act_bwd(dout, raw, stats, act, gamma, beta)
+        dres = _join_plain(res_join, dout) if hand_res else None
         dx = None
-        if ctx.needs_input_grad[0]:
+        if want_dx:
             dx = _dgrad_joined(join, draw, weight, k, stride, x.shape, dtype)
         dw = None
-        if ctx.needs_input_grad[1]:  # (a frozen conv weight: no GEMM, and nothing for a deferred slab sum to write into)
+        if want_dw:  # (a frozen conv weight: no GEMM, and nothing for a deferred slab sum to write into)
             dw, _ = _wgrad_maybe_async(x, draw, o, cin, k, stride, False, (weight,))
         return dx, dw, dgamma, dbeta, None, None, None, None, None, None, dres, None, None, None
 

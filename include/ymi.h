@@ -258,6 +258,23 @@ int ymi_wgrad_hold(int32_t mode);
  * scratch for n records.  The records reach the device inside kernel arguments (no host staging: graph-capturable). */
 int ymi_wgrad_reduce_batch(const ymi_wgrad_pending* host_records, int32_t n, ymi_wgrad_pending* device_table, void* stream);
 
+/* Backward of a 1x1 stride-1 Conv block, act(BN_train(conv1x1(x))), as the reduce and final pass of ymi_bn_act_bwd followed by ONE kernel that
+ * applies the BatchNorm backward on its operand path and forms both products: dx = draw W (+ add1 (+ add2), as ymi_conv2d_bwd_data_add; an addend
+ * may be dx) and the weight-gradient slabs of draw^T x (slab sum as ymi_conv2d_bwd_weight / _deferred: pending == NULL sums before the call returns
+ * control of the stream).  draw, the gradient of the raw convolution output, is never stored; its bfloat16 values are those ymi_bn_act_bwd writes.
+ * Scope (`_ok` says whether these tensors are inside it): bfloat16; dout / raw with 64 or 128 channels; x / dx / addends of one shape with the
+ * pixels of dout and a multiple of 8 up to 512 channels; every tensor may be a channel slice of a wider buffer (16-byte aligned rows).
+ * w_dgrad_packed: ymi_pack_conv_weight_dgrad's operand [cin][cout].  dw_oihw: [cout][cin] float32.  workspace >= ymi_conv1x1_bn_act_bwd_workspace bytes;
+ * with a pending record the caller keeps it alive until ymi_wgrad_reduce_batch.  The launch is never held for a rider (it produces dx); a held
+ * launch rides with this call's final pass as with ymi_bn_act_bwd's.  No reference counterpart (Conv.forward's autograd, nn/modules/conv.py:69-79). */
+int ymi_conv1x1_bn_act_bwd_ok(const ymi_tensor* dout, const ymi_tensor* raw, const ymi_tensor* x, const ymi_tensor* add1, const ymi_tensor* add2,
+                              const ymi_tensor* dx);
+size_t ymi_conv1x1_bn_act_bwd_workspace(int64_t m_rows, int64_t cout, int64_t cin);
+int ymi_conv1x1_bn_act_bwd(const ymi_tensor* dout, const ymi_tensor* raw, const float* gamma, const float* save_mean, const float* save_invstd,
+                           const float* beta, int32_t act, const ymi_tensor* x, const void* w_dgrad_packed, const ymi_tensor* add1,
+                           const ymi_tensor* add2, const ymi_tensor* dx, float* dgamma, float* dbeta, float* dw_oihw, void* workspace,
+                           size_t workspace_bytes, ymi_wgrad_pending* pending, void* stream);
+
 /* The model's FIRST Conv block on the float32 NCHW image the caller hands over (cfg/models/v8/yolov8.yaml:738 `Conv [64, 3, 2]` through
  * nn/modules/conv.py:50-79): act(BatchNorm_train(conv 3x3, stride 2, pad 1)) as DIRECT kernels that never store the raw convolution output
  * (27 products per output: recomputing is cheaper than reading back; csrc/first_conv.hip).  c <= 4, cout in {16, 32, 48, 64}, h even,

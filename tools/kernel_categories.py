@@ -7,6 +7,7 @@ from collections import defaultdict
 CATS = [
     ("igemm", ("igemm_kernel",)),
     ("wgrad", ("wgrad_kernel",)),
+    ("conv1x1_bwd", ("conv1x1_bwd_kernel",)),   # BatchNorm apply + data gradient + weight gradient of a 1x1 Conv block in one launch
     ("wgrad_reduce", ("wgrad_reduce", "wgrad_stage")),
     ("bn_fwd", ("scale_shift_act", "bn_finalize", "stat_rows")),
     ("bn_bwd", ("bn_act_bwd", "chan_reduce")),
