@@ -141,6 +141,14 @@ _SIGNATURES = {
     "ymi_detect_loss_fwd_assign": (_c_i32, [_c_i32, _TP, _TP, ctypes.POINTER(ctypes.c_float), _vp, _c_i64, _c_i32, ctypes.c_float, ctypes.c_float,
                                             _vp, _vp, _vp, _sz, _vp, _sz, _vp, _vp]),
     "ymi_detect_decode_seg": (_c_i32, [_c_i32, _TP, _TP, _TP, ctypes.POINTER(ctypes.c_float), _vp, _vp]),
+    "ymi_obb_angle_fwd": (_c_i32, [_c_i32, _TP, _vp, _vp]),
+    "ymi_obb_angle_bwd": (_c_i32, [_c_i32, _TP, _vp, _TP, _vp]),
+    "ymi_obb_targets": (_c_i32, [_vp, _vp, _vp, _c_i64, _c_i64, _c_i64, ctypes.c_float, ctypes.c_float, _vp, _vp]),
+    "ymi_obb_loss_sizes": (_c_i32, [_c_i64, _c_i64, _c_i64, ctypes.POINTER(ctypes.c_size_t), ctypes.POINTER(ctypes.c_size_t)]),
+    "ymi_obb_loss_fwd": (_c_i32, [_c_i32, _TP, _TP, _vp, ctypes.POINTER(ctypes.c_float), _vp, _c_i64, _c_i32, ctypes.c_float, ctypes.c_float,
+                                  _vp, _vp, _vp, _sz, _vp, _sz, _vp]),
+    "ymi_obb_loss_bwd": (_c_i32, [_c_i32, _TP, _TP, _vp, ctypes.POINTER(ctypes.c_float), _vp, _sz, _vp, _vp, _TP, _TP, _vp, _vp]),
+    "ymi_detect_decode_obb": (_c_i32, [_c_i32, _TP, _TP, _vp, ctypes.POINTER(ctypes.c_float), _vp, _vp]),
     "ymi_mask_loss_sizes": (_c_i32, [_c_i64, _c_i64, _c_i64, _c_i32, ctypes.POINTER(ctypes.c_size_t)]),
     "ymi_mask_loss_fwd": (_c_i32, [_c_i32, _TP, _TP, _vp, _c_i32, _c_i64, _c_i64, _vp, _vp, _c_i64, _c_i32, _c_f32, _c_f32, _vp, _vp, _vp, _vp, _sz, _vp]),
     "ymi_mask_loss_bwd": (_c_i32, [_c_i32, _TP, _TP, _vp, _c_i32, _c_i64, _c_i64, _c_i64, _c_i32, _vp, _sz, _vp, _vp, _TP, _TP, _vp]),

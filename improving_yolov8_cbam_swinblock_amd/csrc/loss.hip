@@ -389,14 +389,22 @@ __device__ __forceinline__ void topk_offer(Best& mine, const Best& prev, float v
     const bool cand = v < prev.v || (v == prev.v && a > prev.i);
     if (cand) mine = better(mine, Best{v, a});
 }
-__global__ __launch_bounds__(256) void topk_kernel(LossGeom g, const float* __restrict__ targets, const float* __restrict__ al,
-                                                   uint8_t* __restrict__ mpos, int topk) {
+// What the scan asks of a gt: "is it a label", "is this anchor's centre inside it".  AxisGt: the xyxy row and centre_inside.  (RotGt, with the
+// oriented-box kernels below: the xywhr row and the inside mask their metric kernel left.)
+struct AxisGt {
+    float gt[4];
+    __device__ __forceinline__ AxisGt(const LossGeom&, const float* targets, const uint8_t*, int bg) { gt_box(gt_row(targets, bg), gt); }
+    __device__ __forceinline__ bool valid() const { return gt_valid(gt); }
+    __device__ __forceinline__ bool inside(const LossGeom& g, int b, int a) const { return centre_inside(anchor_of(g, b, a), gt); }
+};
+template <typename Gt>
+__global__ __launch_bounds__(256) void topk_kernel(LossGeom g, const float* __restrict__ targets, const uint8_t* __restrict__ inm,
+                                                   const float* __restrict__ al, uint8_t* __restrict__ mpos, int topk) {
     __shared__ Best sh[1][4];
     const int bg = blockIdx.x;
     const int b = bg / g.G;
-    float gt[4];
-    gt_box(gt_row(targets, bg), gt);
-    if (!gt_valid(gt)) return;  // padding row: selects nothing (uniform across the block)
+    const Gt gt(g, targets, inm, bg);
+    if (!gt.valid()) return;  // padding row: selects nothing (uniform across the block)
     const float* row = al + (int64_t)bg * g.A;
     Best prev{__builtin_inff(), -1};
     // the gt's metric row is read ONCE into registers when it fits (A <= 256 * TOPK_NV: 8400 anchors at 640x640 are 33 values per
@@ -424,7 +432,7 @@ __global__ __launch_bounds__(256) void topk_kernel(LossGeom g, const float* __re
         block_combine<BestOp>(mine, sh);
         const Best win = mine[0];
         if (win.i == 0x7fffffff) break;
-        if (threadIdx.x == 0 && centre_inside(anchor_of(g, b, win.i), gt)) mpos[(int64_t)bg * g.A + win.i] = 1;
+        if (threadIdx.x == 0 && gt.inside(g, b, win.i)) mpos[(int64_t)bg * g.A + win.i] = 1;
         prev = win;
     }
 }
@@ -473,6 +481,8 @@ __global__ __launch_bounds__(256) void posmax_kernel(LossGeom g, const float* __
 }
 
 // ---- K6: per anchor target box (grid units), weight (= sum of target scores) and label; partial sums of weight --
+// NB values per box: 4 (xyxy) or 5 (xywhr: the angle is no length and keeps its value); the dense target rows hold the class in front of them
+template <int NB>
 __global__ __launch_bounds__(256) void finalize_kernel(LossGeom g, const float* __restrict__ targets, const float* __restrict__ al,
                                                        const int* __restrict__ gidx, const float* __restrict__ pa, const float* __restrict__ po,
                                                        float* __restrict__ tgt, float* __restrict__ wgt, int* __restrict__ lab,
@@ -484,19 +494,25 @@ __global__ __launch_bounds__(256) void finalize_kernel(LossGeom g, const float* 
     if (a < g.A) {
         const int64_t ia = (int64_t)b * g.A + a;
         const int k = gidx[ia];
-        float tb[4] = {0.f, 0.f, 0.f, 0.f};
+        float tb[NB];
+#pragma unroll
+        for (int i = 0; i < NB; ++i) tb[i] = 0.f;
         int lb = -1;
         if (k >= 0) {
             const int64_t bg = (int64_t)b * g.G + k;
-            const float* tg = gt_row(targets, bg);
+            const float* tg = targets + bg * (NB + 1);
             const Anchor an = anchor_of(g, b, a);
             w[0] = al[bg * g.A + a] * po[bg] / (pa[bg] + TAL_EPS);
             lb = clamped_label(tg, g.nc);
-            gt_box(tg, tb);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) tb[i] = tb[i] / an.s;
+            for (int i = 0; i < NB; ++i) tb[i] = i < 4 ? tg[1 + i] / an.s : tg[1 + i];
         }
-        Pack<float, 4>::store(tgt + ia * 4, tb);
+        if constexpr (NB == 4) {
+            Pack<float, 4>::store(tgt + ia * 4, tb);
+        } else {
+#pragma unroll
+            for (int i = 0; i < NB; ++i) tgt[ia * NB + i] = tb[i];
+        }
         wgt[ia] = w[0];
         lab[ia] = lb;
     }
@@ -653,10 +669,10 @@ struct StateView {
     int* lab;
     size_t bytes;
 };
-StateView carve_state(void* state, int64_t BA) {
+StateView carve_state(void* state, int64_t BA, int nb = 4) {
     Carve c{reinterpret_cast<char*>(state), 0};
     StateView v;
-    v.tgt = c.take<float>((size_t)BA * 4);
+    v.tgt = c.take<float>((size_t)BA * nb);
     v.wgt = c.take<float>((size_t)BA);
     v.lab = c.take<int>((size_t)BA);
     v.scal = c.take<float>(4);
@@ -665,18 +681,19 @@ StateView carve_state(void* state, int64_t BA) {
 }
 // the forward's scratch buffers, likewise
 struct WorkView {
-    float *pb, *ov, *al;  // predicted boxes [B, A, 4]; overlaps and alignment metric [B, G, A]
+    float *pb, *ov, *al;  // predicted boxes [B, A, 4] (oriented: [B, A, 5]); overlaps and alignment metric [B, G, A]
     uint8_t* mpos;        // positive mask [B, G, A]
+    uint8_t* inm;         // oriented boxes only: "label, and the anchor's centre is inside it" [B, G, A]
     int* gidx;            // gt index per anchor [B, A]
     float *pa, *po;       // per-gt max metric and max overlap [B, G]
     float *tss_part, *part;  // partial sums: weights per finalize workgroup, (box, cls, dfl) per loss workgroup
     size_t bytes;
 };
-WorkView carve_work(void* workspace, int64_t B, int64_t A, int64_t G) {
+WorkView carve_work(void* workspace, int64_t B, int64_t A, int64_t G, int nb = 4) {
     const int64_t BA = B * A, BGA = BA * G, BG = B * G;
     Carve c{reinterpret_cast<char*>(workspace), 0};
     WorkView v;
-    v.pb = c.take<float>((size_t)BA * 4);
+    v.pb = c.take<float>((size_t)BA * nb);
     v.ov = c.take<float>((size_t)BGA);
     v.al = c.take<float>((size_t)BGA);
     v.mpos = c.take<uint8_t>((size_t)BGA);
@@ -685,6 +702,7 @@ WorkView carve_work(void* workspace, int64_t B, int64_t A, int64_t G) {
     v.po = c.take<float>((size_t)BG);
     v.tss_part = c.take<float>((size_t)(BA / 256 + B + 1));
     v.part = c.take<float>((size_t)(BA * 4 / 256 + 2) * 3);
+    v.inm = nb == 5 ? c.take<uint8_t>((size_t)BGA) : nullptr;
     v.bytes = c.used;
     return v;
 }
@@ -780,10 +798,10 @@ extern "C" int ymi_detect_loss_fwd_assign(int32_t nl, const ymi_tensor* box_maps
         typedef typename decltype(t)::type T;
         launch(decode_kernel<T>, qgrid, s, g, w.pb);
         launch(metric_kernel<T>, agrid, s, g, targets, w.pb, w.ov, w.al, w.mpos, alpha, beta);
-        launch(topk_kernel, ggrid, s, g, targets, w.al, w.mpos, (int)topk);
+        launch(topk_kernel<AxisGt>, ggrid, s, g, targets, (const uint8_t*)nullptr, w.al, w.mpos, (int)topk);
         launch(assign_kernel, agrid, s, g, w.ov, w.mpos, w.gidx);
         launch(posmax_kernel, ggrid, s, g, w.ov, w.al, w.gidx, w.pa, w.po);
-        launch(finalize_kernel, agrid, s, g, targets, w.al, w.gidx, w.pa, w.po, st.tgt, st.wgt, st.lab, w.tss_part);
+        launch(finalize_kernel<4>, agrid, s, g, targets, w.al, w.gidx, w.pa, w.po, st.tgt, st.wgt, st.lab, w.tss_part);
         launch(loss_kernel<T, false>, qgrid, s, g, st.tgt, st.wgt, st.lab, st.scal, nullptr, nullptr, w.part);
         launch(loss_final_kernel, dim3(1), s, w.tss_part, (int)(agrid.x * agrid.y), w.part, (int)qgrid.x, st.scal, loss_out, out_scale);
     });
@@ -845,5 +863,507 @@ extern "C" int ymi_detect_decode_seg(int32_t nl, const ymi_tensor* box_maps, con
     dispatch_dtype(box_maps[0].dtype,
                    [&](auto t) { launch(infer_decode_seg_kernel<typename decltype(t)::type>, quad_grid(g.B, g.A), (hipStream_t)stream, g, mm, y); });
     YMI_CHECK_LAUNCH("detect_decode_seg");
+    return YMI_OK;
+}
+
+// ==== oriented boxes (reference: nn/modules/head.py:211-238 OBB, utils/loss.py:111-132 RotatedBboxLoss, loss.py:607-720 v8OBBLoss,
+// utils/tal.py:329-361 RotatedTaskAlignedAssigner, tal.py:397-416 dist2rbox, utils/metrics.py:178-239 probiou) ==================================
+// A box is (x, y, w, h, r): centre, extents along its own axes, angle in radians.  The DFL and class branches, top-k, claim, per-gt maxima and the
+// final sums are the kernels above; what reads a box as a box is stated here once each: rot_of / rbox_of (dist2rbox), cov_of and probiou_cov
+// (the Gaussian overlap and its gradient), GtAux (a label's covariance, corner and edge vectors: the inside test), RotGt.
+namespace {
+constexpr float PI_F = 3.14159265358979323846f;
+constexpr int OBB_ROW = 6;  // dense target row: class, x, y, w, h (pixels), angle
+
+struct AngleMaps {  // the one-channel angle logit maps [B, H, W, 1] (rows of padded buffers: a pixel stride) and their gradient maps
+    const void* lg[LOSS_MAXL];
+    void* dlg[LOSS_MAXL];
+    int64_t ld[LOSS_MAXL], ldd[LOSS_MAXL];
+    int dcw;  // channels of the gradient maps: the ones behind the first are written as zeros
+};
+
+// ---- angle = (sigmoid(logit) - 0.25) * pi per anchor, in anchor order (head.py:225-227), and its gradient ----------------------------------
+template <typename T, bool GRAD>
+__global__ __launch_bounds__(256) void obb_angle_kernel(LossGeom g, AngleMaps am, float* __restrict__ angle, const float* __restrict__ dangle) {
+    const int b = blockIdx.y;
+    const int a = blockIdx.x * 256 + threadIdx.x;
+    if (a >= g.A) return;
+    const Anchor an = anchor_of(g, b, a);
+    const AngleMaps& cm = am;
+    const float x = to_f32(*map_row<const T>(cm.lg, cm.ld, an));
+    const float sg = 1.0f / (1.0f + expf(-x));
+    const int64_t ia = (int64_t)b * g.A + a;
+    if constexpr (!GRAD) {
+        angle[ia] = (sg - 0.25f) * PI_F;
+    } else {
+        T* o = map_row<T>(cm.dlg, cm.ldd, an);
+        o[0] = from_f32<T>(dangle[ia] * PI_F * (sg * (1.0f - sg)));
+        for (int c = 1; c < am.dcw; ++c) o[c] = from_f32<T>(0.f);
+    }
+}
+
+// ---- the rotated forms ------------------------------------------------------------------------------------------------------------------------
+struct Rot {
+    float cs, sn;
+};
+__device__ __forceinline__ Rot rot_of(float r) { return Rot{cosf(r), sinf(r)}; }
+// dist2rbox: the four side distances, turned by the angle about the anchor -> (x, y, w, h) in grid units
+__device__ __forceinline__ void rbox_of(const Anchor& an, const float (&d)[4], const Rot& q, float (&o)[4]) {
+    const float xf = (d[2] - d[0]) * 0.5f, yf = (d[3] - d[1]) * 0.5f;
+    o[0] = xf * q.cs - yf * q.sn + an.ax;
+    o[1] = xf * q.sn + yf * q.cs + an.ay;
+    o[2] = d[0] + d[2];
+    o[3] = d[1] + d[3];
+}
+struct Cov {
+    float a, b, c;
+};
+__device__ __forceinline__ Cov cov_of(float w, float h, const Rot& q) {  // metrics.py:178-195
+    const float A = w * w / 12.0f, B = h * h / 12.0f;
+    const float c2 = q.cs * q.cs, s2 = q.sn * q.sn;
+    return Cov{A * c2 + B * s2, A * s2 + B * c2, (A - B) * q.cs * q.sn};
+}
+// probiou of box 1 (centre x1, y1, covariance c1) and box 2, in the reference's operand order (metrics.py:215-231).  GRAD: also
+// gp[5] = d / d(x1, y1, c1.a, c1.b, c1.c).  The clamps pass no gradient outside their range (torch's clamp: the ends included).
+template <bool GRAD = false>
+__device__ __forceinline__ float probiou_cov(float x1, float y1, const Cov& c1, float x2, float y2, const Cov& c2, float* gp = nullptr) {
+    const float eps = 1e-7f;
+    const float Sa = c1.a + c2.a, Sb = c1.b + c2.b, Sc = c1.c + c2.c;
+    const float dx = x1 - x2, dy = y1 - y2;
+    const float D = Sa * Sb - Sc * Sc;
+    const float den = D + eps;
+    const float N1 = Sa * (dy * dy) + Sb * (dx * dx);
+    const float N2 = Sc * (x2 - x1) * (y1 - y2);
+    const float t1 = N1 / den * 0.25f;
+    const float t2 = N2 / den * 0.5f;
+    const float r1 = c1.a * c1.b - c1.c * c1.c, r2 = c2.a * c2.b - c2.c * c2.c;
+    const float d1 = fmaxf(r1, 0.f), d2 = fmaxf(r2, 0.f);
+    const float sq = sqrtf(d1 * d2);
+    const float q = 4.0f * sq + eps;
+    const float u = D / q + eps;
+    const float t3 = logf(u) * 0.5f;
+    const float raw = t1 + t2 + t3;
+    const float bd = fminf(fmaxf(raw, eps), 100.0f);
+    const float ex = expf(-bd);
+    const float hd = sqrtf(1.0f - ex + eps);
+    if constexpr (GRAD) {
+        const float dbd = (raw >= eps && raw <= 100.0f) ? -ex / (2.0f * hd) : 0.f;  // d iou / d raw
+        const float inv = 1.0f / den;
+        const float M = (0.25f * N1 + 0.5f * N2) * inv * inv;  // (t1 + t2) / den
+        const float l = 0.5f / (u * q);                        // d t3 / d D
+        const float gSa = 0.25f * dy * dy * inv - M * Sb + l * Sb;
+        const float gSb = 0.25f * dx * dx * inv - M * Sa + l * Sa;
+        const float gSc = -0.5f * dx * dy * inv + 2.0f * M * Sc - 2.0f * l * Sc;
+        // d t3 / d d1 through q = 4 sqrt(d1 d2) + eps; a degenerate box (d1 d2 = 0, where torch's sqrt has no finite slope) passes nothing
+        const float gd1 = (r1 >= 0.f && sq > 0.f) ? (-0.5f * D / (u * q * q)) * (2.0f * d2 / sq) : 0.f;
+        gp[0] = dbd * (0.5f * Sb * dx - 0.5f * Sc * dy) * inv;
+        gp[1] = dbd * (0.5f * Sa * dy - 0.5f * Sc * dx) * inv;
+        gp[2] = dbd * (gSa + gd1 * c1.b);
+        gp[3] = dbd * (gSb + gd1 * c1.a);
+        gp[4] = dbd * (gSc - 2.0f * gd1 * c1.c);
+    }
+    return 1.0f - hd;
+}
+// the chain from the covariance back to (w, h, r): gc = d / d(c.a, c.b, c.c) -> gw, gh, gr
+__device__ __forceinline__ void cov_grad(float w, float h, const Rot& q, const Cov& c, const float* gc, float& gw, float& gh, float& gr) {
+    const float c2 = q.cs * q.cs, s2 = q.sn * q.sn, cs = q.cs * q.sn;
+    const float gA = gc[0] * c2 + gc[1] * s2 + gc[2] * cs;
+    const float gB = gc[0] * s2 + gc[1] * c2 - gc[2] * cs;
+    gw = gA * w / 6.0f;
+    gh = gB * h / 6.0f;
+    gr = 2.0f * c.c * (gc[1] - gc[0]) + gc[2] * (w * w / 12.0f - h * h / 12.0f) * (c2 - s2);
+}
+
+// ---- targets: ragged (image, class, xywhr; xywh normalised) rows -> dense [B, G, OBB_ROW]; loss.py:652-657 with the tiny-box filter -----------
+__global__ void obb_targets_kernel(const float* __restrict__ batch_idx, const float* __restrict__ cls, const float* __restrict__ xywhr, int n, int B,
+                                   int G, float img_w, float img_h, float* __restrict__ out) {
+    const int t = blockIdx.x * blockDim.x + threadIdx.x;
+    if (t >= B * G) return;
+    const int b = t / G, slot = t - b * G;
+    int seen = 0, row = -1;
+    for (int i = 0; i < n; ++i) {
+        // the reference multiplies the WIDTH by the image height and the height by the image width (loss.py:655)
+        const bool keep = xywhr[i * 5 + 2] * img_h >= 2.0f && xywhr[i * 5 + 3] * img_w >= 2.0f;
+        if (keep && (int)batch_idx[i] == b) {
+            if (seen == slot) {
+                row = i;
+                break;
+            }
+            ++seen;
+        }
+    }
+    float o[OBB_ROW] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (row >= 0) {
+        o[0] = cls[row];
+        o[1] = xywhr[row * 5 + 0] * img_w;
+        o[2] = xywhr[row * 5 + 1] * img_h;
+        o[3] = xywhr[row * 5 + 2] * img_w;
+        o[4] = xywhr[row * 5 + 3] * img_h;
+        o[5] = xywhr[row * 5 + 4];
+    }
+#pragma unroll
+    for (int k = 0; k < OBB_ROW; ++k) out[(int64_t)t * OBB_ROW + k] = o[k];
+}
+__device__ __forceinline__ bool obb_valid(const float* tg) { return ((((tg[1] + tg[2]) + tg[3]) + tg[4]) + tg[5]) > 0.f; }  // loss.py:659
+
+struct RotGt {  // topk_kernel's view of an oriented label
+    bool v;
+    const uint8_t* in;
+    __device__ __forceinline__ RotGt(const LossGeom& g, const float* targets, const uint8_t* inm, int bg)
+        : v(obb_valid(targets + (int64_t)bg * OBB_ROW)), in(inm + (int64_t)bg * g.A) {}
+    __device__ __forceinline__ bool valid() const { return v; }
+    __device__ __forceinline__ bool inside(const LossGeom&, int, int a) const { return in[a] != 0; }
+};
+
+// ---- decode: DFL expectation, dist2rbox -> [B, A, 5] in grid units ----------------------------------------------------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void obb_decode_kernel(LossGeom g, const float* __restrict__ angle, float* __restrict__ pb) {
+    Side s;
+    float x[REG], p[REG];
+    side_of<T>(g, s, x, p);
+    if (s.live && s.side == 0) {
+        const float r = angle[s.ia];
+        float o[4];
+        rbox_of(s.an, s.d, rot_of(r), o);
+#pragma unroll
+        for (int k = 0; k < 4; ++k) pb[s.ia * 5 + k] = o[k];
+        pb[s.ia * 5 + 4] = r;
+    }
+}
+
+// ---- eval output: rows 0..3 = (x, y, w, h) * stride, 4..4+nc = class sigmoid, 4+nc = angle (head.py:222-238) ---------------------------------
+template <typename T>
+__global__ __launch_bounds__(256) void infer_decode_obb_kernel(LossGeom g, const float* __restrict__ angle, float* __restrict__ y) {
+    Side s;
+    float x[REG], p[REG];
+    side_of<T>(g, s, x, p);
+    if (!s.live) return;
+    float* yo = y + (int64_t)s.b * (4 + g.nc + 1) * g.A + s.a;
+    const float r = angle[s.ia];
+    float o[4];
+    rbox_of(s.an, s.d, rot_of(r), o);
+    const float mine = s.side == 0 ? o[0] : s.side == 1 ? o[1] : s.side == 2 ? o[2] : o[3];
+    yo[(int64_t)s.side * g.A] = mine * s.an.s;
+    const T* cp = map_row<const T>(g.cls, g.ldc, s.an);
+    for (int c = s.side; c < g.nc; c += 4) yo[(int64_t)(4 + c) * g.A] = 1.0f / (1.0f + expf(-to_f32(cp[c])));
+    if (s.side == 0) yo[(int64_t)(4 + g.nc) * g.A] = r;
+}
+
+// ---- metric: inside test, probiou overlap and alignment metric for every (image, gt, anchor) ------------------------------------------------
+// A label's facts are worked out once per workgroup, 64 labels at a time, into LDS (its sine and cosine would otherwise be taken per anchor)
+struct GtAux {
+    float valid, x, y, ca, cb, cc;    // label?, centre, covariance
+    float px, py, abx, aby, adx, ady;  // corner a, edge vectors ab and ad (tal.py:349-353)
+    float nab, nad;
+    int lab;
+};
+__device__ __forceinline__ GtAux gt_aux(const float* tg, int nc) {
+    GtAux r;
+    r.valid = obb_valid(tg) ? 1.f : 0.f;
+    r.lab = clamped_label(tg, nc);
+    r.x = tg[1];
+    r.y = tg[2];
+    const float w = tg[3], h = tg[4];
+    const Rot q = rot_of(tg[5]);
+    const Cov c = cov_of(w, h, q);
+    r.ca = c.a;
+    r.cb = c.b;
+    r.cc = c.c;
+    // xywhr2xyxyxyxy (utils/ops.py:573-601): pt1 = ctr + v1 + v2 (a), pt2 = ctr + v1 - v2 (b), pt4 = ctr - v1 + v2 (d)
+    const float v1x = w / 2 * q.cs, v1y = w / 2 * q.sn, v2x = -h / 2 * q.sn, v2y = h / 2 * q.cs;
+    const float ax = r.x + v1x + v2x, ay = r.y + v1y + v2y;
+    const float bx = r.x + v1x - v2x, by = r.y + v1y - v2y;
+    const float ex = r.x - v1x + v2x, ey = r.y - v1y + v2y;
+    r.px = ax;
+    r.py = ay;
+    r.abx = bx - ax;
+    r.aby = by - ay;
+    r.adx = ex - ax;
+    r.ady = ey - ay;
+    r.nab = r.abx * r.abx + r.aby * r.aby;
+    r.nad = r.adx * r.adx + r.ady * r.ady;
+    return r;
+}
+template <typename T>
+__global__ __launch_bounds__(256) void obb_metric_kernel(LossGeom g, const float* __restrict__ targets, const float* __restrict__ pb,
+                                                         float* __restrict__ ov, float* __restrict__ al, uint8_t* __restrict__ mpos,
+                                                         uint8_t* __restrict__ inm, float alpha, float beta) {
+    __shared__ GtAux gs[64];
+    const int b = blockIdx.y;
+    const int a0 = blockIdx.x * 256 + threadIdx.x;
+    const bool live = a0 < g.A;
+    const int a = live ? a0 : 0;
+    const Anchor an = anchor_of(g, b, a);
+    const float* pr = pb + ((int64_t)b * g.A + a) * 5;
+    const float px = pr[0] * an.s, py = pr[1] * an.s, pw = pr[2] * an.s, ph = pr[3] * an.s;
+    const Cov pc = cov_of(pw, ph, rot_of(pr[4]));
+    const float cx = an.ax * an.s, cy = an.ay * an.s;
+    const T* cp = map_row<const T>(g.cls, g.ldc, an);
+    for (int k0 = 0; k0 < g.G; k0 += 64) {
+        __syncthreads();  // (the previous chunk's readers)
+        if (threadIdx.x < 64 && k0 + (int)threadIdx.x < g.G) gs[threadIdx.x] = gt_aux(targets + ((int64_t)b * g.G + k0 + threadIdx.x) * OBB_ROW, g.nc);
+        __syncthreads();
+        const int kn = min(64, g.G - k0);
+        for (int kk = 0; kk < kn; ++kk) {
+            const GtAux& t = gs[kk];
+            const float apx = cx - t.px, apy = cy - t.py;
+            const float dab = apx * t.abx + apy * t.aby, dad = apx * t.adx + apy * t.ady;
+            const bool in = t.valid != 0.f && dab >= 0.f && dab <= t.nab && dad >= 0.f && dad <= t.nad;  // an edge is inside (tal.py:361)
+            float o = 0.f, m = 0.f;
+            if (in) {
+                const float score = sigmoidf_(to_f32(cp[t.lab]));
+                o = fmaxf(probiou_cov(t.x, t.y, Cov{t.ca, t.cb, t.cc}, px, py, pc), 0.f);
+                m = powf(score, alpha) * powf(o, beta);
+            }
+            if (live) {
+                const int64_t idx = ((int64_t)b * g.G + k0 + kk) * g.A + a;
+                ov[idx] = o;
+                al[idx] = m;
+                mpos[idx] = 0;
+                inm[idx] = in ? 1 : 0;
+            }
+        }
+    }
+}
+
+// ---- loss sums (GRAD = false) or gradients with respect to the maps and the angle (GRAD = true); four lanes per anchor as loss_kernel -----------
+// box: (1 - probiou(pred, target)) * weight; DFL against the target's UNROTATED extents (loss.py:126); BCE as loss_kernel states it
+template <typename T, bool GRAD>
+__global__ __launch_bounds__(256) void obb_loss_kernel(LossGeom g, const float* __restrict__ angle, const float* __restrict__ tgt,
+                                                       const float* __restrict__ wgt, const int* __restrict__ lab, const float* __restrict__ scal,
+                                                       const float* __restrict__ gout, const float* __restrict__ gscale, float* __restrict__ part,
+                                                       float* __restrict__ dangle) {
+    __shared__ float sh[3][4];
+    Side s;
+    float x[REG], p[REG];
+    side_of<T>(g, s, x, p);
+    const Anchor& an = s.an;
+    const int side = s.side;
+    const float w = wgt[s.ia];
+    const int lb = lab[s.ia];
+    float tb[5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k) tb[k] = tgt[s.ia * 5 + k];
+    float s_box = 0.f, s_cls = 0.f, s_dfl = 0.f;
+    // DFL target of this side: bbox2dist(anchor, xywh2xyxy(target xywh)) (loss.py:126, tal.py:391-394)
+    const float raw_t = side == 0   ? an.ax - (tb[0] - tb[2] / 2)
+                        : side == 1 ? an.ay - (tb[1] - tb[3] / 2)
+                        : side == 2 ? (tb[0] + tb[2] / 2) - an.ax
+                                    : (tb[1] + tb[3] / 2) - an.ay;
+    const float tt = fminf(fmaxf(raw_t, 0.f), (float)(REG - 1) - 0.01f);
+    const int tl = (int)tt;
+    const float wl = (float)(tl + 1) - tt, wr = 1.0f - wl;
+    float g_box = 0.f, g_cls = 0.f, g_dfl = 0.f;
+    if (GRAD) {
+        const float inv_t = 1.0f / fmaxf(scal[0], 1.0f);
+        g_box = gout[0] * (gscale ? gscale[0] : 1.0f) * inv_t;
+        g_cls = gout[1] * (gscale ? gscale[1] : 1.0f) * inv_t;
+        g_dfl = gout[2] * (gscale ? gscale[2] : 1.0f) * inv_t;
+    }
+    if (lb >= 0) {  // foreground anchor
+        const float r = angle[s.ia];
+        const Rot q = rot_of(r);
+        float pbx[4];
+        rbox_of(an, s.d, q, pbx);
+        const Cov pc = cov_of(pbx[2], pbx[3], q);
+        const Cov tc = cov_of(tb[2], tb[3], rot_of(tb[4]));
+        if (!GRAD) {
+            if (side == 0) s_box = (1.0f - probiou_cov(pbx[0], pbx[1], pc, tb[0], tb[1], tc)) * w;
+            float xl = 0.f, xr = 0.f;
+#pragma unroll
+            for (int j = 0; j < REG; ++j) {
+                xl = j == tl ? x[j] : xl;
+                xr = j == tl + 1 ? x[j] : xr;
+            }
+            s_dfl = ((s.lse - xl) * wl + (s.lse - xr) * wr) * 0.25f * w;
+        } else {
+            float gp[5], gw, gh, gr;
+            (void)probiou_cov<true>(pbx[0], pbx[1], pc, tb[0], tb[1], tc, gp);
+            cov_grad(pbx[2], pbx[3], q, pc, gp + 2, gw, gh, gr);
+            // x = xf cs - yf sn + ax, y = xf sn + yf cs + ay with xf = (d2 - d0) / 2, yf = (d3 - d1) / 2; w = d0 + d2, h = d1 + d3
+            const float gx = gp[0], gy = gp[1];
+            const float gside = side == 0   ? -0.5f * (gx * q.cs + gy * q.sn) + gw
+                                : side == 1 ? 0.5f * (gx * q.sn - gy * q.cs) + gh
+                                : side == 2 ? 0.5f * (gx * q.cs + gy * q.sn) + gw
+                                            : 0.5f * (gy * q.cs - gx * q.sn) + gh;
+            const float gd = -gside * w * g_box;  // loss = (1 - probiou) * w
+            const float kd = 0.25f * w * g_dfl;
+            float o[REG];
+#pragma unroll
+            for (int j = 0; j < REG; ++j) {
+                const float hot = (j == tl ? wl : 0.f) + (j == tl + 1 ? wr : 0.f);
+                o[j] = gd * p[j] * ((float)j - s.e) + kd * (p[j] - hot);
+            }
+            if (s.live) store16<T>(map_row<T>(g.dbox, g.lddb, an) + side * REG, o);
+            // the angle turns the centre about the anchor (d x / d r = -(y - ay), d y / d r = x - ax) and the covariance
+            if (s.live && side == 0) dangle[s.ia] = -(gr - gx * (pbx[1] - an.ay) + gy * (pbx[0] - an.ax)) * w * g_box;
+        }
+    } else if (GRAD && s.live) {
+        float o[REG];
+#pragma unroll
+        for (int j = 0; j < REG; ++j) o[j] = 0.f;
+        store16<T>(map_row<T>(g.dbox, g.lddb, an) + side * REG, o);
+        if (side == 0) dangle[s.ia] = 0.f;
+    }
+    if (s.live) {  // classification, as loss_kernel
+        const T* cp = map_row<const T>(g.cls, g.ldc, an);
+        for (int c = side; c < g.nc; c += 4) {
+            const float xv = to_f32(cp[c]);
+            const float tv = c == lb ? w : 0.f;
+            if (!GRAD) s_cls += fmaxf(xv, 0.f) - xv * tv + log1pf(__expf(-fabsf(xv)));
+            else map_row<T>(g.dcls, g.lddc, an)[c] = from_f32<T>((sigmoidf_(xv) - tv) * g_cls);
+        }
+        if (GRAD) {
+            for (int c = g.nc + side; c < g.dcw; c += 4) map_row<T>(g.dcls, g.lddc, an)[c] = from_f32<T>(0.f);
+        }
+    }
+    if (!GRAD) {
+        if (!s.live) s_box = s_cls = s_dfl = 0.f;
+        float sum[3] = {s_box, s_cls, s_dfl};
+        block_combine<SumOp>(sum, sh);
+        if (threadIdx.x == 0) {
+#pragma unroll
+            for (int k = 0; k < 3; ++k) part[(int64_t)blockIdx.x * 3 + k] = sum[k];
+        }
+    }
+}
+
+// geometry of the angle kernels: the logit maps alone give levels, sizes and anchor order
+int fill_angle_geom(LossGeom& g, AngleMaps& am, int32_t nl, const ymi_tensor* maps, const char* what) {
+    YMI_CHECK_ARG(nl >= 1 && nl <= LOSS_MAXL && maps, "%s: 1..%d levels", what, LOSS_MAXL);
+    g = LossGeom{};
+    am = AngleMaps{};
+    g.nl = nl;
+    int64_t off = 0;
+    for (int l = 0; l < nl; ++l) {
+        const ymi_tensor& m = maps[l];
+        YMI_CHECK_ARG(ymi_tensor_ok(&m) && m.c == 1 && m.n == maps[0].n && m.dtype == maps[0].dtype, "%s: level %d is a one-channel map of the batch", what, l);
+        am.lg[l] = m.data;
+        am.ld[l] = m.ld;
+        g.H[l] = (int)m.h;
+        g.W[l] = (int)m.w;
+        g.off[l] = (int)off;
+        g.stride[l] = 1.0f;
+        off += m.h * m.w;
+    }
+    for (int l = nl; l <= LOSS_MAXL; ++l) g.off[l] = (int)off;
+    g.B = (int)maps[0].n;
+    g.A = (int)off;
+    YMI_CHECK_ARG((int64_t)g.B * off < (1ll << 31), "%s: B*A < 2^31", what);
+    return YMI_OK;
+}
+}  // namespace
+
+extern "C" int ymi_obb_angle_fwd(int32_t nl, const ymi_tensor* logit_maps, float* angle, void* stream) {
+    LossGeom g;
+    AngleMaps am;
+    int rc = fill_angle_geom(g, am, nl, logit_maps, "obb_angle_fwd");
+    if (rc) return rc;
+    YMI_CHECK_ARG(angle, "obb_angle_fwd: null output");
+    dispatch_dtype(logit_maps[0].dtype, [&](auto t) {
+        launch(obb_angle_kernel<typename decltype(t)::type, false>, anchor_grid(g.B, g.A), (hipStream_t)stream, g, am, angle, (const float*)nullptr);
+    });
+    YMI_CHECK_LAUNCH("obb_angle_fwd");
+    return YMI_OK;
+}
+
+extern "C" int ymi_obb_angle_bwd(int32_t nl, const ymi_tensor* logit_maps, const float* dangle, const ymi_tensor* dlogit_maps, void* stream) {
+    LossGeom g;
+    AngleMaps am;
+    int rc = fill_angle_geom(g, am, nl, logit_maps, "obb_angle_bwd");
+    if (rc) return rc;
+    YMI_CHECK_ARG(dangle && dlogit_maps && ymi_tensor_ok(&dlogit_maps[0]), "obb_angle_bwd: null argument");
+    am.dcw = (int)dlogit_maps[0].c;
+    for (int l = 0; l < nl; ++l) {
+        const ymi_tensor &d = dlogit_maps[l], &m = logit_maps[l];
+        YMI_CHECK_ARG(ymi_tensor_ok(&d) && d.n == m.n && d.h == m.h && d.w == m.w && d.c >= 1 && d.c == am.dcw && d.dtype == m.dtype,
+                      "obb_angle_bwd: gradient map %d", l);
+        am.dlg[l] = d.data;
+        am.ldd[l] = d.ld;
+    }
+    dispatch_dtype(logit_maps[0].dtype, [&](auto t) {
+        launch(obb_angle_kernel<typename decltype(t)::type, true>, anchor_grid(g.B, g.A), (hipStream_t)stream, g, am, (float*)nullptr, dangle);
+    });
+    YMI_CHECK_LAUNCH("obb_angle_bwd");
+    return YMI_OK;
+}
+
+extern "C" int ymi_obb_targets(const float* batch_idx, const float* cls, const float* bboxes_xywhr, int64_t n, int64_t batch, int64_t max_boxes,
+                               float img_w, float img_h, float* out, void* stream) {
+    YMI_CHECK_ARG(out && batch > 0 && max_boxes > 0 && n >= 0 && (n == 0 || (batch_idx && cls && bboxes_xywhr)), "obb_targets: args");
+    const int total = (int)(batch * max_boxes);
+    hipLaunchKernelGGL(obb_targets_kernel, dim3((total + 127) / 128), dim3(128), 0, (hipStream_t)stream, batch_idx, cls, bboxes_xywhr, (int)n, (int)batch,
+                       (int)max_boxes, img_w, img_h, out);
+    YMI_CHECK_LAUNCH("obb_targets");
+    return YMI_OK;
+}
+
+extern "C" int ymi_obb_loss_sizes(int64_t batch, int64_t anchors, int64_t max_boxes, size_t* state_bytes, size_t* workspace_bytes) {
+    YMI_CHECK_ARG(batch > 0 && anchors > 0 && max_boxes > 0 && state_bytes && workspace_bytes, "obb_loss_sizes: args");
+    *state_bytes = carve_state(nullptr, batch * anchors, 5).bytes;
+    *workspace_bytes = carve_work(nullptr, batch, anchors, max_boxes, 5).bytes;
+    return YMI_OK;
+}
+
+extern "C" int ymi_obb_loss_fwd(int32_t nl, const ymi_tensor* box_maps, const ymi_tensor* cls_maps, const float* angle, const float* strides,
+                                const float* targets, int64_t max_boxes, int32_t topk, float alpha, float beta, const float* out_scale, float* loss_out,
+                                void* state, size_t state_bytes, void* workspace, size_t workspace_bytes, void* stream) {
+    LossGeom g;
+    int rc = fill_geom(g, nl, box_maps, cls_maps, strides, "obb_loss_fwd");
+    if (rc) return rc;
+    g.G = (int)max_boxes;
+    YMI_CHECK_ARG(max_boxes >= 1 && (int64_t)g.B * g.G * g.A < (1ll << 31), "obb_loss_fwd: max_boxes >= 1 and B*G*A < 2^31");
+    YMI_CHECK_ARG(angle && targets && loss_out && state && workspace && topk >= 1, "obb_loss_fwd: null argument");
+    const StateView st = carve_state(state, (int64_t)g.B * g.A, 5);
+    const WorkView w = carve_work(workspace, g.B, g.A, g.G, 5);
+    if (state_bytes < st.bytes || workspace_bytes < w.bytes) {
+        ymi_set_error("obb_loss_fwd: state %zu < %zu or workspace %zu < %zu bytes", state_bytes, st.bytes, workspace_bytes, w.bytes);
+        return YMI_EWORKSPACE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const dim3 qgrid = quad_grid(g.B, g.A), agrid = anchor_grid(g.B, g.A), ggrid((unsigned)(g.B * g.G));
+    dispatch_dtype(box_maps[0].dtype, [&](auto t) {
+        typedef typename decltype(t)::type T;
+        launch(obb_decode_kernel<T>, qgrid, s, g, angle, w.pb);
+        launch(obb_metric_kernel<T>, agrid, s, g, targets, w.pb, w.ov, w.al, w.mpos, w.inm, alpha, beta);
+        launch(topk_kernel<RotGt>, ggrid, s, g, targets, (const uint8_t*)w.inm, w.al, w.mpos, (int)topk);
+        launch(assign_kernel, agrid, s, g, w.ov, w.mpos, w.gidx);
+        launch(posmax_kernel, ggrid, s, g, w.ov, w.al, w.gidx, w.pa, w.po);
+        launch(finalize_kernel<5>, agrid, s, g, targets, w.al, w.gidx, w.pa, w.po, st.tgt, st.wgt, st.lab, w.tss_part);
+        launch(obb_loss_kernel<T, false>, qgrid, s, g, angle, st.tgt, st.wgt, st.lab, st.scal, nullptr, nullptr, w.part, nullptr);
+        launch(loss_final_kernel, dim3(1), s, w.tss_part, (int)(agrid.x * agrid.y), w.part, (int)qgrid.x, st.scal, loss_out, out_scale);
+    });
+    YMI_CHECK_LAUNCH("obb_loss_fwd");
+    return YMI_OK;
+}
+
+extern "C" int ymi_obb_loss_bwd(int32_t nl, const ymi_tensor* box_maps, const ymi_tensor* cls_maps, const float* angle, const float* strides,
+                                const void* state, size_t state_bytes, const float* grad_loss, const float* grad_scale, const ymi_tensor* dbox_maps,
+                                const ymi_tensor* dcls_maps, float* dangle, void* stream) {
+    LossGeom g;
+    int rc = fill_geom(g, nl, box_maps, cls_maps, strides, "obb_loss_bwd");
+    if (rc) return rc;
+    YMI_CHECK_ARG(angle && state && grad_loss && dbox_maps && dcls_maps && dangle, "obb_loss_bwd: null argument");
+    const StateView st = carve_state(const_cast<void*>(state), (int64_t)g.B * g.A, 5);
+    YMI_CHECK_ARG(state_bytes >= st.bytes, "obb_loss_bwd: state too small");
+    rc = fill_grad_geom(g, box_maps, cls_maps, dbox_maps, dcls_maps, "obb_loss_bwd");
+    if (rc) return rc;
+    dispatch_dtype(box_maps[0].dtype, [&](auto t) {
+        launch(obb_loss_kernel<typename decltype(t)::type, true>, quad_grid(g.B, g.A), (hipStream_t)stream, g, angle, st.tgt, st.wgt, st.lab, st.scal,
+               grad_loss, grad_scale, nullptr, dangle);
+    });
+    YMI_CHECK_LAUNCH("obb_loss_bwd");
+    return YMI_OK;
+}
+
+extern "C" int ymi_detect_decode_obb(int32_t nl, const ymi_tensor* box_maps, const ymi_tensor* cls_maps, const float* angle, const float* strides,
+                                     float* y, void* stream) {
+    LossGeom g;
+    int rc = fill_geom(g, nl, box_maps, cls_maps, strides, "detect_decode_obb");
+    if (rc) return rc;
+    YMI_CHECK_ARG(y && angle, "detect_decode_obb: null argument");
+    dispatch_dtype(box_maps[0].dtype,
+                   [&](auto t) { launch(infer_decode_obb_kernel<typename decltype(t)::type>, quad_grid(g.B, g.A), (hipStream_t)stream, g, angle, y); });
+    YMI_CHECK_LAUNCH("detect_decode_obb");
     return YMI_OK;
 }

@@ -21,6 +21,9 @@ class DetectionPredictor:
     def __init__(self, model, imgsz=640, conf=0.25, iou=0.7, classes=None, agnostic_nms=False, max_det=300, batch=32, dtype=torch.bfloat16,
                  augment=False, rect=False):
         layers = getattr(model, "model", None)
+        if layers is not None and getattr(layers[-1], "ne", 0):
+            raise NotImplementedError("a predictor on an OBBModel needs rotated NMS (batch_probiou), boxes with their angle in image coordinates and an OBB "
+                                      "results class: not built yet; the head's eval output [B, 4 + nc + 1, A] is model(img)[0]")
         if bool(layers is not None and getattr(layers[-1], "nm", 0)) != self._segment:
             if self._segment:
                 raise ValueError("SegmentationPredictor takes a model whose head is a Segment; a detector goes to DetectionPredictor")

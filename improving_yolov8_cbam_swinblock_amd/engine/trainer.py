@@ -12,7 +12,7 @@ import torch
 import torch.nn as nn
 
 from .. import _lib, ops
-from ..nn.modules.head import Segment
+from ..nn.modules.head import OBB, Segment
 from .ddp import GradientBuckets
 from .optim import FlatFold, FusedAdamax, FusedAdamW, FusedNAdam, FusedRAdam, FusedRMSprop, FusedSGD, ModelEMA
 
@@ -84,6 +84,16 @@ def synthetic_seg_batch(batch, imgsz, device, seed, boxes_per_image=4):
     return out
 
 
+def synthetic_obb_batch(batch, imgsz, device, seed, boxes_per_image=4):
+    """synthetic_batch with oriented labels: "bboxes" [n, 5] = (xywh normalised, angle in radians drawn from [-pi/4, 3pi/4), the range of the
+    OBB head's output) - the batch an OBBModel trains on."""
+    out = synthetic_batch(batch, imgsz, device, seed, boxes_per_image)
+    g = torch.Generator().manual_seed(seed + 1)
+    r = (torch.rand(batch * boxes_per_image, 1, generator=g) - 0.25) * math.pi
+    out["bboxes"] = torch.cat((out["bboxes"], r.to(device)), 1)
+    return out
+
+
 def preprocess_batch(batch, imgsz, stride, multi_scale=False, rng=random, device=None):
     """DetectionTrainer.preprocess_batch of reference models/yolo/detect/train.py:90-115 -> a NEW dict whose "img" is float32 NCHW on the
     device: a uint8 image batch (what a dataloader produces; host or device) becomes img.float() / 255, and with multi_scale the batch is
@@ -123,6 +133,11 @@ def augment_batch(samples, imgsz, hyp=None, mosaic=True, transforms=None, device
     then warped alone with border 0, as RandomPerspective's pre_transform does (:1220-1221).  The draws consume `random` / `np.random`."""
     from ..data.augment import V8_DEFAULTS, v8_transforms
 
+    for smp in samples:
+        lab, box = smp.get("labels"), smp.get("bboxes")
+        if (lab is not None and len(lab) and lab.shape[-1] == 6) or (box is not None and len(box) and box.shape[-1] == 5):
+            raise NotImplementedError("augment_batch warps axis-aligned (cls, xywh) labels: oriented xywhr rows would need their corners warped and "
+                                      "refitted (the reference's segment-based path), which is not built")
     if transforms is None:
         h = dict(V8_DEFAULTS)
         h.update(hyp if isinstance(hyp, dict) else {k: getattr(hyp, k) for k in V8_DEFAULTS if hasattr(hyp, k)} if hyp is not None else {})
@@ -208,6 +223,11 @@ class TrainStep:
             # (built and tested: eager, graph=True and graph="split" on one rank)
             raise NotImplementedError('TrainStep on a SegmentationModel is built for one rank, eager, graph=True or graph="split": '
                                       f"world_size={world_size}, graph={graph!r} is not")
+        self.obb = isinstance(model.model[-1], OBB)
+        if self.obb and (world_size != 1 or graph == "tail" or int(image_shapes) != 1):
+            # (built and tested: eager, graph=True and graph="split" on one rank, one image shape)
+            raise NotImplementedError('TrainStep on an OBBModel is built for one rank and one image shape, eager, graph=True or graph="split": '
+                                      f"world_size={world_size}, graph={graph!r}, image_shapes={image_shapes} is not")
         self.full_graph = self.use_graph and world_size == 1 and graph not in ("split", "tail")
         self.overlap_graphs = self.use_graph and not self.full_graph and graph != "tail"
         self.params = [p for p in model.parameters() if p.requires_grad]
@@ -382,6 +402,8 @@ class TrainStep:
     def _accumulating_call(self, batch, update):
         if self.segment:
             raise NotImplementedError("gradient accumulation (update=False) is not built for a SegmentationModel")
+        if self.obb:
+            raise NotImplementedError("gradient accumulation (update=False) is not built for an OBBModel")
         if not update:
             if self.use_graph and not (self.full_graph or self.overlap_graphs):
                 raise ValueError('update=False is not supported with graph="tail": gradient accumulation needs eager mode, graph=True or graph="split"')

@@ -40,6 +40,9 @@ class DetectionValidator:
                  loss=False):
         if match not in ("device", "host"):
             raise ValueError(f"match is 'device' or 'host', got {match!r}")
+        if getattr(model.model[-1], "ne", 0):
+            raise NotImplementedError("a validator on an OBBModel needs rotated NMS and batch_probiou matching of xywhr labels: not built yet; "
+                                      "model.loss(batch) gives the validation loss")
         if bool(getattr(model.model[-1], "nm", 0)) != self._segment:
             if self._segment:
                 raise ValueError("SegmentationValidator takes a model whose head is a Segment; a detector goes to DetectionValidator")

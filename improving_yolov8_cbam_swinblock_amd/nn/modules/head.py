@@ -209,3 +209,51 @@ class Segment(Detect):
         p, mcs = self._mask_maps(x)
         box, cls = self._maps(x)
         return SegPreds(box, cls, mcs, p)
+
+
+class OBBPreds:
+    """train-mode OBB output for the loss, nothing concatenated: box[i] [B, 64, H, W], cls[i] [B, nc, H, W] (the NHWC maps the convolutions
+    wrote) and angle [B, 1, A] float32 radians."""
+
+    def __init__(self, box, cls, angle):
+        self.box, self.cls, self.angle = box, cls, angle
+
+
+class OBB(Detect):
+    """Detect plus one angle per anchor (cv4, ne = 1): reference head.py:211-238.
+    train -> (feats, angle [B, 1, A]); eval -> (cat([y, angle], 1) [B, 4 + nc + 1, A], (feats, angle)), y's box rows from dist2rbox."""
+
+    def __init__(self, nc=80, ne=1, ch=()):
+        super().__init__(nc, ch)
+        if ne != 1:
+            raise NotImplementedError(f"the oriented-box kernels are built for ne = 1 extra value per anchor (the angle), got ne = {ne}")
+        self.ne = ne
+        c4 = max(ch[0] // 4, self.ne)
+        self.cv4 = nn.ModuleList(nn.Sequential(Conv(x, c4, 3), Conv(c4, c4, 3), _Out1x1(c4, self.ne, 1)) for x in ch)
+
+    def _angle(self, x):
+        """angle [B, 1, A] = (sigmoid(cv4 logits) - 0.25) * pi in [-pi/4, 3pi/4]; cv4 runs level by level, its one-channel outputs (rows of
+        padded buffers) go through one launch (ops.obb_angle: no view + cat + sigmoid + scale)."""
+        return ops.obb_angle([self._branch(self.cv4[i], ops.to_internal(x[i])) for i in range(self.nl)])
+
+    def forward(self, x):
+        x = list(x)
+        angle = self._angle(x)
+        box, cls = self._maps(x)
+        for i in range(self.nl):
+            x[i] = ops.concat([box[i], cls[i]])
+        if self.training:
+            return x, angle
+        if self.reg_max != 16:
+            raise NotImplementedError("the decode kernel is built for reg_max = 16")
+        self.angle = angle
+        y = ops.detect_decode_obb(box, cls, angle, self._strides())  # rotated box decode, class sigmoid and the angle row in one launch
+        self.shape = x[0].shape
+        return y if self.export else (y, (x, angle))
+
+    def forward_split(self, x):
+        """train-mode maps without any concat, for v8OBBLoss: -> OBBPreds."""
+        x = list(x)
+        angle = self._angle(x)
+        box, cls = self._maps(x)
+        return OBBPreds(box, cls, angle)

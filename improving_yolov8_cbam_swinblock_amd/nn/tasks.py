@@ -16,10 +16,10 @@ import torch.nn as nn
 import yaml
 
 from .. import ops
-from ..utils.loss import DEFAULT_HYP, SplitPreds, v8DetectionLoss, v8SegmentationLoss
+from ..utils.loss import DEFAULT_HYP, SplitPreds, v8DetectionLoss, v8OBBLoss, v8SegmentationLoss
 from ..utils.ops import make_divisible
 from ..utils.torch_utils import fuse_conv_and_bn, initialize_weights, intersect_dicts
-from .modules import C2f, C2PSA, C3, C3k2, CBAM, PSA, SPPF, Bottleneck, C3Ghost, Concat, Conv, Detect, DWConv, GhostBottleneck, GhostConv, Segment, SwinBlock, Upsample
+from .modules import C2f, C2PSA, C3, C3k2, CBAM, OBB, PSA, SPPF, Bottleneck, C3Ghost, Concat, Conv, Detect, DWConv, GhostBottleneck, GhostConv, Segment, SwinBlock, Upsample
 
 CFG_DIR = Path(__file__).resolve().parents[1] / "cfg" / "models" / "v8"
 CFG_DIRS = (CFG_DIR, CFG_DIR.parent / "11")  # bare YAML names are looked up here, in this order
@@ -43,6 +43,7 @@ MODULES = {
     "Concat": Concat,
     "Detect": Detect,
     "Segment": Segment,
+    "OBB": OBB,
     "nn.Upsample": Upsample,  # the YAML's torch.nn.Upsample row runs as the HIP nearest-2x kernel
 }
 BASE_MODULES = frozenset({Conv, C2f, SPPF, Bottleneck, DWConv, GhostConv, GhostBottleneck, C3, C3Ghost, C3k2, C2PSA, PSA})  # width-scaled (c1, c2, ...) constructors: tasks.py:1376-1413
@@ -55,11 +56,13 @@ def srcs_of(m):
 
 
 def _head_reads(m, first):
-    """convolutions of a Detect / Segment head that read one of its inputs: the box and class branches (ONE convolution when the sibling
-    first convolutions run as a pair), Segment's coefficient branch cv4 and, on the first input, its Proto."""
+    """convolutions of a Detect / Segment / OBB head that read one of its inputs: the box and class branches (ONE convolution when the sibling
+    first convolutions run as a pair), the cv4 branch of Segment (coefficients) and OBB (angle) and, on Segment's first input, its Proto."""
     n = 1 if m.pair_ok else 2
     if isinstance(m, Segment):
         n += 2 if first else 1
+    elif isinstance(m, OBB):
+        n += 1
     return n
 
 
@@ -132,7 +135,7 @@ def parse_model(d, ch, verbose=False):
                     args[3] = True
         elif m is Concat:
             c2 = sum(ch[x] for x in f)
-        elif m in (Detect, Segment):
+        elif m in (Detect, Segment, OBB):
             args.append([ch[x] for x in f])
             if m is Segment:  # the prototype width is width-scaled (tasks.py:1482-1488)
                 args[2] = make_divisible(min(args[2], max_channels) * width, 8)
@@ -140,7 +143,7 @@ def parse_model(d, ch, verbose=False):
         else:  # CBAM, SwinBlock, Upsample: arguments untouched, channels pass through (tasks.py:1503-1504)
             c2 = ch[f]
         m_ = nn.Sequential(*(m(*args) for _ in range(n))) if n > 1 else m(*args)
-        if m in (Detect, Segment):  # (the instance keeps its branch) the class default goes back to the v8 one for heads built outside parse_model
+        if m in (Detect, Segment, OBB):  # (the instance keeps its branch) the class default goes back to the v8 one for heads built outside parse_model
             m.legacy = True
         t = str(m)[8:-2].replace("__main__.", "")
         m_.np = sum(x.numel() for x in m_.parameters())
@@ -194,7 +197,7 @@ class BaseModel(nn.Module):
                 if leaf_of and m.i >= nb_layers:  # a head layer: boundary tensors are read through their detached leaves
                     x = [leaf_of.get(id(t), t) for t in x] if isinstance(x, list) else leaf_of.get(id(x), x)
                 if split_head and isinstance(m, Detect):
-                    return m.forward_split(x) if isinstance(m, Segment) else SplitPreds(*m.forward_split(x))
+                    return m.forward_split(x) if isinstance(m, (Segment, OBB)) else SplitPreds(*m.forward_split(x))
                 if plan is None:
                     x = m(x)
                 elif isinstance(m, Concat):
@@ -486,3 +489,17 @@ class SegmentationModel(DetectionModel):
 
     def _predict_augment(self, x):
         raise NotImplementedError("test-time augmentation merges box rows only: it is not built for the mask coefficients of a SegmentationModel")
+
+
+class OBBModel(DetectionModel):
+    """YOLO oriented-box model (reference tasks.py:446-463): a DetectionModel whose head is an OBB and whose criterion is v8OBBLoss."""
+
+    def __init__(self, cfg="yolov8n-obb.yaml", ch=3, nc=None, verbose=False):
+        super().__init__(cfg=cfg, ch=ch, nc=nc, verbose=verbose)
+
+    def init_criterion(self):
+        return v8OBBLoss(self)
+
+    def _predict_augment(self, x):
+        raise NotImplementedError("test-time augmentation merges axis-aligned box rows only: it is not built for the rotated boxes and the angle row of an "
+                                  "OBBModel")

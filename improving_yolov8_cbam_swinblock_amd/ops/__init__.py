@@ -39,6 +39,7 @@ from .seg import (  # noqa: F401
     _ConvTranspose2x2, _DetectLossAssign, _MaskLoss, conv_transpose2x2, conv_transpose2x2_ok, depth_to_space2, detect_decode_seg, detect_loss_assign, mask_loss,
     mask_overlap, process_mask, space_to_depth2,
 )
+from .obb import _ObbAngle, _ObbLoss, detect_decode_obb, obb_angle, obb_loss, obb_targets  # noqa: F401
 from .resize import letterbox, letterbox_geometry, scale_boxes, scale_boxes_params, scale_image, scale_rows, tta_clip_ranges, tta_merge  # noqa: F401
 from .augment import affine_matrix, augment_batch, hsv_luts, invert_affine, mosaic_placement  # noqa: F401
 from .validate import VAL_MATCH_LABEL_CHUNK, val_match, val_match_masks  # noqa: F401

@@ -129,3 +129,45 @@ class v8SegmentationLoss(v8DetectionLoss):
         s0 = self.stride_list[0]
         loss3, items3, gidx = ops.detect_loss_assign(box, cls, self.stride_list, targets, scale, self.topk, self.alpha, self.beta)
         return ops.mask_loss(loss3, items3, gidx, targets, masks, scale, self.topk, w * s0, h * s0, proto, mc)
+
+
+class v8OBBLoss(v8DetectionLoss):
+    """criterion(preds, batch) -> (loss * batch_size [3], loss.detach() [3]) as box, cls, dfl (reference loss.py:607-720).
+
+    preds: the OBB head's OBBPreds (training fast path), its train-mode output (feats, angle [B, 1, A]) or its eval output (y, (feats, angle)).
+    batch["bboxes"]: [n, 5] xywhr rows, xywh normalised, the angle in radians.  The stages run in csrc/loss.hip (ops.obb_loss): the rotated
+    decode, inside test, probiou metric and box term, with the detection loss's top-k, claim and final-sum kernels between them; every shape is
+    static given max_boxes and nothing is read back."""
+
+    def __call__(self, preds, batch):
+        if hasattr(preds, "angle"):  # OBBPreds
+            box, cls, angle = list(preds.box), list(preds.cls), preds.angle
+        else:  # (feats, angle), or the eval tuple (y, (feats, angle)): split the channels again (loss.py:636-640)
+            feats, angle = preds if isinstance(preds[0], (list, tuple)) else preds[1]
+            box = [f[:, : self.reg_max * 4] for f in feats]
+            cls = [f[:, self.reg_max * 4 :] for f in feats]
+        if not box[0].is_cuda:
+            raise RuntimeError("v8OBBLoss runs in libyolo_mi355 kernels: predictions must be on the MI355X (cuda) device; there is no CPU path")
+        box = [_nhwc_map(t, True) for t in box]
+        cls = [_nhwc_map(t if t.dtype == box[0].dtype else t.to(box[0].dtype), False) for t in cls]
+        B = box[0].shape[0]
+        h, w = box[0].shape[2:]
+        s0 = self.stride_list[0]
+        A = sum(int(t.shape[2] * t.shape[3]) for t in box)
+        if tuple(angle.shape) != (B, 1, A):
+            raise ValueError(f"v8OBBLoss: the angle is [B, 1, A] = {(B, 1, A)}, got {tuple(angle.shape)}")
+        if angle.dtype != torch.float32 or not angle.is_contiguous():
+            angle = angle.float().contiguous()
+        bboxes = batch["bboxes"]
+        if bboxes.numel() and (bboxes.dim() != 2 or bboxes.shape[1] != 5):
+            raise TypeError(f"v8OBBLoss: batch['bboxes'] holds xywhr rows [n, 5], got {tuple(bboxes.shape)}: is this an oriented-box dataset?")
+        g = batch.get("max_boxes")
+        if g is None:
+            g = self.max_boxes(batch["batch_idx"], B)
+        g = max(int(g), 1)
+        targets = ops.obb_targets(batch["batch_idx"], batch["cls"], bboxes, B, g, w * s0, h * s0, box[0].device)
+        scale = self._scales.get(B)
+        if scale is None:
+            gh = [float(self.hyp.box), float(self.hyp.cls), float(self.hyp.dfl)]
+            scale = self._scales[B] = torch.tensor([v * B for v in gh] + gh, dtype=torch.float32, device=box[0].device)
+        return ops.obb_loss(box, cls, angle, self.stride_list, targets, scale, self.topk, self.alpha, self.beta)

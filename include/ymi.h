@@ -457,6 +457,46 @@ int ymi_detect_loss_fwd_assign(int32_t nl, const ymi_tensor* box_maps, const ymi
  * y [B][4+nc+nm][A] float32; mc_maps[l]: [B,H_l,W_l,nm] of Segment.cv4[l]. */
 int ymi_detect_decode_seg(int32_t nl, const ymi_tensor* box_maps, const ymi_tensor* cls_maps, const ymi_tensor* mc_maps, const float* strides,
                           float* y, void* stream);
+/* ---- oriented boxes: the OBB head's angle, v8OBBLoss and the head's eval output ------------------------------------------------------
+ * Reference: nn/modules/head.py:211-238 (OBB), utils/loss.py:607-720 (v8OBBLoss), loss.py:111-132 (RotatedBboxLoss), utils/tal.py:329-361
+ * (RotatedTaskAlignedAssigner), tal.py:397-416 (dist2rbox), utils/metrics.py:178-239 (probiou).  A box is (x, y, w, h, r): centre, extents
+ * along its own axes, angle in radians.  float32 arithmetic on bf16 or float32 maps; fixed summation order, no atomics, nothing read back,
+ * every shape static given max_boxes. */
+
+/* angle[B][A] (float32 radians) = (sigmoid(logit) - 0.25) * pi from the per-level one-channel logit maps [B,H_l,W_l,1] of OBB.cv4[l] (channel
+ * slices of padded buffers: a pixel stride), anchors level by level, row-major, as the reference's view + cat (head.py:225-227). */
+int ymi_obb_angle_fwd(int32_t nl, const ymi_tensor* logit_maps, float* angle, void* stream);
+/* dlogit = dangle * pi * s * (1 - s), s = sigmoid(logit).  dlogit_maps[l] is shaped as logit_maps[l] but may have MORE channels (the same count
+ * on every level): the channels behind the first are written as zeros. */
+int ymi_obb_angle_bwd(int32_t nl, const ymi_tensor* logit_maps, const float* dangle, const ymi_tensor* dlogit_maps, void* stream);
+/* ragged label rows (image index, class, xywhr with xywh normalised) -> dense out[batch, max_boxes, 6] = (class, xywh in pixels, angle), in
+ * stable order within an image, unused slots zero.  The reference's filter comes first (loss.py:655-656): a row is dropped unless
+ * w * img_h >= 2 and h * img_w >= 2 - the width against the image HEIGHT, as the reference multiplies them. */
+int ymi_obb_targets(const float* batch_idx, const float* cls, const float* bboxes_xywhr, int64_t n, int64_t batch, int64_t max_boxes, float img_w,
+                    float img_h, float* out, void* stream);
+int ymi_obb_loss_sizes(int64_t batch, int64_t anchors, int64_t max_boxes, size_t* state_bytes, size_t* workspace_bytes);
+/* v8OBBLoss.__call__ in the stages of ymi_detect_loss_fwd; box_maps, cls_maps, strides, out_scale and loss_out as there; angle: device
+ * [batch, anchors] as ymi_obb_angle_fwd writes it; targets: device [batch, max_boxes, 6] as ymi_obb_targets writes them (a row is a label when
+ * its five box values sum to more than 0).
+ *   decode  : DFL expectation, dist2rbox -> [B, A, 5] in grid units
+ *   metric  : inside test of the rotated rectangle (four dot products, an edge counts as inside), overlap = probiou(gt, pred * stride)
+ *             clamped at 0, metric = score^alpha * overlap^beta
+ *   top-k, claim by highest overlap, per-gt maxima: the detection loss's kernels
+ *   finalize: target (xywh / stride, angle), weight, label per anchor
+ *   sums    : (1 - probiou(pred, target)) * weight; DFL against the target's unrotated extents; BCE; the fixed-order final sums */
+int ymi_obb_loss_fwd(int32_t nl, const ymi_tensor* box_maps, const ymi_tensor* cls_maps, const float* angle, const float* strides, const float* targets,
+                     int64_t max_boxes, int32_t topk, float alpha, float beta, const float* out_scale, float* loss_out, void* state, size_t state_bytes,
+                     void* workspace, size_t workspace_bytes, void* stream);
+/* gradients as ymi_detect_loss_bwd, and dangle [batch, anchors] float32: through the covariance and through the centre's rotation about the
+ * anchor.  probiou's clamps pass no gradient outside their range; background anchors get exact zeros in dbox_maps and dangle. */
+int ymi_obb_loss_bwd(int32_t nl, const ymi_tensor* box_maps, const ymi_tensor* cls_maps, const float* angle, const float* strides, const void* state,
+                     size_t state_bytes, const float* grad_loss, const float* grad_scale, const ymi_tensor* dbox_maps, const ymi_tensor* dcls_maps,
+                     float* dangle, void* stream);
+/* OBB's eval output (head.py:222-238): y [B][4+nc+1][A] float32, rows 0..3 = dist2rbox(DFL(box), angle, anchor) * stride as (x, y, w, h),
+ * rows 4..4+nc-1 the class sigmoids, row 4+nc the angle.  ymi_detect_decode is untouched. */
+int ymi_detect_decode_obb(int32_t nl, const ymi_tensor* box_maps, const ymi_tensor* cls_maps, const float* angle, const float* strides, float* y,
+                          void* stream);
+
 /* The mask term of v8SegmentationLoss (utils/loss.py:349-438; crop_mask utils/ops.py:661-677) with overlap-encoded masks, nm = 32.
  * mc_maps[l]: [B,H_l,W_l,32] coefficient maps, proto: [B,mh,mw,32] (both f32 or bf16, read as they are; sums in f32); masks: device
  * [B,masks_h,masks_w] uint8 (masks_f32 = 0) or float32, read with F.interpolate(mode="nearest")'s index rule when its size is not (mh, mw);
