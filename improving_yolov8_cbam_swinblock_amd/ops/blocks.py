@@ -614,20 +614,101 @@ def window_partition(x, ws):
 
 
 # ---- v8 detection loss on the Detect maps (csrc/loss.hip) -------------------------------------------------------
-def detect_targets(batch_idx, cls, bboxes, batch_size, max_boxes, img_w, img_h, device):
-    """ragged label rows -> dense [B, max_boxes, 5] (class, xyxy pixels); reference loss.py:176-191 preprocess."""
+def _dense_targets(entry, what, width, batch_idx, cls, bboxes, batch_size, max_boxes, img_w, img_h, device):
+    """ragged label rows (image, class, `width` box values) -> dense [B, max_boxes, 1 + width] through the targets entry point `entry`."""
     n = int(batch_idx.numel())
-    out = torch.empty(batch_size, max_boxes, 5, dtype=torch.float32, device=device)
+    out = torch.empty(batch_size, max_boxes, 1 + width, dtype=torch.float32, device=device)
     bi = batch_idx.to(device=device, dtype=torch.float32).reshape(-1).contiguous()
     cl = cls.to(device=device, dtype=torch.float32).reshape(-1).contiguous()
-    bb = bboxes.to(device=device, dtype=torch.float32).reshape(-1, 4).contiguous()
-    check(L().ymi_detect_targets(ptr(bi) if n else None, ptr(cl) if n else None, ptr(bb) if n else None, n, batch_size, max_boxes, float(img_w),
-                                 float(img_h), ptr(out), stream_ptr()), "detect_targets")
+    bb = bboxes.to(device=device, dtype=torch.float32).reshape(-1, width).contiguous()
+    check(entry(ptr(bi) if n else None, ptr(cl) if n else None, ptr(bb) if n else None, n, batch_size, max_boxes, float(img_w), float(img_h), ptr(out),
+                stream_ptr()), what)
     return out
+
+
+def detect_targets(batch_idx, cls, bboxes, batch_size, max_boxes, img_w, img_h, device):
+    """ragged label rows -> dense [B, max_boxes, 5] (class, xyxy pixels); reference loss.py:176-191 preprocess."""
+    return _dense_targets(L().ymi_detect_targets, "detect_targets", 4, batch_idx, cls, bboxes, batch_size, max_boxes, img_w, img_h, device)
 
 
 def _map_array(maps):
     return (_lib.YmiTensor * len(maps))(*[as_ymi(t) for t in maps])
+
+
+def one_width_grads(maps, dense):
+    """gradient buffers for per-level maps whose kernel takes ONE channel width for all levels -> [(the buffer the kernel writes, the gradient
+    handed to autograd)]: the consumers' padded buffers where the levels are padded alike (the kernel zeroes the padding channels), else
+    what `dense(map)` makes per level."""
+    pairs = [padded_grad_like(t, zero=False) for t in maps]
+    if len({p[0].shape[1] for p in pairs}) != 1:
+        pairs = [(v, v) for v in (dense(t) for t in maps)]
+    return pairs
+
+
+# the entry-point families of the loss: (sizes, forward, backward, workspace key, name in error texts)
+_DETECT_FAMILY = ("ymi_detect_loss_sizes", "ymi_detect_loss_fwd_assign", "ymi_detect_loss_bwd", "detloss", "detect_loss")
+_OBB_FAMILY = ("ymi_obb_loss_sizes", "ymi_obb_loss_fwd", "ymi_obb_loss_bwd", "obbloss", "obb_loss")
+
+
+def _loss_forward(ctx, family, targets, strides, topk, alpha, beta, scale6, maps, angle=None, assign=False):
+    """the one forward body of _DetectLoss, _DetectLossAssign (ops.seg) and _ObbLoss (ops.obb) -> (loss, items, gidx).  angle: the oriented
+    family's [B, 1, A] float32 argument.  assign: the assignment's gt index per anchor [B, A] int32 (-1: background) is handed over too;
+    without it gidx is None and the library keeps the index in its workspace."""
+    sizes, fwd, _, ws_key, what = family
+    nl = len(maps) // 2
+    box, cls = maps[:nl], maps[nl:]
+    dev = box[0].device
+    b = box[0].shape[0]
+    anchors = sum(int(t.shape[2] * t.shape[3]) for t in box)
+    g = int(targets.shape[1])
+    if angle is not None and (angle.numel() != b * anchors or angle.dtype != torch.float32 or not angle.is_contiguous() or tuple(targets.shape) != (b, g, 6)):
+        raise ValueError(f"obb_loss: angle {tuple(angle.shape)} {angle.dtype} / targets {tuple(targets.shape)} do not belong to {b} images of {anchors} anchors")
+    sb, wb = ctypes.c_size_t(0), ctypes.c_size_t(0)
+    check(getattr(L(), sizes)(b, anchors, g, _byref(sb), _byref(wb)), what + "_sizes")
+    state = torch.empty(sb.value, dtype=torch.uint8, device=dev)
+    ws = workspace(wb.value, dev, ws_key)
+    out = torch.empty(6, dtype=torch.float32, device=dev)
+    gidx = torch.empty((b, anchors), dtype=torch.int32, device=dev) if assign else None
+    st = (ctypes.c_float * nl)(*[float(s) for s in strides])
+    boxes, classes = _map_array(box), _map_array(cls)
+    shared = (ptr(targets), g, int(topk), float(alpha), float(beta), ptr(scale6), ptr(out), ptr(state), state.numel(), ptr(ws), ws.numel())
+    if angle is None:  # ymi_detect_loss_fwd_assign(nl, box, cls, strides, <shared>, gidx_out, stream)
+        rc = getattr(L(), fwd)(nl, boxes, classes, st, *shared, ptr(gidx), stream_ptr())
+    else:  # ymi_obb_loss_fwd(nl, box, cls, angle, strides, <shared>, stream)
+        rc = getattr(L(), fwd)(nl, boxes, classes, ptr(angle), st, *shared, stream_ptr())
+    check(rc, what + "_fwd")
+    ctx.save_for_backward(state, scale6, *(() if angle is None else (angle,)), *maps)
+    ctx.strides = st
+    loss, items = out[:3], out[3:]
+    ctx.mark_non_differentiable(*((items,) if gidx is None else (items, gidx)))
+    ctx.set_materialize_grads(False)  # (no zero tensor for `items`: it was a fill launch per step)
+    return loss, items, gidx
+
+
+def _loss_backward(ctx, family, gl, has_angle=False):
+    """the one backward body -> (None x 6, [dangle,] *dbox, *dcls) for forward(ctx, targets, strides, topk, alpha, beta, scale6, [angle,] *maps)."""
+    _, _, bwd, _, what = family
+    state, scale6, *rest = ctx.saved_tensors
+    angle, maps = (rest[0], rest[1:]) if has_angle else (None, rest)
+    nl = len(maps) // 2
+    box, cls = maps[:nl], maps[nl:]
+    if gl is None:
+        return (None,) * (6 + len(rest))
+    if gl.dtype != torch.float32 or not gl.is_contiguous():
+        gl = gl.to(torch.float32).contiguous()
+    dbox = [torch.empty_like(t) for t in box]
+    pairs = one_width_grads(cls, lambda t: padded_grad_like(t)[1])  # (else: zeroed buffers, class channels only)
+    boxes, classes = _map_array(box), _map_array(cls)
+    # the kernel differentiates the unscaled sums: the forward's scale rides along as grad_scale; padding channels are zeroed there
+    shared = (ptr(state), state.numel(), ptr(gl), ptr(scale6), _map_array(dbox), _map_array([p[0] for p in pairs]))
+    if angle is None:  # ymi_detect_loss_bwd(nl, box, cls, strides, <shared>, stream)
+        dangle = ()
+        rc = getattr(L(), bwd)(nl, boxes, classes, ctx.strides, *shared, stream_ptr())
+    else:  # ymi_obb_loss_bwd(nl, box, cls, angle, strides, <shared>, dangle, stream)
+        dangle = (torch.empty_like(angle),)
+        rc = getattr(L(), bwd)(nl, boxes, classes, ptr(angle), ctx.strides, *shared, ptr(dangle[0]), stream_ptr())
+    check(rc, what + "_bwd")
+    return (None, None, None, None, None, None, *dangle, *dbox, *[p[1] for p in pairs])
 
 
 class _DetectLoss(torch.autograd.Function):
@@ -636,57 +717,11 @@ class _DetectLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, targets, strides, topk, alpha, beta, scale6, *maps):
-        return _DetectLoss.run(ctx, targets, strides, topk, alpha, beta, scale6, maps)[:2]
-
-    @staticmethod
-    def run(ctx, targets, strides, topk, alpha, beta, scale6, maps, assign=False):
-        """the forward's one body -> (loss, items, gidx): with `assign` the assignment's gt index per anchor [B, A] int32 (-1: background) is
-        handed over too (ops.seg._DetectLossAssign); without it gidx is None and the library keeps the index in its workspace."""
-        nl = len(maps) // 2
-        box, cls = maps[:nl], maps[nl:]
-        dev = box[0].device
-        b = box[0].shape[0]
-        anchors = sum(int(t.shape[2] * t.shape[3]) for t in box)
-        g = int(targets.shape[1])
-        sb, wb = ctypes.c_size_t(0), ctypes.c_size_t(0)
-        check(L().ymi_detect_loss_sizes(b, anchors, g, _byref(sb), _byref(wb)), "detect_loss_sizes")
-        state = torch.empty(sb.value, dtype=torch.uint8, device=dev)
-        ws = workspace(wb.value, dev, "detloss")
-        out = torch.empty(6, dtype=torch.float32, device=dev)
-        gidx = torch.empty((b, anchors), dtype=torch.int32, device=dev) if assign else None
-        st = (ctypes.c_float * nl)(*[float(s) for s in strides])
-        check(
-            L().ymi_detect_loss_fwd_assign(nl, _map_array(box), _map_array(cls), st, ptr(targets), g, int(topk), float(alpha), float(beta), ptr(scale6),
-                                           ptr(out), ptr(state), state.numel(), ptr(ws), ws.numel(), ptr(gidx), stream_ptr()),
-            "detect_loss_fwd",
-        )
-        ctx.save_for_backward(state, scale6, *maps)
-        ctx.strides = st
-        loss, items = out[:3], out[3:]
-        ctx.mark_non_differentiable(*((items,) if gidx is None else (items, gidx)))
-        ctx.set_materialize_grads(False)  # (no zero tensor for `items`: it was a fill launch per step)
-        return loss, items, gidx
+        return _loss_forward(ctx, _DETECT_FAMILY, targets, strides, topk, alpha, beta, scale6, maps)[:2]
 
     @staticmethod
     def backward(ctx, gl, _gitems):
-        state, scale6, *maps = ctx.saved_tensors
-        nl = len(maps) // 2
-        box, cls = maps[:nl], maps[nl:]
-        if gl is None:
-            return (None,) * (6 + len(maps))
-        if gl.dtype != torch.float32 or not gl.is_contiguous():
-            gl = gl.to(torch.float32).contiguous()
-        dbox = [torch.empty_like(t) for t in box]
-        pairs = [padded_grad_like(t, zero=False) for t in cls]
-        if len({p[0].shape[1] for p in pairs}) != 1:  # (levels padded differently: the kernel takes one width) zeroed buffers, class channels only
-            pairs = [(v, v) for v in (padded_grad_like(t)[1] for t in cls)]
-        dcls_k, dcls = [p[0] for p in pairs], [p[1] for p in pairs]
-        check(  # the kernel differentiates the unscaled sums: the forward's scale rides along as grad_scale; padding channels are zeroed there
-            L().ymi_detect_loss_bwd(nl, _map_array(box), _map_array(cls), ctx.strides, ptr(state), state.numel(), ptr(gl), ptr(scale6), _map_array(dbox),
-                                    _map_array(dcls_k), stream_ptr()),
-            "detect_loss_bwd",
-        )
-        return (None, None, None, None, None, None, *dbox, *dcls)
+        return _loss_backward(ctx, _DETECT_FAMILY, gl)
 
 
 def detect_loss(box_maps, cls_maps, strides, targets, scale6, topk=10, alpha=0.5, beta=6.0):
@@ -694,16 +729,22 @@ def detect_loss(box_maps, cls_maps, strides, targets, scale6, topk=10, alpha=0.5
     return _DetectLoss.apply(targets, tuple(strides), topk, alpha, beta, scale6, *box_maps, *cls_maps)
 
 
-def detect_decode(box_maps, cls_maps, strides):
-    """Detect._inference of reference head.py:103-142 on the per-level maps -> [B, 4+nc, A] float32 (no gradient)."""
+def _decode(entry, what, box_maps, cls_maps, strides, extra_rows, *extra_args):
+    """the eval decodes' one body: [B, 4 + nc + extra_rows, A] float32 from the per-level maps in one launch (no gradient); extra_args: what
+    the entry point takes between the class maps and the strides."""
     nl = len(box_maps)
     b = box_maps[0].shape[0]
     nc = cls_maps[0].shape[1]
     anchors = sum(int(t.shape[2] * t.shape[3]) for t in box_maps)
-    y = torch.empty((b, 4 + nc, anchors), dtype=torch.float32, device=box_maps[0].device)
+    y = torch.empty((b, 4 + nc + extra_rows, anchors), dtype=torch.float32, device=box_maps[0].device)
     st = (ctypes.c_float * nl)(*[float(s) for s in strides])
-    check(L().ymi_detect_decode(nl, _map_array([t.detach() for t in box_maps]), _map_array([t.detach() for t in cls_maps]), st, ptr(y), stream_ptr()), "detect_decode")
+    check(entry(nl, _map_array([t.detach() for t in box_maps]), _map_array([t.detach() for t in cls_maps]), *extra_args, st, ptr(y), stream_ptr()), what)
     return y
+
+
+def detect_decode(box_maps, cls_maps, strides):
+    """Detect._inference of reference head.py:103-142 on the per-level maps -> [B, 4+nc, A] float32 (no gradient)."""
+    return _decode(L().ymi_detect_decode, "detect_decode", box_maps, cls_maps, strides, 0)
 
 
 def _detect_nms(y, nc, conf_thres, iou_thres, multi_label, agnostic, classes, max_det, max_nms, max_wh):

@@ -1,13 +1,12 @@
 """Oriented-box ops over the C ABI (csrc/loss.hip): the OBB head's angle, the dense xywhr targets, v8OBBLoss's stages and the head's eval
-output (reference: nn/modules/head.py:211-238, utils/loss.py:607-720, utils/tal.py:329-416, utils/metrics.py:178-239)."""
-import ctypes
-
+output (reference: nn/modules/head.py:211-238, utils/loss.py:607-720, utils/tal.py:329-416, utils/metrics.py:178-239).  The loss, the targets
+and the decode are the detection ops' bodies (ops.blocks: _loss_forward / _loss_backward, _dense_targets, _decode, one_width_grads) with the
+oriented entry points and the angle."""
 import torch
 
-from .._lib import as_ymi, check, is_nhwc, ptr, stream_ptr, workspace
+from .._lib import check, is_nhwc, ptr, stream_ptr
 from .base import L
-from .blocks import _map_array
-from .conv import padded_grad_like
+from .blocks import _OBB_FAMILY, _decode, _dense_targets, _loss_backward, _loss_forward, _map_array, one_width_grads
 
 
 def _logit_maps(maps):
@@ -33,9 +32,7 @@ class _ObbAngle(torch.autograd.Function):
         maps = ctx.saved_tensors
         if g.dtype != torch.float32 or not g.is_contiguous():
             g = g.to(torch.float32).contiguous()
-        pairs = [padded_grad_like(t, zero=False) for t in maps]
-        if len({p[0].shape[1] for p in pairs}) != 1:  # (levels padded differently: the kernel takes one width)
-            pairs = [(v, v) for v in (torch.empty_like(t) for t in maps)]
+        pairs = one_width_grads(maps, torch.empty_like)
         check(L().ymi_obb_angle_bwd(len(maps), _map_array(maps), ptr(g), _map_array([p[0] for p in pairs]), stream_ptr()), "obb_angle_bwd")
         return tuple(p[1] for p in pairs)
 
@@ -56,13 +53,7 @@ def obb_targets(batch_idx, cls, bboxes, batch_size, max_boxes, img_w, img_h, dev
     n = int(batch_idx.numel())
     if bboxes.numel() != n * 5:
         raise ValueError(f"oriented-box labels are [n, 5] xywhr rows, got {tuple(bboxes.shape)} for {n} labels")
-    out = torch.empty(batch_size, max_boxes, 6, dtype=torch.float32, device=device)
-    bi = batch_idx.to(device=device, dtype=torch.float32).reshape(-1).contiguous()
-    cl = cls.to(device=device, dtype=torch.float32).reshape(-1).contiguous()
-    bb = bboxes.to(device=device, dtype=torch.float32).reshape(-1, 5).contiguous()
-    check(L().ymi_obb_targets(ptr(bi) if n else None, ptr(cl) if n else None, ptr(bb) if n else None, n, batch_size, max_boxes, float(img_w),
-                              float(img_h), ptr(out), stream_ptr()), "obb_targets")
-    return out
+    return _dense_targets(L().ymi_obb_targets, "obb_targets", 5, batch_idx, cls, bboxes, batch_size, max_boxes, img_w, img_h, device)
 
 
 class _ObbLoss(torch.autograd.Function):
@@ -71,53 +62,11 @@ class _ObbLoss(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, targets, strides, topk, alpha, beta, scale6, angle, *maps):
-        nl = len(maps) // 2
-        box, cls = maps[:nl], maps[nl:]
-        dev = box[0].device
-        b = box[0].shape[0]
-        anchors = sum(int(t.shape[2] * t.shape[3]) for t in box)
-        g = int(targets.shape[1])
-        if angle.numel() != b * anchors or angle.dtype != torch.float32 or not angle.is_contiguous() or tuple(targets.shape) != (b, g, 6):
-            raise ValueError(f"obb_loss: angle {tuple(angle.shape)} {angle.dtype} / targets {tuple(targets.shape)} do not belong to {b} images of {anchors} anchors")
-        sb, wb = ctypes.c_size_t(0), ctypes.c_size_t(0)
-        check(L().ymi_obb_loss_sizes(b, anchors, g, ctypes.byref(sb), ctypes.byref(wb)), "obb_loss_sizes")
-        state = torch.empty(sb.value, dtype=torch.uint8, device=dev)
-        ws = workspace(wb.value, dev, "obbloss")
-        out = torch.empty(6, dtype=torch.float32, device=dev)
-        st = (ctypes.c_float * nl)(*[float(s) for s in strides])
-        check(
-            L().ymi_obb_loss_fwd(nl, _map_array(box), _map_array(cls), ptr(angle), st, ptr(targets), g, int(topk), float(alpha), float(beta), ptr(scale6),
-                                 ptr(out), ptr(state), state.numel(), ptr(ws), ws.numel(), stream_ptr()),
-            "obb_loss_fwd",
-        )
-        ctx.save_for_backward(state, scale6, angle, *maps)
-        ctx.strides = st
-        loss, items = out[:3], out[3:]
-        ctx.mark_non_differentiable(items)
-        ctx.set_materialize_grads(False)
-        return loss, items
+        return _loss_forward(ctx, _OBB_FAMILY, targets, strides, topk, alpha, beta, scale6, maps, angle=angle)[:2]
 
     @staticmethod
     def backward(ctx, gl, _gitems):
-        state, scale6, angle, *maps = ctx.saved_tensors
-        nl = len(maps) // 2
-        box, cls = maps[:nl], maps[nl:]
-        if gl is None:
-            return (None,) * (7 + len(maps))
-        if gl.dtype != torch.float32 or not gl.is_contiguous():
-            gl = gl.to(torch.float32).contiguous()
-        dbox = [torch.empty_like(t) for t in box]
-        pairs = [padded_grad_like(t, zero=False) for t in cls]
-        if len({p[0].shape[1] for p in pairs}) != 1:
-            pairs = [(v, v) for v in (padded_grad_like(t)[1] for t in cls)]
-        dcls_k, dcls = [p[0] for p in pairs], [p[1] for p in pairs]
-        dangle = torch.empty_like(angle)
-        check(
-            L().ymi_obb_loss_bwd(nl, _map_array(box), _map_array(cls), ptr(angle), ctx.strides, ptr(state), state.numel(), ptr(gl), ptr(scale6),
-                                 _map_array(dbox), _map_array(dcls_k), ptr(dangle), stream_ptr()),
-            "obb_loss_bwd",
-        )
-        return (None, None, None, None, None, None, dangle, *dbox, *dcls)
+        return _loss_backward(ctx, _OBB_FAMILY, gl, has_angle=True)
 
 
 def obb_loss(box_maps, cls_maps, angle, strides, targets, scale6, topk=10, alpha=0.5, beta=6.0):
@@ -127,15 +76,9 @@ def obb_loss(box_maps, cls_maps, angle, strides, targets, scale6, topk=10, alpha
 
 def detect_decode_obb(box_maps, cls_maps, angle, strides):
     """OBB's eval output cat([dist2rbox boxes * stride, class sigmoids, angle], 1) -> [B, 4 + nc + 1, A] float32 in one launch (no gradient)."""
-    nl = len(box_maps)
     b = box_maps[0].shape[0]
-    nc = cls_maps[0].shape[1]
     anchors = sum(int(t.shape[2] * t.shape[3]) for t in box_maps)
     angle = angle.detach()
     if angle.numel() != b * anchors or angle.dtype != torch.float32 or not angle.is_contiguous():
         raise ValueError(f"detect_decode_obb: angle {tuple(angle.shape)} {angle.dtype} is not the float32 [B, 1, A] of {b} images of {anchors} anchors")
-    y = torch.empty((b, 4 + nc + 1, anchors), dtype=torch.float32, device=box_maps[0].device)
-    st = (ctypes.c_float * nl)(*[float(s) for s in strides])
-    check(L().ymi_detect_decode_obb(nl, _map_array([t.detach() for t in box_maps]), _map_array([t.detach() for t in cls_maps]), ptr(angle), st, ptr(y),
-                                    stream_ptr()), "detect_decode_obb")
-    return y
+    return _decode(L().ymi_detect_decode_obb, "detect_decode_obb", box_maps, cls_maps, strides, 1, ptr(angle))

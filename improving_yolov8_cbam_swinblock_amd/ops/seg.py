@@ -7,7 +7,7 @@ import torch
 
 from .._lib import ACT_NONE, as_ymi, check, chunk_elems, empty_nhwc, is_nhwc, ptr, stream_ptr, workspace, ymi_dtype
 from .base import L, _byref, _note_use, grad_nhwc, join_of
-from .blocks import _DetectLoss, _map_array
+from .blocks import _DETECT_FAMILY, _DetectLoss, _decode, _loss_forward, _map_array
 from .conv import _dgrad_joined
 
 NM = 32  # prototypes the mask-loss kernels are built for (csrc/seg.hip)
@@ -97,11 +97,11 @@ def conv_transpose2x2(x, weight, bias):
 # ---- detection loss + mask loss ------------------------------------------------------------------------------------------------------
 class _DetectLossAssign(_DetectLoss):
     """_DetectLoss whose forward also returns the assignment's gt index per anchor [B, A] int32 (-1: background); the three loss sums, their
-    gradients and the saved state are the detection criterion's own (one forward body: _DetectLoss.run)."""
+    gradients and the saved state are the detection criterion's own (one forward body: blocks._loss_forward)."""
 
     @staticmethod
     def forward(ctx, targets, strides, topk, alpha, beta, scale6, *maps):
-        return _DetectLoss.run(ctx, targets, strides, topk, alpha, beta, scale6, maps, assign=True)
+        return _loss_forward(ctx, _DETECT_FAMILY, targets, strides, topk, alpha, beta, scale6, maps, assign=True)
 
     @staticmethod
     def backward(ctx, gl, _gitems, _ggidx):
@@ -174,15 +174,7 @@ def mask_loss(det_loss, det_items, gidx, targets, masks, scale6, topk, img_w, im
 
 def detect_decode_seg(box_maps, cls_maps, mc_maps, strides):
     """Segment's eval output cat([Detect._inference, mc], 1) -> [B, 4 + nc + nm, A] float32 in one launch (no gradient)."""
-    nl = len(box_maps)
-    b = box_maps[0].shape[0]
-    nc, nm = cls_maps[0].shape[1], mc_maps[0].shape[1]
-    anchors = sum(int(t.shape[2] * t.shape[3]) for t in box_maps)
-    y = torch.empty((b, 4 + nc + nm, anchors), dtype=torch.float32, device=box_maps[0].device)
-    st = (ctypes.c_float * nl)(*[float(s) for s in strides])
-    check(L().ymi_detect_decode_seg(nl, _map_array([t.detach() for t in box_maps]), _map_array([t.detach() for t in cls_maps]),
-                                    _map_array([t.detach() for t in mc_maps]), st, ptr(y), stream_ptr()), "detect_decode_seg")
-    return y
+    return _decode(L().ymi_detect_decode_seg, "detect_decode_seg", box_maps, cls_maps, strides, mc_maps[0].shape[1], _map_array([t.detach() for t in mc_maps]))
 
 
 # ---- mask decode and mask overlap (csrc/maskdec.hip) ---------------------------------------------------------------------------------

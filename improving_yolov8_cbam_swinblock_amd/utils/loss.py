@@ -52,17 +52,40 @@ class v8DetectionLoss:
             return 0
         return int(torch.bincount(batch_idx.reshape(-1).long(), minlength=batch_size).max())
 
+    name = "v8DetectionLoss"  # in the refusal of CPU tensors
+
     def __call__(self, preds, batch):
-        if hasattr(preds, "box") and hasattr(preds, "cls"):  # SplitPreds, or Segment's SegPreds
-            box, cls = list(preds.box), list(preds.cls)
-        else:  # list of [B, no, H, W] maps (reference layout): split the channels again (loss.py:205-207)
-            feats = self._feats(preds)
-            box = [f[:, : self.reg_max * 4] for f in feats]
-            cls = [f[:, self.reg_max * 4 :] for f in feats]
+        """the criterion's one body; a subclass overrides the steps that differ: _split (how preds gives box maps, class maps and its
+        extras), _targets (the dense target rows, and what is asked of the labels) and _finish (the loss op)."""
+        box, cls, extras = self._split(preds)
         if not box[0].is_cuda:
-            raise RuntimeError("v8DetectionLoss runs in libyolo_mi355 kernels: predictions must be on the MI355X (cuda) device; there is no CPU path")
+            raise RuntimeError(f"{self.name} runs in libyolo_mi355 kernels: predictions must be on the MI355X (cuda) device; there is no CPU path")
         box = [_nhwc_map(t, True) for t in box]
         cls = [_nhwc_map(t if t.dtype == box[0].dtype else t.to(box[0].dtype), False) for t in cls]
+        B = box[0].shape[0]
+        targets = self._targets(batch, box, extras)
+        # both results leave the last loss kernel: loss * gains * B (differentiable) and loss * gains (reference loss.py:250-255)
+        scale = self._scales.get(B)
+        if scale is None:
+            gh = [float(self.hyp.box), float(self.hyp.cls), float(self.hyp.dfl)]
+            scale = self._scales[B] = torch.tensor([g * B for g in gh] + gh, dtype=torch.float32, device=box[0].device)
+        return self._finish(box, cls, targets, scale, extras, batch)
+
+    def _split_feats(self, feats):
+        """[B, no, H, W] maps (reference layout): split the channels again (loss.py:205-207)."""
+        return [f[:, : self.reg_max * 4] for f in feats], [f[:, self.reg_max * 4 :] for f in feats]
+
+    def _split(self, preds):
+        """-> (box maps, class maps, extras): SplitPreds, or the per-level [B, no, H, W] maps of a Detect output (the train-mode list, or the
+        second entry of the eval-mode tuple)."""
+        if hasattr(preds, "box") and hasattr(preds, "cls"):
+            return list(preds.box), list(preds.cls), None
+        return (*self._split_feats(preds[1] if isinstance(preds, tuple) else preds), None)
+
+    targets_op = "detect_targets"  # the ops function that makes the dense target rows
+
+    def _targets(self, batch, box, extras):
+        """the dense target rows of the batch, by ops.<targets_op>, for the image the first level's map and stride span."""
         B = box[0].shape[0]
         h, w = box[0].shape[2:]
         s0 = self.stride_list[0]
@@ -70,19 +93,9 @@ class v8DetectionLoss:
         if g is None:
             g = self.max_boxes(batch["batch_idx"], B)
         g = max(int(g), 1)  # an all-background batch still needs one (empty) slot per image
-        targets = ops.detect_targets(batch["batch_idx"], batch["cls"], batch["bboxes"], B, g, w * s0, h * s0, box[0].device)
-        # both results leave the last loss kernel: loss * gains * B (differentiable) and loss * gains (reference loss.py:250-255)
-        scale = self._scales.get(B)
-        if scale is None:
-            gh = [float(self.hyp.box), float(self.hyp.cls), float(self.hyp.dfl)]
-            scale = self._scales[B] = torch.tensor([g * B for g in gh] + gh, dtype=torch.float32, device=box[0].device)
-        return self._finish(box, cls, targets, scale, preds, batch)
+        return getattr(ops, self.targets_op)(batch["batch_idx"], batch["cls"], batch["bboxes"], B, g, w * s0, h * s0, box[0].device)
 
-    def _feats(self, preds):
-        """the per-level [B, no, H, W] maps of a Detect output: the train-mode list, or the second entry of the eval-mode tuple."""
-        return preds[1] if isinstance(preds, tuple) else preds
-
-    def _finish(self, box, cls, targets, scale, preds, batch):
+    def _finish(self, box, cls, targets, scale, extras, batch):
         return ops.detect_loss(box, cls, self.stride_list, targets, scale, self.topk, self.alpha, self.beta)
 
 
@@ -103,19 +116,20 @@ class v8SegmentationLoss(v8DetectionLoss):
                                       "the overlap encoding [B, H, W]")
         self.nm = model.model[-1].nm
 
-    def _feats(self, preds):
-        return (preds if len(preds) == 3 else preds[1])[0]
-
-    def _finish(self, box, cls, targets, scale, preds, batch):
+    def _split(self, preds):
+        """SegPreds, the train-mode output (feats, mc [B, nm, A], p) or the eval output (y, (feats, mc, p)) -> extras (mc maps, proto)."""
         from ..nn.modules.head import SegPreds
 
         if isinstance(preds, SegPreds):
-            mc, proto = list(preds.mc), preds.proto
-        else:
-            feats, mcat, proto = preds if len(preds) == 3 else preds[1]
-            B = mcat.shape[0]
-            sizes = [int(f.shape[2] * f.shape[3]) for f in feats]
-            mc = [m.reshape(B, self.nm, f.shape[2], f.shape[3]) for m, f in zip(mcat.split(sizes, 2), feats)]
+            return list(preds.box), list(preds.cls), (list(preds.mc), preds.proto)
+        feats, mcat, proto = preds if len(preds) == 3 else preds[1]
+        B = mcat.shape[0]
+        sizes = [int(f.shape[2] * f.shape[3]) for f in feats]
+        mc = [m.reshape(B, self.nm, f.shape[2], f.shape[3]) for m, f in zip(mcat.split(sizes, 2), feats)]
+        return (*self._split_feats(feats), (mc, proto))
+
+    def _finish(self, box, cls, targets, scale, extras, batch):
+        mc, proto = extras
         dt = box[0].dtype
         mc = [_nhwc_map(t if t.dtype == dt else t.to(dt), True) for t in mc]
         proto = _nhwc_map(ops.to_internal(proto, dt), True)
@@ -139,35 +153,27 @@ class v8OBBLoss(v8DetectionLoss):
     decode, inside test, probiou metric and box term, with the detection loss's top-k, claim and final-sum kernels between them; every shape is
     static given max_boxes and nothing is read back."""
 
-    def __call__(self, preds, batch):
+    name = "v8OBBLoss"
+    targets_op = "obb_targets"
+
+    def _split(self, preds):
         if hasattr(preds, "angle"):  # OBBPreds
-            box, cls, angle = list(preds.box), list(preds.cls), preds.angle
-        else:  # (feats, angle), or the eval tuple (y, (feats, angle)): split the channels again (loss.py:636-640)
-            feats, angle = preds if isinstance(preds[0], (list, tuple)) else preds[1]
-            box = [f[:, : self.reg_max * 4] for f in feats]
-            cls = [f[:, self.reg_max * 4 :] for f in feats]
-        if not box[0].is_cuda:
-            raise RuntimeError("v8OBBLoss runs in libyolo_mi355 kernels: predictions must be on the MI355X (cuda) device; there is no CPU path")
-        box = [_nhwc_map(t, True) for t in box]
-        cls = [_nhwc_map(t if t.dtype == box[0].dtype else t.to(box[0].dtype), False) for t in cls]
+            return list(preds.box), list(preds.cls), preds.angle
+        # (feats, angle), or the eval tuple (y, (feats, angle)): split the channels again (loss.py:636-640)
+        feats, angle = preds if isinstance(preds[0], (list, tuple)) else preds[1]
+        return (*self._split_feats(feats), angle)
+
+    def _targets(self, batch, box, angle):
         B = box[0].shape[0]
-        h, w = box[0].shape[2:]
-        s0 = self.stride_list[0]
         A = sum(int(t.shape[2] * t.shape[3]) for t in box)
         if tuple(angle.shape) != (B, 1, A):
             raise ValueError(f"v8OBBLoss: the angle is [B, 1, A] = {(B, 1, A)}, got {tuple(angle.shape)}")
-        if angle.dtype != torch.float32 or not angle.is_contiguous():
-            angle = angle.float().contiguous()
         bboxes = batch["bboxes"]
         if bboxes.numel() and (bboxes.dim() != 2 or bboxes.shape[1] != 5):
             raise TypeError(f"v8OBBLoss: batch['bboxes'] holds xywhr rows [n, 5], got {tuple(bboxes.shape)}: is this an oriented-box dataset?")
-        g = batch.get("max_boxes")
-        if g is None:
-            g = self.max_boxes(batch["batch_idx"], B)
-        g = max(int(g), 1)
-        targets = ops.obb_targets(batch["batch_idx"], batch["cls"], bboxes, B, g, w * s0, h * s0, box[0].device)
-        scale = self._scales.get(B)
-        if scale is None:
-            gh = [float(self.hyp.box), float(self.hyp.cls), float(self.hyp.dfl)]
-            scale = self._scales[B] = torch.tensor([v * B for v in gh] + gh, dtype=torch.float32, device=box[0].device)
+        return super()._targets(batch, box, angle)
+
+    def _finish(self, box, cls, targets, scale, angle, batch):
+        if angle.dtype != torch.float32 or not angle.is_contiguous():
+            angle = angle.float().contiguous()
         return ops.obb_loss(box, cls, angle, self.stride_list, targets, scale, self.topk, self.alpha, self.beta)
